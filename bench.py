@@ -12,6 +12,15 @@ followed for N > 1 by the RCCL all-gather of the output batch (north_star). Inpu
 HBM before the timed region. N > 1 is launched by torch.distributed.run, one rank per GPU, each
 rank samples its own shard (weak scaling, no data-path collective besides the output gather).
 
+A plain run sets up, warms up, times the K steps and prints the line: `metric`, `value`, `unit`, `ms_per_step` (= the timed region
+/ K), `higher_is_better`, `dtype` and the workload's `config`. Everything else the line can carry (the roofline block with its HIP-event
+conv timings, power and clock, the single-stream and GC-on regions, the other precision, the f16x3-vs-exact check, the CPU baseline,
+other_configs; for --workload train the other optimiser and the phase split) is measured only with --full, and is null without it.
+--dump-outputs DIR writes what the last timed step returned as DIR/<name>.npy (float32): `hr` (the HR batch; for N > 1 the gathered
+one), `lr_quantised` for the rescaling round trip, `nll` and `params` (the trained tensors after the step) for --workload train; an
+array over its share of 48 MB is a fixed seeded sample of its elements. Inputs, weights and eps are seeded: the same arguments give
+the same inputs in every run.
+
 Other lines the driver can ask for with one flag each (none of them has been measured at N > 1: no multi-GPU node was available):
     --preset Rescaling_DF2K_4X --batch 8        BASELINE config 4 (rescaling forward -> Quant -> inverse, 64 images over 8 GPUs)
     --workload train [--optim native]           BASELINE config 5 (DDP NLL training step, 16 HR patches per GPU, global batch 128)
@@ -85,6 +94,22 @@ IDEAL_GB_PER_IMAGE = 23.02            # layer-wise-ideal fp32 HBM t
 GFLOP_FACE_X8_IMAGE = 146.64          # Face-SR x8 inverse, one 160x160 HR image (LR 20x20)
 GFLOP_RESCALE_ROUNDTRIP = 1087.69     # rescaling x4 forward + inverse, one 640x640 image
 GFLOP_TRAIN_SAMPLE = 184.27 * 3.0     # SR x4 NLL step, one 160x160 HR sample: forward x ~3 with the backward pass
+DUMP_BYTES = 48 * 10 ** 6             # --dump-outputs: payload of all arrays together (headroom under 64 MB for the .npy headers)
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: each tensor of `arrays` ({name: tensor}) as <path>/<name>.npy in float32. One over its even share of
+    DUMP_BYTES is replaced by a fixed seeded sample of its elements: the same flat indices, in increasing order, for the same size in
+    every run, so that two builds of the project can be compared element for element."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BYTES // len(arrays)
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if a.nbytes > share:
+            idx = np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False, shuffle=False)
+            a = a.reshape(-1)[np.sort(idx)]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 @contextlib.contextmanager
@@ -206,7 +231,14 @@ def main():
                     help="skip the short timed runs of BASELINE.json configs 1 / 3 / 4 / 5 after the headline (N = 1 only)")
     ap.add_argument("--other-steps", type=int, default=8, help="timed steps per other configuration")
     ap.add_argument("--cpu-passes", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline (roofline, single-stream / GC-on regions, other precision, "
+                         "exact check, CPU baseline, other_configs; train: the other optimiser, phase split); the --no-* flags trim it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float32, at most 48 MB in all)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
 
     import torch
     import torch.distributed as dist
@@ -293,14 +325,21 @@ def main():
             return sum(e.weight_bytes() for e in self._all())
 
     def timed(mode, warmup, steps):
-        """`steps` timed steps of `mode` between barrier + synchronize pairs; conv launches timed with HIP events on the stream."""
+        """`steps` timed steps of `mode` between barrier + synchronize pairs -> (seconds, roofline block, last step's output).
+        --full: conv launches timed with HIP events on the stream, the clock probe and the power sampler run in the region and the
+        roofline block is built from them; a plain run times the steps alone and has no block."""
         net.set_precision(mode)
         eng = Engines()
+        keep = {}
         with torch.no_grad():
             for i in range(warmup):
                 step(i)
+            if not args.full:
+                with quiet_gc():
+                    dt = timed_region(lambda i: keep.__setitem__("out", step(i)), steps, first=warmup)
+                assert bool(torch.isfinite(keep["out"]).all())
+                return dt, None, keep["out"]
             eng.profile_convs(True)
-            keep = {}
 
             stamps = []
 
@@ -326,7 +365,7 @@ def main():
         per = sorted(1e3 * (b - a) for a, b in zip([t_first] + stamps[:-1], stamps))
         roof["step_ms_host"] = {"p50": round(per[len(per) // 2], 3), "p95": round(per[min(len(per) - 1, int(0.95 * len(per)))], 3),
                                 "max": round(per[-1], 3), "note": "wall time between the returns of consecutive calls inside the timed region"}
-        return dt, roof
+        return dt, roof, keep["out"]
 
     def roofline_block(eng, mode, steps, dt, clk_mhz, power):
         """`frac` = ALGORITHMIC TFLOP/s of the dominant conv family / the guide's dense peak of the arithmetic it runs on (f16x3:
@@ -426,11 +465,17 @@ def main():
 
     default_mode = args.precision                       # = the module's default unless overridden on the command line
     other_mode = "exact" if default_mode == "f16x3" else "f16x3"
-    dt, roof = timed(default_mode, args.warmup, args.steps)
+    dt, roof, out = timed(default_mode, args.warmup, args.steps)
+    if args.dump_outputs and rank == 0:
+        outs = {"hr": out_all if world > 1 else out}
+        if roundtrip:
+            outs = {"lr_quantised": last["lrq"], **outs}
+        dump_outputs(args.dump_outputs, outs)
+    del out
     # the same steps as a plain Python caller runs them: cyclic GC left ON (quiet_gc makes `value` an upper bound for a
     # caller whose loop pays a generation-2 pause every few hundred calls)
     gc_on = None
-    if not args.no_single_stream_leg:
+    if args.full and not args.no_single_stream_leg:
         with torch.no_grad():
             ks = min(args.steps, 20)
             dtg = timed_region(lambda i: step(i), ks, first=args.warmup + args.steps)
@@ -442,11 +487,11 @@ def main():
     # HCFLOW_STREAMS=1 (profiles/). `value` / `ms_per_step` are the default region's; the single-stream region's are in the block.
     single = None
     split_on = net._nstreams[0] >= 2 and B >= 4
-    if split_on and not args.no_single_stream_leg:
+    if args.full and split_on and not args.no_single_stream_leg:
         headline_power, headline_steps = roof.get("power"), roof.get("step_ms_host")
         net.set_streams(1)
         try:
-            dt1, roof = timed(default_mode, 2, args.steps)
+            dt1, roof, _ = timed(default_mode, 2, args.steps)
         finally:
             net.set_streams(2)
         single = {"value": round(world * B * args.steps / dt1, 4), "unit": "HR images/s", "ms_per_step": round(1e3 * dt1 / args.steps, 3),
@@ -458,17 +503,17 @@ def main():
                                "then do not add up to the step; `power` is the headline (two-stream) region's"
                                % (single["value"], single["ms_per_step"]))
     other = None
-    if not args.no_other_precision:
+    if args.full and not args.no_other_precision:
         net.set_streams(1)                                # (one stream: this leg's per-kernel table is what it is reported for)
         try:
-            dt_o, roof_o = timed(other_mode, 1, args.steps)
+            dt_o, roof_o, _ = timed(other_mode, 1, args.steps)
         finally:
             net.set_streams(2 if split_on else net._nstreams[0])
         other = {"mode": other_mode, "value": round(world * B * args.steps / dt_o, 4), "unit": "HR images/s",
                  "ms_per_step": round(1e3 * dt_o / args.steps, 3), "steps": args.steps, "streams": 1, "roofline": roof_o}
     # same inputs / same device eps in both precisions: deviation of the default mode from the exact fp32-MFMA kernels
     check = None
-    if not args.no_exact_check:
+    if args.full and not args.no_exact_check:
         with torch.no_grad():
             net.set_precision("f16x3")
             y_fast = step(10 ** 6)
@@ -493,7 +538,7 @@ def main():
     if rank == 0:
         img_s = world * B * args.steps / dt
         cpu = None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             cpu, cpu_lr, cpu_out = cpu_baseline(cfg, params, h, args.cpu_passes)
             # DIRECT parity at full size: the oracle's config-1 output (B=1, tau=0, this LR size) against the engine on the same
             # LR, both conv precisions, outside the timed region (north_star: within 1e-4 of the CPU path)
@@ -533,7 +578,7 @@ def main():
                           "check": check},
             "roofline": roof, "single_stream": single, "gc_enabled": gc_on, "other_precision": other, "cpu_baseline": cpu,
         }
-        if world == 1 and not args.no_other_configs and args.preset == "SR_DF2K_4X" and B == 16 and h == 160:
+        if args.full and world == 1 and not args.no_other_configs and args.preset == "SR_DF2K_4X" and B == 16 and h == 160:
             del net, lr, out_all, hr_in
             torch.cuda.empty_cache()
             try:                                     # the headline line is printed whatever happens in the side measurements
@@ -576,7 +621,7 @@ def train_workload(args, dev, world, rank):
 
     power = {}
 
-    def run(native):
+    def run(native, dump=False):
         net.load_state_dict(params, strict=True)                      # both variants start from the same weights (in-place copy)
         ps = [q for q in net.parameters() if q.requires_grad]        # the reference builds its optimiser AFTER the wrap (:118)
         if native:
@@ -593,45 +638,51 @@ def train_workload(args, dev, world, rank):
             side = torch.cuda.Stream()
             side.wait_stream(torch.cuda.current_stream())
             side_ctx = torch.cuda.stream(side)
+        psamp = PowerSampler(int(os.environ.get("LOCAL_RANK", "0"))) if args.full else contextlib.nullcontext()
         with side_ctx:
             for i in range(max(2, args.warmup)):                      # >= 2: step 1 builds plans / buckets, step 2 sees a device refresh
                 one(i)
-            with PowerSampler(int(os.environ.get("LOCAL_RANK", "0"))) as psamp, quiet_gc():
+            with psamp, quiet_gc():
                 dt = timed_region(one, args.steps, first=args.warmup)
-        power[native] = psamp.block()
+        if dump:                                                      # the loss and the trained tensors after the last timed step
+            dump_outputs(args.dump_outputs, {"nll": keep["nll"], "params": torch.cat([q.detach().reshape(-1) for q in ps])})
         nll = float(keep["nll"])
         assert nll == nll, "NLL is NaN"
-        # phase split of ONE more step with host syncs between the phases (outside the timed region: the syncs break the overlap
-        # of the all-reduce with the optimiser's host work)
-        sync = torch.cuda.synchronize
-        sync(); t0 = time.perf_counter()
-        opt.zero_grad(set_to_none=True)
-        _, l = ddp(hr=hr, lr=lr, reverse=False)
-        sync(); t1 = time.perf_counter()
-        l.backward()
-        sync(); t2 = time.perf_counter()
-        clip(net.parameters(), 100.0)
-        opt.step()
-        sync(); t3 = time.perf_counter()
         res = {"value": round(world * B * args.steps / dt, 3), "ms_per_step": round(1e3 * dt / args.steps, 3), "nll_last": round(nll, 5),
-               "phases_ms_one_synchronised_step": {"forward_incl_refresh": round(1e3 * (t1 - t0), 2),
-                                                   "backward_incl_allreduce": round(1e3 * (t2 - t1), 2),
-                                                   "clip_adam": round(1e3 * (t3 - t2), 2)},
                "mfma_frac": round(B * args.steps / dt * GFLOP_TRAIN_SAMPLE / 1e3 / peak, 4),
-               # per phase (synchronised step): forward = 184.27 GFLOP per sample (incl. the per-step pack refresh in its time),
-               # backward = data + weight gradients = 2x that
-               "mfma_frac_forward": round(B * (GFLOP_TRAIN_SAMPLE / 3.0) / 1e3 / (t1 - t0) / peak, 4),
-               "mfma_frac_backward": round(B * (2.0 * GFLOP_TRAIN_SAMPLE / 3.0) / 1e3 / (t2 - t1) / peak, 4),
                "allreduce_MB_per_step": round(grad_allreduce_bytes(net) / 1e6, 1) if world > 1 else 0.0,
                "activation_arena_GB": round(net.engine().workspace_bytes() / 2 ** 30, 2)}
+        if args.full:
+            power[native] = psamp.block()
+            # phase split of ONE more step with host syncs between the phases (outside the timed region: the syncs break the overlap
+            # of the all-reduce with the optimiser's host work)
+            sync = torch.cuda.synchronize
+            sync(); t0 = time.perf_counter()
+            opt.zero_grad(set_to_none=True)
+            _, l = ddp(hr=hr, lr=lr, reverse=False)
+            sync(); t1 = time.perf_counter()
+            l.backward()
+            sync(); t2 = time.perf_counter()
+            clip(net.parameters(), 100.0)
+            opt.step()
+            sync(); t3 = time.perf_counter()
+            res.update({"phases_ms_one_synchronised_step": {"forward_incl_refresh": round(1e3 * (t1 - t0), 2),
+                                                            "backward_incl_allreduce": round(1e3 * (t2 - t1), 2),
+                                                            "clip_adam": round(1e3 * (t3 - t2), 2)},
+                        # per phase (synchronised step): forward = 184.27 GFLOP per sample (incl. the per-step pack refresh in its
+                        # time), backward = data + weight gradients = 2x that
+                        "mfma_frac_forward": round(B * (GFLOP_TRAIN_SAMPLE / 3.0) / 1e3 / (t1 - t0) / peak, 4),
+                        "mfma_frac_backward": round(B * (2.0 * GFLOP_TRAIN_SAMPLE / 3.0) / 1e3 / (t2 - t1) / peak, 4)})
         del opt
         return res
 
-    first = run(args.optim == "native")
-    try:
-        second = run(args.optim != "native")
-    except Exception as e:  # noqa: BLE001 -- the side line must not cost the headline
-        second = {"error": "%s: %s" % (type(e).__name__, str(e)[:200])}
+    first = run(args.optim == "native", dump=bool(args.dump_outputs) and rank == 0)
+    second = None
+    if args.full:
+        try:
+            second = run(args.optim != "native")
+        except Exception as e:  # noqa: BLE001 -- the side line must not cost the headline
+            second = {"error": "%s: %s" % (type(e).__name__, str(e)[:200])}
     names = {True: "hcflow_amd.optim.Adam + hcflow_amd.optim.clip_grad_norm_ (INTEGRATION.md: two lines of the caller switched)",
              False: "torch.optim.Adam + torch.nn.utils.clip_grad_norm_ (the reference caller's own lines, unchanged)"}
     if rank == 0:
@@ -647,7 +698,7 @@ def train_workload(args, dev, world, rank):
                        "global_batch": world * B, "hr_size": H, "parallelism": "ddp%d" % world,
                        "optimizer": names[args.optim == "native"]},
             "detail": first,
-            "other_optimizer": dict(second, optimizer=names[args.optim != "native"]),
+            "other_optimizer": dict(second, optimizer=names[args.optim != "native"]) if second is not None else None,
             # as the sampling line: `peak` = the guide's dense peak of the matrix pipe the mode uses (f16x3: 2 500, of which three
             # MFMAs go into one fp32-equivalent product block -> `frac_of_split_yardstick` against 2 500 / 3; exact: 157.3)
             "roofline": {"bound": "mfma", "achieved": round(first["mfma_frac"] * peak, 2),

@@ -99,7 +99,8 @@ def test_reference_written_checkpoint_loads_strictly_on_cpu(name, tmp_path):
     _load_network(path, torch.nn.DataParallel(net), strict=True)
     want = [(k, tuple(s)) for k, s, _ in param_spec(cfg)]
     assert [(k, tuple(v.shape)) for k, v in net.state_dict().items()] == want
-    p = {k: v.clone() for k, v in net.state_dict().items()}
+    # (where a GPU is visible nn.DataParallel has moved the module to cuda:0; the oracle runs on the CPU)
+    p = {k: v.detach().cpu().clone() for k, v in net.state_dict().items()}
     lr = t(g["lr"])
     B, _, h, w = lr.shape
     with torch.no_grad():

@@ -3,9 +3,9 @@
 FETCH_SIZE and WRITE_SIZE do not fit one pass; on gfx950 FETCH_SIZE counts 64 B per 128-B request -> doubled;
 both counters are in KiB... see UNIT below).
 
-    rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d gpurun_out/pmc_fetch -- python bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-exact-check
-    rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d gpurun_out/pmc_write -- python bench.py ... (same)
-    python tools/pmc_traffic.py gpurun_out/pmc_fetch gpurun_out/pmc_write > profiles/rNN_traffic_pmc.json
+    rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d pmc_fetch -- python bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-exact-check
+    rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d pmc_write -- python bench.py ... (same)
+    python tools/pmc_traffic.py pmc_fetch pmc_write > profiles/rNN_traffic_pmc.json
 """
 import csv
 import glob
@@ -64,7 +64,7 @@ def collect(d, counter):
 
 def main(fetch_dir, write_dir):
     fe, wr = collect(fetch_dir, "FETCH_SIZE"), collect(write_dir, "WRITE_SIZE")
-    out = {"source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) over `python bench.py --steps 5 --warmup 2 --no-other-precision "
+    out = {"source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) over `python bench.py --full --steps 5 --warmup 2 --no-other-precision "
                      "--warmup 1`, B=16; FETCH_SIZE doubled per MI355X_MICROARCH.md (gfx950 reports 64 B per 128 B "
                      "request); averaged over all launches of the kernel in the run (tools/pmc_traffic.py)",
            "kernels": {}}
