@@ -1,4 +1,5 @@
-// Fused implicit-GEMM convolution (3x3 pad 1 / 1x1) on fp32 MFMA for gfx950.
+// Fused implicit-GEMM convolution (3x3 pad 1 / 1x1, and 5x5 pad 2 for the LPIPS AlexNet in hcf_lpips.hip) on fp32 MFMA for
+// gfx950.
 //
 // This one kernel carries ~99 % of the FLOPs of the HCFlow forward/inverse pass: the RRDB trunks
 // (Basic.py:360-398), the coupling networks FCN / DenseBlock (Basic.py:329-356,426-447), conv_first /
@@ -9,7 +10,7 @@
 //     wave w owns tile rows {2w, 2w+1} -> 2 x NT accumulators of v_mfma_f32_32x32x2_f32
 //     (exact fp32, 64 cycles each: the kernel is MFMA-bound by design).
 //   * K is walked in chunks of 16 "virtual" channels. The input halo tile (10 x 34 pixels x 16 ch,
-//     21.8 KB) is staged through LDS once per chunk and reused by all 9 taps; double buffered
+//     21.8 KB; 12 x 36 = 27.6 KB for 5x5) is staged through LDS once per chunk and reused by all taps; double buffered
 //     -> one barrier per chunk (18 K-steps x 16 MFMAs per wave between barriers at NT = 2).
 //   * A fragments: lane (i = l&31, half = l>>5) reads 4 consecutive channels with one ds_read_b128
 //     (the K order inside an 8-channel group is permuted so each lane's 4 k's are contiguous).
@@ -51,7 +52,8 @@ __device__ __forceinline__ gfptr uniform_ptr(const float* p) {
 
 template <int TAPS, int NT, bool VEC>
 __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(const ConvArgs a) {
-  constexpr int PAD = (TAPS == 9) ? 1 : 0;
+  constexpr int PAD = (TAPS == 25) ? 2 : (TAPS == 9) ? 1 : 0;
+  constexpr int KS = 2 * PAD + 1;                  // kernel side
   constexpr int HH = TH + 2 * PAD, HW = TW + 2 * PAD, HP = HH * HW;
   constexpr int NLOAD = HP * (KC / 4);
   constexpr int NSLOT = (NLOAD + 255) / 256;
@@ -190,7 +192,7 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(const ConvArgs a) {
         __builtin_amdgcn_sched_barrier(0);         // ... provided they are ISSUED here and not sunk to the LDS write
       }
       const int tap = s >> 1, kg = s & 1;
-      const int dy = (TAPS == 9) ? tap / 3 : 0, dx = (TAPS == 9) ? tap % 3 : 0;
+      const int dy = (TAPS == 1) ? 0 : tap / KS, dx = (TAPS == 1) ? 0 : tap % KS;
       f32x4 af[2];
 #pragma unroll
       for (int m = 0; m < 2; ++m)
@@ -334,6 +336,8 @@ int launch_conv(const ConvArgs& a, int taps, hipStream_t st) {
       case 2: return launch_t<1, 2>(a, st);
       case 3: return launch_t<1, 3>(a, st);
     }
+  } else if (taps == 25 && nt == 2) {            // 5x5 pad 2, 64-channel blocks: AlexNet conv1 (on the 4x4 space-to-depth grid) / conv2
+    return launch_t<25, 2>(a, st);
   }
   return HCF_ERR_UNSUPPORTED;
 }

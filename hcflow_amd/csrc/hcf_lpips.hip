@@ -1,0 +1,343 @@
+// LPIPS v0.1 with AlexNet (the perceptual column of the reference's test log: codes/test_HCFlow.py:48,132-133,
+// `lpips.LPIPS(net='alex')` applied to (2 gt - 1, 2 sr - 1)) as one call on device tensors, hcflow_amd/lpips.py.
+//
+//   prep      scaling layer (x - shift) / scale, NCHW -> NHWC, space-to-depth by 4 (channel c*16 + a*4 + b for input row 4Y+a,
+//             col 4X+b; zeros beyond the image), in0 and in1 stacked into one batch of 2B images: every later launch covers both
+//   conv1     11x11 stride 4 pad 2 == 5x5 stride 1 pad 2 on the s2d grid with the re-indexed weight [64,48,5,5] (lpips.py:
+//             alex_conv1_as_s2d): the flow's fp32-MFMA conv kernel (hcf_conv.hip, TAPS = 25), bias + ReLU fused
+//   pool1     MaxPool 3 / 2 (floor mode) over the valid conv1 rows / cols only (the s2d grid carries one or two spare ones)
+//   conv2     5x5 pad 2, 64 -> 192, same kernel, three 64-channel blocks
+//   pool2
+//   conv3..5  3x3 pad 1 through hcf_aux_conv2d (exact fp32 MFMA), bias + ReLU fused
+//   head      per layer and pixel: n_i = sum_c f_i^2, d = sum_c w_c (f0 / (sqrt n0 + 1e-10) - f1 / (sqrt n1 + 1e-10))^2; per-block
+//             partial sums in a fixed order, then out[b] = sum_l (sum of layer l's partials) / (h_l w_l), in layer order.
+// Every reduction has a fixed order that depends only on (H, W): results are bit-reproducible and per image independent of B.
+#include <algorithm>
+#include <cstring>
+
+#include "../../include/hcflow.h"
+#include "hcf_common.h"
+
+namespace hcf {
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+constexpr int kLpipsLayers = 5;
+constexpr int kHeadPix = 128;                       // pixels per head block: 16 groups of 16 lanes, 8 pixels each
+static const int kAlexC[kLpipsLayers] = {64, 192, 384, 256, 256};
+
+static inline size_t lp_al256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+struct LpipsPlan {
+  int Hs, Ws, H1, W1, H2, W2, H3, W3;
+  int chunk0[kLpipsLayers], nchunk[kLpipsLayers], nchunk_total;
+  size_t o_s2d, o_f1, o_p1, o_f2, o_p2, o_f3, o_f4, o_f5, o_pk, o_bias, o_scale, o_part, o_aux, aux_bytes, total;
+};
+
+static bool lpips_plan(int B, int H, int W, LpipsPlan& p) {
+  memset(&p, 0, sizeof(p));
+  if (B < 1 || H < 31 || W < 31 || H >= 32768 || W >= 32768) return false;
+  p.Hs = (H + 3) / 4; p.Ws = (W + 3) / 4;
+  p.H1 = (H - 7) / 4 + 1; p.W1 = (W - 7) / 4 + 1;            // conv1: floor((H + 4 - 11) / 4) + 1
+  p.H2 = (p.H1 - 3) / 2 + 1; p.W2 = (p.W1 - 3) / 2 + 1;
+  p.H3 = (p.H2 - 3) / 2 + 1; p.W3 = (p.W2 - 3) / 2 + 1;
+  const int hw[kLpipsLayers] = {p.H1 * p.W1, p.H2 * p.W2, p.H3 * p.W3, p.H3 * p.W3, p.H3 * p.W3};
+  int c0 = 0;
+  for (int l = 0; l < kLpipsLayers; ++l) {
+    p.chunk0[l] = c0;
+    p.nchunk[l] = (hw[l] + kHeadPix - 1) / kHeadPix;
+    c0 += p.nchunk[l];
+  }
+  p.nchunk_total = c0;
+  const size_t N = 2 * (size_t)B, f = sizeof(float);
+  const size_t gs = N * p.Hs * p.Ws, g2 = N * p.H2 * p.W2, g3 = N * p.H3 * p.W3;
+  size_t o = 256;                                              // [0, 256): unused header
+  auto take = [&](size_t bytes) { const size_t r = o; o += lp_al256(bytes); return r; };
+  p.o_s2d = take(gs * 48 * f);
+  p.o_f1 = take(gs * 64 * f);
+  p.o_p1 = take(g2 * 64 * f);
+  p.o_f2 = take(g2 * 192 * f);
+  p.o_p2 = take(N * p.H3 * p.W3 * 192 * f);
+  p.o_f3 = take(g3 * 384 * f);
+  p.o_f4 = take(g3 * 256 * f);
+  p.o_f5 = take(g3 * 256 * f);
+  // fp32 conv pack [chunk][tap][2][64][8] + one zero K-step: conv1 3 chunks, conv2 4 chunks of 16 input channels
+  p.o_pk = take(((size_t)4 * 25 * 2 + 1) * 64 * 8 * f);
+  p.o_bias = take(64 * f);
+  p.o_scale = take(64 * f);
+  p.o_part = take((size_t)B * p.nchunk_total * f);
+  size_t aux = 0;
+  for (int l = 2; l < kLpipsLayers; ++l)
+    aux = std::max(aux, hcf_aux_conv2d_workspace(kAlexC[l - 1], kAlexC[l], 3, (int)N, p.H3, p.W3));
+  p.aux_bytes = aux;
+  p.o_aux = take(aux);
+  p.total = o;
+  return aux > 0;
+}
+
+// ---- prep: one thread per (image n of 2B, s2d pixel, 4-channel unit q = c * 4 + a) -> 4 input columns 4X .. 4X+3 of row 4Y+a
+__global__ __launch_bounds__(256) void lpips_prep_kernel(const float* __restrict__ in0, const float* __restrict__ in1, int B,
+                                                         int H, int W, int Hs, int Ws, int normalize,
+                                                         const float* __restrict__ shift, const float* __restrict__ scale,
+                                                         float* __restrict__ out) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  const long long total = 2LL * B * Hs * Ws * 12;
+  if (i >= total) return;
+  const int q = (int)(i % 12);
+  const long long pix = i / 12;
+  const int X = (int)(pix % Ws);
+  const int Y = (int)((pix / Ws) % Hs);
+  const int n = (int)(pix / ((long long)Ws * Hs));
+  const int c = q >> 2, a = q & 3;
+  const float* src = (n < B) ? in0 + (size_t)n * 3 * H * W : in1 + (size_t)(n - B) * 3 * H * W;
+  const int y = 4 * Y + a;
+  const float sh = shift[c], sc = scale[c];
+  float v[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int x = 4 * X + j;
+    float t = 0.f;                                              // zero padding in the SCALED domain (conv1's padding)
+    if (y < H && x < W) {
+      float s = src[((size_t)c * H + y) * W + x];
+      if (normalize) s = 2.f * s - 1.f;
+      t = (s - sh) / sc;
+    }
+    v[j] = t;
+  }
+  f32x4 o4 = {v[0], v[1], v[2], v[3]};
+  *reinterpret_cast<f32x4*>(out + (size_t)pix * 48 + q * 4) = o4;
+}
+
+// ---- MaxPool 3 / 2, floor mode, NHWC: in [N][Hst][Wst][C] with the valid region Hin x Win, out dense [N][Ho][Wo][C]
+__global__ __launch_bounds__(256) void lpips_maxpool_kernel(const float* __restrict__ in, int N, int Hst, int Wst, int C,
+                                                            int Ho, int Wo, float* __restrict__ out) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  const int C4 = C >> 2;
+  const long long total = (long long)N * Ho * Wo * C4;
+  if (i >= total) return;
+  const int c4 = (int)(i % C4);
+  const long long pix = i / C4;
+  const int ox = (int)(pix % Wo);
+  const int oy = (int)((pix / Wo) % Ho);
+  const int n = (int)(pix / ((long long)Wo * Ho));
+  const float* base = in + (size_t)n * Hst * Wst * C + 4 * c4;
+  f32x4 m = *reinterpret_cast<const f32x4*>(base + ((size_t)(2 * oy) * Wst + 2 * ox) * C);
+#pragma unroll
+  for (int dy = 0; dy < 3; ++dy)
+#pragma unroll
+    for (int dx = 0; dx < 3; ++dx) {
+      const f32x4 v = *reinterpret_cast<const f32x4*>(base + ((size_t)(2 * oy + dy) * Wst + 2 * ox + dx) * C);
+      m.x = fmaxf(m.x, v.x); m.y = fmaxf(m.y, v.y); m.z = fmaxf(m.z, v.z); m.w = fmaxf(m.w, v.w);
+    }
+  *reinterpret_cast<f32x4*>(out + (size_t)pix * C + 4 * c4) = m;
+}
+
+// ---- head
+struct LpipsLayer {
+  const float* f;     // [2B][Hst][Wst][C]: images 0..B-1 from in0, B..2B-1 from in1
+  const float* lin;   // [C]
+  int C, Hst, Wst, h, w, chunk0;
+};
+struct LpipsHeadArgs {
+  LpipsLayer L[kLpipsLayers];
+  int B, nchunk_total;
+  float* part;        // [B][nchunk_total]
+};
+
+__device__ __forceinline__ float group16_sum(float v) {      // butterfly over the 16 lanes of a group; lane 0 of it is used
+#pragma unroll
+  for (int o = 8; o >= 1; o >>= 1) v += __shfl_xor(v, o, 16);
+  return v;
+}
+
+// grid (nchunk_total, B), 256 threads: 16 groups x 16 lanes, one pixel per group at a time, lanes over float4 channel units
+__global__ __launch_bounds__(256) void lpips_head_kernel(const LpipsHeadArgs a) {
+  __shared__ float gsum[16];
+  const int b = blockIdx.y, blk = blockIdx.x;
+  int l = 0;
+#pragma unroll
+  for (int k = 1; k < kLpipsLayers; ++k) l = (blk >= a.L[k].chunk0) ? k : l;
+  const LpipsLayer L = a.L[l];
+  const int g = threadIdx.x >> 4, j = threadIdx.x & 15;
+  const int hw = L.h * L.w, C = L.C, ni = C >> 6;              // C / 4 float4 units over 16 lanes: 1 .. 6 each
+  const float eps = 1e-10f;
+  float s = 0.f;
+  for (int k = 0; k < kHeadPix / 16; ++k) {
+    const int p = (blk - L.chunk0) * kHeadPix + k * 16 + g;
+    if (p >= hw) break;                                         // (uniform over the group)
+    const int y = p / L.w, x = p - y * L.w;
+    const float* f0 = L.f + (((size_t)b * L.Hst + y) * L.Wst + x) * C;
+    const float* f1 = L.f + (((size_t)(a.B + b) * L.Hst + y) * L.Wst + x) * C;
+    f32x4 v0[6], v1[6];
+    float n0 = 0.f, n1 = 0.f;
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+      if (i < ni) {
+        v0[i] = *reinterpret_cast<const f32x4*>(f0 + 4 * (j + 16 * i));
+        v1[i] = *reinterpret_cast<const f32x4*>(f1 + 4 * (j + 16 * i));
+        n0 += v0[i].x * v0[i].x + v0[i].y * v0[i].y + v0[i].z * v0[i].z + v0[i].w * v0[i].w;
+        n1 += v1[i].x * v1[i].x + v1[i].y * v1[i].y + v1[i].z * v1[i].z + v1[i].w * v1[i].w;
+      }
+    }
+    n0 = __shfl(group16_sum(n0), 0, 16);
+    n1 = __shfl(group16_sum(n1), 0, 16);
+    const float d0 = sqrtf(n0) + eps, d1 = sqrtf(n1) + eps;
+    float t = 0.f;
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+      if (i < ni) {
+        const float* w = L.lin + 4 * (j + 16 * i);                // (any alignment: four scalar loads)
+        const float ex = v0[i].x / d0 - v1[i].x / d1, ey = v0[i].y / d0 - v1[i].y / d1;
+        const float ez = v0[i].z / d0 - v1[i].z / d1, ew = v0[i].w / d0 - v1[i].w / d1;
+        t += w[0] * ex * ex + w[1] * ey * ey + w[2] * ez * ez + w[3] * ew * ew;
+      }
+    }
+    s += group16_sum(t);                                        // lane 0's value is the one kept
+  }
+  if (j == 0) gsum[g] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float t = 0.f;
+    for (int k = 0; k < 16; ++k) t += gsum[k];
+    a.part[(size_t)b * a.nchunk_total + blk] = t;
+  }
+}
+
+struct LpipsFinalArgs {
+  int chunk0[kLpipsLayers], nchunk[kLpipsLayers], hw[kLpipsLayers];
+  int nchunk_total;
+  const float* part;
+  float* out;         // [B]
+  float* out_layers;  // [B][5] or null
+};
+
+// one block per image: thread l sums layer l's partials in order (double), then thread 0 adds the five layer means in order
+__global__ void lpips_final_kernel(const LpipsFinalArgs a) {
+  __shared__ float lay[kLpipsLayers];
+  const int b = blockIdx.x, l = threadIdx.x;
+  if (l < kLpipsLayers) {
+    const float* p = a.part + (size_t)b * a.nchunk_total + a.chunk0[l];
+    double s = 0.0;
+    for (int k = 0; k < a.nchunk[l]; ++k) s += (double)p[k];
+    const float v = (float)(s / (double)a.hw[l]);
+    lay[l] = v;
+    if (a.out_layers) a.out_layers[(size_t)b * kLpipsLayers + l] = v;
+  }
+  __syncthreads();
+  if (l == 0) {
+    float v = lay[0];
+    for (int k = 1; k < kLpipsLayers; ++k) v += lay[k];
+    a.out[b] = v;
+  }
+}
+
+static int lpips_grid(long long total, unsigned* g) {
+  const long long n = (total + 255) / 256;
+  if (n < 1 || n > 0x7fffffffLL) return HCF_ERR_ARG;
+  *g = (unsigned)n;
+  return HCF_OK;
+}
+
+// conv 5x5 pad 2 (TAPS = 25) of x [N][H][W][cin] (cin % 16 == 0) into y[..., oc0 .. oc0+64) of a cs_out-channel slab, bias + ReLU
+static int lpips_conv5(const float* x, int cin, int N, int H, int W, const float* w, const float* bias, float* y, int cs_out,
+                       int oc0, char* wk, const LpipsPlan& p, hipStream_t st) {
+  float* bvec = (float*)(wk + p.o_bias);
+  float* svec = (float*)(wk + p.o_scale);
+  int rc = launch_repack_epilogue(0, bias + oc0, nullptr, 64, bvec, svec, st);
+  if (rc != HCF_OK) return rc;
+  RepackArgs r;
+  memset(&r, 0, sizeof(r));
+  r.w = w + (size_t)oc0 * cin * 25; r.cin_w = cin; r.taps = 25; r.cout = 64;
+  r.srcs[0] = cin; r.nsrc = 1; r.nchunk = cin / 16; r.npad = 64;
+  r.pk = (float*)(wk + p.o_pk);
+  if (hipMemsetAsync(r.pk, 0, ((size_t)r.nchunk * 25 * 2 + 1) * 64 * 8 * sizeof(float), st) != hipSuccess) return HCF_ERR_HIP;
+  rc = launch_repack_conv(r, st);
+  if (rc != HCF_OK) return rc;
+  ConvArgs a;
+  memset(&a, 0, sizeof(a));
+  a.src[0] = mkview(const_cast<float*>(x), cin, 0, cin);
+  a.src[1] = a.src[2] = a.src[0];
+  a.nsrc = 1; a.B = N; a.H = H; a.W = W;
+  a.wpack = r.pk; a.nchunk = r.nchunk; a.bias = bvec; a.scale = svec; a.act = ACT_RELU;
+  a.out = mkview(y, cs_out, oc0, 64);
+  a.res1 = mkview(nullptr, 0, 0, 0);
+  a.res2 = mkview(nullptr, 0, 0, 0);
+  return launch_conv(a, 25, st);
+}
+
+static int lpips_pool(const float* in, int N, int Hst, int Wst, int C, int Ho, int Wo, float* out, hipStream_t st) {
+  unsigned g;
+  if (lpips_grid((long long)N * Ho * Wo * (C / 4), &g) != HCF_OK) return HCF_ERR_ARG;
+  hipLaunchKernelGGL(lpips_maxpool_kernel, dim3(g), dim3(256), 0, st, in, N, Hst, Wst, C, Ho, Wo, out);
+  return hipGetLastError() == hipSuccess ? HCF_OK : HCF_ERR_HIP;
+}
+
+}  // namespace hcf
+
+using namespace hcf;
+
+extern "C" {
+
+size_t hcf_lpips_workspace(int32_t B, int32_t H, int32_t W) {
+  LpipsPlan p;
+  return lpips_plan(B, H, W, p) ? p.total : 0;
+}
+
+int hcf_lpips_alex(const float* in0, const float* in1, int32_t B, int32_t H, int32_t W, int32_t normalize,
+                   const float* const* params, float* out, float* out_layers, void* work, size_t work_bytes,
+                   hcf_stream_t stream) {
+  if (!in0 || !in1 || !params || !out || !work) return HCF_ERR_ARG;
+  for (int i = 0; i < HCF_LPIPS_NPARAMS; ++i)
+    if (!params[i]) return HCF_ERR_ARG;
+  LpipsPlan p;
+  if (!lpips_plan(B, H, W, p)) return HCF_ERR_SHAPE;
+  if (work_bytes < p.total) return HCF_ERR_NOMEM;
+  hipStream_t st = (hipStream_t)stream;
+  char* wk = (char*)work;
+  const int N = 2 * B;
+  float *s2d = (float*)(wk + p.o_s2d), *f1 = (float*)(wk + p.o_f1), *p1 = (float*)(wk + p.o_p1), *f2 = (float*)(wk + p.o_f2);
+  float *p2 = (float*)(wk + p.o_p2), *f3 = (float*)(wk + p.o_f3), *f4 = (float*)(wk + p.o_f4), *f5 = (float*)(wk + p.o_f5);
+  const float *shift = params[0], *scale = params[1];
+  const float* cw[kLpipsLayers] = {params[2], params[4], params[6], params[8], params[10]};
+  const float* cb[kLpipsLayers] = {params[3], params[5], params[7], params[9], params[11]};
+
+  unsigned g;
+  if (lpips_grid((long long)N * p.Hs * p.Ws * 12, &g) != HCF_OK) return HCF_ERR_ARG;
+  hipLaunchKernelGGL(lpips_prep_kernel, dim3(g), dim3(256), 0, st, in0, in1, B, H, W, p.Hs, p.Ws, normalize, shift, scale, s2d);
+  if (hipGetLastError() != hipSuccess) return HCF_ERR_HIP;
+  int rc = lpips_conv5(s2d, 48, N, p.Hs, p.Ws, cw[0], cb[0], f1, 64, 0, wk, p, st);
+  if (rc == HCF_OK) rc = lpips_pool(f1, N, p.Hs, p.Ws, 64, p.H2, p.W2, p1, st);
+  for (int oc0 = 0; oc0 < 192 && rc == HCF_OK; oc0 += 64) rc = lpips_conv5(p1, 64, N, p.H2, p.W2, cw[1], cb[1], f2, 192, oc0, wk, p, st);
+  if (rc == HCF_OK) rc = lpips_pool(f2, N, p.H2, p.W2, 192, p.H3, p.W3, p2, st);
+  if (rc != HCF_OK) return rc;
+  void* aux = wk + p.o_aux;
+  if (hipMemsetAsync(aux, 0, 256, st) != hipSuccess) return HCF_ERR_HIP;          // hcf_aux_conv2d's flag + zero page
+  const float* xin[3] = {p2, f3, f4};
+  float* yout[3] = {f3, f4, f5};
+  for (int l = 2; l < kLpipsLayers && rc == HCF_OK; ++l)
+    rc = hcf_aux_conv2d(xin[l - 2], kAlexC[l - 1], kAlexC[l - 1], N, p.H3, p.W3, cw[l], cb[l], kAlexC[l], 3, ACT_RELU,
+                        yout[l - 2], kAlexC[l], aux, p.aux_bytes, HCF_PRECISION_EXACT, stream);
+  if (rc != HCF_OK) return rc;
+
+  LpipsHeadArgs h;
+  memset(&h, 0, sizeof(h));
+  const float* feat[kLpipsLayers] = {f1, f2, f3, f4, f5};
+  const int hst[kLpipsLayers] = {p.Hs, p.H2, p.H3, p.H3, p.H3}, wst[kLpipsLayers] = {p.Ws, p.W2, p.W3, p.W3, p.W3};
+  const int hh[kLpipsLayers] = {p.H1, p.H2, p.H3, p.H3, p.H3}, ww[kLpipsLayers] = {p.W1, p.W2, p.W3, p.W3, p.W3};
+  LpipsFinalArgs fa;
+  memset(&fa, 0, sizeof(fa));
+  for (int l = 0; l < kLpipsLayers; ++l) {
+    h.L[l].f = feat[l]; h.L[l].C = kAlexC[l]; h.L[l].Hst = hst[l]; h.L[l].Wst = wst[l]; h.L[l].h = hh[l]; h.L[l].w = ww[l];
+    h.L[l].chunk0 = p.chunk0[l];
+    h.L[l].lin = params[12 + l];
+    fa.chunk0[l] = p.chunk0[l]; fa.nchunk[l] = p.nchunk[l]; fa.hw[l] = hh[l] * ww[l];
+  }
+  h.B = B; h.nchunk_total = p.nchunk_total; h.part = (float*)(wk + p.o_part);
+  hipLaunchKernelGGL(lpips_head_kernel, dim3((unsigned)p.nchunk_total, (unsigned)B), dim3(256), 0, st, h);
+  if (hipGetLastError() != hipSuccess) return HCF_ERR_HIP;
+  fa.nchunk_total = p.nchunk_total; fa.part = h.part; fa.out = out; fa.out_layers = out_layers;
+  hipLaunchKernelGGL(lpips_final_kernel, dim3((unsigned)B), dim3(64), 0, st, fa);
+  return hipGetLastError() == hipSuccess ? HCF_OK : HCF_ERR_HIP;
+}
+
+}  // extern "C"

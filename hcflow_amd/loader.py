@@ -12,8 +12,8 @@ image, B = 16: 8.6 ms per image). This module is the drop-in for those two piece
 * ``evaluate_batch(net, batch, heats, n_sample, scale, crop_border)`` runs what ``HCFlowSRModel.test()`` runs
   (``HCFlow_SR_model.py:281-301``: NLL pass + one sampling pass per heat and sample) on the whole batch and computes the log
   line's numbers per image on the device (hcflow_amd/metrics.py: PSNR / SSIM / PSNR_Y / SSIM_Y of SR vs GT with the border
-  crop, the same on the bicubic down-scaled pair, LR consistency, sample diversity). LPIPS needs the AlexNet weights the
-  ``lpips`` package downloads and is not computed (``lpips`` is absent from this image).
+  crop, the same on the bicubic down-scaled pair, LR consistency, sample diversity). LPIPS is computed when an ``lpips_fn`` is
+  passed, e.g. ``hcflow_amd.lpips.LPIPS(...).cuda()`` (AlexNet v0.1 on the HIP kernels, weights from local files).
 
 The numbers per image are identical to feeding the images one at a time (every op of the path is per sample)."""
 from __future__ import annotations

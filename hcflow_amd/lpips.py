@@ -1,0 +1,205 @@
+"""LPIPS v0.1 with AlexNet on the MI355X kernels: the LPIPS column of the reference's test log.
+
+``test_HCFlow.py:48`` builds ``loss_fn_alex = lpips.LPIPS(net='alex')`` and ``:132-133`` evaluates it on
+``(2 * gt - 1, 2 * sr - 1)``. ``LPIPS`` here is a drop-in for ``lpips.LPIPS(net='alex')`` (version 0.1, ``lpips=True``,
+``spatial=False``) that runs the whole network as ONE call of the C ABI (``hcf_lpips_alex`` in ``include/hcflow.h``,
+``csrc/hcf_lpips.hip``), exact fp32 throughout. The math, for inputs x0, x1 in [-1, 1] (``normalize=True``: in [0, 1], mapped by
+2x - 1 first):
+
+* scaling layer: ``x' = (x - shift) / scale``, shift ``[-.030, -.088, -.188]``, scale ``[.458, .448, .450]``, applied before
+  conv1's zero padding;
+* AlexNet features ``relu_l``, l = 1..5 (the ReLU output after each conv):
+  conv1 3 -> 64, 11x11, stride 4, pad 2; MaxPool 3 / 2; conv2 64 -> 192, 5x5, pad 2; MaxPool 3 / 2;
+  conv3 192 -> 384, 3x3, pad 1; conv4 384 -> 256, 3x3, pad 1; conv5 256 -> 256, 3x3, pad 1;
+* per layer: unit-normalise every pixel over channels, ``f / (sqrt(sum_c f^2) + 1e-10)``, square the difference of the two
+  normalised maps, apply the 1x1 linear head ``lin_l`` (no bias), average over space;
+* ``d(x0, x1) = sum_l`` of the five layer terms, returned as ``[B, 1, 1, 1]`` fp32 (``retPerLayer=True``: also the list of
+  the five ``[B, 1, 1, 1]`` terms).
+
+conv1 runs as a 5x5 stride-1 conv on the 4x4 space-to-depth grid of the scaled image (``alex_conv1_as_s2d`` re-indexes the
+weight); H, W >= 31 is AlexNet's minimum (conv1 gives >= 7 rows, pool1 >= 3, pool2 >= 1).
+
+``state_dict()`` has the keys and shapes of ``lpips.LPIPS(net='alex')``: ``scaling_layer.shift / scale``,
+``net.slice{1..5}.{0,3,6,8,10}.weight / bias``, ``lin{0..4}.model.1.weight`` ``[1, C, 1, 1]``; ``lins.K.*`` aliases (the
+``ModuleList`` lpips also registers) are accepted on load. ``load_pretrained(tv_alexnet, lpips_lin)`` fills the module from the
+two files users keep offline: torchvision's AlexNet state dict (``features.{0,3,6,8,10}.*``, ``alexnet-owt-7be5be79.pth``) and
+lpips' ``weights/v0.1/alex.pth``. Nothing is ever downloaded: without weights the parameters are seeded random.
+
+No CPU fallback (off-GPU inputs raise ``HcfError``) and no backward (inputs that require grad raise). The call runs on the
+current stream without host synchronisation, is bit-reproducible, and an image's value does not depend on the rest of the batch.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Mapping, Optional, Union
+
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from . import _lib
+
+ALEX_CHANNELS = (64, 192, 384, 256, 256)
+ALEX_CONV_INDEX = (0, 3, 6, 8, 10)          # torchvision alexnet().features indices of the five convs
+MIN_SIDE = 31
+
+
+def alex_conv1_as_s2d(w: torch.Tensor) -> torch.Tensor:
+    """AlexNet conv1 weight [O, C, 11, 11] (stride 4, pad 2) -> the 5x5 stride-1 pad-2 weight [O, 16 C, 5, 5] acting on the 4x4
+    space-to-depth grid (channel c * 16 + a * 4 + b holds input row 4Y + a, column 4X + b; zero padded to a multiple of 4).
+    Output row y reads input rows 4y - 2 + i, i = 0..10: tap i sits on s2d row y + (i - 2) div 4, sub-row (i - 2) mod 4, i.e.
+    j = i + 2 = 4 (dY + 1) + a with dY in -1..2; the 5x5 offset -2 is unused (zero). Same for columns. Exact, differentiable."""
+    O, Cc = w.shape[0], w.shape[1]
+    assert w.shape[2:] == (11, 11)
+    wp = F.pad(w, (2, 3, 2, 3))                                   # j = i + 2 over [0, 16)
+    wp = wp.reshape(O, Cc, 4, 4, 4, 4).permute(0, 1, 3, 5, 2, 4)  # [O, C, a, b, dY + 1, dX + 1]
+    return F.pad(wp.reshape(O, Cc * 16, 4, 4), (1, 0, 1, 0))      # offsets -2..2 -> 5 taps
+
+
+class ScalingLayer(nn.Module):
+    def __init__(self):
+        super().__init__()
+        self.register_buffer("shift", torch.Tensor([-.030, -.088, -.188])[None, :, None, None])
+        self.register_buffer("scale", torch.Tensor([.458, .448, .450])[None, :, None, None])
+
+
+class NetLinLayer(nn.Module):
+    """lpips' 1x1 linear head (dropout in front, as ``use_dropout=True``; the dropout is inert in eval and in this module)."""
+
+    def __init__(self, chn_in: int):
+        super().__init__()
+        self.model = nn.Sequential(nn.Dropout(), nn.Conv2d(chn_in, 1, 1, stride=1, padding=0, bias=False))
+
+
+class AlexNetSlices(nn.Module):
+    """lpips.pretrained_networks.alexnet's module tree: torchvision's ``features`` split after each ReLU, global indices kept."""
+
+    def __init__(self):
+        super().__init__()
+        feats = [nn.Conv2d(3, 64, 11, 4, 2), nn.ReLU(inplace=True), nn.MaxPool2d(3, 2),
+                 nn.Conv2d(64, 192, 5, padding=2), nn.ReLU(inplace=True), nn.MaxPool2d(3, 2),
+                 nn.Conv2d(192, 384, 3, padding=1), nn.ReLU(inplace=True),
+                 nn.Conv2d(384, 256, 3, padding=1), nn.ReLU(inplace=True),
+                 nn.Conv2d(256, 256, 3, padding=1), nn.ReLU(inplace=True)]
+        bounds = ((0, 2), (2, 5), (5, 8), (8, 10), (10, 12))
+        for s, (lo, hi) in enumerate(bounds, start=1):
+            sl = nn.Sequential()
+            for x in range(lo, hi):
+                sl.add_module(str(x), feats[x])
+            setattr(self, "slice%d" % s, sl)
+        self.N_slices = 5
+
+    def convs(self):
+        return [getattr(getattr(self, "slice%d" % (s + 1)), str(i)) for s, i in enumerate(ALEX_CONV_INDEX)]
+
+
+class LPIPS(nn.Module):
+    """Drop-in for ``lpips.LPIPS(net='alex')`` (v0.1) on the MI355X kernels. ``pnet_path`` / ``model_path``: local files of
+    torchvision's AlexNet state dict and lpips' ``alex.pth`` (either may be omitted: those parameters stay seeded random)."""
+
+    def __init__(self, pretrained: bool = True, net: str = "alex", version: str = "0.1", lpips: bool = True,
+                 spatial: bool = False, pnet_rand: bool = False, pnet_tune: bool = False, use_dropout: bool = True,
+                 model_path: Optional[str] = None, eval_mode: bool = True, verbose: bool = False,
+                 pnet_path: Optional[str] = None, seed: int = 0):
+        super().__init__()
+        if net != "alex" or version != "0.1" or not lpips or spatial:
+            raise _lib.HcfError("hcflow_amd.lpips implements LPIPS v0.1 with AlexNet, lpips=True, spatial=False only")
+        self.pnet_type, self.version, self.lpips, self.spatial = net, version, lpips, spatial
+        self.scaling_layer = ScalingLayer()
+        with torch.random.fork_rng(devices=[]):
+            torch.manual_seed(seed)
+            self.net = AlexNetSlices()
+            for l, c in enumerate(ALEX_CHANNELS):
+                lin = NetLinLayer(c)
+                with torch.no_grad():                                   # trained heads are non-negative
+                    lin.model[1].weight.uniform_(0.0, 2.0 / c)
+                setattr(self, "lin%d" % l, lin)
+        self.L = 5
+        for p in self.parameters():
+            p.requires_grad = False
+        self._register_load_state_dict_pre_hook(self._lins_alias)
+        self._s2d_cache = None
+        if pnet_path is not None or (pretrained and model_path is not None):
+            self.load_pretrained(pnet_path, model_path if pretrained else None)
+        if eval_mode:
+            self.eval()
+
+    @staticmethod
+    def _lins_alias(state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs):
+        for k in [k for k in state_dict if k.startswith(prefix + "lins.")]:
+            rest = k[len(prefix) + 5:]
+            idx, tail = rest.split(".", 1)
+            v = state_dict.pop(k)
+            state_dict.setdefault("%slin%s.%s" % (prefix, idx, tail), v)
+
+    def load_pretrained(self, tv_alexnet: Union[None, str, Mapping[str, torch.Tensor]] = None,
+                        lpips_lin: Union[None, str, Mapping[str, torch.Tensor]] = None):
+        """Copy torchvision's AlexNet weights (``features.{0,3,6,8,10}.weight / bias``; the classifier is ignored) and lpips'
+        linear heads (``lin{0..4}.model.1.weight`` or ``lins.K.``) into this module. Paths are read with ``torch.load``."""
+        def _get(src):
+            return torch.load(src, map_location="cpu") if isinstance(src, str) else src
+
+        sd = {}
+        tv = _get(tv_alexnet)
+        if tv is not None:
+            for s, i in enumerate(ALEX_CONV_INDEX, start=1):
+                for kind in ("weight", "bias"):
+                    sd["net.slice%d.%d.%s" % (s, i, kind)] = tv["features.%d.%s" % (i, kind)]
+        lin = _get(lpips_lin)
+        if lin is not None:
+            for l in range(5):
+                k = "lin%d.model.1.weight" % l
+                sd[k] = lin[k] if k in lin else lin["lins.%d.model.1.weight" % l]
+        own = self.state_dict()
+        for k, v in sd.items():
+            if tuple(v.shape) != tuple(own[k].shape):
+                raise _lib.HcfError("%s: shape %s, expected %s" % (k, tuple(v.shape), tuple(own[k].shape)))
+        self.load_state_dict(sd, strict=False)
+        return self
+
+    def _params(self):
+        convs = self.net.convs()
+        w1 = convs[0].weight
+        key = (w1.data_ptr(), w1._version, w1.device)
+        if self._s2d_cache is None or self._s2d_cache[0] != key:
+            self._s2d_cache = (key, alex_conv1_as_s2d(w1.detach().float()).contiguous())
+        ts = [self.scaling_layer.shift, self.scaling_layer.scale, self._s2d_cache[1], convs[0].bias]
+        for c in convs[1:]:
+            ts += [c.weight, c.bias]
+        ts += [getattr(self, "lin%d" % l).model[1].weight for l in range(5)]
+        return [t.detach().float().contiguous() for t in ts]
+
+    def forward(self, in0: torch.Tensor, in1: torch.Tensor, retPerLayer: bool = False, normalize: bool = False):
+        if not (in0.is_cuda and in1.is_cuda):
+            raise _lib.HcfError("hcflow_amd.lpips runs on MI355X only (no CPU fallback): move the module and its inputs to a GPU")
+        if in0.requires_grad or in1.requires_grad:
+            raise _lib.HcfError("hcflow_amd.lpips.LPIPS has no backward pass: call it on detached inputs (e.g. under torch.no_grad())")
+        if in0.dim() != 4 or in0.shape[1] != 3 or in0.shape != in1.shape:
+            raise _lib.HcfError("LPIPS expects two [B,3,H,W] tensors of the same shape, got %s and %s"
+                                % (tuple(in0.shape), tuple(in1.shape)))
+        B, _, H, W = in0.shape
+        if H < MIN_SIDE or W < MIN_SIDE:
+            raise _lib.HcfError("LPIPS (AlexNet) needs H, W >= %d, got %dx%d" % (MIN_SIDE, H, W))
+        dev = in0.device
+        if in1.device != dev:
+            raise _lib.HcfError("in0 and in1 are on different devices")
+        params = self._params()
+        if any(t.device != dev for t in params):
+            raise _lib.HcfError("the LPIPS module's parameters are not on %s: call .to(%s) first" % (dev, dev))
+        x0 = in0.to(torch.float32).contiguous()
+        x1 = in1.to(torch.float32).contiguous()
+        lib = _lib.load()
+        need = lib.hcf_lpips_workspace(B, H, W)
+        work = torch.empty(need, dtype=torch.uint8, device=dev)       # stream-ordered reuse by the caching allocator
+        out = torch.empty(B, dtype=torch.float32, device=dev)
+        layers = torch.empty(B, 5, dtype=torch.float32, device=dev) if retPerLayer else None
+        ptrs = (C.c_void_p * len(params))(*[t.data_ptr() for t in params])
+        with torch.cuda.device(dev):
+            rc = lib.hcf_lpips_alex(x0.data_ptr(), x1.data_ptr(), B, H, W, int(bool(normalize)), ptrs, out.data_ptr(),
+                                    None if layers is None else layers.data_ptr(), C.c_void_p(work.data_ptr()), need,
+                                    C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+        _lib.check(rc, None, "hcf_lpips_alex")
+        val = out.view(B, 1, 1, 1)
+        if retPerLayer:
+            return val, [layers[:, l].reshape(B, 1, 1, 1) for l in range(5)]
+        return val

@@ -336,6 +336,23 @@ int hcf_aux_conv2d_backward(const float* x, int32_t cs_in, int32_t cin, int32_t 
                             int32_t cout, int32_t k, const float* g, int32_t cs_g, float* dx, int32_t cs_dx, float* dw,
                             void* work, size_t work_bytes, int32_t precision, hcf_stream_t stream);
 
+/* ---- LPIPS v0.1, AlexNet (the LPIPS column of the reference's test log: test_HCFlow.py:48 builds lpips.LPIPS(net='alex'),
+ * :132 evaluates it on (2 gt - 1, 2 sr - 1)); hcflow_amd/lpips.py is the module around it. One call runs the whole network on
+ * both inputs and the LPIPS head, in exact fp32 (fp32 MFMA), on `stream`, without host synchronisation; the result for an image
+ * depends on that image pair only and is bit-reproducible.
+ *   in0, in1: device [B,3,H,W] fp32 NCHW, in [-1, 1] (normalize != 0: in [0, 1], mapped by 2x - 1); H, W >= 31
+ *   params:   HOST array of HCF_LPIPS_NPARAMS device pointers, PyTorch layouts: shift[3], scale[3], conv1 weight re-indexed
+ *             to the 5x5 conv on the 4x4 space-to-depth grid [64][48][5][5] (hcflow_amd/lpips.py: alex_conv1_as_s2d), conv1
+ *             bias[64], conv2 w[192][64][5][5] / b, conv3 w[384][192][3][3] / b, conv4 w[256][384][3][3] / b,
+ *             conv5 w[256][256][3][3] / b, then the five linear heads lin0..lin4 ([C_l] each)
+ *   out:      device [B] = LPIPS per image pair;  out_layers: device [B][5] per-layer terms, or NULL
+ *   work:     device scratch of hcf_lpips_workspace(B, H, W) bytes (0: shape below AlexNet's minimum) */
+#define HCF_LPIPS_NPARAMS 17
+size_t hcf_lpips_workspace(int32_t B, int32_t H, int32_t W);
+int hcf_lpips_alex(const float* in0, const float* in1, int32_t B, int32_t H, int32_t W, int32_t normalize,
+                   const float* const* params, float* out, float* out_layers, void* work, size_t work_bytes,
+                   hcf_stream_t stream);
+
 /* Range-headroom probe of the f16x3 path (tools/range_headroom.py): while enabled, every conv launch of the following passes
  * also records max |x| over its input windows and -- for layers that own a Winograd pack -- max |B^T d B| over the F(2x2,3x3)
  * input patches, i.e. the values the split has to represent (f16 limit 65504). hcf_debug_range_probe_read returns record
