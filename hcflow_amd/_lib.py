@@ -35,6 +35,7 @@ SYMBOLS = [
     "hcf_debug_range_probe", "hcf_debug_range_probe_read",
     "hcf_aux_conv2d_workspace", "hcf_aux_conv2d", "hcf_aux_conv2d_backward", "hcf_adam_step",
     "hcf_lpips_workspace", "hcf_lpips_alex",
+    "hcf_aux_bn_act_workspace", "hcf_aux_bn_act", "hcf_aux_bn_act_backward",
 ]
 
 
@@ -114,6 +115,12 @@ def load() -> C.CDLL:
     lib.hcf_aux_conv2d_workspace.restype = C.c_size_t
     lib.hcf_aux_conv2d.argtypes = [fp, i32, i32, i32, i32, i32, fp, fp, i32, i32, i32, fp, i32, vp, C.c_size_t, i32, vp]
     lib.hcf_aux_conv2d_backward.argtypes = [fp, i32, i32, i32, i32, i32, fp, i32, i32, fp, i32, fp, i32, fp, vp, C.c_size_t, i32, vp]
+    lib.hcf_aux_bn_act_workspace.argtypes = [i32, i32, i32, i32]
+    lib.hcf_aux_bn_act_workspace.restype = C.c_size_t
+    lib.hcf_aux_bn_act.argtypes = [fp, i32, i32, i32, i32, i32, i32, i32, i32, i32, fp, fp, fp, fp, i32, C.c_double, C.c_double,
+                                   i32, fp, i32, fp, fp, vp, C.c_size_t, vp]
+    lib.hcf_aux_bn_act_backward.argtypes = [fp, i32, i32, i32, i32, i32, i32, i32, i32, i32, fp, fp, fp, fp, i32, i32, fp, i32, fp,
+                                            i32, fp, fp, vp, C.c_size_t, vp]
     lib.hcf_lpips_workspace.argtypes = [i32, i32, i32]
     lib.hcf_lpips_workspace.restype = C.c_size_t
     lib.hcf_lpips_alex.argtypes = [fp, fp, i32, i32, i32, i32, C.POINTER(fp), fp, fp, vp, C.c_size_t, vp]
@@ -140,7 +147,8 @@ def load() -> C.CDLL:
     for name in SYMBOLS:
         fn = getattr(lib, name)
         if name not in ("hcf_destroy", "hcf_last_error", "hcf_workspace_bytes", "hcf_weight_bytes",
-                        "hcf_fallback_count", "hcf_debug_last_clock_mhz", "hcf_aux_conv2d_workspace", "hcf_lpips_workspace"):
+                        "hcf_fallback_count", "hcf_debug_last_clock_mhz", "hcf_aux_conv2d_workspace", "hcf_lpips_workspace",
+                        "hcf_aux_bn_act_workspace"):
             fn.restype = C.c_int
     _lib = lib
     return lib

@@ -1,7 +1,8 @@
 """The auxiliary nets of the HCFlow+ / HCFlow++ recipes on the MI355X conv kernels.
 
 ``HCFlow_SR_model.py:75-95`` builds, beside netG, a VGG19 feature extractor (``networks.define_F`` -> ``VGGFeatureExtractor``,
-``discriminator_vgg_arch.py:110-137``) for the perceptual loss and a ``Discriminator_VGG_160`` (``:68-107``) trained with the
+``discriminator_vgg_arch.py:110-137``) for the perceptual loss and a ``Discriminator_VGG_160`` (``:68-107``; ``networks.define_D``
+also builds ``Discriminator_VGG_128`` and ``PatchGANDiscriminator``, ``networks.py:44-56``) trained with the
 reference's own ``GANLoss`` (``loss.py:19-51``: stock PyTorch criteria, no kernel behind it -- it stays the reference's file and is
 not restated here); ``optimize_parameters`` (``HCFlow_SR_model.py:219-285``) runs them forward and backward every
 step on ``fake_H`` / ``real_H`` batches. The classes here keep the reference's constructor signatures, ``state_dict`` keys /
@@ -14,8 +15,12 @@ f16x3 / Winograd forward, fp32-MFMA data gradient, fixed-order weight gradient):
 * the discriminator's 4x4 stride-2 convs are a ``squeeze2d`` (space-to-depth) followed by a 3x3 conv on 4C channels whose
   weight is the 4x4 kernel re-indexed (``_w4s2_as_3x3``; exact, differentiable);
 * bias + LeakyReLU / ReLU are fused into the conv epilogue where no BatchNorm sits in between;
-* BatchNorm (batch statistics in train(), running statistics in eval()), the two Linear layers, max-pooling and the losses
-  are a few elementwise / reduction ops per layer and stay on stock PyTorch ops.
+* ``Discriminator_VGG_128`` and ``PatchGANDiscriminator`` (``:6-65``, ``:159-189``) run every BatchNorm + LeakyReLU through the
+  fused NHWC kernels ``hcf_aux_bn_act`` / ``hcf_aux_bn_act_backward`` (batch statistics in train(), running statistics in
+  eval(), the module's own buffers updated on the device); PatchGAN's padding-0 convs are the interior window of the
+  same-padded conv, which those kernels read (forward) and zero-border (backward);
+* in ``Discriminator_VGG_160`` and ``VGGFeatureExtractor``, BatchNorm stays on stock PyTorch ops; the Linear layers,
+  max-pooling and the losses are a few elementwise / reduction ops per layer and stay on stock PyTorch ops everywhere.
 
 ``VGGFeatureExtractor`` needs torchvision's pretrained VGG19 weights, which cannot be downloaded here: the layer stack is
 rebuilt from the VGG19 configuration with the same ``features.N`` keys, so a torchvision ``vgg19().features`` state dict loads
@@ -125,6 +130,104 @@ class _ConvNHWC(torch.autograd.Function):
         return dx, dw, db, None, None, None, None
 
 
+_BN_NONE, _BN_TRAIN, _BN_EVAL = 0, 1, 2
+
+
+def _interior(y: torch.Tensor):
+    """The window (y0, x0, Ho, Wo) of a same-padded 3x3 conv's output [B,H,W,c] that equals the padding-0 conv's output."""
+    return (1, 1, y.shape[1] - 2, y.shape[2] - 2)
+
+
+def _bn_workspace(work, x, need):
+    # one scratch per device and stream: calls on a stream run in order, and nothing in it outlives a call
+    key = ("bn", x.device.index, torch.cuda.current_stream(x.device).cuda_stream)
+    wk = work.get(key)
+    if wk is None or wk.numel() < need:
+        wk = torch.empty(max(need, 256), dtype=torch.uint8, device=x.device)
+        work[key] = wk
+    return wk
+
+
+class _BnActNHWC(torch.autograd.Function):
+    """y = act(BatchNorm2d(x[:, y0:y0+Ho, x0:x0+Wo, :C])) as a compact NHWC [B,Ho,Wo,roundup4(C)] device tensor through the C ABI
+    (hcf_aux_bn_act); bn None: the window and the activation only. act in {0 none, 1 relu, 2 lrelu 0.2}. train() mode (or no
+    running statistics) normalises with the batch statistics and moves bn's running_mean / running_var in place on the device;
+    the backward pass returns dx over the whole H x W input with a zero border."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, bn, Cc, window, act, work):
+        if not x.is_cuda:
+            raise _lib.HcfError("hcflow_amd.gan runs on MI355X only (no CPU fallback): move the module and its inputs to a GPU")
+        lib = _lib.load()
+        B, H, W, cs = x.shape
+        y0, x0, Ho, Wo = window
+        assert cs % 4 == 0 and cs >= Cc and x.is_contiguous() and x.dtype == torch.float32
+        stream = torch.cuda.current_stream(x.device).cuda_stream
+        y = torch.empty(B, Ho, Wo, (Cc + 3) & ~3, device=x.device, dtype=torch.float32)
+        smean = sinv = rmean = rvar = wk = None
+        momentum, eps = 0.0, 1e-5
+        if bn is None:
+            mode = _BN_NONE
+        else:
+            eps = float(bn.eps)
+            tracked = bn.track_running_stats and bn.running_mean is not None
+            mode = _BN_TRAIN if (bn.training or not tracked) else _BN_EVAL
+            if tracked:
+                rmean, rvar = bn.running_mean, bn.running_var
+                assert rmean.is_contiguous() and rvar.is_contiguous() and rmean.dtype == torch.float32
+            if mode == _BN_TRAIN:
+                if B * Ho * Wo < 2:
+                    raise ValueError("Expected more than 1 value per channel when training, got input size %r"
+                                     % ([B, Cc, Ho, Wo],))
+                momentum = 0.0 if bn.momentum is None else float(bn.momentum)
+                if bn.training and tracked:
+                    with torch.no_grad():
+                        bn.num_batches_tracked.add_(1)
+                    if bn.momentum is None:                  # cumulative moving average (nn.BatchNorm2d)
+                        momentum = 1.0 / float(bn.num_batches_tracked)
+                else:
+                    rmean = rvar = None                       # batch statistics without running statistics to move
+                wk = _bn_workspace(work, x, lib.hcf_aux_bn_act_workspace(Cc, B, Ho, Wo))
+            smean = torch.empty(Cc, device=x.device, dtype=torch.float32)
+            sinv = torch.empty(Cc, device=x.device, dtype=torch.float32)
+            gamma, beta = gamma.contiguous(), beta.contiguous()
+        ptr = lambda t: None if t is None else t.data_ptr()
+        with torch.cuda.device(x.device):
+            rc = lib.hcf_aux_bn_act(x.data_ptr(), cs, Cc, B, H, W, y0, x0, Ho, Wo, ptr(gamma), ptr(beta), ptr(rmean), ptr(rvar),
+                                    mode, momentum, eps, act, y.data_ptr(), y.shape[3], ptr(smean), ptr(sinv),
+                                    None if wk is None else C.c_void_p(wk.data_ptr()), 0 if wk is None else wk.numel(),
+                                    C.c_void_p(stream))
+        _lib.check(rc, None, "hcf_aux_bn_act")
+        ctx.save_for_backward(x, gamma, beta, smean, sinv)
+        ctx.meta = (Cc, window, act, mode, work)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        lib = _lib.load()
+        x, gamma, beta, smean, sinv = ctx.saved_tensors
+        Cc, (y0, x0, Ho, Wo), act, mode, work = ctx.meta
+        B, H, W, cs = x.shape
+        g = g.contiguous()
+        dx = torch.empty_like(x)                              # every element written, the border and the padding channels as 0
+        need_p = mode != _BN_NONE and (ctx.needs_input_grad[1] or ctx.needs_input_grad[2])
+        dgamma = torch.empty_like(gamma) if need_p else None  # frozen parameters (netD during the G step): skipped
+        dbeta = torch.empty_like(beta) if need_p else None
+        wk = None
+        if mode == _BN_TRAIN or need_p:
+            wk = _bn_workspace(work, x, lib.hcf_aux_bn_act_workspace(Cc, B, Ho, Wo))
+        ptr = lambda t: None if t is None else t.data_ptr()
+        with torch.cuda.device(x.device):
+            rc = lib.hcf_aux_bn_act_backward(x.data_ptr(), cs, Cc, B, H, W, y0, x0, Ho, Wo, ptr(gamma), ptr(beta), ptr(smean),
+                                             ptr(sinv), mode, act, g.data_ptr(), g.shape[3], dx.data_ptr(), cs, ptr(dgamma),
+                                             ptr(dbeta), None if wk is None else C.c_void_p(wk.data_ptr()),
+                                             0 if wk is None else wk.numel(),
+                                             C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream))
+        _lib.check(rc, None, "hcf_aux_bn_act_backward")
+        return (dx, dgamma if ctx.needs_input_grad[1] else None, dbeta if ctx.needs_input_grad[2] else None,
+                None, None, None, None, None)
+
+
 class _AuxNet(nn.Module):
     """Shared plumbing: precision policy and the per-layer workspaces."""
 
@@ -145,6 +248,13 @@ class _AuxNet(nn.Module):
             x = squeeze2d_nhwc(x)
             w = _w4s2_as_3x3(w)
         return _ConvNHWC.apply(x, w, conv.bias, act, prec, self._work, flags)
+
+    def _bn_act(self, y, bn: Optional[nn.BatchNorm2d], Cc: int, window=None, act: int = 2):
+        """act(bn(window of y)) on the fused kernels (bn None: window + act only); window None: the whole of y."""
+        win = (0, 0, y.shape[1], y.shape[2]) if window is None else window
+        if bn is None:
+            return _BnActNHWC.apply(y, None, None, None, Cc, win, act, self._work)
+        return _BnActNHWC.apply(y, bn.weight, bn.bias, bn, Cc, win, act, self._work)
 
     def _run(self, body, x):
         prec = _PREC[self._prec[0]]
@@ -168,6 +278,48 @@ class _AuxNet(nn.Module):
                         m.num_batches_tracked.copy_(cnt)
                 out = body(x, [], 0)
         return out
+
+
+class Discriminator_VGG_128(_AuxNet):
+    """Drop-in for discriminator_vgg_arch.Discriminator_VGG_128 (:6-65): same modules / state_dict (128 x 128 input,
+    ``linear1`` on 512 * 4 * 4 features); convs on our conv kernels, every BatchNorm + LeakyReLU on the fused BN kernels."""
+
+    def __init__(self, in_nc, nf):
+        super().__init__()
+        self.conv0_0 = nn.Conv2d(in_nc, nf, 3, 1, 1, bias=True)
+        self.conv0_1 = nn.Conv2d(nf, nf, 4, 2, 1, bias=False)
+        self.bn0_1 = nn.BatchNorm2d(nf, affine=True)
+        chans = [(nf, nf * 2), (nf * 2, nf * 4), (nf * 4, nf * 8), (nf * 8, nf * 8)]
+        for i, (ci, co) in enumerate(chans, start=1):
+            setattr(self, "conv%d_0" % i, nn.Conv2d(ci, co, 3, 1, 1, bias=False))
+            setattr(self, "bn%d_0" % i, nn.BatchNorm2d(co, affine=True))
+            setattr(self, "conv%d_1" % i, nn.Conv2d(co, co, 4, 2, 1, bias=False))
+            setattr(self, "bn%d_1" % i, nn.BatchNorm2d(co, affine=True))
+        self.linear1 = nn.Linear(512 * 4 * 4, 100)
+        self.linear2 = nn.Linear(100, 1)
+        self.lrelu = nn.LeakyReLU(negative_slope=0.2, inplace=True)
+        self._aux_init()
+
+    def _conv_bn(self, fea, conv, bn, flags, prec):
+        return self._bn_act(self._conv(fea, conv, 0, flags, prec), bn, bn.num_features)
+
+    def _body(self, x, flags, prec):
+        fea = self._conv(_nhwc(x), self.conv0_0, 2, flags, prec)                       # bias + LeakyReLU fused
+        fea = self._conv_bn(fea, self.conv0_1, self.bn0_1, flags, prec)
+        for i in range(1, 5):
+            fea = self._conv_bn(fea, getattr(self, "conv%d_0" % i), getattr(self, "bn%d_0" % i), flags, prec)
+            fea = self._conv_bn(fea, getattr(self, "conv%d_1" % i), getattr(self, "bn%d_1" % i), flags, prec)
+        fea = fea.permute(0, 3, 1, 2).reshape(fea.size(0), -1)                         # the reference flattens NCHW
+        fea = self.lrelu(self.linear1(fea))
+        return self.linear2(fea)
+
+    def forward(self, x):
+        return self._run(self._body, x)
+
+    def reset_parameters(self):
+        for layer in self.children():
+            if hasattr(layer, "reset_parameters"):
+                layer.reset_parameters()
 
 
 class Discriminator_VGG_160(_AuxNet):
@@ -271,4 +423,43 @@ class VGGFeatureExtractor(_AuxNet):
         return _nchw(y, Cc).contiguous()
 
     def forward(self, x):
+        return self._run(self._body, x)
+
+
+class PatchGANDiscriminator(_AuxNet):
+    """Drop-in for discriminator_vgg_arch.PatchGANDiscriminator (:159-189): ``model`` is the reference's ``nn.Sequential`` with its
+    module indices (``model.0`` conv + bias, ``model.{2+3i}`` conv, ``model.{3+3i}`` BatchNorm2d, LeakyReLUs in between,
+    ``model.{2+3n}`` the 1-channel conv), so keys and the seeded default initialisation match. Every 3x3 padding-0 conv runs as
+    the same-padded conv kernel whose interior window the next step reads: the fused BN + LeakyReLU kernels for the n_layers
+    middle layers, the window-only form of the same kernels after the first and the last conv. Output [B, 1, H - 2(n+2),
+    W - 2(n+2)]."""
+
+    def __init__(self, in_nc=3, ndf=64, n_layers=35, norm_layer=nn.BatchNorm2d):
+        super().__init__()
+        seq = [nn.Conv2d(in_nc, ndf, kernel_size=3, stride=1, padding=0), nn.LeakyReLU(0.2, True)]
+        for _ in range(n_layers):
+            seq += [nn.Conv2d(ndf, ndf, kernel_size=3, stride=1, padding=0, bias=False), norm_layer(ndf), nn.LeakyReLU(0.2, True)]
+            if not (type(seq[-2]) is nn.BatchNorm2d and seq[-2].affine):
+                raise NotImplementedError("PatchGANDiscriminator: only norm_layer=nn.BatchNorm2d (affine) has a kernel here")
+        seq += [nn.Conv2d(ndf, 1, kernel_size=3, stride=1, padding=0, bias=False)]
+        self.model = nn.Sequential(*seq)
+        self.n_layers = n_layers
+        self._aux_init()
+
+    def _body(self, x, flags, prec):
+        m, n = self.model, self.n_layers
+        y = self._conv(_nhwc(x), m[0], 2, flags, prec)                                 # bias + LeakyReLU fused
+        y = self._bn_act(y, None, m[0].out_channels, _interior(y), act=0)
+        for i in range(n):
+            conv, bn = m[2 + 3 * i], m[3 + 3 * i]
+            y = self._conv(y, conv, 0, flags, prec)
+            y = self._bn_act(y, bn, bn.num_features, _interior(y))
+        y = self._conv(y, m[2 + 3 * n], 0, flags, prec)
+        return _nchw(self._bn_act(y, None, 1, _interior(y), act=0), 1)
+
+    def forward(self, x):
+        shrink = 2 * (self.n_layers + 2)
+        if x.dim() != 4 or x.shape[2] <= shrink or x.shape[3] <= shrink:
+            raise ValueError("PatchGANDiscriminator(n_layers=%d): its %d padding-0 3x3 convs need an input larger than %d x %d, "
+                             "got %s" % (self.n_layers, self.n_layers + 2, shrink, shrink, tuple(x.shape)))
         return self._run(self._body, x)

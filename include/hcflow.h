@@ -336,6 +336,30 @@ int hcf_aux_conv2d_backward(const float* x, int32_t cs_in, int32_t cin, int32_t 
                             int32_t cout, int32_t k, const float* g, int32_t cs_g, float* dx, int32_t cs_dx, float* dw,
                             void* work, size_t work_bytes, int32_t precision, hcf_stream_t stream);
 
+/* BatchNorm2d(C, affine=True) + LeakyReLU(0.2) of Discriminator_VGG_128 / PatchGANDiscriminator
+ * (discriminator_vgg_arch.py:12-33,42-55,171-183), with an output window: reads the window (y0, x0, Ho, Wo) of an H x W input
+ * and writes a compact Ho x Wo output. A padding-0 3x3 conv is the interior (1, 1, H-2, W-2) of hcf_aux_conv2d's same-padded
+ * output, so these entries plus the aux conv give the PatchGAN layers without a conv kernel of their own.
+ *   x:     device NHWC [B][H][W][cs_x];  y: device NHWC [B][Ho][Wo][cs_y], channels >= C written 0 (cs % 4 == 0, 16-byte aligned)
+ *   mode:  0 window (+ activation) only; 1 train(): batch statistics (biased variance), running_mean / running_var (nullable as
+ *          a pair) moved in place with the unbiased variance and `momentum`; 2 eval(): running statistics
+ *   act:   0 none, 1 relu, 2 leaky relu 0.2
+ *   save_mean / save_invstd: device [C], written by the forward pass (modes 1, 2), read by the backward pass
+ * Statistics are reduced through fp64 per-block partials in a fixed order (bit-reproducible, no float atomics); no host sync.
+ * hcf_aux_bn_act_backward writes dx over the FULL H x W input, zero outside the window (the exact gradient of the same-padded
+ * conv's output); dgamma / dbeta (device [C], overwritten) are nullable: a frozen net's pass (netD in the G step,
+ * HCFlow_SR_model.py:237-243) skips them. `work`: device scratch of hcf_aux_bn_act_workspace(C, B, Ho, Wo) bytes, used by the
+ * train() forward and by a backward pass with mode 1 or parameter gradients. */
+size_t hcf_aux_bn_act_workspace(int32_t C, int32_t B, int32_t Ho, int32_t Wo);
+int hcf_aux_bn_act(const float* x, int32_t cs_x, int32_t C, int32_t B, int32_t H, int32_t W, int32_t y0, int32_t x0, int32_t Ho,
+                   int32_t Wo, const float* gamma, const float* beta, float* running_mean, float* running_var, int32_t mode,
+                   double momentum, double eps, int32_t act, float* y, int32_t cs_y, float* save_mean, float* save_invstd,
+                   void* work, size_t work_bytes, hcf_stream_t stream);
+int hcf_aux_bn_act_backward(const float* x, int32_t cs_x, int32_t C, int32_t B, int32_t H, int32_t W, int32_t y0, int32_t x0,
+                            int32_t Ho, int32_t Wo, const float* gamma, const float* beta, const float* save_mean,
+                            const float* save_invstd, int32_t mode, int32_t act, const float* dy, int32_t cs_dy, float* dx,
+                            int32_t cs_dx, float* dgamma, float* dbeta, void* work, size_t work_bytes, hcf_stream_t stream);
+
 /* ---- LPIPS v0.1, AlexNet (the LPIPS column of the reference's test log: test_HCFlow.py:48 builds lpips.LPIPS(net='alex'),
  * :132 evaluates it on (2 gt - 1, 2 sr - 1)); hcflow_amd/lpips.py is the module around it. One call runs the whole network on
  * both inputs and the LPIPS head, in exact fp32 (fp32 MFMA), on `stream`, without host synchronisation; the result for an image
