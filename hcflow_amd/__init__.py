@@ -6,5 +6,6 @@ hand-written HIP kernels behind the C ABI of include/hcflow.h (hcflow_amd/libhcf
 from .config import NetConfig, preset, param_spec, eps_shapes  # noqa: F401
 from .params import make_params  # noqa: F401
 from .arch import HCFlowNet_SR, HCFlowNet_Rescaling  # noqa: F401
+from . import latent  # noqa: F401
 
-__all__ = ["NetConfig", "preset", "param_spec", "eps_shapes", "make_params", "HCFlowNet_SR", "HCFlowNet_Rescaling"]
+__all__ = ["NetConfig", "preset", "param_spec", "eps_shapes", "make_params", "HCFlowNet_SR", "HCFlowNet_Rescaling", "latent"]

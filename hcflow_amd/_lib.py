@@ -23,6 +23,7 @@ FLAG_REUSE_COND = 8
 SYMBOLS = [
     "hcf_create", "hcf_destroy", "hcf_last_error", "hcf_param_count", "hcf_param_info",
     "hcf_set_param", "hcf_finalize", "hcf_inverse", "hcf_inverse_ex", "hcf_check_range", "hcf_check_range_samples", "hcf_aux_stream", "hcf_forward_sr", "hcf_forward_rescale",
+    "hcf_encode_sr",
     "hcf_workspace_bytes", "hcf_weight_bytes", "hcf_profile_convs", "hcf_conv_time_ms",
     "hcf_op_conv2d", "hcf_op_squeeze2d", "hcf_op_unsqueeze2d", "hcf_op_step_inverse",
     "hcf_op_step_forward_head", "hcf_op_step_forward_couple", "hcf_op_gauss_logp",
@@ -85,6 +86,7 @@ def load() -> C.CDLL:
     lib.hcf_aux_stream.argtypes = [i32, i32, C.POINTER(vp)]
     lib.hcf_forward_sr.argtypes = [vp, fp, fp, fp, fp, fp, fp, fp, i32, i32, i32, vp]
     lib.hcf_forward_rescale.argtypes = [vp, fp, fp, fp, fp, i32, i32, i32, u32, vp]
+    lib.hcf_encode_sr.argtypes = [vp, fp, fp, fp, C.POINTER(fp), i32, fp, i32, i32, i32, u32, vp]
     lib.hcf_workspace_bytes.argtypes = [vp]
     lib.hcf_workspace_bytes.restype = C.c_size_t
     lib.hcf_weight_bytes.argtypes = [vp]

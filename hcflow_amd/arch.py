@@ -1132,6 +1132,54 @@ class HCFlowNet_SR(_EngineModule):
         """lr (+ sampled z) -> clamp(HR)   (HCFlowNet_SR_arch.py:70-75)."""
         return self._inverse(lr, eps_std, eps=eps, clamp=clamp, seed=seed, sample_offset=sample_offset, cache_cond=cache_cond)
 
+    # -- latent encoding: hr -> (z_lr, eps per level, log-density) and its exact inverse
+    def encode(self, hr, noise=None, add_gt_noise=False):
+        """hr -> (z_lr, eps, logp): the forward flow of normal_flow_diracLR (HCFlowNet_SR_arch.py:52-56) that RETURNS what each
+        conditional prior standardises, eps_l = (a_l - mean_l) * exp(-logs_l) (ConditionalFlow.py:46-57), instead of folding it
+        into the log-probability. ``z_lr`` [B,3,h,w] is the LR latent before quantisation, unclamped; ``eps`` is a list shaped
+        ``eps_shapes(cfg, B, h, w)`` in the order the inverse pass takes (deepest level first); ``logp`` [B] is
+        logdet + the sum of the prior log-densities in nats WITHOUT the Dirac-LR term (:63) -- the reference's constant
+        -ln(quant) * H * W (:53) is part of it whether or not noise is added. ``decode(z_lr, eps)`` returns hr + noise / quant.
+
+        ``noise``: an explicit U[0,1) tensor; ``add_gt_noise=True`` draws it with torch.rand as the reference does (:52); by
+        default none is added, so that the decode target is ``hr`` itself. Always the inference path (as ``return_internals=True``
+        is): the outputs carry no autograd graph, whatever the grad mode, and un-initialised ActNorms are not fitted.
+        Per sample: a batch of >= 4 runs as two half batches on the two side streams (set_streams)."""
+        dev = self._device()
+        B_ = int(hr.shape[0]) if torch.is_tensor(hr) and hr.dim() == 4 else 0
+        eng, idx = self._engine_for(dev, twin_hint=self._nstreams[0] >= 2 and B_ >= 4)
+        self._cond_key.pop(idx, None)
+        hr = self._prep(hr, dev)
+        B, c, H, W = hr.shape
+        cfg = self.cfg
+        s = cfg.scale
+        assert c == 3 and H % s == 0 and W % s == 0, "{}".format((H, W, s))
+        if noise is None and add_gt_noise:
+            noise = torch.rand(hr.shape, device=dev)
+        if noise is not None:
+            noise = self._prep(noise, dev)
+            assert noise.shape == hr.shape, (tuple(noise.shape), tuple(hr.shape))
+        h, w = H // s, W // s
+        z = torch.empty(B, 3, h, w, device=dev)
+        eps = [torch.empty(sh, device=dev) for sh in eps_shapes(cfg, B, h, w)]
+        logp = torch.empty(B, device=dev)
+        if B == 0:
+            return z, eps, logp
+        fl = _lib.FLAG_NO_RANGE_CHECK if self._range_check[0] == "off" else 0
+
+        def run(eng_, lo, hi, stream_):
+            arr = (C.c_void_p * len(eps))(*[e[lo:hi].data_ptr() for e in eps])      # contiguous NCHW row slices, no copies
+            return eng_.lib.hcf_encode_sr(eng_.handle, hr[lo:hi].data_ptr(), None if noise is None else noise[lo:hi].data_ptr(),
+                                          z[lo:hi].data_ptr(), arr, len(eps), logp[lo:hi].data_ptr(), hi - lo, H, W, fl, stream_)
+
+        self._run_checked(eng, idx, run, "hcf_encode_sr", batch=B, call_sample=lambda b: run(eng, b, b + 1, self._stream(idx)),
+                          parts=self._parts(dev, idx, eng, B), threaded=_split_threaded())
+        return z, eps, logp
+
+    def decode(self, z_lr, eps, clamp=False):
+        """(z_lr, eps) of ``encode`` -> hr (+ noise / quant): the inverse pass fed the encoded latents, unclamped by default."""
+        return self.reverse_flow_diracLR(z_lr, None, None, eps_std=1.0, eps=eps, clamp=clamp)
+
 
 class HCFlowNet_Rescaling(_EngineModule):
     """Drop-in for models.modules.HCFlowNet_Rescaling_arch.HCFlowNet_Rescaling (:13-54)."""
@@ -1197,6 +1245,17 @@ class HCFlowNet_Rescaling(_EngineModule):
                              cache_cond=False):
         """lr (+ sampled z) -> clamp(HR)   (HCFlowNet_Rescaling_arch.py:49-54)."""
         return self._inverse(lr, eps_std, eps=eps, clamp=clamp, seed=seed, sample_offset=sample_offset, cache_cond=cache_cond)
+
+    # -- the interface HCFlowNet_SR.encode / decode has, over the existing calls
+    def encode(self, hr):
+        """hr -> (lr_raw, [z2, z1]): normal_flow_diracLR(hr, clamp=False) with the latents in the order the inverse pass takes
+        (deepest level first)."""
+        lr_raw, z1, z2 = self.normal_flow_diracLR(hr, clamp=False)
+        return lr_raw, [z2, z1]
+
+    def decode(self, lr, eps, clamp=False):
+        """(lr, [z2, z1]) -> hr: reverse_flow_diracLR fed the encoded latents, unclamped by default."""
+        return self.reverse_flow_diracLR(lr, None, None, eps_std=1.0, eps=eps, clamp=clamp)
 
     def get_score(self, disc_loss_sigma, z):
         """HCFlowNet_Rescaling.get_score (:57-60), unused by every config; kept for API parity."""

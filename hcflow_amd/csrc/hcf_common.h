@@ -326,6 +326,7 @@ struct GaussArgs {
 int launch_gauss_sample(const GaussArgs& a, hipStream_t st);
 int launch_gauss_logp(const GaussArgs& a, hipStream_t st);      // SR forward: partial sums of log p
 int launch_gauss_encode(const GaussArgs& a, hipStream_t st);    // rescaling forward
+int launch_gauss_encode_logp(const GaussArgs& a, hipStream_t st);   // SR encode: eps -> aux (NCHW) and the partial sums of log p
 
 int launch_nchw_to_nhwc(const float* src, View dst, int B, int C, int H, int W, hipStream_t st);
 int launch_nhwc_to_nchw(View src, float* dst, int B, int C, int H, int W, int clamp01, hipStream_t st);

@@ -580,6 +580,19 @@ int hcf_forward_sr(hcf_engine* e, const float* hr, const float* lr, const float*
                      (hipStream_t)stream, 0, {2, B, H, W, lr ? 1 : 0, noise ? 1 : 0, out_z ? 1 : 0});
 }
 
+int hcf_encode_sr(hcf_engine* e, const float* hr, const float* noise, float* out_z, float* const* out_eps, int32_t n_eps,
+                  float* out_logp, int32_t B, int32_t H, int32_t W, uint32_t flags, hcf_stream_t stream) {
+  if (!e || !hr || !out_z || !out_eps || B < 1 || H < 1 || W < 1) return HCF_ERR_ARG;
+  if (e->cfg.kind != HCF_KIND_SR) return e->fail(HCF_ERR_STATE, "hcf_encode_sr on a rescaling engine"), HCF_ERR_STATE;
+  if (n_eps != e->cfg.L) return e->fail(HCF_ERR_ARG, "hcf_encode_sr: n_eps must equal the number of levels (one eps tensor per split)"), HCF_ERR_ARG;
+  for (int i = 0; i < n_eps; ++i)
+    if (!out_eps[i]) return e->fail(HCF_ERR_ARG, "hcf_encode_sr: null eps output"), HCF_ERR_ARG;
+  const int m = 1 << e->cfg.L;
+  if (H % m || W % m) return e->fail(HCF_ERR_SHAPE, "H, W must be divisible by the scale (squeeze2d assert, Basic.py:136)"), HCF_ERR_SHAPE;
+  return e->run_pass([&]() { e->cc_valid = false; e->pass_forward(hr, nullptr, noise, nullptr, nullptr, out_logp, out_z, nullptr, nullptr, B, H, W, 0, out_eps); },
+                     (hipStream_t)stream, flags & HCF_FLAG_NO_RANGE_CHECK, {4, B, H, W, noise ? 1 : 0, out_logp ? 1 : 0});
+}
+
 int hcf_forward_rescale(hcf_engine* e, const float* hr, float* out_lr, float* out_z1, float* out_z2, int32_t B, int32_t H,
                         int32_t W, uint32_t flags, hcf_stream_t stream) {
   if (!e || !hr || !out_lr || B < 1 || H < 1 || W < 1) return HCF_ERR_ARG;

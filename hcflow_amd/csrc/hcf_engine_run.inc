@@ -596,7 +596,8 @@
   // ---------------------------------------------------------------- forward pass
   // FlowNet.normal_flow (FlowNet_SR_x4.py:84-101, FlowNet_SR_x8.py:91-116, FlowNet_Rescaling_x4.py:89-106)
   void pass_forward(const float* hr, const float* lr, const float* noise, float* out_lr, float* out_nll,
-                    float* out_logdet, float* out_z, float* out_z1, float* out_z2, int B, int H0, int W0, uint32_t flags) {
+                    float* out_logdet, float* out_z, float* out_z1, float* out_z2, int B, int H0, int W0, uint32_t flags,
+                    float* const* out_eps = nullptr) {
     B_ = B;
     arena.top = 0;
     const int L = cfg.L;
@@ -664,7 +665,13 @@
         g.partial = partial + pslot;
         g.partial_stride = nslots;
         pslot += step_blocks_per_sample(H, W);
-        HCF_LAUNCH(launch_gauss_logp(g, st));
+        if (out_eps) {
+          // encode (hcf_encode_sr): the standardised split half leaves the pass, in hcf_inverse's eps order (deepest level first)
+          g.aux = out_eps[L - 1 - level];
+          HCF_LAUNCH(launch_gauss_encode_logp(g, st));
+        } else {
+          HCF_LAUNCH(launch_gauss_logp(g, st));
+        }
       } else {
         g.rescale = 1;
         g.aux = (level == 0) ? out_z1 : out_z2;

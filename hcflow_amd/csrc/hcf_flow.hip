@@ -300,6 +300,46 @@ __global__ __launch_bounds__(256) void gauss_encode_kernel(const GaussArgs a) {
   }
 }
 
+// SR encode: eps = (a - mean) * exp(-logs) -> NCHW, and the per-block partial sum of -0.5 (2 logs + eps^2 + ln 2pi) into the slot
+// gauss_logp_kernel fills in the NLL pass (ConditionalFlow.py:46-57, Basic.py:78-94): one read of h and a for both.
+// A block owns 256 pixels of one sample (the partial-slot layout of the pixel kernels). Reads run channel fastest over the block's
+// NHWC records (consecutive lanes = consecutive floats, the form gauss_sample_kernel took after the channel walk per lane), the
+// results cross an LDS tile [channel][pixel] (row length 257: the channel-fastest writes hit 64 different banks), and the NCHW
+// stores run pixel fastest (consecutive lanes = consecutive floats of a channel plane). Latents wider than the tile go through it in
+// slices of ENC_TILE_C channels. Fixed order of the sums: bit-identical from call to call and independent of the batch size.
+constexpr int ENC_TILE_C = 24;
+__global__ __launch_bounds__(256) void gauss_encode_logp_kernel(const GaussArgs a) {
+  __shared__ float tile[ENC_TILE_C * 257];
+  __shared__ float sh[4];
+  const int hw = a.H * a.W;
+  const int b = blockIdx.y;
+  const int p0 = blockIdx.x * 256;
+  const int np = min(256, hw - p0);                       // pixels of this block (>= 1: the grid is ceil(hw / 256))
+  float acc = 0.f;
+  for (int c0 = 0; c0 < a.C; c0 += ENC_TILE_C) {
+    const int nc = min(ENC_TILE_C, a.C - c0);
+    const int n = np * nc;
+    for (int t = threadIdx.x; t < n; t += 256) {
+      const int i = t / nc, c = t - i * nc;
+      const size_t pix = (size_t)b * hw + p0 + i;
+      const float* hp = a.h.p + pix * a.h.cs + a.h.c0 + 2 * (c0 + c);
+      const float mean = hp[0], logs = hp[1];
+      const float x = a.out.p[pix * a.out.cs + a.out.c0 + c0 + c];
+      const float eps = (x - mean) * expf(-logs);
+      acc += -0.5f * (logs * 2.f + eps * eps + 1.8378770664093453f);
+      tile[c * 257 + i] = eps;
+    }
+    __syncthreads();
+    for (int t = threadIdx.x; t < n; t += 256) {
+      const int c = t / np, i = t - c * np;
+      a.aux[((size_t)b * a.C + c0 + c) * hw + p0 + i] = tile[c * 257 + i];
+    }
+    __syncthreads();
+  }
+  const float s = block_sum(acc, sh);
+  if (threadIdx.x == 0) a.partial[(size_t)b * a.partial_stride + blockIdx.x] = s;
+}
+
 static inline dim3 pix_grid(int B, int H, int W) { return dim3((unsigned)((H * W + 255) / 256), (unsigned)B); }
 static inline dim3 elem_grid(int B, long long per_sample) { return dim3((unsigned)((per_sample + 255) / 256), (unsigned)B); }
 
@@ -317,6 +357,11 @@ int launch_gauss_logp(const GaussArgs& a, hipStream_t st) {
 int launch_gauss_encode(const GaussArgs& a, hipStream_t st) {
   if (!a.aux) return HCF_ERR_ARG;
   hipLaunchKernelGGL(gauss_encode_kernel, pix_grid(a.B, a.H, a.W), dim3(256), 0, st, a);
+  return hipGetLastError() == hipSuccess ? HCF_OK : HCF_ERR_HIP;
+}
+int launch_gauss_encode_logp(const GaussArgs& a, hipStream_t st) {
+  if (!a.aux || !a.partial || a.rescale || a.C < 1 || a.H < 1 || a.W < 1 || a.B < 1) return HCF_ERR_ARG;
+  hipLaunchKernelGGL(gauss_encode_logp_kernel, pix_grid(a.B, a.H, a.W), dim3(256), 0, st, a);
   return hipGetLastError() == hipSuccess ? HCF_OK : HCF_ERR_HIP;
 }
 

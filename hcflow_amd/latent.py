@@ -1,0 +1,83 @@
+"""Latent-space helpers over ``HCFlowNet_SR.encode`` / ``decode`` (and the rescaling net's aliases).
+
+Plain torch on the tensors the engine returns -- a few elementwise operations on < 100 MB, no kernels of their own. ``eps`` is
+always the list the inverse pass takes: one [B, C_l, h_l, w_l] tensor per level, deepest level first (config.eps_shapes).
+
+The two ``get_*`` functions are the wrapper-level calls the reference's model class names (HCFlow_SR_model.py:328-351:
+get_encode_z_and_nll, get_sr_with_z) with working semantics: there they pass keywords HCFlowNet_SR.forward does not take.
+"""
+import math
+
+import torch
+
+from .config import eps_shapes
+
+
+def scale(eps, tau):
+    """tau * eps per level: the encoded image re-decoded at temperature ``tau`` (tau = 1: the image itself, 0: the prior mean)."""
+    return [e * float(tau) for e in eps]
+
+
+def lerp(eps_a, eps_b, t):
+    """Straight line between two latents, per level; exact at t = 0 and t = 1."""
+    assert len(eps_a) == len(eps_b)
+    return [torch.lerp(a, b, float(t)) for a, b in zip(eps_a, eps_b)]
+
+
+def slerp(eps_a, eps_b, t):
+    """Great-circle interpolation, per SAMPLE over all levels jointly: the angle is the one between a sample's whole latent
+    vectors (every level concatenated), so a path between two N(0, I) draws keeps the norm a Gaussian draw has. Samples whose
+    two latents are (anti)parallel fall back to ``lerp``. Exact at t = 0 and t = 1, and slerp(a, a, t) = a."""
+    assert len(eps_a) == len(eps_b) and len(eps_a) > 0
+    t = float(t)
+    B = eps_a[0].shape[0]
+    dot = sum((a.double() * b.double()).reshape(B, -1).sum(1) for a, b in zip(eps_a, eps_b))
+    na = sum((a.double() ** 2).reshape(B, -1).sum(1) for a in eps_a).sqrt()
+    nb = sum((b.double() ** 2).reshape(B, -1).sum(1) for b in eps_b).sqrt()
+    cos = (dot / (na * nb).clamp_min(1e-300)).clamp(-1.0, 1.0)
+    omega = torch.acos(cos)
+    so = torch.sin(omega)
+    ok = so > 1e-6
+    so_ = torch.where(ok, so, torch.ones_like(so))
+    ca = torch.sin((1.0 - t) * omega) / so_
+    cb = torch.sin(t * omega) / so_
+    out = []
+    for a, b in zip(eps_a, eps_b):
+        shp = (B,) + (1,) * (a.dim() - 1)
+        s = (a * ca.to(a.dtype).view(shp) + b * cb.to(a.dtype).view(shp))
+        out.append(torch.where(ok.view(shp), s, torch.lerp(a, b, t)))
+    return out
+
+
+def dirac_logp(lq, z_lr):
+    """log N(lq; mean = Quant(z_lr), logs = -6) per sample, the Dirac-LR term of the objective (HCFlowNet_SR_arch.py:58-63),
+    in float64. Quant (Basic.py:187-191) is evaluated in float32 as the forward pass does."""
+    zq = (torch.clamp(z_lr.float(), 0, 1) * 255.).round() / 255.
+    d = zq.double() - lq.to(z_lr.device).double()
+    return (-0.5 * (-12.0 + d * d * math.exp(12.0) + math.log(2 * math.pi))).sum(dim=[1, 2, 3])
+
+
+def get_encode_z_and_nll(net, lq, hr, add_gt_noise=True, noise=None):
+    """(eps, nll): the latents of ``hr`` and its negative log-likelihood in bits per dimension PER SAMPLE, with the Dirac term
+    evaluated at ``lq`` -- the mean of ``nll`` is the number ``net(hr=hr, lr=lq)`` returns for the same noise
+    (HCFlowNet_SR_arch.py:63-65). ``noise``: explicit U[0,1) tensor; otherwise drawn when ``add_gt_noise`` (the reference's
+    default for this call)."""
+    z, eps, logp = net.encode(hr, noise=noise, add_gt_noise=add_gt_noise)
+    pixels = int(hr.shape[2]) * int(hr.shape[3])
+    objective = logp.double() + dirac_logp(lq, z)
+    return eps, (-objective) / (math.log(2.0) * pixels)
+
+
+def get_sr_with_z(net, lq, heat=None, seed=None, eps=None):
+    """(sr, eps): ``lq`` super-resolved with the given latents, or -- when ``eps`` is None -- with N(0, heat) draws made here
+    (``seed``: a generator of its own; None: torch's global one; ``heat`` None = 1.0), returned so that the call can be repeated or
+    edited. Given ``eps`` is used as it is (already at its temperature: ``scale(eps, tau)``)."""
+    if eps is None:
+        tau = 1.0 if heat is None else float(heat)
+        B, _, h, w = lq.shape
+        g = None
+        if seed is not None:
+            g = torch.Generator(device=lq.device).manual_seed(int(seed))
+        eps = [torch.randn(s, generator=g, device=lq.device) * tau for s in eps_shapes(net.cfg, B, h, w)]
+    sr = net(lr=lq, eps_std=1.0 if heat is None else float(heat), reverse=True, eps=eps)
+    return sr, eps

@@ -133,6 +133,19 @@ int hcf_inverse_ex(hcf_engine* e, const float* lr, const float* const* eps, int3
 int hcf_forward_sr(hcf_engine* e, const float* hr, const float* lr, const float* noise, float* out_lr, float* out_nll,
                    float* out_logdet, float* out_z, int32_t B, int32_t H, int32_t W, hcf_stream_t stream);
 
+/* Encode for HCFlowNet_SR: the forward flow of normal_flow_diracLR (HCFlowNet_SR_arch.py:52-56 -> FlowNet.normal_flow,
+ * FlowNet_SR_x4.py:84-101, FlowNet_SR_x8.py:91-116) that RETURNS what each conditional prior standardises instead of folding it
+ * into the log-probability (ConditionalFlow.py:46-57, Basic.py:78-94): eps_l = (a_l - mean_l) * exp(-logs_l). Fed back through
+ * hcf_inverse(lr = out_z, eps = out_eps, tau ignored, HCF_FLAG_NO_CLAMP) the flow returns hr + noise / quant.
+ *   hr [B,3,H,W]; noise [B,3,H,W] U[0,1) or NULL (NULL -> no dequantisation noise is added: the decode target is hr itself)
+ *   out_z    [B,3,H/scale,W/scale] pre-quantisation LR latent, not clamped
+ *   out_eps  n_eps device buffers, deepest level first: the order and the shapes of hcf_inverse's eps; n_eps = number of levels
+ *   out_logp [B] (nullable): logdet + sum of the prior log-densities in nats, WITHOUT the Dirac-LR term (HCFlowNet_SR_arch.py:63).
+ *            The reference's constant -ln(quant) * H * W (:53) is part of it whether or not noise is given.
+ *   flags    HCF_FLAG_NO_RANGE_CHECK or 0 */
+int hcf_encode_sr(hcf_engine* e, const float* hr, const float* noise, float* out_z, float* const* out_eps, int32_t n_eps,
+                  float* out_logp, int32_t B, int32_t H, int32_t W, uint32_t flags, hcf_stream_t stream);
+
 /* netG(hr=hr, reverse=False) for HCFlowNet_Rescaling: normal_flow_diracLR
  * (HCFlowNet_Rescaling_arch.py:39-46): out_lr = clamp(LR^), out_z1 [B,6,H/2,W/2], out_z2 [B,21,H/4,W/4] */
 int hcf_forward_rescale(hcf_engine* e, const float* hr, float* out_lr, float* out_z1, float* out_z2, int32_t B, int32_t H,
