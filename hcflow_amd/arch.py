@@ -1119,8 +1119,11 @@ class HCFlowNet_SR(_EngineModule):
         if _grad_nodes() == 2:
             params = self._params()
             early_idx = [i for i, k in enumerate(self._spec_keys) if k.startswith("flow.level0_condFlow.")]
-            if early_idx and len(early_idx) < len(params):
-                eset = set(early_idx)
+            eset = set(early_idx)
+            # a group without a gradient-requiring parameter gets no backward call from autograd: a frozen `late` group would leave
+            # phase 1 (and the side-stream joins behind it) unissued -> the one-node step
+            if (any(params[i].requires_grad for i in early_idx) and
+                    any(p.requires_grad for i, p in enumerate(params) if i not in eset)):
                 st = _SRNLLTwoPhase(self, hr, lr, noise, params, early_idx)
                 out_lr, nll, _ = two_phase_apply(st, [params[i] for i in early_idx], [p for i, p in enumerate(params) if i not in eset])
                 return out_lr, nll

@@ -451,18 +451,13 @@ void hcf_destroy(hcf_engine* e) {
   if (e->ovf_ev) hipEventDestroy(e->ovf_ev);
   if (e->stats_dev) hipFree(e->stats_dev);
   if (e->probe_dev) hipFree(e->probe_dev);
-  if (e->garena.base) hipFree(e->garena.base);
   for (auto& t : e->slots) { if (t.a.base) hipFree(t.a.base); if (t.g.base) hipFree(t.g.base); }
   if (e->wg_scratch) hipFree(e->wg_scratch);
-  if (e->wg_jobs_dev) hipFree(e->wg_jobs_dev);
-  if (e->wg_stream) hipStreamSynchronize(e->wg_stream);      // (the stream belongs to the process' pool: aux_stream)
-  if (e->wg_ev) hipEventDestroy(e->wg_ev);
-  if (e->wg_done) hipEventDestroy(e->wg_done);
-  if (e->dg_stream) hipStreamSynchronize(e->dg_stream);
-  if (e->dg_ev) hipEventDestroy(e->dg_ev);
-  if (e->dg_done) hipEventDestroy(e->dg_done);
-  if (e->axpy_jobs_dev) hipFree(e->axpy_jobs_dev);
-  if (e->sum_jobs_dev) hipFree(e->sum_jobs_dev);
+  e->wg_stream.close();
+  e->dg_stream.close();
+  if (e->wg_jobs.dev) hipFree(e->wg_jobs.dev);
+  if (e->axpy_jobs.dev) hipFree(e->axpy_jobs.dev);
+  if (e->sum_jobs.dev) hipFree(e->sum_jobs.dev);
   if (e->rt.blob) hipFree(e->rt.blob);
   if (e->rt.wino) hipFree(e->rt.wino);
   for (auto& pr : e->prof_events) { hipEventDestroy(pr.e0); hipEventDestroy(pr.e1); }
@@ -615,7 +610,7 @@ int64_t hcf_fallback_count(const hcf_engine* e) { return e ? e->n_fallbacks : -1
 
 size_t hcf_workspace_bytes(const hcf_engine* e) {      // inference arena + the training tapes' activation / gradient arenas
   if (!e) return 0;
-  size_t n = e->arena.cap + e->garena.cap;
+  size_t n = e->arena.cap;
   for (const auto& t : e->slots) n += t.a.cap + t.g.cap;
   return n;
 }
@@ -626,7 +621,8 @@ int hcf_train_forward_sr(hcf_engine* e, const float* hr, const float* lr, const 
   if (!e || !hr || !lr || !noise || !out_lr || !out_nll || !out_logdet || B < 1 || H < 1 || W < 1) return HCF_ERR_ARG;
   const int m = 1 << e->cfg.L;
   if (H % m || W % m) return e->fail(HCF_ERR_SHAPE, "H, W must be divisible by the scale (squeeze2d assert, Basic.py:136)");
-  return e->run_train_forward(hr, lr, noise, out_lr, out_nll, out_logdet, B, H, W, (hipStream_t)stream);
+  return e->run_train(1, e->sr() ? nullptr : "hcf_train_forward_sr on a rescaling engine", (hipStream_t)stream,
+                      [&]() { e->pass_train_forward_sr(hr, lr, noise, out_lr, out_nll, out_logdet, B, H, W); });
 }
 
 int hcf_train_backward(hcf_engine* e, float grad_nll, float* dparams, int64_t numel, hcf_stream_t stream) {
@@ -643,7 +639,7 @@ int hcf_train_backward_phase(hcf_engine* e, int32_t phase, float grad_nll, float
 
 int hcf_train_select_tape(hcf_engine* e, int32_t slot) {
   if (!e || slot < 0 || slot > 1) return HCF_ERR_ARG;
-  e->cur_slot = slot;
+  e->tape = &e->slots[slot];
   return HCF_OK;
 }
 
@@ -651,7 +647,8 @@ int hcf_train_forward_rescale(hcf_engine* e, const float* hr, float* out_lr, flo
                               int32_t H, int32_t W, uint32_t flags, hcf_stream_t stream) {
   if (!e || !hr || !out_lr || !out_z1 || !out_z2 || B < 1 || H < 1 || W < 1) return HCF_ERR_ARG;
   if (H % 4 || W % 4) return e->fail(HCF_ERR_SHAPE, "H, W must be divisible by 4");
-  return e->run_train_forward_rescale(hr, out_lr, out_z1, out_z2, B, H, W, flags, (hipStream_t)stream);
+  return e->run_train(3, e->sr() ? "hcf_train_forward_rescale on an SR engine" : nullptr, (hipStream_t)stream,
+                      [&]() { e->pass_train_forward_rescale(hr, out_lr, out_z1, out_z2, B, H, W, flags); });
 }
 
 int hcf_train_backward_rescale(hcf_engine* e, const float* g_lr, const float* g_z1, const float* g_z2, float* dparams,
@@ -664,7 +661,7 @@ int hcf_train_backward_rescale(hcf_engine* e, const float* g_lr, const float* g_
 int hcf_train_inverse(hcf_engine* e, const float* lr, const float* const* eps, int32_t n_eps, float tau, uint64_t seed,
                       float* out_hr, int32_t B, int32_t h, int32_t w, uint32_t flags, hcf_stream_t stream) {
   if (!e || !lr || !out_hr || B < 1 || h < 1 || w < 1) return HCF_ERR_ARG;
-  return e->run_train_inverse(lr, eps, n_eps, tau, seed, out_hr, B, h, w, flags, (hipStream_t)stream);
+  return e->run_train(2, nullptr, (hipStream_t)stream, [&]() { e->pass_train_inverse(lr, eps, n_eps, tau, seed, out_hr, B, h, w, flags); });
 }
 
 int hcf_train_backward_inverse(hcf_engine* e, const float* grad_out, float* dparams, int64_t numel, float* grad_lr,

@@ -17,63 +17,128 @@
   struct TB { Buf v, g; };
   struct VG { View v, g; };
 
-  Arena garena;
-  std::vector<std::function<void()>> tape;
-  bool tape_valid = false;
-  float gobj = 0.f;                       // dL / d objective_b (same for every sample), set by pass_backward
-  float* gparams = nullptr;               // caller's flat gradient buffer (state_dict order) during pass_backward
-  std::map<std::string, size_t> poff;     // parameter key -> offset (floats) in that buffer
+  // One taped pass and the backward pass that runs on it: the single declaration of what belongs to a tape. Two tapes can be alive
+  // at once (the rescaling step differentiates forward -> Quant -> inverse as ONE graph; an HCFlow+ step holds the NLL pass in slot 0
+  // and the inverse pass in slot 1): the training entry points and the records work on `tape`, the slot hcf_train_select_tape chose.
+  // The forward code shared with the inference path (hcf_engine_run.inc) allocates from the engine's `arena` and reads `B_`: those
+  // two change places with the tape's `a` and `B` for the duration of a call (tape_swap), so that between calls the inference path
+  // has its own arena and batch whatever tapes are alive.
+  struct Tape {
+    Arena a, g;                                      // activations; gradients (one memset clears them before the backward pass)
+    std::vector<std::function<void()>> recs;         // one closure per taped op, run in reverse by the backward pass
+    std::vector<const float*> late_bufs;             // gradient buffers of the conditional features taped in this pass
+    bool valid = false;
+    bool f16 = false;                                // the taped pass completed on the f16x3 kernels (slot 0 may have fallen back to the exact ones while slot 1 did not)
+    int kind = 0;                                    // 1: NLL forward, 2: inverse (sampling) pass, 3: rescaling forward
+    int B = 0;
+    double pixels = 0;
+    Buf tfat = {nullptr, 0, 0};                      // the fat launches' stored partial sum (consumed by the completion behind it): one per conditional net
+    // Two-phase backward of the NLL pass (DDP overlap, HCFlow_SR_model.py:33-36): records [mark, end) are the level-0 conditional
+    // flow (taped last, so first in the backward pass) + the output terms; after them every gradient of the parameters under
+    // "flow.level0_condFlow." is final, the caller can hand them to its gradient all-reduce while phase 1 runs the rest.
+    size_t mark = 0;
+    bool mid = false;                                // phase 0 has run on this tape, phase 1 is pending (hcf_train_backward_phase)
+    // The backward pass on this tape: set when it starts, read by the records. Phase 0 leaves it here for phase 1, whatever runs on
+    // the other slot in between.
+    struct Bwd {
+      float* gparams = nullptr;                      // caller's flat gradient buffer (state_dict order)
+      float gobj = 0.f;                              // dL / d objective_b (same for every sample)
+      bool f16 = false;                              // data-gradient 3x3 convs on the f16x3 kernels (scaled by gmax)
+      long long dgrad_wino_min_pix = 4096;           // HCF_DGRAD_WINO_MIN_PIX, read at the start of each backward pass
+      bool epi_fuse_off = false;                     // HCF_NO_EPI_FUSE (A/B knob), read at the start of each backward pass
+      bool fcn_fuse_off = false;                     // HCF_NO_FCN_FUSE (A/B knob), likewise
+      const float* g_out_nchw = nullptr;             // inverse pass: dL / d output
+      float* g_in_nchw = nullptr;                    // inverse pass, optional: receives dL / d lr
+      const float* g_fwd_lr = nullptr;               // rescaling forward: upstream gradients of (clamp(LR^), z1, z2)
+      const float* g_fwd_z[2] = {nullptr, nullptr};
+      // this pass uses the side streams below (their `on` flags: per pass, a pass on the other slot ends with its own switched off)
+      bool wg_async = false, dg_async = false;
+      bool dg_dirty = false;                         // dg_stream has been given work that the caller's stream has not waited for
+    } bwd;
+  };
+  Tape slots[2];
+  Tape* tape = &slots[0];
+  void tape_swap() { std::swap(arena, tape->a); std::swap(B_, tape->B); }
+  void invalidate_tapes() { slots[0].valid = slots[1].valid = false; }
+
+  std::map<std::string, size_t> poff;     // parameter key -> offset (floats) in the flat gradient buffer
   size_t ptotal = 0;
   bool train_ready = false;
-  float* wg_scratch = nullptr;            // partial dW tiles of the weight-gradient kernel (grown on demand)
-  size_t wg_cap = 0;
+
+  // Engine-wide, shared by both tapes: the job queues, the weight-gradient ring and the side streams. Every backward pass and every
+  // phase 0 ends with the queues flushed and wg_used == 0, so nothing of one pass is left in them when another starts; the work on a
+  // side stream is in order across passes.
+  template <class J>
+  struct JobQueue {
+    std::vector<J> host;
+    J* dev = nullptr;
+    size_t cap = 0;                                  // jobs `dev` has room for
+  };
+  // the queued jobs into the queue's device buffer on stream `s`; too small: a new one of `want` jobs, once `s` has drained
+  template <class J>
+  int upload_jobs(JobQueue<J>& q, size_t want, hipStream_t s, const char* what) {
+    if (q.host.size() > q.cap) {
+      if (q.dev) { hipStreamSynchronize(s); hipFree(q.dev); q.dev = nullptr; q.cap = 0; }
+      if (hipMalloc((void**)&q.dev, want * sizeof(J)) != hipSuccess) return fail(HCF_ERR_NOMEM, std::string("hipMalloc failed (") + what + " jobs)");
+      q.cap = want;
+    }
+    // pageable source: the runtime stages it before returning, so the vector may be reused right away
+    if (hipMemcpyAsync(q.dev, q.host.data(), q.host.size() * sizeof(J), hipMemcpyHostToDevice, s) != hipSuccess)
+      return fail(HCF_ERR_HIP, std::string("hipMemcpyAsync failed (") + what + " jobs)");
+    return HCF_OK;
+  }
   // per-channel parameter-gradient sums (conv bias / logs, ActNorm bias / logs): every backward kernel leaves per-block
   // partials in the gradient arena, ONE launch at the end of the pass reduces them in a fixed order (bit-reproducible)
-  std::vector<SumJob> sum_jobs;
-  SumJob* sum_jobs_dev = nullptr;
-  size_t sum_jobs_cap = 0;
+  JobQueue<SumJob> sum_jobs;
   void add_sum_job(const float* part, int nblk, int n, int pstride, float* d0, float* d1, float mult1) {
     SumJob j; j.part = part; j.nblk = nblk; j.n = n; j.pstride = pstride; j.dst0 = d0; j.dst1 = d1; j.mult1 = mult1;
-    sum_jobs.push_back(j);
+    sum_jobs.host.push_back(j);
   }
   // data-independent log-det terms (logs += k, dW += k W^-T): queued, one launch at the end of the pass
-  std::vector<AxpyJob> axpy_jobs;
-  AxpyJob* axpy_jobs_dev = nullptr;
-  size_t axpy_jobs_cap = 0;
+  JobQueue<AxpyJob> axpy_jobs;
   void add_axpy_job(const float* x, float* y, int n, float alpha) {
     AxpyJob j; j.x = x; j.y = y; j.n = n; j.alpha = alpha;
-    axpy_jobs.push_back(j);
+    axpy_jobs.host.push_back(j);
   }
   int flush_axpy_jobs() {
-    if (axpy_jobs.empty() || rc != HCF_OK) { axpy_jobs.clear(); return rc; }
-    if (axpy_jobs.size() > axpy_jobs_cap) {
-      if (axpy_jobs_dev) { hipStreamSynchronize(st); hipFree(axpy_jobs_dev); axpy_jobs_dev = nullptr; axpy_jobs_cap = 0; }
-      const size_t want = axpy_jobs.size() + 64;
-      if (hipMalloc((void**)&axpy_jobs_dev, want * sizeof(AxpyJob)) != hipSuccess) return fail(HCF_ERR_NOMEM, "hipMalloc failed (axpy jobs)");
-      axpy_jobs_cap = want;
-    }
-    if (hipMemcpyAsync(axpy_jobs_dev, axpy_jobs.data(), axpy_jobs.size() * sizeof(AxpyJob), hipMemcpyHostToDevice, st) != hipSuccess)
-      return fail(HCF_ERR_HIP, "hipMemcpyAsync failed (axpy jobs)");
-    HCF_LAUNCH(launch_axpy_jobs(axpy_jobs_dev, (int)axpy_jobs.size(), st));
-    axpy_jobs.clear();
+    if (axpy_jobs.host.empty() || rc != HCF_OK) { axpy_jobs.host.clear(); return rc; }
+    if (upload_jobs(axpy_jobs, axpy_jobs.host.size() + 64, st, "axpy") != HCF_OK) return rc;
+    HCF_LAUNCH(launch_axpy_jobs(axpy_jobs.dev, (int)axpy_jobs.host.size(), st));
+    axpy_jobs.host.clear();
     return rc;
   }
   int flush_sum_jobs() {
-    if (sum_jobs.empty() || rc != HCF_OK) { sum_jobs.clear(); return rc; }
-    if (sum_jobs.size() > sum_jobs_cap) {
-      if (sum_jobs_dev) { hipStreamSynchronize(st); hipFree(sum_jobs_dev); sum_jobs_dev = nullptr; sum_jobs_cap = 0; }
-      const size_t want = sum_jobs.size() + sum_jobs.size() / 4 + 64;
-      if (hipMalloc((void**)&sum_jobs_dev, want * sizeof(SumJob)) != hipSuccess) return fail(HCF_ERR_NOMEM, "hipMalloc failed (sum jobs)");
-      sum_jobs_cap = want;
-    }
-    // pageable source: the runtime stages it before returning, so the vector may be reused by the next pass
-    if (hipMemcpyAsync(sum_jobs_dev, sum_jobs.data(), sum_jobs.size() * sizeof(SumJob), hipMemcpyHostToDevice, st) != hipSuccess)
-      return fail(HCF_ERR_HIP, "hipMemcpyAsync failed (sum jobs)");
-    HCF_LAUNCH(launch_sum_jobs(sum_jobs_dev, (int)sum_jobs.size(), st));
-    sum_jobs.clear();
+    if (sum_jobs.host.empty() || rc != HCF_OK) { sum_jobs.host.clear(); return rc; }
+    if (upload_jobs(sum_jobs, sum_jobs.host.size() + sum_jobs.host.size() / 4 + 64, st, "sum") != HCF_OK) return rc;
+    HCF_LAUNCH(launch_sum_jobs(sum_jobs.dev, (int)sum_jobs.host.size(), st));
+    sum_jobs.host.clear();
     return rc;
   }
 
+  // A side stream of the backward pass, from the process' pool (hcf_aux_stream: never more than two side streams per device), and
+  // its two events: work forks off behind everything the caller's stream has been given, the caller's stream joins everything the
+  // side stream has been given.
+  struct SideStream {
+    hipStream_t s = nullptr;
+    hipEvent_t fork_ev = nullptr, done_ev = nullptr;
+    bool open(int pool_slot) {                       // on first use; false: not available, the work stays on the caller's stream
+      if (s) return true;
+      s = aux_stream(pool_slot);
+      if (!s) return false;
+      if (hipEventCreateWithFlags(&fork_ev, hipEventDisableTiming) != hipSuccess ||
+          hipEventCreateWithFlags(&done_ev, hipEventDisableTiming) != hipSuccess) {
+        s = nullptr; return false;
+      }
+      return true;
+    }
+    bool fork(hipStream_t from) { return hipEventRecord(fork_ev, from) == hipSuccess && hipStreamWaitEvent(s, fork_ev, 0) == hipSuccess; }
+    bool join(hipStream_t into) { return hipEventRecord(done_ev, s) == hipSuccess && hipStreamWaitEvent(into, done_ev, 0) == hipSuccess; }
+    void close() {                                   // (the stream belongs to the process' pool: aux_stream)
+      if (s) hipStreamSynchronize(s);
+      if (fork_ev) hipEventDestroy(fork_ev);
+      if (done_ev) hipEventDestroy(done_ev);
+    }
+  };
   // Weight gradients: each launch leaves its per-block partial tiles in a slice of a ring buffer (kept small enough to stay in the
   // 256 MB Infinity Cache) and queues its fixed-order reduce step; the queue runs as ONE launch when the ring is full, when somebody
   // needs a dW (the LU chain) and at the end of the pass. ~630 reduce launches of ~7 us per training step become ~40.
@@ -82,114 +147,84 @@
   // that produced its dL/dpre, and the pass joins that stream before it touches a dW again (LU chain, log-det terms, return). Both
   // halves are latency-bound on their own at training sizes (100-400 blocks per launch); side by side they fill each other's gaps.
   // HCF_NO_WGRAD_STREAM=1: everything on the caller's stream (A/B).
-  hipStream_t wg_stream = nullptr;
-  hipEvent_t wg_ev = nullptr, wg_done = nullptr;
-  bool wg_async = false;
-  hipStream_t wgs() const { return wg_async ? wg_stream : st; }
+  SideStream wg_stream;
+  hipStream_t wgs() const { return tape->bwd.wg_async ? wg_stream.s : st; }
   void wg_begin_pass() {
     static const bool off = getenv("HCF_NO_WGRAD_STREAM") != nullptr;
-    wg_async = false;
-    if (off) return;
-    if (!wg_stream) {
-      wg_stream = aux_stream(0);                    // the process' pool (hcf_aux_stream): never more than two side streams per device
-      if (!wg_stream) return;
-      if (hipEventCreateWithFlags(&wg_ev, hipEventDisableTiming) != hipSuccess ||
-          hipEventCreateWithFlags(&wg_done, hipEventDisableTiming) != hipSuccess) {
-        wg_stream = nullptr; return;
-      }
-    }
-    wg_async = true;
+    tape->bwd.wg_async = !off && wg_stream.open(0);
   }
   // the caller's stream waits for everything the weight-gradient stream has been given so far
   void wg_join() {
-    if (!wg_async) return;
-    if (hipEventRecord(wg_done, wg_stream) != hipSuccess || hipStreamWaitEvent(st, wg_done, 0) != hipSuccess)
-      fail(HCF_ERR_HIP, "joining the weight-gradient stream failed");
+    if (tape->bwd.wg_async && !wg_stream.join(st)) fail(HCF_ERR_HIP, "joining the weight-gradient stream failed");
   }
   // Third stream: the data gradients that flow into a level's conditional features. Every conditional flow step adds its FCN conv1's
   // gradient w.r.t. the 128 feature channels (two 64-channel convs, ~65 us per step at 16 x 40 x 40) to ONE buffer that nothing reads
   // before the backward pass reaches the conditional net -- off the dependency chain they go, in program order on their own stream
   // (every writer of such a buffer: the accumulations stay ordered), joined by a tape entry in front of the conditional net's records.
   // HCF_NO_DG_STREAM=1: on the caller's stream (A/B).
-  hipStream_t dg_stream = nullptr;
-  hipEvent_t dg_ev = nullptr, dg_done = nullptr;
-  bool dg_async = false, dg_dirty = false;
-  std::vector<const float*> late_bufs;              // gradient buffers of the conditional features taped in this pass
-  bool is_late(const float* p) const { for (const float* q : late_bufs) if (q == p) return true; return false; }
+  SideStream dg_stream;
+  bool is_late(const float* p) const { for (const float* q : tape->late_bufs) if (q == p) return true; return false; }
   void dg_begin_pass() {
     static const bool off = getenv("HCF_NO_DG_STREAM") != nullptr;
-    dg_async = false; dg_dirty = false;
-    if (off || late_bufs.empty()) return;
-    if (!dg_stream) {
-      dg_stream = aux_stream(1);
-      if (!dg_stream) return;
-      if (hipEventCreateWithFlags(&dg_ev, hipEventDisableTiming) != hipSuccess ||
-          hipEventCreateWithFlags(&dg_done, hipEventDisableTiming) != hipSuccess) {
-        dg_stream = nullptr; return;
-      }
-    }
-    dg_async = true;
+    tape->bwd.dg_dirty = false;
+    tape->bwd.dg_async = !off && !tape->late_bufs.empty() && dg_stream.open(1);
   }
   void dg_join() {
-    if (!dg_async || !dg_dirty) return;
-    dg_dirty = false;
-    if (hipEventRecord(dg_done, dg_stream) != hipSuccess || hipStreamWaitEvent(st, dg_done, 0) != hipSuccess)
-      fail(HCF_ERR_HIP, "joining the conditional-feature gradient stream failed");
+    if (!tape->bwd.dg_async || !tape->bwd.dg_dirty) return;
+    tape->bwd.dg_dirty = false;
+    if (!dg_stream.join(st)) fail(HCF_ERR_HIP, "joining the conditional-feature gradient stream failed");
   }
-  std::vector<WgradReduceJob> wg_jobs;
-  WgradReduceJob* wg_jobs_dev = nullptr;
-  size_t wg_jobs_cap = 0, wg_used = 0;
+  float* wg_scratch = nullptr;            // the ring: partial dW tiles of the weight-gradient kernel (grown on demand)
+  size_t wg_cap = 0, wg_used = 0;
+  JobQueue<WgradReduceJob> wg_jobs;
   static constexpr size_t kWgRingFloats = (size_t)32 << 20;      // 128 MB
   static constexpr size_t kWgMaxJobs = 24;
   int flush_wgrad() {
-    if (wg_jobs.empty()) { wg_used = 0; return rc; }
-    if (rc != HCF_OK) { wg_jobs.clear(); wg_used = 0; return rc; }
+    if (wg_jobs.host.empty()) { wg_used = 0; return rc; }
+    if (rc != HCF_OK) { wg_jobs.host.clear(); wg_used = 0; return rc; }
     long long nblk = 0;
-    for (WgradReduceJob& j : wg_jobs) { j.blk0 = nblk; nblk += (long long)j.nbx * j.nicb * j.nocb; }
-    if (wg_jobs.size() > wg_jobs_cap) {
-      if (wg_jobs_dev) { hipStreamSynchronize(wgs()); hipFree(wg_jobs_dev); wg_jobs_dev = nullptr; wg_jobs_cap = 0; }
-      const size_t want = std::max<size_t>(kWgMaxJobs, wg_jobs.size());
-      if (hipMalloc((void**)&wg_jobs_dev, want * sizeof(WgradReduceJob)) != hipSuccess) return fail(HCF_ERR_NOMEM, "hipMalloc failed (wgrad jobs)");
-      wg_jobs_cap = want;
-    }
-    // pageable source: the runtime stages it before returning, so the vector may be reused right away
-    if (hipMemcpyAsync(wg_jobs_dev, wg_jobs.data(), wg_jobs.size() * sizeof(WgradReduceJob), hipMemcpyHostToDevice, wgs()) != hipSuccess)
-      return fail(HCF_ERR_HIP, "hipMemcpyAsync failed (wgrad jobs)");
-    const int r = launch_wgrad_reduce_batch(wg_jobs_dev, (int)wg_jobs.size(), nblk, wgs());
+    for (WgradReduceJob& j : wg_jobs.host) { j.blk0 = nblk; nblk += (long long)j.nbx * j.nicb * j.nocb; }
+    if (upload_jobs(wg_jobs, std::max<size_t>(kWgMaxJobs, wg_jobs.host.size()), wgs(), "wgrad") != HCF_OK) return rc;
+    const int r = launch_wgrad_reduce_batch(wg_jobs.dev, (int)wg_jobs.host.size(), nblk, wgs());
     ++launch_seq;
-    wg_jobs.clear();
+    wg_jobs.host.clear();
     wg_used = 0;
     if (r != HCF_OK) return fail(r, "weight-gradient reduce launch failed");
     return rc;
+  }
+  // room in the ring for `need` more floats and in the queue for `njobs` more reduce steps: the queue runs when either is full, and
+  // the ring grows once it is idle. HCF_ERR_NOMEM (not yet recorded by fail()) when it cannot.
+  int wg_reserve(size_t need, size_t njobs) {
+    if (wg_used + need <= wg_cap && wg_jobs.host.size() + njobs <= kWgMaxJobs) return HCF_OK;
+    if (flush_wgrad() != HCF_OK) return rc;
+    if (need > wg_cap) {
+      hipStreamSynchronize(wgs());
+      if (wg_scratch) hipFree(wg_scratch);
+      wg_scratch = nullptr;
+      wg_cap = 0;
+      const size_t want = std::max(need + need / 4, kWgRingFloats);
+      if (hipMalloc((void**)&wg_scratch, want * sizeof(float)) != hipSuccess) return HCF_ERR_NOMEM;
+      wg_cap = want;
+    }
+    return HCF_OK;
   }
   int run_wgrad(WgradArgs& w) {
     // beside the data-gradient chain (105 .. 160 blocks per launch at the training sizes) a full round of 256 blocks shares CUs
     // with it and slows both: 160 measured best (backward 45.0 / 43.3 / 42.4 / 42.7 / 43.9 / 50.0 ms at 256 / 192 / 160 / 144 /
     // 128 / 96, profiles/r04_notes.md); alone on the stream 256 stays best
-    w.blocks_hint = wg_async ? 160 : 0;
+    w.blocks_hint = tape->bwd.wg_async ? 160 : 0;
     const size_t need = (conv_wgrad_scratch_floats(w) + 63) & ~(size_t)63;
-    if (wg_used + need > wg_cap || wg_jobs.size() >= kWgMaxJobs) {
-      if (flush_wgrad() != HCF_OK) return rc;
-      if (need > wg_cap) {
-        hipStreamSynchronize(wgs());
-        if (wg_scratch) hipFree(wg_scratch);
-        wg_scratch = nullptr;
-        wg_cap = 0;
-        const size_t want = std::max(need + need / 4, kWgRingFloats);
-        if (hipMalloc((void**)&wg_scratch, want * sizeof(float)) != hipSuccess) return HCF_ERR_NOMEM;
-        wg_cap = want;
-      }
-    }
+    const int rr = wg_reserve(need, 1);
+    if (rr != HCF_OK) return rr;
     w.part = wg_scratch + wg_used;
     w.part_cap = need;
-    if (wg_async) {                                  // everything enqueued so far (this conv's epilogue backward) precedes the launch
-      if (hipEventRecord(wg_ev, st) != hipSuccess || hipStreamWaitEvent(wg_stream, wg_ev, 0) != hipSuccess) return HCF_ERR_HIP;
-    }
+    // everything enqueued so far (this conv's epilogue backward) precedes the launch
+    if (tape->bwd.wg_async && !wg_stream.fork(st)) return HCF_ERR_HIP;
     WgradReduceJob job;
     const int r = launch_conv_wgrad(w, wgs(), &job);
     if (r != HCF_OK) return r;
     wg_used += need;
-    wg_jobs.push_back(job);
+    wg_jobs.host.push_back(job);
     return HCF_OK;
   }
 
@@ -232,30 +267,17 @@
       need[i] = (conv_wgrad_scratch_floats(rdb_wg[i]) + 63) & ~(size_t)63;
       sum += need[i];
     }
-    if (wg_used + sum > wg_cap || wg_jobs.size() + n > kWgMaxJobs) {
-      if (flush_wgrad() != HCF_OK) { rdb_wg.clear(); return rc; }
-      if (sum > wg_cap) {
-        hipStreamSynchronize(wgs());
-        if (wg_scratch) hipFree(wg_scratch);
-        wg_scratch = nullptr;
-        wg_cap = 0;
-        const size_t want = std::max(sum + sum / 4, kWgRingFloats);
-        if (hipMalloc((void**)&wg_scratch, want * sizeof(float)) != hipSuccess) { rdb_wg.clear(); return fail(HCF_ERR_NOMEM, "hipMalloc failed (wgrad ring)"); }
-        wg_cap = want;
-      }
-    }
+    if (wg_reserve(sum, n) != HCF_OK) { rdb_wg.clear(); return rc != HCF_OK ? rc : fail(HCF_ERR_NOMEM, "hipMalloc failed (wgrad ring)"); }
     size_t off = wg_used;
     for (int i = 0; i < n; ++i) { rdb_wg[i].part = wg_scratch + off; rdb_wg[i].part_cap = need[i]; off += need[i]; }
-    if (wg_async) {
-      if (hipEventRecord(wg_ev, st) != hipSuccess || hipStreamWaitEvent(wg_stream, wg_ev, 0) != hipSuccess) { rdb_wg.clear(); return fail(HCF_ERR_HIP, "event on the weight-gradient stream failed"); }
-    }
+    if (tape->bwd.wg_async && !wg_stream.fork(st)) { rdb_wg.clear(); return fail(HCF_ERR_HIP, "event on the weight-gradient stream failed"); }
     WgradReduceJob jobs[kWgBatchMax];
     const int r = launch_conv_wgrad_batch(rdb_wg.data(), n, wgs(), jobs);
     ++launch_seq;
     rdb_wg.clear();
     if (r != HCF_OK) return fail(r, "batched weight-gradient launch failed");
     wg_used = off;
-    for (int i = 0; i < n; ++i) wg_jobs.push_back(jobs[i]);
+    for (int i = 0; i < n; ++i) wg_jobs.host.push_back(jobs[i]);
     return rc;
   }
 
@@ -264,7 +286,7 @@
     t.v = alloc(B, H, W, C);
     t.g.C = C;
     t.g.cs = ru4(C);
-    t.g.p = garena.alloc((size_t)B * H * W * t.g.cs);
+    t.g.p = tape->g.alloc((size_t)B * H * W * t.g.cs);
     return t;
   }
   static VG vg(const TB& t, int c0, int n, int up = 0) { VG r; r.v = t.v.v(c0, n, up); r.g = t.g.v(c0, n, up); return r; }
@@ -287,8 +309,8 @@
   }
   float* gp(const std::string& key) {
     auto it = poff.find(key);
-    if (it == poff.end()) { fail(HCF_ERR_KEY, "training: no gradient slot for " + key); return gparams; }
-    return gparams + it->second;
+    if (it == poff.end()) { fail(HCF_ERR_KEY, "training: no gradient slot for " + key); return tape->bwd.gparams; }
+    return tape->bwd.gparams + it->second;
   }
 
   // ---- one-time preparation: gradient offsets, transposed packs ---------------------------------------------------
@@ -322,7 +344,7 @@
   // it and by the record whose epilogue backward it fuses (the rows of partial sums differ: one per block of the launch).
   // HCF_DGRAD_WINO_MIN_PIX (default 4 096 = 64 x 64: at 40 x 40 both forms are one 24 us round) = smallest H * W that takes it.
   bool rdb_dgrad_wino(const Rdb* rdb, int m, int H, int W) const {
-    if (!rdb || m < 0 || m > 4 || !bwd_f16 || !rdb->gtw[m] || (long long)H * W < dgrad_wino_min_pix) return false;
+    if (!rdb || m < 0 || m > 4 || !tape->bwd.f16 || !rdb->gtw[m] || (long long)H * W < tape->bwd.dgrad_wino_min_pix) return false;
     // (the Winograd kernels address their sources with 31-bit byte offsets: the widest one is the block's 4 gc-channel gradient slab)
     if ((long long)B_ * H * W * std::max(4 * cfg.rrdb_gc, cfg.rrdb_nf) * 4 >= 0x7fffe000LL) return false;
     return conv_wino_rounds_ok(B_, H, W, m == 0 ? cfg.rrdb_nf / 32 : cfg.rrdb_gc / 32);
@@ -853,7 +875,7 @@
     const Conv* prev_cv;
   };
   bool rdb_fuse_ok(const Rdb* rdb, int m) const {
-    if (epi_fuse_off || !rdb || m < 1 || m > 4 || !bwd_f16 || !rdb->gt[m].wpack16 || (cfg.rrdb_gc & 3)) return false;
+    if (tape->bwd.epi_fuse_off || !rdb || m < 1 || m > 4 || !tape->bwd.f16 || !rdb->gt[m].wpack16 || (cfg.rrdb_gc & 3)) return false;
     const Conv& pc = rdb->c[m - 1];                    // the producer of x_m: LeakyReLU(conv + bias), no learned output scale
     return pc.act == ACT_LRELU && pc.lkey.empty();      // (no logs key: its scale array is all ones)
   }
@@ -861,12 +883,8 @@
   // buffers are sized for the larger per-image grid
   static int conv_tile_blocks(int B, int H, int W) { int sw = 0, th = 8; return conv_f16x3_scaled_blocks(B, H, W, &sw, &th); }
   static int conv_tile_blocks_max(int B, int H, int W) { return B * ((W + 31) / 32) * ((H + 3) / 4); }
-  bool bwd_f16 = false;        // data-gradient 3x3 convs on the f16x3 kernels (scaled by gmax)
-  long long dgrad_wino_min_pix = 4096;      // HCF_DGRAD_WINO_MIN_PIX, read at the start of each backward pass
-  bool epi_fuse_off = false;   // HCF_NO_EPI_FUSE (A/B knob), read at the start of each backward pass
-  bool fcn_fuse_off = false;   // HCF_NO_FCN_FUSE (A/B knob), likewise
   bool gen_fuse_ok(const Conv& consumer) const {
-    return !epi_fuse_off && !fcn_fuse_off && bwd_f16 && consumer.nsrc == 1 && consumer.tpacks.size() == 1 && consumer.tpacks[0].wpack16 &&
+    return !tape->bwd.epi_fuse_off && !tape->bwd.fcn_fuse_off && tape->bwd.f16 && consumer.nsrc == 1 && consumer.tpacks.size() == 1 && consumer.tpacks[0].wpack16 &&
            (consumer.taps == 9 || consumer.taps == 1) && (consumer.src_n[0] & 3) == 0 && consumer.src_n[0] <= 64;
   }
 
@@ -903,7 +921,7 @@
     // weight gradient on the f16 matrix cores: only where the taped FORWARD of this very layer ran on the f16x3 kernels, whose
     // range check then covered X (run_conv: 3x3 / stand-alone 1x1 with an f16x3 pack); > 64 output channels ran exactly, their
     // inputs were never checked -> fp32 weight-gradient kernel
-    if (bwd_f16 && tape_f16 && (cv.taps == 9 || cv.taps == 1) && cv.wpack16) w.g_max = r.gmax;
+    if (tape->bwd.f16 && tape->f16 && (cv.taps == 9 || cv.taps == 1) && cv.wpack16) w.g_max = r.gmax;
     if (r.rdb) {
       rdb_wg.push_back(w);                             // the block's five weight gradients go out as one launch (flush_rdb_wgrad)
       if (r.rdb_m == 0 && flush_rdb_wgrad() != HCF_OK) return;
@@ -925,7 +943,7 @@
       a.res1 = a.out; a.rs1 = 1.f;                      // accumulate (x_0 also feeds the block's residual path)
       int lr_ = HCF_ERR_UNSUPPORTED;
       const bool fuse = rdb_fuse_ok(r.rdb, r.rdb_m);
-      if (bwd_f16 && tp.wpack16 && rc == HCF_OK) {
+      if (tape->bwd.f16 && tp.wpack16 && rc == HCF_OK) {
         ConvArgs f = a;
         f.wpack = tp.wpack16;
         f.ovf = ovf_flag;
@@ -954,13 +972,13 @@
       if (!gs.p) continue;
       const int up = r.src[tp.src].up;
       hipStream_t ls = st;
-      if (dg_async && up == 0 && ((r.late_mask >> tp.src) & 1)) {      // into a conditional-feature gradient: off the chain (dg_stream)
+      if (tape->bwd.dg_async && up == 0 && ((r.late_mask >> tp.src) & 1)) {      // into a conditional-feature gradient: off the chain (dg_stream)
         if (!dg_waits) {                               // behind this conv's epilogue backward
-          if (hipEventRecord(dg_ev, st) != hipSuccess || hipStreamWaitEvent(dg_stream, dg_ev, 0) != hipSuccess) { fail(HCF_ERR_HIP, "event on the conditional-feature gradient stream failed"); return; }
+          if (!dg_stream.fork(st)) { fail(HCF_ERR_HIP, "event on the conditional-feature gradient stream failed"); return; }
           dg_waits = true;
         }
-        ls = dg_stream;
-        dg_dirty = true;
+        ls = dg_stream.s;
+        tape->bwd.dg_dirty = true;
       }
       ConvArgs a;
       memset(&a, 0, sizeof(a));
@@ -977,7 +995,7 @@
         a.out = mkview(r.uptmp[tp.src], ru4(r.src[tp.src].n), tp.c0, tp.n);
       }
       int lr_ = HCF_ERR_UNSUPPORTED;
-      if (bwd_f16 && tp.wpack16 && (cv.taps == 9 || cv.taps == 1) && rc == HCF_OK) {
+      if (tape->bwd.f16 && tp.wpack16 && (cv.taps == 9 || cv.taps == 1) && rc == HCF_OK) {
         ConvArgs f = a;
         f.wpack = tp.wpack16;
         f.ovf = ovf_flag;
@@ -1045,14 +1063,14 @@
     } else if (link && link->own_part) {
       r.gmax = link->own_gmax; r.part = link->own_part;
     } else {
-      r.gmax = garena.alloc(1);
-      r.part = garena.alloc((size_t)conv_epilogue_bwd_blocks(B_, H, W) * 2 * cv.cout);
+      r.gmax = tape->g.alloc(1);
+      r.part = tape->g.alloc((size_t)conv_epilogue_bwd_blocks(B_, H, W) * 2 * cv.cout);
     }
     if (link) {
       r.next_cv = link->next; r.prev_cv = link->prev;
       if (link->prev) { r.prev_y = link->prev_y; r.prev_part = link->prev_part; r.prev_gmax = link->prev_gmax; }
     }
-    if (!dry()) tape.push_back([this, r]() { bwd_conv(r); });
+    if (!dry()) tape->recs.push_back([this, r]() { bwd_conv(r); });
   }
 
   // ---- flow step --------------------------------------------------------------------------------------------------
@@ -1075,8 +1093,8 @@
       const size_t rows = (size_t)std::max(conv_epilogue_bwd_blocks(B_, H, W), conv_tile_blocks_max(B_, H, W)) * 2;
       EpiLink l0, l1, l2;
       memset(&l0, 0, sizeof(l0)); memset(&l1, 0, sizeof(l1)); memset(&l2, 0, sizeof(l2));
-      l0.own_part = garena.alloc(rows * s.c[0].cout); l0.own_gmax = garena.alloc(1); l0.next = &s.c[1];
-      l1.own_part = garena.alloc(rows * s.c[1].cout); l1.own_gmax = garena.alloc(1); l1.next = &s.c[2];
+      l0.own_part = tape->g.alloc(rows * s.c[0].cout); l0.own_gmax = tape->g.alloc(1); l0.next = &s.c[1];
+      l1.own_part = tape->g.alloc(rows * s.c[1].cout); l1.own_gmax = tape->g.alloc(1); l1.next = &s.c[2];
       l1.prev = &s.c[0]; l1.prev_y = h1.v.v(0, s.hid); l1.prev_part = l0.own_part; l1.prev_gmax = l0.own_gmax;
       l2.prev = &s.c[1]; l2.prev_y = h2.v.v(0, s.hid); l2.prev_part = l1.own_part; l2.prev_gmax = l1.own_gmax;
       t_conv(s.c[0], in, H, W, vg(h1, 0, s.hid), nullptr, 0.f, nullptr, 0.f, nullptr, &l0);
@@ -1103,8 +1121,8 @@
     a.z = zin.v.all(); a.out = zb.v.all(); a.aux = za.all();
     a.mat = s.has_mat ? s.mat_fwd : nullptr; a.an_bias = s.bias; a.an_mul = s.mul_fwd;
     HCF_LAUNCH(launch_step_head_fwd(a, st));
-    float* const spart = garena.alloc((size_t)B_ * step_blocks_per_sample(H, W) * 2 * s.cmax);
-    if (!dry()) tape.push_back([this, sp, zin, zb, za, H, W, spart]() {
+    float* const spart = tape->g.alloc((size_t)B_ * step_blocks_per_sample(H, W) * 2 * s.cmax);
+    if (!dry()) tape->recs.push_back([this, sp, zin, zb, za, H, W, spart]() {
       const Step& s = *sp;
       StepBwdArgs b;
       memset(&b, 0, sizeof(b));
@@ -1115,7 +1133,7 @@
       b.part = spart;
       HCF_LAUNCH(launch_step_head_bwd(b, st));
       add_sum_job(spart, B_ * step_blocks_per_sample(H, W), s.C, s.cmax, b.g_bias, b.g_logs, 1.f);
-      const float k = gobj * (float)B_ * (float)H * (float)W;          // d(sum_b logdet_b): logs * pixels, slogdet W * pixels
+      const float k = tape->bwd.gobj * (float)B_ * (float)H * (float)W;          // d(sum_b logdet_b): logs * pixels, slogdet W * pixels
       add_axpy_job(nullptr, b.g_logs, s.C, k);
       if (s.has_mat) {
         WgradArgs w;
@@ -1138,14 +1156,14 @@
       pslot += step_blocks_per_sample(H, W);
     }
     HCF_LAUNCH(launch_step_couple_fwd(a, st));
-    if (!dry()) tape.push_back([this, sp, zb, zout, ho, H, W]() {
+    if (!dry()) tape->recs.push_back([this, sp, zb, zout, ho, H, W]() {
       const Step& s = *sp;
       StepBwdArgs b;
       memset(&b, 0, sizeof(b));
       b.B = B_; b.H = H; b.W = W; b.C = s.C; b.ns = s.ns; b.mode = s.mode;
       b.gzout = zout.g.all(); b.zout = zout.v.all(); b.h = ho.v.v(0, s.f_out);
       b.gzb = zb.g.all(); b.gh = ho.g.v(0, s.f_out);
-      b.gobj = gobj;
+      b.gobj = tape->bwd.gobj;
       HCF_LAUNCH(launch_step_couple_bwd(b, st));
     });
     return zout;
@@ -1157,11 +1175,11 @@
     TB grow = talloc(B_, H, W, 4 * gc);
     RdbCtx ctx[5];
     if (r.gather) {
-      float* const gmax2 = garena.alloc(5);
+      float* const gmax2 = tape->g.alloc(5);
       // every conv's max slot and partial-sum rows up front: the gather conv of x_m writes conv m's (fused epilogue backward)
       const size_t rows = (size_t)std::max(conv_epilogue_bwd_blocks(B_, H, W), conv_tile_blocks_max(B_, H, W)) * 2;
       float *gm[5], *pt[5];
-      for (int i = 0; i < 5; ++i) { gm[i] = garena.alloc(1); pt[i] = garena.alloc(rows * (i < 4 ? gc : nf)); }
+      for (int i = 0; i < 5; ++i) { gm[i] = tape->g.alloc(1); pt[i] = tape->g.alloc(rows * (i < 4 ? gc : nf)); }
       const View none = mkview(nullptr, 0, 0, 0);
       for (int m = 0; m < 5; ++m) {                    // ctx[m]: the record of conv index m (its output: x_{m+1}), which gathers dL/dx_m
         ctx[m].rdb = &r; ctx[m].m = m;
@@ -1179,7 +1197,7 @@
     // conv 2j+2 as one 64-wide launch + the completion; same tensors x_1 .. x_4, out in the same buffers), then one tape record per
     // conv: the backward pass needs each conv's inputs and output, not the launches that produced them
     const View none_v = mkview(nullptr, 0, 0, 0);
-    run_rdb(r, xin.v, grow.v, H, W, out.v, res2 ? res2->v : none_v, rs2, tfat.p ? &tfat : nullptr);
+    run_rdb(r, xin.v, grow.v, H, W, out.v, res2 ? res2->v : none_v, rs2, tape->tfat.p ? &tape->tfat : nullptr);
     for (int i = 0; i < 4; ++i) {
       std::vector<VG> in;
       in.push_back(xin);
@@ -1188,7 +1206,6 @@
     }
     t_conv(r.c[4], {xin, vg(grow, 0, 4 * gc)}, H, W, out, &xin, 0.2f, res2, rs2, r.gather ? &ctx[4] : nullptr, nullptr, true);
   }
-  Buf tfat;                                // the fat launches' stored partial sum (consumed by the completion behind it): one per conditional net
 
   void t_rrdb(const Rrdb& rr, VG x0, VG out, int H, int W) {
     const int nf = cfg.rrdb_nf;
@@ -1205,7 +1222,7 @@
     const bool srn = sr();
     TB f0 = talloc(B_, H, W, nf);
     t_conv(cf.conv_first, u, H, W, vgall(f0));
-    tfat = alloc(B_, H, W, cfg.rrdb_gc);
+    tape->tfat = alloc(B_, H, W, cfg.rrdb_gc);
     VG cur = vgall(f0);
     const VG f1 = vg(cfb, 0, nf);
     for (size_t n = 0; n < cf.trunk0.size(); ++n) {
@@ -1217,7 +1234,7 @@
     if (srn && cf.trunk0.empty()) {
       HCF_LAUNCH(launch_copy_view(cur.v, f1.v, B_, H, W, st));
       const VG src = cur;
-      if (!dry()) tape.push_back([this, src, f1, H, W]() { HCF_LAUNCH(launch_add_view(f1.g, src.g, B_, H, W, 1.f, st)); });
+      if (!dry()) tape->recs.push_back([this, src, f1, H, W]() { HCF_LAUNCH(launch_add_view(f1.g, src.g, B_, H, W, 1.f, st)); });
       cur = f1;
     }
     for (size_t n = 0; n < cf.trunk1.size(); ++n) {
@@ -1230,21 +1247,16 @@
     if (!dry() && cfb.g.p) {
       // everything taped AFTER this point that reads the features adds its gradient to cfb.g on dg_stream (bwd_conv); the entry below
       // runs in front of the records above: the conditional net's backward starts from the complete gradient
-      late_bufs.push_back(cfb.g.p);
-      tape.push_back([this]() { dg_join(); });
+      tape->late_bufs.push_back(cfb.g.p);
+      tape->recs.push_back([this]() { dg_join(); });
     }
   }
 
   // ---- the taped forward pass of the rescaling net: HCFlowNet_Rescaling.normal_flow_diracLR (:39-46) ------------------
-  const float* g_fwd_lr = nullptr;          // upstream gradients of (clamp(LR^), z1, z2), set by run_backward
-  const float* g_fwd_z[2] = {nullptr, nullptr};
 
   void pass_train_forward_rescale(const float* hr, float* out_lr, float* out_z1, float* out_z2, int B, int H0, int W0,
                                   uint32_t flags) {
-    B_ = B;
-    arena.top = 0;
-    garena.top = 0;
-    if (!dry()) { tape.clear(); late_bufs.clear(); tape_mark = 0; tape_mid = false; }
+    tape_begin(B);
     const int L = cfg.L;
     int pslot = 0;
     std::vector<TB> zlev(L), cfb(L);
@@ -1260,7 +1272,7 @@
         HCF_LAUNCH(launch_haar_fwd(prev.v.v(0, up.ns), z.v.all(), B, up.ns, H * 2, W * 2, st));
         Buf tmp = alloc(B, H * 2, W * 2, up.ns);
         const int C4 = lv.C, ns = up.ns;
-        if (!dry()) tape.push_back([this, z, prev, tmp, C4, ns, H, W]() {      // (Haar fwd)^T = Haar inv / 4
+        if (!dry()) tape->recs.push_back([this, z, prev, tmp, C4, ns, H, W]() {      // (Haar fwd)^T = Haar inv / 4
           HCF_LAUNCH(launch_haar_inv(z.g.all(), tmp.all(), B_, C4, H, W, st));
           HCF_LAUNCH(launch_add_view(tmp.all(), prev.g.v(0, ns), B_, H * 2, W * 2, 0.25f, st));
         });
@@ -1279,7 +1291,7 @@
       {
         const TB a0 = a;
         const int ns = lv.ns, Ca = cf.Ca;
-        if (!dry()) tape.push_back([this, a0, zl, ns, Ca, H, W]() {
+        if (!dry()) tape->recs.push_back([this, a0, zl, ns, Ca, H, W]() {
           HCF_LAUNCH(launch_add_view(a0.g.all(), zl.g.v(ns, Ca), B_, H, W, 1.f, st));
         });
       }
@@ -1302,13 +1314,13 @@
       {
         const TB af = a;
         const int Ca = cf.Ca, zi = (level == 0) ? 0 : 1;
-        if (!dry()) tape.push_back([this, af, ho, Ca, zi, H, W]() {
+        if (!dry()) tape->recs.push_back([this, af, ho, Ca, zi, H, W]() {
           PriorBwdArgs p;
           memset(&p, 0, sizeof(p));
           p.B = B_; p.H = H; p.W = W; p.C = Ca;
           p.a = af.v.all(); p.h = ho.v.v(0, 2 * Ca); p.ga = af.g.all(); p.gh = ho.g.v(0, 2 * Ca);
           p.rescale = 1;
-          p.gz_nchw = g_fwd_z[zi];
+          p.gz_nchw = tape->bwd.g_fwd_z[zi];
           HCF_LAUNCH(launch_gauss_encode_bwd(p, st));
         });
       }
@@ -1317,18 +1329,15 @@
     const TB zd = zlev[L - 1];
     const int clamp = (flags & HCF_FLAG_NO_CLAMP) ? 0 : 1;
     HCF_LAUNCH(launch_nhwc_to_nchw(zd.v.v(0, 3), out_lr, B, 3, h, w, clamp, st));
-    if (!dry()) tape.push_back([this, zd, h, w, clamp]() {
-      if (g_fwd_lr) HCF_LAUNCH(launch_add_nchw_grad(g_fwd_lr, zd.v.v(0, 3), zd.g.v(0, 3), B_, h, w, clamp, st));
+    if (!dry()) tape->recs.push_back([this, zd, h, w, clamp]() {
+      if (tape->bwd.g_fwd_lr) HCF_LAUNCH(launch_add_nchw_grad(tape->bwd.g_fwd_lr, zd.v.v(0, 3), zd.g.v(0, 3), B_, h, w, clamp, st));
     });
   }
 
   // ---- the taped forward pass: HCFlowNet_SR.normal_flow_diracLR (HCFlowNet_SR_arch.py:47-67) ------------------------
   void pass_train_forward_sr(const float* hr, const float* lr, const float* noise, float* out_lr, float* out_nll,
                              float* out_logdet, int B, int H0, int W0) {
-    B_ = B;
-    arena.top = 0;
-    garena.top = 0;
-    if (!dry()) { tape.clear(); late_bufs.clear(); tape_mark = 0; tape_mid = false; }
+    tape_begin(B);
     const int L = cfg.L;
     int nslots = 0;
     for (int level = 0; level < L; ++level) {
@@ -1352,7 +1361,7 @@
         HCF_LAUNCH(launch_squeeze(prev.v.v(0, up.ns), z.v.all(), B, up.ns, H * 2, W * 2, st));
         Buf tmp = alloc(B, H * 2, W * 2, up.ns);
         const int C4 = lv.C, ns = up.ns;
-        if (!dry()) tape.push_back([this, z, prev, tmp, C4, ns, H, W]() {
+        if (!dry()) tape->recs.push_back([this, z, prev, tmp, C4, ns, H, W]() {
           HCF_LAUNCH(launch_unsqueeze(z.g.all(), tmp.all(), B_, C4, H, W, st));
           HCF_LAUNCH(launch_add_view(tmp.all(), prev.g.v(0, ns), B_, H * 2, W * 2, 1.f, st));
         });
@@ -1368,11 +1377,11 @@
       const TB zl = zlev[level];
       TB a = talloc(B, H, W, cf.Ca);
       HCF_LAUNCH(launch_copy_view(zl.v.v(lv.ns, cf.Ca), a.v.all(), B, H, W, st));
-      if (level == 0 && !dry()) tape_mark = tape.size();      // from here on: level-0 conditional flow + the output terms (two-phase backward)
+      if (level == 0 && !dry()) tape->mark = tape->recs.size();      // from here on: level-0 conditional flow + the output terms (two-phase backward)
       {
         const TB a0 = a;
         const int ns = lv.ns, Ca = cf.Ca;
-        if (!dry()) tape.push_back([this, a0, zl, ns, Ca, H, W]() {
+        if (!dry()) tape->recs.push_back([this, a0, zl, ns, Ca, H, W]() {
           HCF_LAUNCH(launch_add_view(a0.g.all(), zl.g.v(ns, Ca), B_, H, W, 1.f, st));       // Split: z = cat(z1, a)
         });
       }
@@ -1396,12 +1405,12 @@
       {
         const TB af = a;
         const int Ca = cf.Ca;
-        if (!dry()) tape.push_back([this, af, ho, Ca, H, W]() {
+        if (!dry()) tape->recs.push_back([this, af, ho, Ca, H, W]() {
           PriorBwdArgs p;
           memset(&p, 0, sizeof(p));
           p.B = B_; p.H = H; p.W = W; p.C = Ca;
           p.a = af.v.all(); p.h = ho.v.v(0, 2 * Ca); p.ga = af.g.all(); p.gh = ho.g.v(0, 2 * Ca);
-          p.gobj = gobj;
+          p.gobj = tape->bwd.gobj;
           HCF_LAUNCH(launch_gauss_logp_bwd(p, st));
         });
       }
@@ -1411,8 +1420,8 @@
     float* pp = partial + pslot;
     pslot += step_blocks_per_sample(h, w);
     HCF_LAUNCH(launch_quant_logp(zd.v.v(0, 3), lr, out_lr, B, h, w, pp, nslots, st));
-    if (!dry()) tape.push_back([this, zd, lr, h, w]() {
-      HCF_LAUNCH(launch_quant_logp_bwd(zd.v.v(0, 3), lr, zd.g.v(0, 3), B_, h, w, gobj, st));
+    if (!dry()) tape->recs.push_back([this, zd, lr, h, w]() {
+      HCF_LAUNCH(launch_quant_logp_bwd(zd.v.v(0, 3), lr, zd.g.v(0, 3), B_, h, w, tape->bwd.gobj, st));
     });
     if (pslot > nslots) fail(HCF_ERR_STATE, "internal: partial slot overflow (training)");
     double ld_const = -log((double)cfg.quant) * (double)H0 * W0;
@@ -1422,9 +1431,8 @@
       for (const Step& s : levels[level].cf.steps) ld_const += s.ld_const * px;
     }
     HCF_LAUNCH(launch_reduce_partials(partial, nslots, nslots, B, ld_const, (double)H0 * W0, out_logdet, out_nll, st));
-    t_pixels = (double)H0 * W0;
+    tape->pixels = (double)H0 * W0;
   }
-  double t_pixels = 0;
 
   // ================= reverse (sampling) path with gradients: HCFlowNet_SR.reverse_flow_diracLR =======================
   // (the HR pixel / GAN losses of the HCFlow+ / ++ recipes, HCFlow_SR_model.py:207-255)
@@ -1439,8 +1447,8 @@
     a.z = zin.v.all(); a.h = ho.v.v(0, s.f_out); a.out = x.v.all(); a.aux = zc.v.all();
     a.mat = s.has_mat ? s.mat_inv : nullptr; a.an_bias = s.bias; a.an_mul = s.mul_inv;
     HCF_LAUNCH(launch_step_tail_inv(a, st));
-    float* const spart = garena.alloc((size_t)B_ * step_blocks_per_sample(H, W) * 2 * s.cmax);
-    if (!dry()) tape.push_back([this, sp, zin, zc, x, y, ho, H, W, spart]() {
+    float* const spart = tape->g.alloc((size_t)B_ * step_blocks_per_sample(H, W) * 2 * s.cmax);
+    if (!dry()) tape->recs.push_back([this, sp, zin, zc, x, y, ho, H, W, spart]() {
       const Step& s = *sp;
       StepInvBwdArgs b;
       memset(&b, 0, sizeof(b));
@@ -1466,15 +1474,10 @@
     return x;
   }
 
-  const float* g_out_nchw = nullptr;       // dL / d output of the taped inverse pass (set by run_backward_inverse)
-  float* g_in_nchw = nullptr;              // optional: receives dL / d lr of the taped inverse pass
 
   void pass_train_inverse(const float* lr, const float* const* eps, int n_eps, float tau, uint64_t seed, float* out,
                           int B, int h, int w, uint32_t flags) {
-    B_ = B;
-    arena.top = 0;
-    garena.top = 0;
-    if (!dry()) { tape.clear(); late_bufs.clear(); tape_mark = 0; tape_mid = false; }
+    tape_begin(B);
     const int L = cfg.L;
     std::vector<TB> cfb(L);
     TB zprev;
@@ -1487,8 +1490,8 @@
       TB z = talloc(B, H, W, lv.C);
       if (level == L - 1) {
         HCF_LAUNCH(launch_nchw_to_nhwc(lr, z.v.v(0, 3), B, 3, H, W, st));
-        if (!dry()) tape.push_back([this, z, H, W]() {                                     // d / d lr (last to run)
-          if (g_in_nchw) HCF_LAUNCH(launch_nhwc_to_nchw(z.g.v(0, 3), g_in_nchw, B_, 3, H, W, 0, st));
+        if (!dry()) tape->recs.push_back([this, z, H, W]() {                                     // d / d lr (last to run)
+          if (tape->bwd.g_in_nchw) HCF_LAUNCH(launch_nhwc_to_nchw(z.g.v(0, 3), tape->bwd.g_in_nchw, B_, 3, H, W, 0, st));
         });
       } else {
         const Level& dp = levels[level + 1];
@@ -1497,13 +1500,13 @@
         if (cfg.squeeze == HCF_SQUEEZE_HAAR) {
           HCF_LAUNCH(launch_haar_inv(zp.v.all(), z.v.v(0, lv.ns), B, dp.C, H / 2, W / 2, st));
           Buf tmp = alloc(B, H / 2, W / 2, dp.C);
-          if (!dry()) tape.push_back([this, z, zp, tmp, ns, H, W]() {                     // (Haar inv)^T = 4 Haar fwd
+          if (!dry()) tape->recs.push_back([this, z, zp, tmp, ns, H, W]() {                     // (Haar inv)^T = 4 Haar fwd
             HCF_LAUNCH(launch_haar_fwd(z.g.v(0, ns), tmp.all(), B_, ns, H, W, st));
             HCF_LAUNCH(launch_add_view(tmp.all(), zp.g.all(), B_, H / 2, W / 2, 4.f, st));
           });
         } else {
           HCF_LAUNCH(launch_unsqueeze(zp.v.all(), z.v.v(0, lv.ns), B, dp.C, H / 2, W / 2, st));
-          if (!dry()) tape.push_back([this, z, zp, ns, H, W]() {
+          if (!dry()) tape->recs.push_back([this, z, zp, ns, H, W]() {
             HCF_LAUNCH(launch_squeeze(z.g.v(0, ns), zp.g.all(), B_, ns, H, W, st));        // (=): its only consumer
           });
         }
@@ -1529,7 +1532,7 @@
         HCF_LAUNCH(launch_gauss_sample(g, st));
         const TB a0 = a;
         const int Ca = cf.Ca;
-        if (!dry()) tape.push_back([this, a0, ho, Ca, H, W]() {
+        if (!dry()) tape->recs.push_back([this, a0, ho, Ca, H, W]() {
           PriorBwdArgs p;
           memset(&p, 0, sizeof(p));
           p.B = B_; p.H = H; p.W = W; p.C = Ca;
@@ -1543,7 +1546,7 @@
       {
         const TB af = a;
         const int ns = lv.ns, Ca = cf.Ca;
-        if (!dry()) tape.push_back([this, af, z, ns, Ca, H, W]() {
+        if (!dry()) tape->recs.push_back([this, af, z, ns, Ca, H, W]() {
           HCF_LAUNCH(launch_copy_view(z.g.v(ns, Ca), af.g.all(), B_, H, W, st));
         });
       }
@@ -1560,15 +1563,15 @@
         float* gm = (haar) ? arena.alloc(nout) : nullptr;
         Buf tmp = haar ? alloc(B, H, W, C0) : Buf{nullptr, 0, 0};
         if (raw) HCF_LAUNCH(launch_unsqueeze_nchw(zz.v.all(), raw, B, lv.C, H, W, haar, 0, st));
-        if (!dry()) tape.push_back([this, zz, C0, H, W, clamp, haar, raw, gm, tmp, nout]() {
+        if (!dry()) tape->recs.push_back([this, zz, C0, H, W, clamp, haar, raw, gm, tmp, nout]() {
           if (!haar) {
             // out = clamp(unsqueeze2d(z)): gradient = squeeze2d(g_out), zeroed where the raw value left [0, 1]
-            HCF_LAUNCH(launch_nchw_squeeze(g_out_nchw, nullptr, 1.f, zz.g.all(), B_, C0 / 4, H * 2, W * 2, 0, st));
+            HCF_LAUNCH(launch_nchw_squeeze(tape->bwd.g_out_nchw, nullptr, 1.f, zz.g.all(), B_, C0 / 4, H * 2, W * 2, 0, st));
             if (clamp) HCF_LAUNCH(launch_mask_unit_range(zz.v.all(), zz.g.all(), B_, H, W, st));
           } else {
             // out = clamp(Haar^-1 z): gradient = (Haar^-1)^T (g_out * mask) = 4 Haar(g_out * mask)
-            const float* g = g_out_nchw;
-            if (clamp) { HCF_LAUNCH(launch_mask_flat(g_out_nchw, raw, gm, nout, st)); g = gm; }
+            const float* g = tape->bwd.g_out_nchw;
+            if (clamp) { HCF_LAUNCH(launch_mask_flat(tape->bwd.g_out_nchw, raw, gm, nout, st)); g = gm; }
             HCF_LAUNCH(launch_nchw_squeeze(g, nullptr, 1.f, tmp.all(), B_, C0 / 4, H * 2, W * 2, 1, st));
             HCF_LAUNCH(launch_add_view(tmp.all(), zz.g.all(), B_, H, W, 4.f, st));
           }
@@ -1577,61 +1580,40 @@
     }
   }
 
-  // Two tapes can be alive at once (the rescaling step differentiates forward -> Quant -> inverse as ONE graph): a
-  // slot owns its activation / gradient arenas and closures and is swapped into the engine's working members for
-  // the duration of a taped pass or a backward pass.
-  struct TapeSlot {
-    Arena a, g;
-    std::vector<std::function<void()>> tape;
-    std::vector<const float*> late;                  // late_bufs of this tape
-    bool valid = false, f16 = false;
-    int kind = 0, B = 0;
-    double pixels = 0;
-    size_t mark = 0;                                 // tape_mark of this tape
-    bool mid = false;                                // phase 0 of a two-phase backward has run on this tape (hcf_train_backward_phase)
-  };
-  TapeSlot slots[2];
-  // Two-phase backward of the NLL pass (DDP overlap, HCFlow_SR_model.py:33-36): records [tape_mark, end) are the level-0 conditional
-  // flow (taped last, so first in the backward pass) + the output terms; after them every gradient of the parameters under
-  // "flow.level0_condFlow." is final, the caller can hand them to its gradient all-reduce while phase 1 runs the rest.
-  size_t tape_mark = 0;
-  bool tape_mid = false;
-  int cur_slot = 0;
-  void slot_swap() {
-    TapeSlot& t = slots[cur_slot];
-    std::swap(arena, t.a); std::swap(garena, t.g); tape.swap(t.tape); late_bufs.swap(t.late);
-    std::swap(tape_valid, t.valid); std::swap(tape_kind, t.kind); std::swap(B_, t.B); std::swap(t_pixels, t.pixels);
-    std::swap(tape_f16, t.f16);      // per tape: slot 0 may have fallen back to the exact kernels while slot 1 did not
-    std::swap(tape_mark, t.mark); std::swap(tape_mid, t.mid);
+  // a taped pass starts (each walk of it: sizing run, real run, exact re-run)
+  void tape_begin(int B) {
+    B_ = B;
+    arena.top = 0;
+    tape->g.top = 0;
+    if (!dry()) { tape->recs.clear(); tape->late_bufs.clear(); tape->mark = 0; tape->mid = false; }
   }
-  void invalidate_tapes() { slots[0].valid = slots[1].valid = false; }
 
-  int train_prepare(hipStream_t stream) {
+  // A taped pass of kind `kind` (Tape::kind) on the selected slot: sizing run, arenas, real run (+ exact re-run when an activation left
+  // the f16 range). `wrong_net`: the refusal when this engine's net has no such pass (null: it has).
+  template <class F>
+  int run_train(int kind, const char* wrong_net, hipStream_t stream, F&& body) {
     if (!finalized) return fail(HCF_ERR_STATE, "hcf_finalize() has not been called");
     if (hipSetDevice(device) != hipSuccess) return fail(HCF_ERR_HIP, "hipSetDevice failed");
     rc = HCF_OK;
     st = stream;
-    tape_valid = false;
-    return ensure_train_ready();
-  }
-
-  template <class F>
-  int train_run(F&& body) {          // sizing run, arenas, real run (+ exact re-run when an activation left the f16 range)
+    if (ensure_train_ready() != HCF_OK) return rc;
+    if (wrong_net) return fail(HCF_ERR_STATE, wrong_net);
+    tape_swap();
     taping = true;
     tape_fat = getenv("HCF_NO_TAPE_FAT") == nullptr;
-    tfat.p = nullptr;
+    tape->tfat.p = nullptr;
     cc_valid = false;
     use_f16 = (precision == PREC_F16X3);          // forward convs; fused epilogues are off while taping
-    arena.dry = garena.dry = true;
-    arena.peak = garena.peak = 0;
+    arena.dry = tape->g.dry = true;
+    arena.peak = tape->g.peak = 0;
     body();
-    arena.dry = garena.dry = false;
+    arena.dry = tape->g.dry = false;
     if (rc == HCF_OK) ensure_arena(arena.peak);
-    if (rc == HCF_OK && garena.peak > garena.cap) {
-      if (garena.base) { hipStreamSynchronize(st); hipFree(garena.base); garena.base = nullptr; garena.cap = 0; }
+    if (rc == HCF_OK && tape->g.peak > tape->g.cap) {
+      if (tape->g.base) { hipStreamSynchronize(st); hipFree(tape->g.base); tape->g.base = nullptr; tape->g.cap = 0; }
       void* p = nullptr;
-      if (hipMalloc(&p, garena.peak) != hipSuccess) fail(HCF_ERR_NOMEM, "hipMalloc failed for the gradient arena");
-      else { garena.base = (char*)p; garena.cap = garena.peak; }
+      if (hipMalloc(&p, tape->g.peak) != hipSuccess) fail(HCF_ERR_NOMEM, "hipMalloc failed for the gradient arena");
+      else { tape->g.base = (char*)p; tape->g.cap = tape->g.peak; }
     }
     if (rc == HCF_OK && precision == PREC_F16X3) {
       ovf_latch();                   // an unread overflow of an earlier lazy inference pass survives the memset below
@@ -1651,44 +1633,12 @@
         body();
       }
     }
-    tape_f16 = use_f16;              // the taped pass completed on the f16x3 kernels: every conv input is inside the f16 range
+    tape->f16 = use_f16;              // the taped pass completed on the f16x3 kernels: every conv input is inside the f16 range
     use_f16 = false;
     taping = false;
-    tape_valid = (rc == HCF_OK);
-    return rc;
-  }
-  bool tape_f16 = false;
-  int tape_kind = 0;                 // 1: NLL forward, 2: inverse (sampling) pass
-
-  int run_train_inverse(const float* lr, const float* const* eps, int n_eps, float tau, uint64_t seed, float* out, int B,
-                        int h, int w, uint32_t flags, hipStream_t stream) {
-    if (train_prepare(stream) != HCF_OK) return rc;
-    slot_swap();
-    train_run([&]() { pass_train_inverse(lr, eps, n_eps, tau, seed, out, B, h, w, flags); });
-    tape_kind = 2;
-    slot_swap();
-    return rc;
-  }
-
-  int run_train_forward_rescale(const float* hr, float* out_lr, float* out_z1, float* out_z2, int B, int H0, int W0,
-                                uint32_t flags, hipStream_t stream) {
-    if (train_prepare(stream) != HCF_OK) return rc;
-    if (sr()) return fail(HCF_ERR_STATE, "hcf_train_forward_rescale on an SR engine");
-    slot_swap();
-    train_run([&]() { pass_train_forward_rescale(hr, out_lr, out_z1, out_z2, B, H0, W0, flags); });
-    tape_kind = 3;
-    slot_swap();
-    return rc;
-  }
-
-  int run_train_forward(const float* hr, const float* lr, const float* noise, float* out_lr, float* out_nll,
-                        float* out_logdet, int B, int H0, int W0, hipStream_t stream) {
-    if (train_prepare(stream) != HCF_OK) return rc;
-    if (!sr()) return fail(HCF_ERR_STATE, "hcf_train_forward_sr on a rescaling engine");
-    slot_swap();
-    train_run([&]() { pass_train_forward_sr(hr, lr, noise, out_lr, out_nll, out_logdet, B, H0, W0); });
-    tape_kind = 1;
-    slot_swap();
+    tape->valid = (rc == HCF_OK);
+    tape->kind = kind;
+    tape_swap();
     return rc;
   }
 
@@ -1700,56 +1650,56 @@
     float* gin;                     // kind 2: receives dL / d lr (nullable)
     const float* gz1; const float* gz2;   // kind 3: dL / d z1, z2 (nullable)
   };
-  // phase: -1 the whole pass; 0 records [tape_mark, end) + a flush of every pending parameter-gradient job; 1 the rest
+  // phase: -1 the whole pass; 0 records [mark, end) + a flush of every pending parameter-gradient job; 1 the rest
   int run_backward(const BwdIn& in, float* dparams, size_t n, hipStream_t stream, int phase = -1) {
-    slot_swap();
+    tape_swap();
     const int r = run_backward_swapped(in, dparams, n, stream, phase);
-    slot_swap();
+    tape_swap();
     return r;
   }
   int run_backward_swapped(const BwdIn& in, float* dparams, size_t n, hipStream_t stream, int phase) {
-    if (!tape_valid || tape_kind != in.kind)
+    if (!tape->valid || tape->kind != in.kind)
       return fail(HCF_ERR_STATE, "backward without a matching taped pass on the selected tape slot before it");
     if (in.kind == 2 && !in.gout) return fail(HCF_ERR_ARG, "hcf_train_backward_inverse: null output gradient");
     if (n != ptotal || !dparams) return fail(HCF_ERR_ARG, "backward: gradient buffer size mismatch");
     if (phase >= 0 && in.kind != 1) return fail(HCF_ERR_UNSUPPORTED, "two-phase backward: NLL pass only");
-    if (phase == 1 && (!tape_mid || dparams != gparams)) return fail(HCF_ERR_STATE, "backward phase 1 without phase 0 on this tape (same gradient buffer) before it");
-    if (phase != 1 && tape_mid) return fail(HCF_ERR_STATE, "backward: phase 1 of a two-phase backward is pending on this tape");
+    if (phase == 1 && (!tape->mid || dparams != tape->bwd.gparams)) return fail(HCF_ERR_STATE, "backward phase 1 without phase 0 on this tape (same gradient buffer) before it");
+    if (phase != 1 && tape->mid) return fail(HCF_ERR_STATE, "backward: phase 1 of a two-phase backward is pending on this tape");
     if (hipSetDevice(device) != hipSuccess) return fail(HCF_ERR_HIP, "hipSetDevice failed");
     rc = HCF_OK;
     st = stream;
     use_f16 = false;
     if (phase == 1) {
-      tape_mid = false;
-      for (size_t i = tape_mark; i-- > 0 && rc == HCF_OK;) tape[i]();
+      tape->mid = false;
+      for (size_t i = tape->mark; i-- > 0 && rc == HCF_OK;) tape->recs[i]();
       return finish_backward();
     }
-    bwd_f16 = (precision == PREC_F16X3) && ovf_flag != nullptr;
-    epi_fuse_off = getenv("HCF_NO_EPI_FUSE") != nullptr;
-    dgrad_wino_min_pix = getenv("HCF_DGRAD_WINO_MIN_PIX") ? atoll(getenv("HCF_DGRAD_WINO_MIN_PIX")) : 4096;
-    fcn_fuse_off = getenv("HCF_NO_FCN_FUSE") != nullptr;
-    if (bwd_f16) { ovf_latch(); ovf_clear = false; }
-    if (bwd_f16 && hipMemsetAsync(ovf_flag, 0, 256, st) != hipSuccess) return fail(HCF_ERR_HIP, "hipMemsetAsync failed (backward)");
-    gparams = dparams;
-    g_out_nchw = (in.kind == 2) ? in.gout : nullptr;
-    g_in_nchw = (in.kind == 2) ? in.gin : nullptr;
-    g_fwd_lr = (in.kind == 3) ? in.gout : nullptr;
-    g_fwd_z[0] = (in.kind == 3) ? in.gz1 : nullptr;
-    g_fwd_z[1] = (in.kind == 3) ? in.gz2 : nullptr;
+    tape->bwd.f16 = (precision == PREC_F16X3) && ovf_flag != nullptr;
+    tape->bwd.epi_fuse_off = getenv("HCF_NO_EPI_FUSE") != nullptr;
+    tape->bwd.dgrad_wino_min_pix = getenv("HCF_DGRAD_WINO_MIN_PIX") ? atoll(getenv("HCF_DGRAD_WINO_MIN_PIX")) : 4096;
+    tape->bwd.fcn_fuse_off = getenv("HCF_NO_FCN_FUSE") != nullptr;
+    if (tape->bwd.f16) { ovf_latch(); ovf_clear = false; }
+    if (tape->bwd.f16 && hipMemsetAsync(ovf_flag, 0, 256, st) != hipSuccess) return fail(HCF_ERR_HIP, "hipMemsetAsync failed (backward)");
+    tape->bwd.gparams = dparams;
+    tape->bwd.g_out_nchw = (in.kind == 2) ? in.gout : nullptr;
+    tape->bwd.g_in_nchw = (in.kind == 2) ? in.gin : nullptr;
+    tape->bwd.g_fwd_lr = (in.kind == 3) ? in.gout : nullptr;
+    tape->bwd.g_fwd_z[0] = (in.kind == 3) ? in.gz1 : nullptr;
+    tape->bwd.g_fwd_z[1] = (in.kind == 3) ? in.gz2 : nullptr;
     // nll = mean_b( -objective_b / (ln 2 * pixels) ); the other objectives have no log-det term
-    gobj = (in.kind == 1) ? -in.gscale / (float)((double)B_ * log(2.0) * t_pixels) : 0.f;
-    if (hipMemsetAsync(garena.base, 0, garena.top, st) != hipSuccess ||
+    tape->bwd.gobj = (in.kind == 1) ? -in.gscale / (float)((double)B_ * log(2.0) * tape->pixels) : 0.f;
+    if (hipMemsetAsync(tape->g.base, 0, tape->g.top, st) != hipSuccess ||
         hipMemsetAsync(dparams, 0, ptotal * sizeof(float), st) != hipSuccess)
       return fail(HCF_ERR_HIP, "hipMemsetAsync failed (backward)");
-    sum_jobs.clear();
-    wg_jobs.clear();
+    sum_jobs.host.clear();
+    wg_jobs.host.clear();
     rdb_wg.clear();
     wg_used = 0;
-    axpy_jobs.clear();
+    axpy_jobs.host.clear();
     wg_begin_pass();
     dg_begin_pass();
     if (phase == 0) {
-      for (size_t i = tape.size(); i-- > tape_mark && rc == HCF_OK;) tape[i]();
+      for (size_t i = tape->recs.size(); i-- > tape->mark && rc == HCF_OK;) tape->recs[i]();
       // every parameter-gradient job enqueued so far is completed on the caller's stream: weight-gradient reductions (side stream
       // joined), axpy and per-channel sums -- the gradients of the level-0 conditional flow are final
       flush_rdb_wgrad();
@@ -1757,24 +1707,24 @@
       wg_join();
       flush_axpy_jobs();
       flush_sum_jobs();
-      if (rc != HCF_OK) { dg_dirty = dg_async; dg_join(); dg_async = false; wg_async = false; tape_valid = false; gparams = nullptr; return rc; }
-      tape_mid = true;
+      if (rc != HCF_OK) { tape->bwd.dg_dirty = tape->bwd.dg_async; dg_join(); tape->bwd.dg_async = false; tape->bwd.wg_async = false; tape->valid = false; tape->bwd.gparams = nullptr; return rc; }
+      tape->mid = true;
       return rc;
     }
-    for (size_t i = tape.size(); i-- > 0 && rc == HCF_OK;) tape[i]();
+    for (size_t i = tape->recs.size(); i-- > 0 && rc == HCF_OK;) tape->recs[i]();
     return finish_backward();
   }
   int finish_backward() {
-    dg_dirty = dg_async;                               // (also on a failed pass: nothing of it may still be in flight)
+    tape->bwd.dg_dirty = tape->bwd.dg_async;                               // (also on a failed pass: nothing of it may still be in flight)
     dg_join();
-    dg_async = false;
+    tape->bwd.dg_async = false;
     flush_rdb_wgrad();
     flush_wgrad();
     wg_join();                                         // also on a failed pass: nothing of it may still be in flight on the side stream
-    wg_async = false;
+    tape->bwd.wg_async = false;
     flush_axpy_jobs();
     flush_sum_jobs();
-    tape_valid = false;          // the epilogue backward overwrote the gradient buffers in place: one backward per forward
-    gparams = nullptr;
+    tape->valid = false;          // the epilogue backward overwrote the gradient buffers in place: one backward per forward
+    tape->bwd.gparams = nullptr;
     return rc;
   }

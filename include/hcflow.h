@@ -202,7 +202,8 @@ int hcf_train_backward(hcf_engine* e, float grad_nll, float* dparams, int64_t nu
  * of the pass that was taped last -- the output terms and the level-0 conditional flow -- and completes every parameter-gradient
  * reduction it enqueued on `stream`: when it returns (stream order), the slices of `dparams` of all parameters whose key starts with
  * "flow.level0_condFlow." (about half of an SR x4 net) are FINAL and nothing later touches them. phase 1 (same `dparams`) runs the
- * rest. The two calls together write exactly what hcf_train_backward writes, bit for bit. */
+ * rest. The two calls together write exactly what hcf_train_backward writes, bit for bit. Calls on the other tape slot
+ * (hcf_train_select_tape) may run between the phases. */
 int hcf_train_backward_phase(hcf_engine* e, int32_t phase, float grad_nll, float* dparams, int64_t numel, hcf_stream_t stream);
 
 /* Gradients through the REVERSE (sampling) path (reference: the HR pixel / feature / GAN losses of the HCFlow+ / ++

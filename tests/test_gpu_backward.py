@@ -944,3 +944,104 @@ def test_two_phase_backward_equals_the_single_call_and_finishes_the_early_group_
     _lib.check(lib.hcf_train_backward(h, 1.0, one.data_ptr(), total, st), h, "backward")
     assert torch.equal(one, flat)
     assert lib.hcf_train_backward_phase(h, 1, 1.0, one.data_ptr(), total, st) != 0    # no phase 0 before it
+
+
+@pytest.mark.parametrize("precision", ["exact", "f16x3"])
+def test_two_phase_backward_survives_a_backward_on_the_other_tape_slot(precision):
+    """include/hcflow.h allows calls on the other tape slot between the phases of hcf_train_backward_phase: phase 0 on slot 0, a
+    complete hcf_train_backward_inverse on slot 1, phase 1 on slot 0 write bit for bit what the two backward passes write one
+    after the other (the state phase 0 hands to phase 1 belongs to the tape, not to the engine); the refusals stay."""
+    import ctypes as C
+    from hcflow_amd import _lib
+    cfg, net = _fresh_sr("SR_4X_tiny", 11)
+    net.train().set_precision(precision)
+    g = torch.Generator().manual_seed(31)
+    hr = torch.rand(2, 3, 64, 96, generator=g).cuda()
+    lr = torch.rand(2, 3, 16, 24, generator=g).cuda()
+    noise = torch.rand(hr.shape, generator=g).cuda()
+    g_out = torch.randn(hr.shape, generator=g).cuda()
+    eng = net.engine()
+    lib, h = eng.lib, eng.handle
+    total = sum(p.numel() for p in net._params())
+    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    out_lr = torch.empty(2, 3, 16, 24, device="cuda"); nll = torch.empty(1, device="cuda"); ld = torch.empty(2, device="cuda")
+    fake = torch.empty_like(hr)
+
+    def select(slot):
+        _lib.check(lib.hcf_train_select_tape(h, slot), h, "select")
+
+    def forwards():
+        select(0)
+        _lib.check(lib.hcf_train_forward_sr(h, hr.data_ptr(), lr.data_ptr(), noise.data_ptr(), out_lr.data_ptr(), nll.data_ptr(),
+                                            ld.data_ptr(), 2, 64, 96, st), h, "fwd")
+        select(1)
+        _lib.check(lib.hcf_train_inverse(h, lr.data_ptr(), None, 0, 0.8, 7, fake.data_ptr(), 2, 16, 24, 0, st), h, "inverse")
+
+    def backward_inverse(flat, glr):
+        select(1)
+        _lib.check(lib.hcf_train_backward_inverse(h, g_out.data_ptr(), flat.data_ptr(), total, glr.data_ptr(), st), h, "bwd inverse")
+    try:
+        ref0, ref1, ref_glr = torch.zeros(total, device="cuda"), torch.zeros(total, device="cuda"), torch.zeros_like(lr)
+        forwards()
+        select(0)
+        _lib.check(lib.hcf_train_backward(h, 1.0, ref0.data_ptr(), total, st), h, "backward")
+        backward_inverse(ref1, ref_glr)
+        got0, got1, got_glr = torch.zeros(total, device="cuda"), torch.zeros(total, device="cuda"), torch.zeros_like(lr)
+        forwards()
+        select(0)
+        _lib.check(lib.hcf_train_backward_phase(h, 0, 1.0, got0.data_ptr(), total, st), h, "phase 0")
+        backward_inverse(got1, got_glr)
+        select(0)
+        assert lib.hcf_train_backward(h, 1.0, got0.data_ptr(), total, st) != 0      # phase 1 is still pending on slot 0
+        _lib.check(lib.hcf_train_backward_phase(h, 1, 1.0, got0.data_ptr(), total, st), h, "phase 1")
+        assert torch.equal(got0, ref0)
+        assert torch.equal(got1, ref1)
+        assert torch.equal(got_glr, ref_glr)
+        assert bool(ref0.abs().max() > 0) and bool(ref1.abs().max() > 0) and bool(ref_glr.abs().max() > 0)
+        assert lib.hcf_train_backward_phase(h, 1, 1.0, got0.data_ptr(), total, st) != 0   # consumed: no phase 0 before it
+    finally:
+        net.set_precision("exact")
+
+
+@pytest.mark.parametrize("precision", ["exact", "f16x3"])
+@pytest.mark.parametrize("frozen", ["late", "early"])
+def test_two_node_step_with_a_frozen_group_takes_the_one_node_step(precision, frozen, monkeypatch):
+    """HCFLOW_GRAD_NODES=2 with one of the two parameter groups frozen: autograd would never call the frozen group's node (a frozen
+    `late` group: no phase 1, no side-stream joins), so the module takes the one-node step -- two consecutive steps give the nll, the
+    gradients and the None pattern of HCFLOW_GRAD_NODES=1, and a reverse-path step on tape slot 1 still runs behind them."""
+    cfg, net = _fresh_sr("SR_4X_tiny", 11)
+    net.train().set_precision(precision)
+    g = torch.Generator().manual_seed(37)
+    hr = torch.rand(2, 3, 64, 96, generator=g).cuda()
+    lr = torch.rand(2, 3, 16, 24, generator=g).cuda()
+    noise = torch.rand(hr.shape, generator=g).cuda()
+    for k, p in net.named_parameters():
+        if k.startswith("flow.level0_condFlow.") == (frozen == "early"):
+            p.requires_grad_(False)
+    assert any(p.requires_grad for p in net.parameters()) and not all(p.requires_grad for p in net.parameters())
+
+    def steps(nodes):
+        monkeypatch.setenv("HCFLOW_GRAD_NODES", str(nodes))
+        out = []
+        for _ in range(2):
+            for p in net.parameters():
+                p.grad = None
+            _, nll = net(hr=hr, lr=lr, reverse=False, noise=noise)
+            nll.backward()
+            out.append((float(nll.detach()), [None if p.grad is None else p.grad.clone() for p in net.parameters()]))
+        return out
+    try:
+        one, two = steps(1), steps(2)
+        for (n1, g1), (n2, g2) in zip(one, two):
+            assert n1 == n2
+            assert [a is None for a in g1] == [p.requires_grad is False for p in net.parameters()]
+            assert all((a is None) == (b is None) for a, b in zip(g1, g2))
+            assert all(torch.equal(a, b) for a, b in zip(g1, g2) if a is not None)
+        for p in net.parameters():
+            p.grad = None
+        fake = net(lr=lr, z=None, u=None, eps_std=0.8, reverse=True)
+        F.l1_loss(fake, hr).backward()
+        got = [p.grad for p in net.parameters() if p.grad is not None]
+        assert got and all(bool(torch.isfinite(a).all()) for a in got)
+    finally:
+        net.set_precision("exact")
