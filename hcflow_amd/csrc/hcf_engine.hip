@@ -622,7 +622,7 @@ int hcf_train_forward_sr(hcf_engine* e, const float* hr, const float* lr, const 
   const int m = 1 << e->cfg.L;
   if (H % m || W % m) return e->fail(HCF_ERR_SHAPE, "H, W must be divisible by the scale (squeeze2d assert, Basic.py:136)");
   return e->run_train(1, e->sr() ? nullptr : "hcf_train_forward_sr on a rescaling engine", (hipStream_t)stream,
-                      [&]() { e->pass_train_forward_sr(hr, lr, noise, out_lr, out_nll, out_logdet, B, H, W); });
+                      [&]() { e->pass_train_forward(hr, lr, noise, out_lr, out_nll, out_logdet, nullptr, nullptr, B, H, W, 0); });
 }
 
 int hcf_train_backward(hcf_engine* e, float grad_nll, float* dparams, int64_t numel, hcf_stream_t stream) {
@@ -648,7 +648,7 @@ int hcf_train_forward_rescale(hcf_engine* e, const float* hr, float* out_lr, flo
   if (!e || !hr || !out_lr || !out_z1 || !out_z2 || B < 1 || H < 1 || W < 1) return HCF_ERR_ARG;
   if (H % 4 || W % 4) return e->fail(HCF_ERR_SHAPE, "H, W must be divisible by 4");
   return e->run_train(3, e->sr() ? "hcf_train_forward_rescale on an SR engine" : nullptr, (hipStream_t)stream,
-                      [&]() { e->pass_train_forward_rescale(hr, out_lr, out_z1, out_z2, B, H, W, flags); });
+                      [&]() { e->pass_train_forward(hr, nullptr, nullptr, out_lr, nullptr, nullptr, out_z1, out_z2, B, H, W, flags); });
 }
 
 int hcf_train_backward_rescale(hcf_engine* e, const float* g_lr, const float* g_z1, const float* g_z2, float* dparams,

@@ -31,9 +31,18 @@
   }
 
   struct FatExtra { View out2; int act2; bool pre; const float* w4f_frag; };   // Winograd-only routing: fat launches (see Rdb), fused 1x1 layer (Step::c1w)
-  void run_conv(const Conv& cv, std::vector<View> srcs, int H, int W, View out, View res1 = mkview(nullptr, 0, 0, 0),
-                float rs1 = 0.f, View res2 = mkview(nullptr, 0, 0, 0), float rs2 = 0.f, const Conv* fuse2 = nullptr,
-                const StepArgs* tail = nullptr, const FatExtra* fat = nullptr) {
+  struct ConvOpt {       // run_conv's optionals: out = res2 + rs2 * (res1 + rs1 * act(conv)) (a residual with p == nullptr: none)
+    View res1 = View(), res2 = View();
+    float rs1 = 0.f, rs2 = 0.f;
+    const Conv* fuse2 = nullptr;        // a 1x1 second layer in the epilogue (can_fuse_fcn)
+    const StepArgs* tail = nullptr;     // the inverse flow step's tail in the epilogue (can_fuse_tail)
+    const FatExtra* fat = nullptr;
+  };
+  void run_conv(const Conv& cv, std::vector<View> srcs, int H, int W, View out) { run_conv(cv, std::move(srcs), H, W, out, ConvOpt()); }
+  void run_conv(const Conv& cv, std::vector<View> srcs, int H, int W, View out, const ConvOpt& o) {
+    const View res1 = o.res1, res2 = o.res2;
+    const float rs1 = o.rs1, rs2 = o.rs2;
+    const Conv* const fuse2 = o.fuse2; const StepArgs* const tail = o.tail; const FatExtra* const fat = o.fat;
     if (rc != HCF_OK) return;
     if ((int)srcs.size() != cv.nsrc) { fail(HCF_ERR_STATE, "internal: conv source count"); return; }
     ConvArgs a;
@@ -270,22 +279,20 @@
     if (s.fcn) {
       if (w4f_ok(s, u, H, W, sc)) {
         // conv1 on the Winograd kernel (sources: z1 padded to one 16-channel chunk, the features), conv2 in its epilogue
-        const View none = mkview(nullptr, 0, 0, 0);
         if (!zpad_valid) HCF_LAUNCH(launch_copy_pad16(z1, sc.zpad.p, B_, H, W, st));    // (else: the previous step's tail wrote it)
         zpad_valid = false;
-        const FatExtra fx = {none, ACT_NONE, false, s.w4f_frag};
-        run_conv(s.c1w, {sc.zpad.v(0, 16), *u}, H, W, sc.h2.v(0, s.hid), none, 0.f, none, 0.f, &s.c[1], nullptr, &fx);
+        const FatExtra fx = {View(), ACT_NONE, false, s.w4f_frag};
+        ConvOpt o; o.fuse2 = &s.c[1]; o.fat = &fx;
+        run_conv(s.c1w, {sc.zpad.v(0, 16), *u}, H, W, sc.h2.v(0, s.hid), o);
       } else if (can_fuse_fcn(s.c[0], s.c[1])) {
-        const View none = mkview(nullptr, 0, 0, 0);
-        run_conv(s.c[0], in, H, W, sc.h2.v(0, s.hid), none, 0.f, none, 0.f, &s.c[1]);
+        ConvOpt o; o.fuse2 = &s.c[1];
+        run_conv(s.c[0], in, H, W, sc.h2.v(0, s.hid), o);
       } else {
         run_conv_an(s.c[0], in, H, W, sc.h1.v(0, s.hid));
         run_conv_an(s.c[1], {sc.h1.v(0, s.hid)}, H, W, sc.h2.v(0, s.hid));
       }
-      {
-        const View none = mkview(nullptr, 0, 0, 0);
-        run_conv(s.c[2], {sc.h2.v(0, s.hid)}, H, W, sc.hout.v(0, s.f_out), none, 0.f, none, 0.f, nullptr, tail);
-      }
+      ConvOpt o3; o3.tail = tail;
+      run_conv(s.c[2], {sc.h2.v(0, s.hid)}, H, W, sc.hout.v(0, s.f_out), o3);
     } else {
       // DenseBlock: conv i >= 1 in Winograd form over [z1 padded | growth] where that form exists and this level qualifies
       bool need64 = false;
@@ -297,9 +304,9 @@
       for (int i = 0; i < 5; ++i) {
         const View out_i = i < 4 ? sc.grow.v(i * s.hid, s.hid) : sc.hout.v(0, s.f_out);
         if (dw && s.cw[i].wpack_wino) {
-          const View none = mkview(nullptr, 0, 0, 0);
-          const FatExtra fx = {none, ACT_NONE, false, nullptr};       // (no per-launch fallback: the direct packs have another source list)
-          run_conv(s.cw[i], {sc.zpadd.v(0, s.dw_pad), sc.grow.v(0, i * s.hid)}, H, W, out_i, none, 0.f, none, 0.f, nullptr, nullptr, &fx);
+          const FatExtra fx = {View(), ACT_NONE, false, nullptr};     // (no per-launch fallback: the direct packs have another source list)
+          ConvOpt o; o.fat = &fx;
+          run_conv(s.cw[i], {sc.zpadd.v(0, s.dw_pad), sc.grow.v(0, i * s.hid)}, H, W, out_i, o);
           continue;
         }
         std::vector<View> srcs = in;
@@ -314,15 +321,26 @@
     return z.v(3, s.C - 3);
   }
 
+  // The fields every flow-step launch shares, the rest zero. A: StepArgs, StepBwdArgs, StepInvBwdArgs.
+  template <class A>
+  A step_dims(const Step& s, int H, int W) const {
+    A a;
+    memset(&a, 0, sizeof(a));
+    a.B = B_; a.H = H; a.W = W; a.C = s.C; a.ns = s.ns; a.mode = s.mode;
+    return a;
+  }
+  StepArgs step_args(const Step& s, int H, int W, bool fwd) const {      // + the direction's ActNorm table and W (forward) / W^-1
+    StepArgs a = step_dims<StepArgs>(s, H, W);
+    a.mat = s.has_mat ? (fwd ? s.mat_fwd : s.mat_inv) : nullptr; a.an_bias = s.bias; a.an_mul = fwd ? s.mul_fwd : s.mul_inv;
+    return a;
+  }
+
   // FlowStep.reverse_flow (FlowStep.py:53-64), in place on z
   // `next` = the step that runs after this one on the same z (or null): when it takes the Winograd form of its FCN, this
   // step's tail also writes next's z1 as the padded 16-channel tensor that form reads (saves a copy launch per step)
   void run_step_inverse(const Step& s, const Buf& z, const View* u, int H, int W, Scratch& sc, const Step* next = nullptr) {
-    StepArgs a;
-    memset(&a, 0, sizeof(a));
-    a.B = B_; a.H = H; a.W = W; a.C = s.C; a.ns = s.ns; a.mode = s.mode;
+    StepArgs a = step_args(s, H, W, false);
     a.z = z.all(); a.h = sc.hout.v(0, s.f_out); a.out = z.all();
-    a.mat = s.has_mat ? s.mat_inv : nullptr; a.an_bias = s.bias; a.an_mul = s.mul_inv;
     const bool pad_next = next && next->C == s.C && w4f_ok(*next, u, H, W, sc);
     if (pad_next) { a.zpad16 = sc.zpad.p; a.zpad_n = next->ns; }
     if (can_fuse_tail(s)) {
@@ -337,11 +355,8 @@
   // FlowStep.normal_flow (FlowStep.py:40-51), in place on z; partial slot advanced when `partial`
   void run_step_forward(const Step& s, const Buf& z, const View* u, int H, int W, Scratch& sc, float* partial,
                         int pstride, int& pslot) {
-    StepArgs a;
-    memset(&a, 0, sizeof(a));
-    a.B = B_; a.H = H; a.W = W; a.C = s.C; a.ns = s.ns; a.mode = s.mode;
+    StepArgs a = step_args(s, H, W, true);
     a.z = z.all(); a.out = z.all();
-    a.mat = s.has_mat ? s.mat_fwd : nullptr; a.an_bias = s.bias; a.an_mul = s.mul_fwd;
     if (an_wants(s.an_key)) an_refit_step(const_cast<Step&>(s), z.all(), H, W);     // same device arrays, new contents
     HCF_LAUNCH(launch_step_head_fwd(a, st));
     run_coupling_net(s, step_z1(s, z), u, H, W, sc);
@@ -371,18 +386,20 @@
     // (16-channel blocks: both halves of a pair run on the 32-channel kernel, whose fixed cost the per-conv schedule pays too:
     //  pair (1, 2) at every size)
     const bool use_fat[2] = {fat_ok && r.fat[0] && (gc == 16 || (long long)H * W <= fat12_pixels), fat_ok && r.fat[1]};
+    ConvOpt last;          // conv 5: out = res2 + rs2 * (xin + 0.2 * conv)
+    last.res1 = xin; last.rs1 = 0.2f; last.res2 = res2; last.rs2 = rs2;
     if (use_fat[0] || use_fat[1]) {
-      const View none = mkview(nullptr, 0, 0, 0);
       for (int j = 0; j < 2; ++j) {
         std::vector<View> srcs;
         srcs.push_back(xin);
         if (j > 0) srcs.push_back(grow.v(0, 2 * j * gc));
         if (use_fat[j]) {
-          FatExtra fa = {fatp->v(0, gc), ACT_NONE, false};        // tile 0 -> x_{2j+1} (bias, LeakyReLU), tile 1 -> raw partial of conv 2j+2
-          run_conv(r.ca[j], srcs, H, W, grow.v(2 * j * gc, gc), none, 0.f, none, 0.f, nullptr, nullptr, &fa);
-          FatExtra fb = {none, ACT_NONE, true};                   // x_{2j+2} = lrelu(W[x_{2j+1}] * x_{2j+1} + partial + bias)
-          run_conv(r.cb[j], {grow.v(2 * j * gc, gc)}, H, W, grow.v((2 * j + 1) * gc, gc), fatp->v(0, gc), 0.f, none, 0.f, nullptr,
-                   nullptr, &fb);
+          const FatExtra fa = {fatp->v(0, gc), ACT_NONE, false};  // tile 0 -> x_{2j+1} (bias, LeakyReLU), tile 1 -> raw partial of conv 2j+2
+          ConvOpt oa; oa.fat = &fa;
+          run_conv(r.ca[j], srcs, H, W, grow.v(2 * j * gc, gc), oa);
+          const FatExtra fb = {View(), ACT_NONE, true};           // x_{2j+2} = lrelu(W[x_{2j+1}] * x_{2j+1} + partial + bias)
+          ConvOpt ob; ob.res1 = fatp->v(0, gc); ob.fat = &fb;
+          run_conv(r.cb[j], {grow.v(2 * j * gc, gc)}, H, W, grow.v((2 * j + 1) * gc, gc), ob);
         } else {
           run_conv(r.c[2 * j], srcs, H, W, grow.v(2 * j * gc, gc));
           std::vector<View> s2;
@@ -391,7 +408,7 @@
           run_conv(r.c[2 * j + 1], s2, H, W, grow.v((2 * j + 1) * gc, gc));
         }
       }
-      run_conv(r.c[4], {xin, grow.v(0, 4 * gc)}, H, W, out, xin, 0.2f, res2, rs2);
+      run_conv(r.c[4], {xin, grow.v(0, 4 * gc)}, H, W, out, last);
       return;
     }
     for (int i = 0; i < 4; ++i) {
@@ -400,14 +417,13 @@
       if (i > 0) srcs.push_back(grow.v(0, i * gc));
       run_conv(r.c[i], srcs, H, W, grow.v(i * gc, gc));
     }
-    run_conv(r.c[4], {xin, grow.v(0, 4 * gc)}, H, W, out, xin, 0.2f, res2, rs2);
+    run_conv(r.c[4], {xin, grow.v(0, 4 * gc)}, H, W, out, last);
   }
 
   void run_rrdb(const Rrdb& rr, View x0, View out, int H, int W, Scratch& sc) {
     const int nf = cfg.rrdb_nf;
-    const View none = mkview(nullptr, 0, 0, 0);
-    run_rdb(rr.r[0], x0, sc.rgrow, H, W, sc.t1.v(0, nf), none, 0.f, &sc.fatp);
-    run_rdb(rr.r[1], sc.t1.v(0, nf), sc.rgrow, H, W, sc.t2.v(0, nf), none, 0.f, &sc.fatp);
+    run_rdb(rr.r[0], x0, sc.rgrow, H, W, sc.t1.v(0, nf), View(), 0.f, &sc.fatp);
+    run_rdb(rr.r[1], sc.t1.v(0, nf), sc.rgrow, H, W, sc.t2.v(0, nf), View(), 0.f, &sc.fatp);
     run_rdb(rr.r[2], sc.t2.v(0, nf), sc.rgrow, H, W, out, x0, 0.2f, &sc.fatp);
   }
 
@@ -454,7 +470,8 @@
       cur = x;
     }
     const View f2 = sr() ? cfbuf.v(nf, nf) : cfbuf.v(0, nf);
-    run_conv(cf.trunk_conv1, {cur}, H, W, f2, sc.f0.v(0, nf), 1.0f);
+    ConvOpt o; o.res1 = sc.f0.v(0, nf); o.rs1 = 1.0f;
+    run_conv(cf.trunk_conv1, {cur}, H, W, f2, o);
   }
 
   Scratch alloc_scratch(int H, int W) {
@@ -507,6 +524,57 @@
     return HCF_OK;
   }
 
+  // ---------------------------------------------------------------- pieces of the walks (inference passes below, taped passes in hcf_engine_train.inc)
+  // a level's entry squeeze, in: [H, W, C] -> out: [H/2, W/2, 4C], and its inverse, in: [H, W, C4] -> out: [2H, 2W, C4/4]
+  // (squeeze2d / unsqueeze2d, Basic.py:127-157, or HaarDownsampling, :450-487)
+  void run_squeeze(View in, View out, int C, int H, int W) {
+    if (cfg.squeeze == HCF_SQUEEZE_HAAR) HCF_LAUNCH(launch_haar_fwd(in, out, B_, C, H, W, st));
+    else HCF_LAUNCH(launch_squeeze(in, out, B_, C, H, W, st));
+  }
+  void run_unsqueeze(View in, View out, int C4, int H, int W) {
+    if (cfg.squeeze == HCF_SQUEEZE_HAAR) HCF_LAUNCH(launch_haar_inv(in, out, B_, C4, H, W, st));
+    else HCF_LAUNCH(launch_unsqueeze(in, out, B_, C4, H, W, st));
+  }
+  // sources of a level's conditional net: u = cat(z1, up2(cf_{l+1}), up4(cf_{l+2}))  (FlowNet_SR_x8.py:132-137);
+  // cf_at(l2, k) = the features of level l2 read upsampled by 2^k
+  template <class V, class F>
+  std::vector<V> cond_sources(V z1, int level, F&& cf_at) const {
+    std::vector<V> u(1, z1);
+    for (int l2 = level + 1; l2 < cfg.L; ++l2) u.push_back(cf_at(l2, l2 - level));
+    return u;
+  }
+  // the prior of a split-off half `a` (Ca channels) from the head conv's output h = (mean, s) interleaved
+  GaussArgs gauss_args(View h, View a, int Ca, int H, int W) const {
+    GaussArgs g;
+    memset(&g, 0, sizeof(g));
+    g.B = B_; g.H = H; g.W = W; g.C = Ca;
+    g.h = h; g.out = a;
+    g.rescale = sr() ? 0 : 1;
+    return g;
+  }
+  // NLL forward: per-sample partial-sum slots of the log-det terms, in the order the pass fills them
+  int nll_slots(int H0, int W0) const {
+    int n = step_blocks_per_sample(H0 >> cfg.L, W0 >> cfg.L);      // Dirac term
+    for (int level = 0; level < cfg.L; ++level) {
+      const int nb = step_blocks_per_sample(H0 >> (level + 1), W0 >> (level + 1));
+      for (const Step& s : levels[level].steps) if (s.mode == CPL_AFFINE) n += nb;
+      for (const Step& s : levels[level].cf.steps) if (s.mode == CPL_AFFINE) n += nb;
+      n += nb;                           // gaussian logp
+    }
+    return n;
+  }
+  // data-independent log-det terms: -ln(quant) HW + sum over steps of (sum(actnorm logs) + slogdet W) * pixels
+  // (summed after the steps ran: an ActNorm init pass changes them on the way)
+  double ld_const_sum(int H0, int W0) const {
+    double ld_const = -log((double)cfg.quant) * (double)H0 * W0;
+    for (int level = 0; level < cfg.L; ++level) {
+      const double px = (double)(H0 >> (level + 1)) * (W0 >> (level + 1));
+      for (const Step& s : levels[level].steps) ld_const += s.ld_const * px;
+      for (const Step& s : levels[level].cf.steps) ld_const += s.ld_const * px;
+    }
+    return ld_const;
+  }
+
   // ---------------------------------------------------------------- inverse pass
   // FlowNet.reverse_flow (FlowNet_SR_x4.py:106-123, FlowNet_SR_x8.py:121-144, FlowNet_Rescaling_x4.py:111-128)
   void pass_inverse(const float* lr, const float* const* eps, int n_eps, float tau, uint64_t seed, int64_t sample0, float* out,
@@ -536,20 +604,13 @@
         HCF_LAUNCH(launch_nchw_to_nhwc(lr, z.v(0, 3), B, 3, H, W, st));
       } else {
         // squeeze^-1 of the deeper level lands in z[:, :ns]   (Basic.py:143-157 / :479-487)
-        const Level& dp = levels[level + 1];
-        if (cfg.squeeze == HCF_SQUEEZE_HAAR)
-          HCF_LAUNCH(launch_haar_inv(zprev.all(), z.v(0, lv.ns), B, dp.C, H / 2, W / 2, st));
-        else
-          HCF_LAUNCH(launch_unsqueeze(zprev.all(), z.v(0, lv.ns), B, dp.C, H / 2, W / 2, st));
+        run_unsqueeze(zprev.all(), z.v(0, lv.ns), levels[level + 1].C, H / 2, W / 2);
       }
       const size_t mark = arena.top;
       Scratch sc = alloc_scratch(H, W);
       Buf a = alloc(B, H, W, cf.Ca);
-      // conditional features: u = cat(z, up2(cf_{l+1}), up4(cf_{l+2}))  (FlowNet_SR_x8.py:132-137)
-      std::vector<View> u;
-      u.push_back(z.v(0, lv.ns));
-      for (int l2 = level + 1; l2 < L; ++l2) u.push_back(cfb[l2].v(0, cond_ch(), l2 - level));
-      if (!cached) run_cond_features(cf, u, H, W, cfb[level], sc);
+      const auto cf_at = [&](int l2, int k) { return cfb[l2].v(0, cond_ch(), k); };
+      if (!cached) run_cond_features(cf, cond_sources(z.v(0, lv.ns), level, cf_at), H, W, cfb[level], sc);
       const View cfv = cfb[level].v(0, cond_ch());
       // prior: a = mean + exp(logs) * eps   (ConditionalFlow.py:61-64 / 88-91)
       if (!cached) {
@@ -557,15 +618,11 @@
         if (level == L - 1 && keep_c) HCF_LAUNCH(launch_copy_view(sc.hout.v(0, cf.Ca * 2), hkeep.all(), B, H, W, st));
       }
       {
-        GaussArgs g;
-        memset(&g, 0, sizeof(g));
-        g.B = B; g.H = H; g.W = W; g.C = cf.Ca;
-        g.h = (cached || (level == L - 1 && keep_c)) ? hkeep.all() : sc.hout.v(0, cf.Ca * 2);
-        g.rescale = sr() ? 0 : 1;
+        const bool kept = cached || (level == L - 1 && keep_c);
+        GaussArgs g = gauss_args(kept ? hkeep.all() : sc.hout.v(0, cf.Ca * 2), a.all(), cf.Ca, H, W);
         const int draw = L - 1 - level;
         g.eps = (eps && draw < n_eps) ? eps[draw] : nullptr;
         g.tau = tau; g.seed = seed; g.offset = (uint64_t)draw; g.b0 = sample0;
-        g.out = a.all();
         HCF_LAUNCH(launch_gauss_sample(g, st));
       }
       zpad_valid = false;
@@ -602,16 +659,7 @@
     arena.top = 0;
     const int L = cfg.L;
     const bool want_ld = sr();
-    // partial-sum slots
-    int nslots = 0;
-    for (int level = 0; level < L; ++level) {
-      const int H = H0 >> (level + 1), W = W0 >> (level + 1);
-      const int nb = step_blocks_per_sample(H, W);
-      for (const Step& s : levels[level].steps) if (s.mode == CPL_AFFINE) nslots += nb;
-      for (const Step& s : levels[level].cf.steps) if (s.mode == CPL_AFFINE) nslots += nb;
-      nslots += nb;                      // gaussian logp
-    }
-    nslots += step_blocks_per_sample(H0 >> L, W0 >> L);   // Dirac term
+    const int nslots = nll_slots(H0, W0);
     float* partial = nullptr;
     int pslot = 0;
     if (want_ld) {
@@ -628,11 +676,8 @@
         HCF_LAUNCH(launch_nchw_squeeze(hr, noise, cfg.quant, zb[0].all(), B, cfg.in_nc, H0, W0,
                                        cfg.squeeze == HCF_SQUEEZE_HAAR ? 1 : 0, st));
       } else {
-        const Level& up = levels[level - 1];
-        if (cfg.squeeze == HCF_SQUEEZE_HAAR)
-          HCF_LAUNCH(launch_haar_fwd(zb[level - 1].v(0, up.ns), zb[level].all(), B, up.ns, H * 2, W * 2, st));
-        else
-          HCF_LAUNCH(launch_squeeze(zb[level - 1].v(0, up.ns), zb[level].all(), B, up.ns, H * 2, W * 2, st));
+        const int ns = levels[level - 1].ns;
+        run_squeeze(zb[level - 1].v(0, ns), zb[level].all(), ns, H * 2, W * 2);
       }
       const size_t mark = arena.top;
       Scratch sc = alloc_scratch(H, W);
@@ -648,19 +693,13 @@
       const size_t mark = arena.top;
       Scratch sc = alloc_scratch(H, W);
       Buf a = alloc(B, H, W, cf.Ca);
-      std::vector<View> u;
-      u.push_back(zb[level].v(0, lv.ns));
-      for (int l2 = level + 1; l2 < L; ++l2) u.push_back(cfb[l2].v(0, cond_ch(), l2 - level));
-      run_cond_features(cf, u, H, W, cfb[level], sc);
+      const auto cf_at = [&](int l2, int k) { return cfb[l2].v(0, cond_ch(), k); };
+      run_cond_features(cf, cond_sources(zb[level].v(0, lv.ns), level, cf_at), H, W, cfb[level], sc);
       const View cfv = cfb[level].v(0, cond_ch());
       HCF_LAUNCH(launch_copy_view(zb[level].v(lv.ns, cf.Ca), a.all(), B, H, W, st));
       for (size_t k = 0; k < cf.steps.size(); ++k) run_step_forward(cf.steps[k], a, &cfv, H, W, sc, partial, nslots, pslot);
       run_conv(cf.head, {cfv}, H, W, sc.hout.v(0, cf.Ca * 2));
-      GaussArgs g;
-      memset(&g, 0, sizeof(g));
-      g.B = B; g.H = H; g.W = W; g.C = cf.Ca;
-      g.h = sc.hout.v(0, cf.Ca * 2);
-      g.out = a.all();
+      GaussArgs g = gauss_args(sc.hout.v(0, cf.Ca * 2), a.all(), cf.Ca, H, W);
       if (sr()) {
         g.partial = partial + pslot;
         g.partial_stride = nslots;
@@ -673,7 +712,6 @@
           HCF_LAUNCH(launch_gauss_logp(g, st));
         }
       } else {
-        g.rescale = 1;
         g.aux = (level == 0) ? out_z1 : out_z2;
         if (g.aux) HCF_LAUNCH(launch_gauss_encode(g, st));
       }
@@ -687,15 +725,7 @@
       pslot += step_blocks_per_sample(h, w);
       HCF_LAUNCH(launch_quant_logp(zlr, lr, out_lr, B, h, w, lr ? pp : nullptr, nslots, st));
       if (pslot > nslots) fail(HCF_ERR_STATE, "internal: partial slot overflow");
-      // data-independent log-det terms: -ln(quant) HW + sum over steps of (sum(actnorm logs) + slogdet W) * pixels
-      // (summed here, after the steps ran: an ActNorm init pass changes them on the way)
-      double ld_const = -log((double)cfg.quant) * (double)H0 * W0;
-      for (int level = 0; level < L; ++level) {
-        const double px = (double)(H0 >> (level + 1)) * (W0 >> (level + 1));
-        for (const Step& s : levels[level].steps) ld_const += s.ld_const * px;
-        for (const Step& s : levels[level].cf.steps) ld_const += s.ld_const * px;
-      }
-      HCF_LAUNCH(launch_reduce_partials(partial, nslots, nslots, B, ld_const, (double)H0 * W0, out_logdet, out_nll, st));
+      HCF_LAUNCH(launch_reduce_partials(partial, nslots, nslots, B, ld_const_sum(H0, W0), (double)H0 * W0, out_logdet, out_nll, st));
     } else {
       HCF_LAUNCH(launch_nhwc_to_nchw(zlr, out_lr, B, 3, h, w, (flags & HCF_FLAG_NO_CLAMP) ? 0 : 1, st));
     }

@@ -1029,14 +1029,24 @@
     const Conv* next;                                 // the only reader of this conv's output
     const Conv* prev; View prev_y; float *prev_part, *prev_gmax;      // the producer of this conv's single input
   };
-  void t_conv(const Conv& cv, std::vector<VG> in, int H, int W, VG out, const VG* res1 = nullptr, float rs1 = 0.f,
-              const VG* res2 = nullptr, float rs2 = 0.f, const RdbCtx* ctx = nullptr, const EpiLink* link = nullptr,
-              bool already_run = false) {
+  struct TConvOpt {                                  // t_conv's optionals
+    const VG* res1 = nullptr; float rs1 = 0.f;        // the residuals of the conv's epilogue (ConvOpt) with their gradient buffers
+    const VG* res2 = nullptr; float rs2 = 0.f;
+    const RdbCtx* ctx = nullptr;
+    const EpiLink* link = nullptr;
+    bool already_run = false;                        // the caller has launched the forward conv (t_rdb): the record only
+  };
+  void t_conv(const Conv& cv, std::vector<VG> in, int H, int W, VG out) { t_conv(cv, std::move(in), H, W, out, TConvOpt()); }
+  void t_conv(const Conv& cv, std::vector<VG> in, int H, int W, VG out, const TConvOpt& o) {
     if (rc != HCF_OK) return;
+    const VG *const res1 = o.res1, *const res2 = o.res2;
+    const float rs1 = o.rs1, rs2 = o.rs2;
+    const RdbCtx* const ctx = o.ctx; const EpiLink* const link = o.link;
     std::vector<View> srcs;
     for (const VG& s : in) srcs.push_back(s.v);
-    const View none = mkview(nullptr, 0, 0, 0);
-    if (!already_run) run_conv(cv, srcs, H, W, out.v, res1 ? res1->v : none, rs1, res2 ? res2->v : none, rs2);
+    ConvOpt fo;
+    fo.res1 = res1 ? res1->v : View(); fo.rs1 = rs1; fo.res2 = res2 ? res2->v : View(); fo.rs2 = rs2;
+    if (!o.already_run) run_conv(cv, srcs, H, W, out.v, fo);
     ConvRec r;
     memset(&r, 0, sizeof(r));
     r.cv = &cv;
@@ -1053,7 +1063,7 @@
     r.y = out.v; r.y.n = cv.cout;
     r.gy = out.g; r.gy.n = cv.cout;
     r.has1 = res1 != nullptr; r.has2 = res2 != nullptr;
-    r.g1 = res1 ? res1->g : none; r.g2 = res2 ? res2->g : none;
+    r.g1 = res1 ? res1->g : View(); r.g2 = res2 ? res2->g : View();
     r.rs1 = rs1; r.rs2 = rs2;
     if (ctx) {
       r.rdb = ctx->rdb; r.rdb_m = ctx->m; r.gA = ctx->gA; r.gB = ctx->gB; r.gT = ctx->gT; r.gmax2 = ctx->gmax2;
@@ -1097,9 +1107,10 @@
       l1.own_part = tape->g.alloc(rows * s.c[1].cout); l1.own_gmax = tape->g.alloc(1); l1.next = &s.c[2];
       l1.prev = &s.c[0]; l1.prev_y = h1.v.v(0, s.hid); l1.prev_part = l0.own_part; l1.prev_gmax = l0.own_gmax;
       l2.prev = &s.c[1]; l2.prev_y = h2.v.v(0, s.hid); l2.prev_part = l1.own_part; l2.prev_gmax = l1.own_gmax;
-      t_conv(s.c[0], in, H, W, vg(h1, 0, s.hid), nullptr, 0.f, nullptr, 0.f, nullptr, &l0);
-      t_conv(s.c[1], {vg(h1, 0, s.hid)}, H, W, vg(h2, 0, s.hid), nullptr, 0.f, nullptr, 0.f, nullptr, &l1);
-      t_conv(s.c[2], {vg(h2, 0, s.hid)}, H, W, vg(ho, 0, s.f_out), nullptr, 0.f, nullptr, 0.f, nullptr, &l2);
+      TConvOpt o;
+      o.link = &l0; t_conv(s.c[0], in, H, W, vg(h1, 0, s.hid), o);
+      o.link = &l1; t_conv(s.c[1], {vg(h1, 0, s.hid)}, H, W, vg(h2, 0, s.hid), o);
+      o.link = &l2; t_conv(s.c[2], {vg(h2, 0, s.hid)}, H, W, vg(ho, 0, s.f_out), o);
     } else {
       TB grow = talloc(B_, H, W, 4 * s.hid);
       for (int i = 0; i < 5; ++i) {
@@ -1115,18 +1126,13 @@
     const Step* sp = &s;
     Buf za = alloc(B_, H, W, s.C);
     TB zb = talloc(B_, H, W, s.C), zout = talloc(B_, H, W, s.C);
-    StepArgs a;
-    memset(&a, 0, sizeof(a));
-    a.B = B_; a.H = H; a.W = W; a.C = s.C; a.ns = s.ns; a.mode = s.mode;
+    StepArgs a = step_args(s, H, W, true);
     a.z = zin.v.all(); a.out = zb.v.all(); a.aux = za.all();
-    a.mat = s.has_mat ? s.mat_fwd : nullptr; a.an_bias = s.bias; a.an_mul = s.mul_fwd;
     HCF_LAUNCH(launch_step_head_fwd(a, st));
     float* const spart = tape->g.alloc((size_t)B_ * step_blocks_per_sample(H, W) * 2 * s.cmax);
     if (!dry()) tape->recs.push_back([this, sp, zin, zb, za, H, W, spart]() {
       const Step& s = *sp;
-      StepBwdArgs b;
-      memset(&b, 0, sizeof(b));
-      b.B = B_; b.H = H; b.W = W; b.C = s.C; b.ns = s.ns; b.mode = s.mode;
+      StepBwdArgs b = step_dims<StepBwdArgs>(s, H, W);
       b.gzb = zb.g.all(); b.za = za.all(); b.gzin = zin.g.all();
       b.matT = s.has_mat ? s.mat_fwdT : nullptr; b.an_mul = s.mul_fwd;
       b.g_bias = gp(s.an_key + ".bias"); b.g_logs = gp(s.an_key + ".logs");
@@ -1158,9 +1164,7 @@
     HCF_LAUNCH(launch_step_couple_fwd(a, st));
     if (!dry()) tape->recs.push_back([this, sp, zb, zout, ho, H, W]() {
       const Step& s = *sp;
-      StepBwdArgs b;
-      memset(&b, 0, sizeof(b));
-      b.B = B_; b.H = H; b.W = W; b.C = s.C; b.ns = s.ns; b.mode = s.mode;
+      StepBwdArgs b = step_dims<StepBwdArgs>(s, H, W);
       b.gzout = zout.g.all(); b.zout = zout.v.all(); b.h = ho.v.v(0, s.f_out);
       b.gzb = zb.g.all(); b.gh = ho.g.v(0, s.f_out);
       b.gobj = tape->bwd.gobj;
@@ -1180,7 +1184,6 @@
       const size_t rows = (size_t)std::max(conv_epilogue_bwd_blocks(B_, H, W), conv_tile_blocks_max(B_, H, W)) * 2;
       float *gm[5], *pt[5];
       for (int i = 0; i < 5; ++i) { gm[i] = tape->g.alloc(1); pt[i] = tape->g.alloc(rows * (i < 4 ? gc : nf)); }
-      const View none = mkview(nullptr, 0, 0, 0);
       for (int m = 0; m < 5; ++m) {                    // ctx[m]: the record of conv index m (its output: x_{m+1}), which gathers dL/dx_m
         ctx[m].rdb = &r; ctx[m].m = m;
         ctx[m].gmax2 = gmax2 + m; ctx[m].gmax2_next = m < 4 ? gmax2 + m + 1 : nullptr; ctx[m].gmax2_prev = m >= 1 ? gmax2 + m - 1 : nullptr;
@@ -1188,7 +1191,7 @@
         ctx[m].gB = out.g; ctx[m].gB.n = nf;
         ctx[m].gT = (m == 0) ? xin.g : grow.g.v((m - 1) * gc, gc);
         ctx[m].own_part = pt[m]; ctx[m].own_gmax = gm[m]; ctx[m].own_fused = m < 4 ? 1 : 0;
-        ctx[m].prev_y = m >= 1 ? grow.v.v((m - 1) * gc, gc) : none;
+        ctx[m].prev_y = m >= 1 ? grow.v.v((m - 1) * gc, gc) : View();
         ctx[m].prev_part = m >= 1 ? pt[m - 1] : nullptr;
         ctx[m].prev_gmax = m >= 1 ? gm[m - 1] : nullptr;
       }
@@ -1196,15 +1199,19 @@
     // forward: the block as the inference pass runs it (run_rdb: the fat pairs where they pay -- conv 2j+1 and the old-input part of
     // conv 2j+2 as one 64-wide launch + the completion; same tensors x_1 .. x_4, out in the same buffers), then one tape record per
     // conv: the backward pass needs each conv's inputs and output, not the launches that produced them
-    const View none_v = mkview(nullptr, 0, 0, 0);
-    run_rdb(r, xin.v, grow.v, H, W, out.v, res2 ? res2->v : none_v, rs2, tape->tfat.p ? &tape->tfat : nullptr);
+    run_rdb(r, xin.v, grow.v, H, W, out.v, res2 ? res2->v : View(), rs2, tape->tfat.p ? &tape->tfat : nullptr);
+    TConvOpt o;
+    o.already_run = true;
     for (int i = 0; i < 4; ++i) {
       std::vector<VG> in;
       in.push_back(xin);
       if (i > 0) in.push_back(vg(grow, 0, i * gc));
-      t_conv(r.c[i], in, H, W, vg(grow, i * gc, gc), nullptr, 0.f, nullptr, 0.f, r.gather ? &ctx[i] : nullptr, nullptr, true);
+      o.ctx = r.gather ? &ctx[i] : nullptr;
+      t_conv(r.c[i], in, H, W, vg(grow, i * gc, gc), o);
     }
-    t_conv(r.c[4], {xin, vg(grow, 0, 4 * gc)}, H, W, out, &xin, 0.2f, res2, rs2, r.gather ? &ctx[4] : nullptr, nullptr, true);
+    o.ctx = r.gather ? &ctx[4] : nullptr;
+    o.res1 = &xin; o.rs1 = 0.2f; o.res2 = res2; o.rs2 = rs2;
+    t_conv(r.c[4], {xin, vg(grow, 0, 4 * gc)}, H, W, out, o);
   }
 
   void t_rrdb(const Rrdb& rr, VG x0, VG out, int H, int W) {
@@ -1243,7 +1250,8 @@
       cur = vgall(t);
     }
     const VG f0v = vgall(f0);
-    t_conv(cf.trunk_conv1, {cur}, H, W, srn ? vg(cfb, nf, nf) : vg(cfb, 0, nf), &f0v, 1.0f);
+    TConvOpt o; o.res1 = &f0v; o.rs1 = 1.0f;
+    t_conv(cf.trunk_conv1, {cur}, H, W, srn ? vg(cfb, nf, nf) : vg(cfb, 0, nf), o);
     if (!dry() && cfb.g.p) {
       // everything taped AFTER this point that reads the features adds its gradient to cfb.g on dg_stream (bwd_conv); the entry below
       // runs in front of the records above: the conditional net's backward starts from the complete gradient
@@ -1252,101 +1260,29 @@
     }
   }
 
-  // ---- the taped forward pass of the rescaling net: HCFlowNet_Rescaling.normal_flow_diracLR (:39-46) ------------------
-
-  void pass_train_forward_rescale(const float* hr, float* out_lr, float* out_z1, float* out_z2, int B, int H0, int W0,
-                                  uint32_t flags) {
-    tape_begin(B);
-    const int L = cfg.L;
-    int pslot = 0;
-    std::vector<TB> zlev(L), cfb(L);
-    for (int level = 0; level < L; ++level) {
-      const Level& lv = levels[level];
-      const int H = H0 >> (level + 1), W = W0 >> (level + 1);
-      TB z = talloc(B, H, W, lv.C);
-      if (level == 0) {
-        HCF_LAUNCH(launch_nchw_squeeze(hr, nullptr, 1.f, z.v.all(), B, cfg.in_nc, H0, W0, 1, st));
-      } else {
-        const Level& up = levels[level - 1];
-        const TB prev = zlev[level - 1];
-        HCF_LAUNCH(launch_haar_fwd(prev.v.v(0, up.ns), z.v.all(), B, up.ns, H * 2, W * 2, st));
-        Buf tmp = alloc(B, H * 2, W * 2, up.ns);
-        const int C4 = lv.C, ns = up.ns;
-        if (!dry()) tape->recs.push_back([this, z, prev, tmp, C4, ns, H, W]() {      // (Haar fwd)^T = Haar inv / 4
-          HCF_LAUNCH(launch_haar_inv(z.g.all(), tmp.all(), B_, C4, H, W, st));
-          HCF_LAUNCH(launch_add_view(tmp.all(), prev.g.v(0, ns), B_, H * 2, W * 2, 0.25f, st));
-        });
-      }
-      for (size_t k = 0; k < lv.steps.size(); ++k) z = t_step_forward(lv.steps[k], z, nullptr, H, W, nullptr, 0, pslot);
-      zlev[level] = z;
-    }
-    for (int level = L - 1; level >= 0; --level) {
-      const Level& lv = levels[level];
-      const CondFlow& cf = lv.cf;
-      const int H = H0 >> (level + 1), W = W0 >> (level + 1);
-      cfb[level] = talloc(B, H, W, cond_ch());
-      const TB zl = zlev[level];
-      TB a = talloc(B, H, W, cf.Ca);
-      HCF_LAUNCH(launch_copy_view(zl.v.v(lv.ns, cf.Ca), a.v.all(), B, H, W, st));
-      {
-        const TB a0 = a;
-        const int ns = lv.ns, Ca = cf.Ca;
-        if (!dry()) tape->recs.push_back([this, a0, zl, ns, Ca, H, W]() {
-          HCF_LAUNCH(launch_add_view(a0.g.all(), zl.g.v(ns, Ca), B_, H, W, 1.f, st));
-        });
-      }
-      std::vector<VG> u;
-      u.push_back(vg(zl, 0, lv.ns));
-      for (int l2 = level + 1; l2 < L; ++l2) u.push_back(vg(cfb[l2], 0, cond_ch(), l2 - level));
-      t_cond_features(cf, u, H, W, cfb[level]);
-      const VG cfv = vg(cfb[level], 0, cond_ch());
-      for (size_t k = 0; k < cf.steps.size(); ++k) a = t_step_forward(cf.steps[k], a, &cfv, H, W, nullptr, 0, pslot);
-      TB ho = talloc(B, H, W, cf.Ca * 2);
-      t_conv(cf.head, {cfv}, H, W, vg(ho, 0, cf.Ca * 2));
-      GaussArgs g;
-      memset(&g, 0, sizeof(g));
-      g.B = B; g.H = H; g.W = W; g.C = cf.Ca;
-      g.h = ho.v.v(0, cf.Ca * 2);
-      g.out = a.v.all();
-      g.rescale = 1;
-      g.aux = (level == 0) ? out_z1 : out_z2;
-      if (g.aux) HCF_LAUNCH(launch_gauss_encode(g, st));
-      {
-        const TB af = a;
-        const int Ca = cf.Ca, zi = (level == 0) ? 0 : 1;
-        if (!dry()) tape->recs.push_back([this, af, ho, Ca, zi, H, W]() {
-          PriorBwdArgs p;
-          memset(&p, 0, sizeof(p));
-          p.B = B_; p.H = H; p.W = W; p.C = Ca;
-          p.a = af.v.all(); p.h = ho.v.v(0, 2 * Ca); p.ga = af.g.all(); p.gh = ho.g.v(0, 2 * Ca);
-          p.rescale = 1;
-          p.gz_nchw = tape->bwd.g_fwd_z[zi];
-          HCF_LAUNCH(launch_gauss_encode_bwd(p, st));
-        });
-      }
-    }
-    const int h = H0 >> L, w = W0 >> L;
-    const TB zd = zlev[L - 1];
-    const int clamp = (flags & HCF_FLAG_NO_CLAMP) ? 0 : 1;
-    HCF_LAUNCH(launch_nhwc_to_nchw(zd.v.v(0, 3), out_lr, B, 3, h, w, clamp, st));
-    if (!dry()) tape->recs.push_back([this, zd, h, w, clamp]() {
-      if (tape->bwd.g_fwd_lr) HCF_LAUNCH(launch_add_nchw_grad(tape->bwd.g_fwd_lr, zd.v.v(0, 3), zd.g.v(0, 3), B_, h, w, clamp, st));
-    });
+  // backward of a level's prior: a = the split-off half (Ca channels), ho = the head conv's output, both with their gradients
+  PriorBwdArgs prior_bwd_args(const TB& a, const TB& ho, int Ca, int H, int W) const {
+    PriorBwdArgs p;
+    memset(&p, 0, sizeof(p));
+    p.B = B_; p.H = H; p.W = W; p.C = Ca;
+    p.a = a.v.all(); p.h = ho.v.v(0, 2 * Ca); p.ga = a.g.all(); p.gh = ho.g.v(0, 2 * Ca);
+    p.rescale = sr() ? 0 : 1;
+    return p;
   }
 
-  // ---- the taped forward pass: HCFlowNet_SR.normal_flow_diracLR (HCFlowNet_SR_arch.py:47-67) ------------------------
-  void pass_train_forward_sr(const float* hr, const float* lr, const float* noise, float* out_lr, float* out_nll,
-                             float* out_logdet, int B, int H0, int W0) {
+  // ---- the taped forward pass: HCFlowNet_SR.normal_flow_diracLR (HCFlowNet_SR_arch.py:47-67; lr, noise -> out_nll, out_logdet) and
+  // HCFlowNet_Rescaling.normal_flow_diracLR (HCFlowNet_Rescaling_arch.py:39-46; -> out_z1, out_z2, flags). One walk, as pass_forward.
+  void pass_train_forward(const float* hr, const float* lr, const float* noise, float* out_lr, float* out_nll, float* out_logdet,
+                          float* out_z1, float* out_z2, int B, int H0, int W0, uint32_t flags) {
     tape_begin(B);
     const int L = cfg.L;
-    int nslots = 0;
-    for (int level = 0; level < L; ++level) {
-      const int nb = step_blocks_per_sample(H0 >> (level + 1), W0 >> (level + 1));
-      nslots += nb * (int)(levels[level].steps.size() + levels[level].cf.steps.size() + 1);
+    const bool haar = cfg.squeeze == HCF_SQUEEZE_HAAR;
+    const int nslots = sr() ? nll_slots(H0, W0) : 0;      // the log-det partial sums: SR only
+    float* partial = nullptr;
+    if (sr()) {
+      partial = arena.alloc((size_t)B * nslots);
+      HCF_LAUNCH(launch_fill(partial, (size_t)B * nslots, 0.f, st));
     }
-    nslots += step_blocks_per_sample(H0 >> L, W0 >> L);
-    float* partial = arena.alloc((size_t)B * nslots);
-    HCF_LAUNCH(launch_fill(partial, (size_t)B * nslots, 0.f, st));
     int pslot = 0;
     std::vector<TB> zlev(L), cfb(L);
     for (int level = 0; level < L; ++level) {
@@ -1354,16 +1290,15 @@
       const int H = H0 >> (level + 1), W = W0 >> (level + 1);
       TB z = talloc(B, H, W, lv.C);
       if (level == 0) {
-        HCF_LAUNCH(launch_nchw_squeeze(hr, noise, cfg.quant, z.v.all(), B, cfg.in_nc, H0, W0, 0, st));
+        HCF_LAUNCH(launch_nchw_squeeze(hr, noise, cfg.quant, z.v.all(), B, cfg.in_nc, H0, W0, haar ? 1 : 0, st));   // (quant: read with noise only)
       } else {
-        const Level& up = levels[level - 1];
         const TB prev = zlev[level - 1];
-        HCF_LAUNCH(launch_squeeze(prev.v.v(0, up.ns), z.v.all(), B, up.ns, H * 2, W * 2, st));
-        Buf tmp = alloc(B, H * 2, W * 2, up.ns);
-        const int C4 = lv.C, ns = up.ns;
-        if (!dry()) tape->recs.push_back([this, z, prev, tmp, C4, ns, H, W]() {
-          HCF_LAUNCH(launch_unsqueeze(z.g.all(), tmp.all(), B_, C4, H, W, st));
-          HCF_LAUNCH(launch_add_view(tmp.all(), prev.g.v(0, ns), B_, H * 2, W * 2, 1.f, st));
+        const int C4 = lv.C, ns = levels[level - 1].ns;
+        run_squeeze(prev.v.v(0, ns), z.v.all(), ns, H * 2, W * 2);
+        Buf tmp = alloc(B, H * 2, W * 2, ns);
+        if (!dry()) tape->recs.push_back([this, z, prev, tmp, C4, ns, H, W, haar]() {      // squeeze^T = unsqueeze, (Haar fwd)^T = Haar inv / 4
+          run_unsqueeze(z.g.all(), tmp.all(), C4, H, W);
+          HCF_LAUNCH(launch_add_view(tmp.all(), prev.g.v(0, ns), B_, H * 2, W * 2, haar ? 0.25f : 1.f, st));
         });
       }
       for (size_t k = 0; k < lv.steps.size(); ++k) z = t_step_forward(lv.steps[k], z, nullptr, H, W, partial, nslots, pslot);
@@ -1377,7 +1312,8 @@
       const TB zl = zlev[level];
       TB a = talloc(B, H, W, cf.Ca);
       HCF_LAUNCH(launch_copy_view(zl.v.v(lv.ns, cf.Ca), a.v.all(), B, H, W, st));
-      if (level == 0 && !dry()) tape->mark = tape->recs.size();      // from here on: level-0 conditional flow + the output terms (two-phase backward)
+      // SR, from here on: level-0 conditional flow + the output terms (two-phase backward)
+      if (sr() && level == 0 && !dry()) tape->mark = tape->recs.size();
       {
         const TB a0 = a;
         const int ns = lv.ns, Ca = cf.Ca;
@@ -1385,53 +1321,53 @@
           HCF_LAUNCH(launch_add_view(a0.g.all(), zl.g.v(ns, Ca), B_, H, W, 1.f, st));       // Split: z = cat(z1, a)
         });
       }
-      std::vector<VG> u;
-      u.push_back(vg(zl, 0, lv.ns));
-      for (int l2 = level + 1; l2 < L; ++l2) u.push_back(vg(cfb[l2], 0, cond_ch(), l2 - level));
-      t_cond_features(cf, u, H, W, cfb[level]);
+      t_cond_features(cf, cond_sources(vg(zl, 0, lv.ns), level, [&](int l2, int k) { return vg(cfb[l2], 0, cond_ch(), k); }), H, W, cfb[level]);
       const VG cfv = vg(cfb[level], 0, cond_ch());
       for (size_t k = 0; k < cf.steps.size(); ++k) a = t_step_forward(cf.steps[k], a, &cfv, H, W, partial, nslots, pslot);
       TB ho = talloc(B, H, W, cf.Ca * 2);
       t_conv(cf.head, {cfv}, H, W, vg(ho, 0, cf.Ca * 2));
-      GaussArgs g;
-      memset(&g, 0, sizeof(g));
-      g.B = B; g.H = H; g.W = W; g.C = cf.Ca;
-      g.h = ho.v.v(0, cf.Ca * 2);
-      g.out = a.v.all();
-      g.partial = partial + pslot;
-      g.partial_stride = nslots;
-      pslot += step_blocks_per_sample(H, W);
-      HCF_LAUNCH(launch_gauss_logp(g, st));
-      {
-        const TB af = a;
-        const int Ca = cf.Ca;
-        if (!dry()) tape->recs.push_back([this, af, ho, Ca, H, W]() {
-          PriorBwdArgs p;
-          memset(&p, 0, sizeof(p));
-          p.B = B_; p.H = H; p.W = W; p.C = Ca;
-          p.a = af.v.all(); p.h = ho.v.v(0, 2 * Ca); p.ga = af.g.all(); p.gh = ho.g.v(0, 2 * Ca);
+      GaussArgs g = gauss_args(ho.v.v(0, cf.Ca * 2), a.v.all(), cf.Ca, H, W);
+      if (sr()) {
+        g.partial = partial + pslot;
+        g.partial_stride = nslots;
+        pslot += step_blocks_per_sample(H, W);
+        HCF_LAUNCH(launch_gauss_logp(g, st));
+      } else {
+        g.aux = (level == 0) ? out_z1 : out_z2;
+        if (g.aux) HCF_LAUNCH(launch_gauss_encode(g, st));
+      }
+      const TB af = a;
+      const int Ca = cf.Ca, zi = (level == 0) ? 0 : 1;
+      if (!dry()) tape->recs.push_back([this, af, ho, Ca, zi, H, W]() {
+        PriorBwdArgs p = prior_bwd_args(af, ho, Ca, H, W);
+        if (sr()) {
           p.gobj = tape->bwd.gobj;
           HCF_LAUNCH(launch_gauss_logp_bwd(p, st));
-        });
-      }
+        } else {
+          p.gz_nchw = tape->bwd.g_fwd_z[zi];
+          HCF_LAUNCH(launch_gauss_encode_bwd(p, st));
+        }
+      });
     }
     const int h = H0 >> L, w = W0 >> L;
     const TB zd = zlev[L - 1];
-    float* pp = partial + pslot;
-    pslot += step_blocks_per_sample(h, w);
-    HCF_LAUNCH(launch_quant_logp(zd.v.v(0, 3), lr, out_lr, B, h, w, pp, nslots, st));
-    if (!dry()) tape->recs.push_back([this, zd, lr, h, w]() {
-      HCF_LAUNCH(launch_quant_logp_bwd(zd.v.v(0, 3), lr, zd.g.v(0, 3), B_, h, w, tape->bwd.gobj, st));
-    });
-    if (pslot > nslots) fail(HCF_ERR_STATE, "internal: partial slot overflow (training)");
-    double ld_const = -log((double)cfg.quant) * (double)H0 * W0;
-    for (int level = 0; level < L; ++level) {
-      const double px = (double)(H0 >> (level + 1)) * (W0 >> (level + 1));
-      for (const Step& s : levels[level].steps) ld_const += s.ld_const * px;
-      for (const Step& s : levels[level].cf.steps) ld_const += s.ld_const * px;
+    if (sr()) {
+      float* pp = partial + pslot;
+      pslot += step_blocks_per_sample(h, w);
+      HCF_LAUNCH(launch_quant_logp(zd.v.v(0, 3), lr, out_lr, B, h, w, pp, nslots, st));
+      if (!dry()) tape->recs.push_back([this, zd, lr, h, w]() {
+        HCF_LAUNCH(launch_quant_logp_bwd(zd.v.v(0, 3), lr, zd.g.v(0, 3), B_, h, w, tape->bwd.gobj, st));
+      });
+      if (pslot > nslots) fail(HCF_ERR_STATE, "internal: partial slot overflow (training)");
+      HCF_LAUNCH(launch_reduce_partials(partial, nslots, nslots, B, ld_const_sum(H0, W0), (double)H0 * W0, out_logdet, out_nll, st));
+      tape->pixels = (double)H0 * W0;
+    } else {
+      const int clamp = (flags & HCF_FLAG_NO_CLAMP) ? 0 : 1;
+      HCF_LAUNCH(launch_nhwc_to_nchw(zd.v.v(0, 3), out_lr, B, 3, h, w, clamp, st));
+      if (!dry()) tape->recs.push_back([this, zd, h, w, clamp]() {
+        if (tape->bwd.g_fwd_lr) HCF_LAUNCH(launch_add_nchw_grad(tape->bwd.g_fwd_lr, zd.v.v(0, 3), zd.g.v(0, 3), B_, h, w, clamp, st));
+      });
     }
-    HCF_LAUNCH(launch_reduce_partials(partial, nslots, nslots, B, ld_const, (double)H0 * W0, out_logdet, out_nll, st));
-    tape->pixels = (double)H0 * W0;
   }
 
   // ================= reverse (sampling) path with gradients: HCFlowNet_SR.reverse_flow_diracLR =======================
@@ -1441,18 +1377,13 @@
     TB ho = t_coupling_net(s, step_z1_vg(s, zin), u, H, W);
     TB zc = talloc(B_, H, W, s.C), x = talloc(B_, H, W, s.C);
     Buf y = alloc(B_, H, W, s.C);
-    StepArgs a;
-    memset(&a, 0, sizeof(a));
-    a.B = B_; a.H = H; a.W = W; a.C = s.C; a.ns = s.ns; a.mode = s.mode;
+    StepArgs a = step_args(s, H, W, false);
     a.z = zin.v.all(); a.h = ho.v.v(0, s.f_out); a.out = x.v.all(); a.aux = zc.v.all();
-    a.mat = s.has_mat ? s.mat_inv : nullptr; a.an_bias = s.bias; a.an_mul = s.mul_inv;
     HCF_LAUNCH(launch_step_tail_inv(a, st));
     float* const spart = tape->g.alloc((size_t)B_ * step_blocks_per_sample(H, W) * 2 * s.cmax);
     if (!dry()) tape->recs.push_back([this, sp, zin, zc, x, y, ho, H, W, spart]() {
       const Step& s = *sp;
-      StepInvBwdArgs b;
-      memset(&b, 0, sizeof(b));
-      b.B = B_; b.H = H; b.W = W; b.C = s.C; b.ns = s.ns; b.mode = s.mode;
+      StepInvBwdArgs b = step_dims<StepInvBwdArgs>(s, H, W);
       b.gx = x.g.all(); b.x = x.v.all(); b.zc = zc.v.all(); b.h = ho.v.v(0, s.f_out);
       b.gz = zin.g.all(); b.gh = ho.g.v(0, s.f_out); b.gzc = zc.g.all(); b.y = y.all();
       b.matInvT = s.has_mat ? s.mat_invT : nullptr;
@@ -1494,51 +1425,32 @@
           if (tape->bwd.g_in_nchw) HCF_LAUNCH(launch_nhwc_to_nchw(z.g.v(0, 3), tape->bwd.g_in_nchw, B_, 3, H, W, 0, st));
         });
       } else {
-        const Level& dp = levels[level + 1];
+        const int Cd = levels[level + 1].C, ns = lv.ns;
         const TB zp = zprev;
-        const int ns = lv.ns;
-        if (cfg.squeeze == HCF_SQUEEZE_HAAR) {
-          HCF_LAUNCH(launch_haar_inv(zp.v.all(), z.v.v(0, lv.ns), B, dp.C, H / 2, W / 2, st));
-          Buf tmp = alloc(B, H / 2, W / 2, dp.C);
-          if (!dry()) tape->recs.push_back([this, z, zp, tmp, ns, H, W]() {                     // (Haar inv)^T = 4 Haar fwd
-            HCF_LAUNCH(launch_haar_fwd(z.g.v(0, ns), tmp.all(), B_, ns, H, W, st));
-            HCF_LAUNCH(launch_add_view(tmp.all(), zp.g.all(), B_, H / 2, W / 2, 4.f, st));
-          });
-        } else {
-          HCF_LAUNCH(launch_unsqueeze(zp.v.all(), z.v.v(0, lv.ns), B, dp.C, H / 2, W / 2, st));
-          if (!dry()) tape->recs.push_back([this, z, zp, ns, H, W]() {
-            HCF_LAUNCH(launch_squeeze(z.g.v(0, ns), zp.g.all(), B_, ns, H, W, st));        // (=): its only consumer
-          });
-        }
+        const bool haar = cfg.squeeze == HCF_SQUEEZE_HAAR;
+        run_unsqueeze(zp.v.all(), z.v.v(0, ns), Cd, H / 2, W / 2);
+        const Buf tmp = haar ? alloc(B, H / 2, W / 2, Cd) : Buf{nullptr, 0, 0};
+        if (!dry()) tape->recs.push_back([this, z, zp, tmp, ns, H, W, haar]() {
+          // unsqueeze^T = squeeze, straight into the gradient of its only consumer (=); (Haar inv)^T = 4 Haar fwd
+          run_squeeze(z.g.v(0, ns), haar ? tmp.all() : zp.g.all(), ns, H, W);
+          if (haar) HCF_LAUNCH(launch_add_view(tmp.all(), zp.g.all(), B_, H / 2, W / 2, 4.f, st));
+        });
       }
-      std::vector<VG> u;
-      u.push_back(vg(z, 0, lv.ns));
-      for (int l2 = level + 1; l2 < L; ++l2) u.push_back(vg(cfb[l2], 0, cond_ch(), l2 - level));
-      t_cond_features(cf, u, H, W, cfb[level]);
+      t_cond_features(cf, cond_sources(vg(z, 0, lv.ns), level, [&](int l2, int k) { return vg(cfb[l2], 0, cond_ch(), k); }), H, W, cfb[level]);
       const VG cfv = vg(cfb[level], 0, cond_ch());
       TB ho = talloc(B, H, W, cf.Ca * 2);
       t_conv(cf.head, {cfv}, H, W, vg(ho, 0, cf.Ca * 2));
       TB a = talloc(B, H, W, cf.Ca);
       {
-        GaussArgs g;
-        memset(&g, 0, sizeof(g));
-        g.B = B; g.H = H; g.W = W; g.C = cf.Ca;
-        g.h = ho.v.v(0, cf.Ca * 2);
-        g.rescale = sr() ? 0 : 1;
+        GaussArgs g = gauss_args(ho.v.v(0, cf.Ca * 2), a.v.all(), cf.Ca, H, W);
         const int draw = L - 1 - level;
         g.eps = (eps && draw < n_eps) ? eps[draw] : nullptr;
         g.tau = tau; g.seed = seed; g.offset = (uint64_t)draw;
-        g.out = a.v.all();
         HCF_LAUNCH(launch_gauss_sample(g, st));
         const TB a0 = a;
         const int Ca = cf.Ca;
         if (!dry()) tape->recs.push_back([this, a0, ho, Ca, H, W]() {
-          PriorBwdArgs p;
-          memset(&p, 0, sizeof(p));
-          p.B = B_; p.H = H; p.W = W; p.C = Ca;
-          p.a = a0.v.all(); p.h = ho.v.v(0, 2 * Ca); p.ga = a0.g.all(); p.gh = ho.g.v(0, 2 * Ca);
-          p.rescale = sr() ? 0 : 1;
-          HCF_LAUNCH(launch_gauss_sample_bwd(p, st));
+          HCF_LAUNCH(launch_gauss_sample_bwd(prior_bwd_args(a0, ho, Ca, H, W), st));
         });
       }
       for (int k = (int)cf.steps.size() - 1; k >= 0; --k) a = t_step_inverse(cf.steps[k], a, &cfv, H, W);
