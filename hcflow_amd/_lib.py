@@ -37,6 +37,8 @@ SYMBOLS = [
     "hcf_aux_conv2d_workspace", "hcf_aux_conv2d", "hcf_aux_conv2d_backward", "hcf_adam_step",
     "hcf_lpips_workspace", "hcf_lpips_alex",
     "hcf_aux_bn_act_workspace", "hcf_aux_bn_act", "hcf_aux_bn_act_backward",
+    "hcf_op_step_forward_backward", "hcf_op_step_inverse_backward", "hcf_op_prior_backward", "hcf_op_quant_logp_backward",
+    "hcf_op_output_grad_backward", "hcf_op_conv_epilogue_backward", "hcf_op_lu_chain",
 ]
 
 
@@ -146,6 +148,14 @@ def load() -> C.CDLL:
     lib.hcf_op_step_forward_couple.argtypes = [fp, fp, fp, fp, i32, i32, i32, i32, i32, i32, i32, vp]
     lib.hcf_op_gauss_logp.argtypes = [fp, fp, fp, i32, i32, i32, i32, vp]
     lib.hcf_op_gauss_sample.argtypes = [fp, fp, f32, u64, fp, i32, i32, i32, i32, i32, vp]
+    lib.hcf_op_step_forward_backward.argtypes = [fp] * 8 + [i32] * 7 + [fp, fp, f32, vp]
+    lib.hcf_op_step_inverse_backward.argtypes = [fp] * 10 + [i32] * 7 + [fp, fp, fp, vp]
+    lib.hcf_op_prior_backward.argtypes = [i32, fp, fp, fp, fp, fp, i32, i32, i32, i32, i32, f32, vp]
+    lib.hcf_op_quant_logp_backward.argtypes = [fp, fp, fp, i32, i32, i32, f32, vp]
+    lib.hcf_op_output_grad_backward.argtypes = [i32, fp, fp, fp, i32, i32, i32, i32, vp]
+    lib.hcf_op_conv_epilogue_backward.argtypes = [fp, fp, fp, i32, i32, f32, fp, i32, f32, fp, fp, fp, fp, f32, fp, fp, fp,
+                                                  i32, i32, i32, i32, i32, i32, vp]
+    lib.hcf_op_lu_chain.argtypes = [fp] * 7 + [i32, vp]
     for name in SYMBOLS:
         fn = getattr(lib, name)
         if name not in ("hcf_destroy", "hcf_last_error", "hcf_workspace_bytes", "hcf_weight_bytes",

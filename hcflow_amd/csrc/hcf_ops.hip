@@ -469,6 +469,254 @@ int hcf_op_gauss_sample(const float* h, const float* eps, float tau, uint64_t se
   return rc;
 }
 
+
+// ---- backward kernels of the training path (hcf_train.hip), one entry per launcher ------------------------------------
+}  // extern "C"
+
+namespace hcf {
+
+// an NCHW tensor of n channels (nullptr: zeros) as channels [c0, c0 + n) of a dense, zero-filled NHWC buffer of cs floats per pixel
+static View nhwc_window(Tmp& t, const float* x, int B, int n, int H, int W, int cs, int c0, hipStream_t st, int& rc) {
+  const size_t nf = (size_t)B * H * W * cs;
+  float* p = t.dev(nf);
+  View v = mkview(p, cs, c0, n);
+  if (!p) { rc = HCF_ERR_NOMEM; return v; }
+  if (hipMemsetAsync(p, 0, nf * sizeof(float), st) != hipSuccess) rc = HCF_ERR_HIP;
+  if (x) {
+    const int r = launch_nchw_to_nhwc(x, v, B, n, H, W, st);
+    if (r != HCF_OK) rc = r;
+  }
+  return v;
+}
+
+// per-block partial rows as the engine allocates them (hcf_engine_train.inc), every float a NaN until a block writes its row
+static float* part_rows(Tmp& t, size_t nfloat, hipStream_t st, int& rc) {
+  float* p = t.dev(nfloat);
+  if (!p) { rc = HCF_ERR_NOMEM; return nullptr; }
+  if (hipMemsetAsync(p, 0xff, nfloat * sizeof(float), st) != hipSuccess) rc = HCF_ERR_HIP;
+  return p;
+}
+
+// the engine's fixed-order reduction of those rows: one job, one launch_sum_jobs
+static int reduce_rows(Tmp& t, const float* part, int nblk, int n, int pstride, float* d0, float* d1, float mult1, hipStream_t st) {
+  SumJob j;
+  memset(&j, 0, sizeof(j));
+  j.part = part; j.nblk = nblk; j.n = n; j.pstride = pstride; j.dst0 = d0; j.dst1 = d1; j.mult1 = mult1;
+  SumJob* jd = reinterpret_cast<SumJob*>(t.dev((sizeof(SumJob) + 3) / 4));
+  if (!jd) return HCF_ERR_NOMEM;
+  if (hipMemcpyAsync(jd, &j, sizeof(j), hipMemcpyHostToDevice, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+    return HCF_ERR_HIP;
+  return launch_sum_jobs(jd, 1, st);
+}
+
+static bool step_shape_ok(int B, int C, int H, int W, int hC, int mode, int ns) {
+  if (B < 1 || C < 1 || H < 1 || W < 1) return false;
+  if (mode == CPL_AFFINE) return ns >= 0 && ns <= C && hC == 2 * (C - ns) && hC >= 1;
+  return mode == CPL_SHIFT3 && C >= 3 && hC == 3;
+}
+
+}  // namespace hcf
+
+extern "C" {
+
+int hcf_op_step_forward_backward(const float* gzout, const float* zout, const float* h, const float* za, float* gzin,
+                                 float* gh, float* g_bias, float* g_logs, int32_t B, int32_t C, int32_t H, int32_t W,
+                                 int32_t hC, int32_t mode, int32_t ns, const float* mat, const float* an_logs, float gobj,
+                                 hcf_stream_t stream) {
+  if (!gzout || !zout || !h || !za || !gzin || !gh || !g_bias || !g_logs || !an_logs) return HCF_ERR_ARG;
+  if (!step_shape_ok(B, C, H, W, hC, mode, ns)) return HCF_ERR_ARG;
+  const int M = step_cmax(C);
+  if (M < 0) return HCF_ERR_UNSUPPORTED;
+  hipStream_t st = (hipStream_t)stream;
+  Tmp t;
+  int rc = HCF_OK;
+  StepBwdArgs a;
+  memset(&a, 0, sizeof(a));
+  a.B = B; a.H = H; a.W = W; a.C = C; a.ns = ns; a.mode = mode;
+  a.gzout = nhwc_from_nchw(t, gzout, B, C, H, W, st, rc);
+  a.zout = nhwc_from_nchw(t, zout, B, C, H, W, st, rc);
+  a.h = nhwc_from_nchw(t, h, B, hC, H, W, st, rc);
+  a.za = nhwc_from_nchw(t, za, B, C, H, W, st, rc);
+  a.gzb = nhwc_window(t, nullptr, B, C, H, W, ru4(C), 0, st, rc);
+  a.gh = nhwc_window(t, nullptr, B, hC, H, W, ru4(hC), 0, st, rc);
+  a.gzin = nhwc_window(t, nullptr, B, C, H, W, ru4(C), 0, st, rc);
+  a.gobj = gobj;
+  std::vector<float> hm(M, 0.f);
+  for (int c = 0; c < C; ++c) hm[c] = expf(an_logs[c]);
+  a.an_mul = t.up(hm);
+  if (mat) {                                            // row c of the table = column c of W
+    std::vector<float> wt((size_t)M * M, 0.f);
+    for (int r = 0; r < C; ++r)
+      for (int c = 0; c < C; ++c) wt[(size_t)c * M + r] = mat[(size_t)r * C + c];
+    a.matT = t.up(wt);
+  }
+  a.g_bias = g_bias; a.g_logs = g_logs;
+  const int nblk = B * step_blocks_per_sample(H, W);
+  a.part = part_rows(t, (size_t)nblk * 2 * M, st, rc);
+  if (!t.ok) return HCF_ERR_NOMEM;
+  if (rc == HCF_OK) rc = launch_step_couple_bwd(a, st);
+  if (rc == HCF_OK) rc = launch_step_head_bwd(a, st);
+  if (rc == HCF_OK) rc = reduce_rows(t, a.part, nblk, C, M, g_bias, g_logs, 1.f, st);
+  if (rc == HCF_OK) rc = launch_nhwc_to_nchw(a.gzin, gzin, B, C, H, W, 0, st);
+  if (rc == HCF_OK) rc = launch_nhwc_to_nchw(a.gh, gh, B, hC, H, W, 0, st);
+  if (hipStreamSynchronize(st) != hipSuccess) return HCF_ERR_HIP;
+  return rc;
+}
+
+int hcf_op_step_inverse_backward(const float* gx, const float* x, const float* zc, const float* h, float* gz, float* gh,
+                                 float* gzc, float* y, float* g_bias, float* g_logs, int32_t B, int32_t C, int32_t H,
+                                 int32_t W, int32_t hC, int32_t mode, int32_t ns, const float* mat, const float* an_bias,
+                                 const float* an_logs, hcf_stream_t stream) {
+  if (!gx || !x || !zc || !h || !gz || !gh || !gzc || !y || !g_bias || !g_logs || !an_bias || !an_logs) return HCF_ERR_ARG;
+  if (!step_shape_ok(B, C, H, W, hC, mode, ns)) return HCF_ERR_ARG;
+  const int M = step_cmax(C);
+  if (M < 0) return HCF_ERR_UNSUPPORTED;
+  hipStream_t st = (hipStream_t)stream;
+  Tmp t;
+  int rc = HCF_OK;
+  StepInvBwdArgs a;
+  memset(&a, 0, sizeof(a));
+  a.B = B; a.H = H; a.W = W; a.C = C; a.ns = ns; a.mode = mode;
+  a.gx = nhwc_from_nchw(t, gx, B, C, H, W, st, rc);
+  a.x = nhwc_from_nchw(t, x, B, C, H, W, st, rc);
+  a.zc = nhwc_from_nchw(t, zc, B, C, H, W, st, rc);
+  a.h = nhwc_from_nchw(t, h, B, hC, H, W, st, rc);
+  a.gz = nhwc_window(t, nullptr, B, C, H, W, ru4(C), 0, st, rc);
+  a.gh = nhwc_window(t, nullptr, B, hC, H, W, ru4(hC), 0, st, rc);
+  a.gzc = nhwc_window(t, nullptr, B, C, H, W, ru4(C), 0, st, rc);
+  a.y = nhwc_window(t, nullptr, B, C, H, W, ru4(C), 0, st, rc);
+  std::vector<float> hb(M, 0.f), hf(M, 0.f), hi(M, 0.f);
+  for (int c = 0; c < C; ++c) { hb[c] = an_bias[c]; hf[c] = expf(an_logs[c]); hi[c] = expf(-an_logs[c]); }
+  a.an_bias = t.up(hb);
+  a.mul_fwd = t.up(hf);
+  a.mul_inv = t.up(hi);
+  if (mat) {                                            // row j of the table = column j of W^-1
+    std::vector<float> wi;
+    if (!invert64(mat, C, wi, M)) return HCF_ERR_ARG;
+    std::vector<float> wit((size_t)M * M, 0.f);
+    for (int r = 0; r < C; ++r)
+      for (int c = 0; c < C; ++c) wit[(size_t)c * M + r] = wi[(size_t)r * M + c];
+    a.matInvT = t.up(wit);
+  }
+  a.g_bias = g_bias; a.g_logs = g_logs;
+  const int nblk = B * step_blocks_per_sample(H, W);
+  a.part = part_rows(t, (size_t)nblk * 2 * M, st, rc);
+  if (!t.ok) return HCF_ERR_NOMEM;
+  if (rc == HCF_OK) rc = launch_step_inv_bwd(a, st);
+  if (rc == HCF_OK) rc = reduce_rows(t, a.part, nblk, C, M, g_bias, g_logs, 1.f, st);
+  if (rc == HCF_OK) rc = launch_nhwc_to_nchw(a.gz, gz, B, C, H, W, 0, st);
+  if (rc == HCF_OK) rc = launch_nhwc_to_nchw(a.gh, gh, B, hC, H, W, 0, st);
+  if (rc == HCF_OK) rc = launch_nhwc_to_nchw(a.gzc, gzc, B, C, H, W, 0, st);
+  if (rc == HCF_OK) rc = launch_nhwc_to_nchw(a.y, y, B, C, H, W, 0, st);
+  if (hipStreamSynchronize(st) != hipSuccess) return HCF_ERR_HIP;
+  return rc;
+}
+
+int hcf_op_prior_backward(int32_t kind, const float* a, const float* h, float* ga, float* gh, const float* gz_nchw,
+                          int32_t B, int32_t C, int32_t H, int32_t W, int32_t rescale, float gobj, hcf_stream_t stream) {
+  if (!a || !h || !ga || !gh || kind < 0 || kind > 2 || B < 1 || C < 1 || H < 1 || W < 1) return HCF_ERR_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  Tmp t;
+  int rc = HCF_OK;
+  PriorBwdArgs p;
+  memset(&p, 0, sizeof(p));
+  p.B = B; p.H = H; p.W = W; p.C = C;
+  p.a = nhwc_from_nchw(t, a, B, C, H, W, st, rc);
+  p.h = nhwc_from_nchw(t, h, B, 2 * C, H, W, st, rc);
+  p.ga = nhwc_window(t, kind == 1 ? ga : nullptr, B, C, H, W, ru4(C), 0, st, rc);       // sample: ga is the input
+  p.gh = nhwc_window(t, nullptr, B, 2 * C, H, W, ru4(2 * C), 0, st, rc);
+  p.gobj = gobj; p.rescale = rescale; p.gz_nchw = gz_nchw;
+  if (!t.ok) return HCF_ERR_NOMEM;
+  if (rc == HCF_OK) rc = kind == 0 ? launch_gauss_logp_bwd(p, st) : kind == 1 ? launch_gauss_sample_bwd(p, st) : launch_gauss_encode_bwd(p, st);
+  if (rc == HCF_OK && kind != 1) rc = launch_nhwc_to_nchw(p.ga, ga, B, C, H, W, 0, st);
+  if (rc == HCF_OK) rc = launch_nhwc_to_nchw(p.gh, gh, B, 2 * C, H, W, 0, st);
+  if (hipStreamSynchronize(st) != hipSuccess) return HCF_ERR_HIP;
+  return rc;
+}
+
+int hcf_op_quant_logp_backward(const float* z, const float* lr, float* gz, int32_t B, int32_t H, int32_t W, float gobj,
+                               hcf_stream_t stream) {
+  if (!z || !lr || !gz || B < 1 || H < 1 || W < 1) return HCF_ERR_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  Tmp t;
+  int rc = HCF_OK;
+  View zv = nhwc_from_nchw(t, z, B, 3, H, W, st, rc);
+  View gv = nhwc_from_nchw(t, gz, B, 3, H, W, st, rc);
+  if (!t.ok) return HCF_ERR_NOMEM;
+  if (rc == HCF_OK) rc = launch_quant_logp_bwd(zv, lr, gv, B, H, W, gobj, st);
+  if (rc == HCF_OK) rc = launch_nhwc_to_nchw(gv, gz, B, 3, H, W, 0, st);
+  if (hipStreamSynchronize(st) != hipSuccess) return HCF_ERR_HIP;
+  return rc;
+}
+
+int hcf_op_output_grad_backward(int32_t kind, const float* g, const float* z, float* gz, int32_t B, int32_t C, int32_t H,
+                                int32_t W, hcf_stream_t stream) {
+  if (!z || !gz || (!g && kind != 2) || kind < 0 || kind > 3 || B < 1 || C < 1 || H < 1 || W < 1) return HCF_ERR_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  Tmp t;
+  int rc = HCF_OK;
+  if (kind == 3) {
+    rc = launch_mask_flat(g, z, gz, (size_t)B * C * H * W, st);
+  } else {
+    View zv = nhwc_from_nchw(t, z, B, C, H, W, st, rc);
+    View gv = nhwc_from_nchw(t, gz, B, C, H, W, st, rc);
+    if (!t.ok) return HCF_ERR_NOMEM;
+    if (rc == HCF_OK) rc = kind == 2 ? launch_mask_unit_range(zv, gv, B, H, W, st) : launch_add_nchw_grad(g, zv, gv, B, H, W, kind, st);
+    if (rc == HCF_OK) rc = launch_nhwc_to_nchw(gv, gz, B, C, H, W, 0, st);
+  }
+  if (hipStreamSynchronize(st) != hipSuccess) return HCF_ERR_HIP;
+  return rc;
+}
+
+int hcf_op_conv_epilogue_backward(const float* gy, const float* y, const float* scale, int32_t act, int32_t has1, float rs1,
+                                  float* g1, int32_t has2, float rs2, float* g2, float* gpre, float* sum_pre, float* sum_zy,
+                                  float zy_mult, float* absmax, float* absmax2, const float* carry2, int32_t B, int32_t n,
+                                  int32_t H, int32_t W, int32_t cs, int32_t c0, hcf_stream_t stream) {
+  if (!gy || !gpre || B < 1 || n < 1 || n > 256 || H < 1 || W < 1 || c0 < 0 || cs < c0 + n) return HCF_ERR_ARG;
+  if (act < ACT_NONE || act > ACT_LRELU || (!y && (act != ACT_NONE || sum_zy)) || (absmax2 && !absmax)) return HCF_ERR_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  Tmp t;
+  int rc = HCF_OK;
+  EpiBwdArgs e;
+  memset(&e, 0, sizeof(e));
+  e.B = B; e.H = H; e.W = W;
+  e.gy = nhwc_window(t, gy, B, n, H, W, cs, c0, st, rc);
+  e.y = y ? nhwc_window(t, y, B, n, H, W, cs, c0, st, rc) : mkview(nullptr, cs, c0, n);
+  e.gpre = e.gy;                                        // in place, as the engine runs it (bwd_conv)
+  if (scale) {
+    std::vector<float> hs((size_t)((n + 31) / 32) * 32, 1.f);
+    for (int c = 0; c < n; ++c) hs[c] = scale[c];
+    e.scale = t.up(hs);
+  }
+  e.act = act;
+  e.has1 = has1; e.rs1 = rs1; e.has2 = has2; e.rs2 = rs2;
+  e.g1 = (has1 && g1) ? nhwc_window(t, g1, B, n, H, W, cs, c0, st, rc) : mkview(nullptr, cs, c0, n);
+  e.g2 = (has2 && g2) ? nhwc_window(t, g2, B, n, H, W, cs, c0, st, rc) : mkview(nullptr, cs, c0, n);
+  e.sum_pre = sum_pre; e.sum_zy = sum_zy; e.zy_mult = zy_mult;
+  e.absmax = absmax; e.absmax2 = absmax2; e.carry2 = carry2;
+  const int nblk = conv_epilogue_bwd_blocks(B, H, W);
+  if (sum_pre || sum_zy) e.part = part_rows(t, (size_t)nblk * 2 * n, st, rc);
+  if (!t.ok) return HCF_ERR_NOMEM;
+  if (rc == HCF_OK) rc = launch_conv_epilogue_bwd(e, st);
+  if (rc == HCF_OK && e.part) rc = reduce_rows(t, e.part, nblk, n, n, sum_pre, sum_zy, zy_mult, st);
+  if (rc == HCF_OK) rc = launch_nhwc_to_nchw(e.gpre, gpre, B, n, H, W, 0, st);
+  if (rc == HCF_OK && e.g1.p) rc = launch_nhwc_to_nchw(e.g1, g1, B, n, H, W, 0, st);
+  if (rc == HCF_OK && e.g2.p) rc = launch_nhwc_to_nchw(e.g2, g2, B, n, H, W, 0, st);
+  if (hipStreamSynchronize(st) != hipSuccess) return HCF_ERR_HIP;
+  return rc;
+}
+
+int hcf_op_lu_chain(const float* dW, const float* P, const float* L, const float* U, float* dl, float* du, float* dlog_s,
+                    int32_t C, hcf_stream_t stream) {
+  if (!dW || !P || !L || !U || !dl || !du || !dlog_s || C < 1 || C > 48) return HCF_ERR_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  LuChainArgs a;
+  a.dW = dW; a.P = P; a.L = L; a.U = U; a.dl = dl; a.du = du; a.dlog_s = dlog_s; a.C = C;
+  const int rc = launch_lu_chain(a, st);
+  if (hipStreamSynchronize(st) != hipSuccess) return HCF_ERR_HIP;
+  return rc;
+}
+
 }  // extern "C"
 
 // ---- micro-benchmark of the conv kernel (tools/conv_bench.py) ---------------------------------

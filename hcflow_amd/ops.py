@@ -168,3 +168,124 @@ def gauss_sample(h, eps=None, tau: float = 1.0, seed: int = 0, rescale: bool = F
                                        out.data_ptr(), B, C2 // 2, H, W, int(rescale), _stream(h)), None,
                "hcf_op_gauss_sample")
     return out
+
+
+# ---- backward kernels of the training path (hcf_train.hip), one entry per launcher ---------------------------------
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def step_forward_backward(gzout, zout, h, za, mode: int, ns: int, mat, an_logs, gobj: float, g_bias=None, g_logs=None):
+    """Coupling backward, then head backward, of one forward flow step: (gzin, gh, g_bias, g_logs); the two per-channel
+    sums are added to ``g_bias`` / ``g_logs`` when given (zeros otherwise)."""
+    lib = _lib.load()
+    gzout, zout, h, za = _dev(gzout), _dev(zout), _dev(h), _dev(za)
+    B, Cc, H, W = zout.shape
+    gzin, gh = torch.empty_like(zout), torch.empty_like(h)
+    gb = torch.zeros(Cc, device=zout.device) if g_bias is None else _dev(g_bias).flatten().clone()
+    gl = torch.zeros(Cc, device=zout.device) if g_logs is None else _dev(g_logs).flatten().clone()
+    mh, mp = _host(mat)
+    lh, lp = _host(an_logs.flatten())
+    _lib.check(lib.hcf_op_step_forward_backward(gzout.data_ptr(), zout.data_ptr(), h.data_ptr(), za.data_ptr(), gzin.data_ptr(),
+                                                gh.data_ptr(), gb.data_ptr(), gl.data_ptr(), B, Cc, H, W, h.shape[1], mode, ns,
+                                                mp, lp, float(gobj), _stream(zout)), None, "hcf_op_step_forward_backward")
+    return gzin, gh, gb, gl
+
+
+def step_inverse_backward(gx, x, zc, h, mode: int, ns: int, mat, an_bias, an_logs, g_bias=None, g_logs=None):
+    """Backward of one inverse flow step: (gz, gh, gzc, y, g_bias, g_logs)."""
+    lib = _lib.load()
+    gx, x, zc, h = _dev(gx), _dev(x), _dev(zc), _dev(h)
+    B, Cc, H, W = x.shape
+    gz, gh, gzc, y = torch.empty_like(x), torch.empty_like(h), torch.empty_like(x), torch.empty_like(x)
+    gb = torch.zeros(Cc, device=x.device) if g_bias is None else _dev(g_bias).flatten().clone()
+    gl = torch.zeros(Cc, device=x.device) if g_logs is None else _dev(g_logs).flatten().clone()
+    mh, mp = _host(mat)
+    bh, bp = _host(an_bias.flatten())
+    lh, lp = _host(an_logs.flatten())
+    _lib.check(lib.hcf_op_step_inverse_backward(gx.data_ptr(), x.data_ptr(), zc.data_ptr(), h.data_ptr(), gz.data_ptr(),
+                                                gh.data_ptr(), gzc.data_ptr(), y.data_ptr(), gb.data_ptr(), gl.data_ptr(), B, Cc,
+                                                H, W, h.shape[1], mode, ns, mp, bp, lp, _stream(x)), None,
+               "hcf_op_step_inverse_backward")
+    return gz, gh, gzc, y, gb, gl
+
+
+PRIOR_KIND = {"logp": 0, "sample": 1, "encode": 2}
+
+
+def prior_backward(kind: str, a, h, ga=None, gz=None, rescale: bool = False, gobj: float = 1.0):
+    """Gaussian prior backward: (ga, gh). ``ga`` is the input of kind "sample", ``gz`` (or None) that of "encode"."""
+    lib = _lib.load()
+    a, h = _dev(a), _dev(h)
+    B, Cc, H, W = a.shape
+    ga = _dev(ga).clone() if kind == "sample" else torch.empty_like(a)
+    gh = torch.empty_like(h)
+    gzd = _dev(gz) if gz is not None else None
+    _lib.check(lib.hcf_op_prior_backward(PRIOR_KIND[kind], a.data_ptr(), h.data_ptr(), ga.data_ptr(), gh.data_ptr(), _ptr(gzd),
+                                         B, Cc, H, W, int(rescale), float(gobj), _stream(a)), None, "hcf_op_prior_backward")
+    return ga, gh
+
+
+def quant_logp_backward(z, lr, gobj: float, gz=None) -> torch.Tensor:
+    """gz (zeros when None) + gobj * d logp(lr; Quant(z), logs = -6) / dz with the straight-through Quant."""
+    lib = _lib.load()
+    z, lr = _dev(z), _dev(lr)
+    B, _, H, W = z.shape
+    out = torch.zeros_like(z) if gz is None else _dev(gz).clone()
+    _lib.check(lib.hcf_op_quant_logp_backward(z.data_ptr(), lr.data_ptr(), out.data_ptr(), B, H, W, float(gobj), _stream(z)),
+               None, "hcf_op_quant_logp_backward")
+    return out
+
+
+GRAD_KIND = {"add": 0, "add_clamp01": 1, "mask_unit_range": 2, "mask_flat": 3}
+
+
+def output_grad_backward(kind: str, g, z, gz=None) -> torch.Tensor:
+    """The gradient kernels of an NCHW (clamped) output on a copy of ``gz`` (include/hcflow.h: hcf_op_output_grad_backward)."""
+    lib = _lib.load()
+    z = _dev(z)
+    B, Cc, H, W = z.shape
+    gd = _dev(g) if g is not None else None
+    out = torch.zeros_like(z) if gz is None else _dev(gz).clone()
+    _lib.check(lib.hcf_op_output_grad_backward(GRAD_KIND[kind], _ptr(gd), z.data_ptr(), out.data_ptr(), B, Cc, H, W, _stream(z)),
+               None, "hcf_op_output_grad_backward")
+    return out
+
+
+def conv_epilogue_backward(gy, y=None, scale=None, act=None, rs1=None, g1=None, rs2=None, g2=None, want_pre=True, want_zy=False,
+                           zy_mult: float = 1.0, sum_pre=None, sum_zy=None, want_max: int = 0, carry2=None, cs=None, c0: int = 0):
+    """Backward of the fused conv epilogue. rs1 / rs2 not None: the forward conv had that residual (its gradient is added to a copy
+    of g1 / g2 when given). want_max: 1 absmax, 2 absmax and absmax2 (``carry2``: a float folded into absmax2). The tensors sit
+    at channels [c0, c0 + n) of an NHWC buffer of ``cs`` floats per pixel (default: n rounded up to 4).
+    Returns a dict: gpre, g1, g2, sum_pre, sum_zy, absmax, absmax2 (None where not asked for)."""
+    lib = _lib.load()
+    gy = _dev(gy)
+    B, n, H, W = gy.shape
+    dev = gy.device
+    yd = _dev(y) if y is not None else None
+    sh, sp = _host(scale)
+    g1d = _dev(g1).clone() if g1 is not None else None
+    g2d = _dev(g2).clone() if g2 is not None else None
+    gpre = torch.empty_like(gy)
+    sp_ = (torch.zeros(n, device=dev) if sum_pre is None else _dev(sum_pre).clone()) if want_pre else None
+    sz_ = (torch.zeros(n, device=dev) if sum_zy is None else _dev(sum_zy).clone()) if want_zy else None
+    m1 = torch.zeros(1, device=dev) if want_max >= 1 else None
+    m2 = torch.zeros(1, device=dev) if want_max >= 2 else None
+    cr = torch.tensor([float(carry2)], device=dev, dtype=torch.float32) if carry2 is not None else None
+    cs = ((n + 3) // 4) * 4 if cs is None else cs
+    rc = lib.hcf_op_conv_epilogue_backward(gy.data_ptr(), _ptr(yd), sp, ACT[act], int(rs1 is not None), float(rs1 or 0.0), _ptr(g1d),
+                                           int(rs2 is not None), float(rs2 or 0.0), _ptr(g2d), gpre.data_ptr(), _ptr(sp_), _ptr(sz_),
+                                           float(zy_mult), _ptr(m1), _ptr(m2), _ptr(cr), B, n, H, W, int(cs), int(c0), _stream(gy))
+    _lib.check(rc, None, "hcf_op_conv_epilogue_backward")
+    return {"gpre": gpre, "g1": g1d, "g2": g2d, "sum_pre": sp_, "sum_zy": sz_, "absmax": m1, "absmax2": m2}
+
+
+def lu_chain(dW, P, L, U, dl, du, dlog_s):
+    """(dl, du, dlog_s) + the chain rule of dL/dW into the factors of W = P L U' (copies of the given accumulators)."""
+    lib = _lib.load()
+    dW, P, L, U = _dev(dW), _dev(P), _dev(L), _dev(U)
+    Cc = dW.shape[0]
+    dl, du, ds = _dev(dl).clone(), _dev(du).clone(), _dev(dlog_s).clone()
+    _lib.check(lib.hcf_op_lu_chain(dW.data_ptr(), P.data_ptr(), L.data_ptr(), U.data_ptr(), dl.data_ptr(), du.data_ptr(),
+                                   ds.data_ptr(), Cc, _stream(dW)), None, "hcf_op_lu_chain")
+    return dl, du, ds

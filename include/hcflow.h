@@ -332,6 +332,50 @@ int hcf_op_gauss_logp(const float* h, const float* x, float* out_logp, int32_t B
 int hcf_op_gauss_sample(const float* h, const float* eps, float tau, uint64_t seed, float* out, int32_t B, int32_t C,
                         int32_t H, int32_t W, int32_t rescale, hcf_stream_t stream);
 
+/* Backward kernels of the training path (hcf_train.hip), one entry per launcher, on the tensors the engine would have taped.
+ * Tensors are device NCHW fp32 unless noted; per-channel tables are HOST pointers as above. Per-channel sums take the engine's
+ * route: per-block partial rows, then one fixed-order reduction (launch_sum_jobs), ADDED to the caller's device arrays.
+ *
+ * One forward flow step  za = (zin + b) e^s,  zb = W za,  zout = coupling(zb, h):  coupling backward, then head backward.
+ * In: gzout = dL/dzout, zout, h [B,hC,H,W], za; mat = W (HOST [C,C] or NULL), an_logs = s; gobj = dL/d(objective_b) (the
+ * sum of the coupling's log-scales). Out: gzin, gh; g_bias[C] += dL/db, g_logs[C] += dL/ds (device). */
+int hcf_op_step_forward_backward(const float* gzout, const float* zout, const float* h, const float* za, float* gzin,
+                                 float* gh, float* g_bias, float* g_logs, int32_t B, int32_t C, int32_t H, int32_t W,
+                                 int32_t hC, int32_t mode, int32_t ns, const float* mat, const float* an_logs, float gobj,
+                                 hcf_stream_t stream);
+/* One inverse flow step  zc = coupling^-1(z, h),  y = W^-1 zc,  x = y e^-s - b.  In: gx = dL/dx, x, zc, h; mat = W (inverted
+ * in fp64 by the entry, as hcf_op_step_inverse does). Out: gz, gh, gzc = dL/dzc, y; g_bias[C] +=, g_logs[C] += (device). */
+int hcf_op_step_inverse_backward(const float* gx, const float* x, const float* zc, const float* h, float* gz, float* gh,
+                                 float* gzc, float* y, float* g_bias, float* g_logs, int32_t B, int32_t C, int32_t H,
+                                 int32_t W, int32_t hC, int32_t mode, int32_t ns, const float* mat, const float* an_bias,
+                                 const float* an_logs, hcf_stream_t stream);
+/* Gaussian prior backward with (mean, s) = h[:,0::2], h[:,1::2]; rescale: logs = 0.318 atan(2 s), else logs = s.
+ *   kind 0 (logp):   objective += logp(a; mean, s)              -> ga, gh out (scaled by gobj)
+ *   kind 1 (sample): a = mean + e^logs eps, ga = dL/da IN       -> gh out
+ *   kind 2 (encode): z = (a - mean) e^-logs, gz_nchw = dL/dz (NULL: zero) -> ga, gh out */
+int hcf_op_prior_backward(int32_t kind, const float* a, const float* h, float* ga, float* gh, const float* gz_nchw,
+                          int32_t B, int32_t C, int32_t H, int32_t W, int32_t rescale, float gobj, hcf_stream_t stream);
+/* Dirac-LR term with the straight-through Quant: gz [B,3,H,W] += gobj * d logp(lr; mean = Quant(z), logs = -6) / dz */
+int hcf_op_quant_logp_backward(const float* z, const float* lr, float* gz, int32_t B, int32_t H, int32_t W, float gobj,
+                               hcf_stream_t stream);
+/* Gradients of an NCHW (clamped) output: kind 0: gz += g;  1: gz += g where 0 <= z <= 1;  2: gz = 0 where z is outside
+ * [0, 1] (g unused, may be NULL);  3: gz = (0 <= z <= 1) ? g : 0 on the flat tensors. */
+int hcf_op_output_grad_backward(int32_t kind, const float* g, const float* z, float* gz, int32_t B, int32_t C, int32_t H,
+                                int32_t W, hcf_stream_t stream);
+/* Backward of the fused conv epilogue  y = res2 + rs2 * (res1 + rs1 * act((acc + bias) * scale))  given gy = dL/dy:
+ * gpre = dL/dacc out; g1 / g2 (NULL: not wanted) += the residuals' gradients when has1 / has2; sum_pre[n] += sum gpre,
+ * sum_zy[n] += zy_mult * sum dz y (device, NULL: not wanted); absmax / absmax2 (device floats, raised) and carry2 as
+ * hcf_common.h EpiBwdArgs. scale: HOST [n] or NULL; y may be NULL when act is none and sum_zy is NULL. Every tensor is
+ * placed at channels [c0, c0 + n) of an NHWC buffer of cs >= c0 + n floats per pixel, as the engine's windows are. */
+int hcf_op_conv_epilogue_backward(const float* gy, const float* y, const float* scale, int32_t act, int32_t has1, float rs1,
+                                  float* g1, int32_t has2, float rs2, float* g2, float* gpre, float* sum_pre, float* sum_zy,
+                                  float zy_mult, float* absmax, float* absmax2, const float* carry2, int32_t B, int32_t n,
+                                  int32_t H, int32_t W, int32_t cs, int32_t c0, hcf_stream_t stream);
+/* LU-decomposed invertible 1x1 conv, W = P L U': dl, du [C,C] and dlog_s [C] += the chain rule of dW = dL/dW
+ * (hcf_common.h LuChainArgs). All device, row-major, C <= 48. */
+int hcf_op_lu_chain(const float* dW, const float* P, const float* L, const float* U, float* dl, float* du, float* dlog_s,
+                    int32_t C, hcf_stream_t stream);
+
 /* ---- auxiliary nets of the HCFlow+ / ++ recipes (reference: Discriminator_VGG_160 / VGGFeatureExtractor,
  *      codes/models/modules/discriminator_vgg_arch.py:68-157; used by HCFlow_SR_model.py:75-95,219-285) ------------------
  * Stride-1 "same" convolution (k = 3 or 1) and its gradients on DEVICE tensors with the flow's own conv / weight-gradient

@@ -24,6 +24,20 @@ def test_header_symbols_exported():
     assert sorted(_lib.SYMBOLS) == declared
 
 
+def test_backward_op_entries_reject_null_tensors_without_a_device():
+    """The per-op entries of the backward kernels check their arguments before they touch the device."""
+    lib = _lib.load()
+    n = None
+    assert lib.hcf_op_step_forward_backward(n, n, n, n, n, n, n, n, 1, 8, 4, 4, 8, 0, 4, n, n, 1.0, n) == -1
+    assert lib.hcf_op_step_inverse_backward(n, n, n, n, n, n, n, n, n, n, 1, 8, 4, 4, 8, 0, 4, n, n, n, n) == -1
+    assert lib.hcf_op_prior_backward(0, n, n, n, n, n, 1, 4, 4, 4, 0, 1.0, n) == -1
+    assert lib.hcf_op_quant_logp_backward(n, n, n, 1, 4, 4, 1.0, n) == -1
+    for kind in range(4):
+        assert lib.hcf_op_output_grad_backward(kind, n, n, n, 1, 3, 4, 4, n) == -1
+    assert lib.hcf_op_conv_epilogue_backward(n, n, n, 0, 0, 1.0, n, 0, 1.0, n, n, n, n, 1.0, n, n, n, 1, 8, 4, 4, 8, 0, n) == -1
+    assert lib.hcf_op_lu_chain(n, n, n, n, n, n, n, 3, n) == -1
+
+
 @pytest.mark.parametrize("name", PRESETS)
 def test_engine_param_table_matches_python(name):
     cfg = preset(name)
