@@ -152,7 +152,7 @@ struct WgradArgs {
                            // reduction dimension here, so only the walk changes. strip_magic = 2^32 / strip_w + 1 (exact division).
   int dbg;                 // timing ablations (HCF_WG_DBG): 1 no MFMAs, 2 no epilogue, 4 no global loads
 };
-size_t conv_wgrad_scratch_floats(const WgradArgs& a, int* nblk_x = nullptr, int* tpb = nullptr);
+size_t conv_wgrad_scratch_floats(const WgradArgs& a);      // = plan_conv_wgrad(a).scratch_floats
 // The fixed-order reduction of a launch's partial tiles as a JOB: launch_conv_wgrad(a, st, &job) leaves the partial tiles in a.part
 // and returns the reduce step instead of launching it; launch_wgrad_reduce_batch runs any number of them as ONE launch (the training
 // step: ~630 reduce launches of ~7 us become ~40). Same summation order per dW element as the stand-alone reduce.
@@ -355,3 +355,5 @@ int launch_channel_stats(View v, int B, int H, int W, double* out, hipStream_t s
 int launch_sumpool(View in, View out, int B, int Ho, int Wo, int up, int accumulate, hipStream_t st);
 
 }  // namespace hcf
+
+#include "hcf_launch.h"

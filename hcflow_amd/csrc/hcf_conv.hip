@@ -306,12 +306,9 @@ static int launch_t(const ConvArgs& a, hipStream_t st) {
   const long long nblk = (long long)a.B * tiles_x * tiles_y;
   if (nblk <= 0 || nblk > 0x7fffffffLL) return HCF_ERR_ARG;
   bool vec = true;
-  for (int i = 0; i < a.nsrc; ++i) {
-    vec = vec && (((a.src[i].cs | a.src[i].c0) & 3) == 0) && ((reinterpret_cast<uintptr_t>(a.src[i].p) & 15) == 0);
-  }
+  for (int i = 0; i < a.nsrc; ++i) vec = vec && view_vec16(a.src[i]);
   ConvArgs b = a;
-  auto v4 = [](const View& v) { return !v.p || ((((v.cs | v.c0) & 3) == 0) && ((reinterpret_cast<uintptr_t>(v.p) & 15) == 0)); };
-  b.vec_epi = a.out.p && (a.out.n & 3) == 0 && v4(a.out) && v4(a.res1) && v4(a.res2);
+  b.vec_epi = a.out.p && (a.out.n & 3) == 0 && view_vec16_or_null(a.out) && view_vec16_or_null(a.res1) && view_vec16_or_null(a.res2);
   if (vec)
     hipLaunchKernelGGL((conv_mfma_kernel<TAPS, NT, true>), dim3((unsigned)nblk), dim3(256), 0, st, b);
   else
@@ -322,7 +319,7 @@ static int launch_t(const ConvArgs& a, hipStream_t st) {
 int launch_conv(const ConvArgs& a, int taps, hipStream_t st) {
   if (a.nsrc < 1 || a.nsrc > kMaxSrc || a.H >= 32768 || a.W >= 32768 || a.H < 1 || a.W < 1) return HCF_ERR_ARG;
   for (int i = 0; i < a.nsrc; ++i)
-    if ((a.H >> a.src[i].up) << a.src[i].up != a.H || (a.W >> a.src[i].up) << a.src[i].up != a.W) return HCF_ERR_ARG;
+    if (!up_divides(a.H, a.W, a.src[i].up)) return HCF_ERR_ARG;
   const int nt = (a.out.n + 31) / 32;
   if (taps == 9) {
     switch (nt) {

@@ -39,6 +39,7 @@
 //     re-runs the pass on the exact fp32 kernel (hcf_conv.hip).
 #include "hcf_common.h"
 #include <cstdlib>
+#include <cstring>
 #include "hcf_step_math.h"
 
 namespace hcf {
@@ -70,7 +71,7 @@ __device__ __forceinline__ f32x4 split4(const f32x4 v) {
 typedef const float __attribute__((address_space(1)))* gfptr;
 typedef const f32x4 __attribute__((address_space(1)))* gf4ptr;
 
-int g_f16x3_ablation = 0;   // tools/conv_bench.py --ablate N (bit0/bit1 toggle the tall-tile variants, see launch_t)
+int g_f16x3_ablation = 0;   // tools/conv_bench.py --ablate N (bit0/bit1 toggle the tall-tile variants, see plan_conv_f16x3)
 
 // Variants measured and NOT kept (profiles/r01_f16x3_notes.md has the numbers; the code is in the history):
 // a dx-major sliding-window tap loop (fewer LDS reads, same time), a pre-split activation format with register staging,
@@ -97,6 +98,8 @@ int conv_f16x3_scaled_blocks(int B, int H, int W, int* strip_w, int* tile_h) {
   }
   return row_tiles * tiles_y;
 }
+// the bound over both choices above: strips only ever replace MORE per-image tiles, and the 4-row tiles are the shorter ones
+int conv_f16x3_scaled_blocks_max(int B, int H, int W) { return B * ((W + 31) / 32) * ((H + 3) / 4); }
 
 namespace f16x3 {
 
@@ -718,154 +721,112 @@ __global__ __launch_bounds__((TH == 4) ? 256 : 32 * TH, (TH == 16) ? ((NTB == 1)
 
 int g_f16x3_tall = 0;   // 16-row tile variants measured no better than the 8-row tile (profiles/r01_f16x3_notes.md); bit0 NTB=1, bit1 NTB=2
 
-template <int NTB>
-static int launch_t(const ConvArgs& a, hipStream_t st) {
-  const bool plain = !(a.tC > 0) && !a.w2 && !a.in_max;
-  const bool tall = plain && (((g_f16x3_tall ^ g_f16x3_ablation) >> (NTB - 1)) & 1) && a.H >= 16;   // --ablate 1/2/3 turns it off
-  const int THr = tall ? 16 : 8;
-  const int tiles_x = (a.W + TW - 1) / TW, tiles_y = (a.H + THr - 1) / THr;
-  long long nblk = (long long)a.B * tiles_x * tiles_y;
-  if (nblk <= 0 || nblk > 0x7fffffffLL) return HCF_ERR_ARG;
-  bool vec = true;
-  ConvArgs b = a;
-  b.any_up = 0;
-  b.strip_w = 0; b.strip_magic = 0;
-  {
-    auto v4 = [](const View& v) { return !v.p || ((((v.cs | v.c0) & 3) == 0) && ((reinterpret_cast<uintptr_t>(v.p) & 15) == 0)); };
-    b.vec_epi = !tall && !(a.tC > 0) && a.out.p && (a.out.n & 3) == 0 && v4(a.out) && v4(a.res1) && v4(a.res2) &&
-                !(g_f16x3_ablation & 64);                                      // --ablate 64: scalar epilogue
-  }
-  if (a.fb_y.p) {      // fused epilogue backward: the scaled, vector-epilogue variant only, 16-byte addressable y, whole channel quads
-    auto v4b = [](const View& v) { return (((v.cs | v.c0) & 3) == 0) && ((reinterpret_cast<uintptr_t>(v.p) & 15) == 0); };
-    if (!a.in_max || a.fb_max2 == a.in_max || !b.vec_epi || !a.fb_part || !v4b(a.fb_y) || (a.out.n & 3) || a.out.n > 32 * NTB ||
-        (a.fb_scale && (reinterpret_cast<uintptr_t>(a.fb_scale) & 15))) return HCF_ERR_UNSUPPORTED;
-  }
-  for (int i = 0; i < a.nsrc; ++i) {
-    vec = vec && (((a.src[i].cs | a.src[i].c0) & 3) == 0) && ((reinterpret_cast<uintptr_t>(a.src[i].p) & 15) == 0);
-    if (a.src[i].up) b.any_up = 1;
-    // 32-bit element offsets inside the kernel
-    if ((long long)a.B * (a.H >> a.src[i].up) * (a.W >> a.src[i].up) * a.src[i].cs >= 0x7fffffffLL) return HCF_ERR_UNSUPPORTED;
-  }
-  if (a.tC > 0) {  // fused inverse flow-step tail
-    if (!vec || b.any_up || a.w2 || a.res1.p || a.res2.p || a.act != ACT_NONE || a.out.n > ((NTB == 1) ? 32 : 48)) return HCF_ERR_ARG;
-    const int cm = step_cmax(a.tC);
-    if constexpr (NTB == 1) {
-      const long long nblk4 = (long long)a.B * tiles_x * ((a.H + 3) / 4);
-      const bool th4 = nblk4 <= 256 && getenv("HCF_NO_TH4") == nullptr;      // small grids: 4-row tiles (see the plain variant below)
-      static const bool n16_off = getenv("HCF_NO_N16") != nullptr;              // A/B knob: the 16-wide channel tile (<= 16 output channels)
-      const bool n16 = a.out.n <= 16 && !n16_off && !(g_f16x3_ablation & 2048);
-      if (n16 && th4 && cm == 8) hipLaunchKernelGGL((conv_f16x3_kernel<1, true, false, false, 8, 4, false, false, true>), dim3((unsigned)nblk4), dim3(256), 0, st, b);
-      else if (n16 && th4 && cm == 12) hipLaunchKernelGGL((conv_f16x3_kernel<1, true, false, false, 12, 4, false, false, true>), dim3((unsigned)nblk4), dim3(256), 0, st, b);
-      else if (n16 && !th4 && cm == 8) hipLaunchKernelGGL((conv_f16x3_kernel<1, true, false, false, 8, 8, false, false, true>), dim3((unsigned)nblk), dim3(256), 0, st, b);
-      else if (n16 && !th4 && cm == 12) hipLaunchKernelGGL((conv_f16x3_kernel<1, true, false, false, 12, 8, false, false, true>), dim3((unsigned)nblk), dim3(256), 0, st, b);
-      else
-      if (th4 && cm == 8) hipLaunchKernelGGL((conv_f16x3_kernel<1, true, false, false, 8, 4>), dim3((unsigned)nblk4), dim3(256), 0, st, b);
-      else if (th4 && cm == 12) hipLaunchKernelGGL((conv_f16x3_kernel<1, true, false, false, 12, 4>), dim3((unsigned)nblk4), dim3(256), 0, st, b);
-      else if (th4 && cm == 24) hipLaunchKernelGGL((conv_f16x3_kernel<1, true, false, false, 24, 4>), dim3((unsigned)nblk4), dim3(256), 0, st, b);
-      else
-      if (cm == 8) hipLaunchKernelGGL((conv_f16x3_kernel<1, true, false, false, 8>), dim3((unsigned)nblk), dim3(256), 0, st, b);
-      else if (cm == 12) hipLaunchKernelGGL((conv_f16x3_kernel<1, true, false, false, 12>), dim3((unsigned)nblk), dim3(256), 0, st, b);
-      else if (cm == 24) hipLaunchKernelGGL((conv_f16x3_kernel<1, true, false, false, 24>), dim3((unsigned)nblk), dim3(256), 0, st, b);
-      else return HCF_ERR_UNSUPPORTED;
-    } else {
-      return HCF_ERR_UNSUPPORTED;     // 45/48-channel steps (x8 level 2) keep the stand-alone tail kernel
-    }
-  } else if (a.w2) {      // fused FCN conv1 + conv2
-    if constexpr (NTB == 2) {
-      if (!vec || a.out.n != 64 || !a.bias2 || !a.scale2 || a.res1.p || a.res2.p) return HCF_ERR_ARG;
-      const long long nblk4 = (long long)a.B * tiles_x * ((a.H + 3) / 4);
-      if (b.any_up)
-        hipLaunchKernelGGL((conv_f16x3_kernel<2, true, true, true>), dim3((unsigned)nblk), dim3(256), 0, st, b);
-      else if (b.vec_epi && nblk4 <= 256 && getenv("HCF_NO_TH4") == nullptr)      // small grids: 4-row tiles
-        hipLaunchKernelGGL((conv_f16x3_kernel<2, true, false, true, 0, 4>), dim3((unsigned)nblk4), dim3(256), 0, st, b);
-      else
-        hipLaunchKernelGGL((conv_f16x3_kernel<2, true, false, true>), dim3((unsigned)nblk), dim3(256), 0, st, b);
-    } else {
-      return HCF_ERR_ARG;
-    }
-  } else if (tall && vec && !b.any_up)
-    hipLaunchKernelGGL((conv_f16x3_kernel<NTB, true, false, false, 0, 16>), dim3((unsigned)nblk), dim3(512), 0, st, b);
-  else if (tall && vec)
-    hipLaunchKernelGGL((conv_f16x3_kernel<NTB, true, true, false, 0, 16>), dim3((unsigned)nblk), dim3(512), 0, st, b);
-  else if (tall)
-    hipLaunchKernelGGL((conv_f16x3_kernel<NTB, false, true, false, 0, 16>), dim3((unsigned)nblk), dim3(512), 0, st, b);
-  else if (a.in_max && vec && !b.any_up) {
-    int th = 8;
-    if (b.vec_epi) {                               // strips on narrow images (the vector epilogue maps pixels back per image)
-      nblk = conv_f16x3_scaled_blocks(a.B, a.H, a.W, &b.strip_w, &th);
-      b.strip_magic = b.strip_w ? (unsigned)(0x100000000ull / (unsigned)b.strip_w) + 1u : 0u;
-    }
-    if (th == 4) hipLaunchKernelGGL((conv_f16x3_kernel<NTB, true, false, false, 0, 4, true>), dim3((unsigned)nblk), dim3(256), 0, st, b);
-    else
-    hipLaunchKernelGGL((conv_f16x3_kernel<NTB, true, false, false, 0, 8, true>), dim3((unsigned)nblk), dim3(256), 0, st, b);
-  }
-  else if (a.in_max)
-    return HCF_ERR_UNSUPPORTED;
-  else if (vec && !b.any_up) {
-    // small grids: 4-row tiles while even they stay within one block per CU (bit-identical to the 8-row form; HCF_NO_TH4: A/B knob)
-    const long long nblk4 = (long long)a.B * tiles_x * ((a.H + 3) / 4);
-    if (b.vec_epi && nblk4 <= 256 && getenv("HCF_NO_TH4") == nullptr)
-      hipLaunchKernelGGL((conv_f16x3_kernel<NTB, true, false, false, 0, 4>), dim3((unsigned)nblk4), dim3(256), 0, st, b);
-    else
-    hipLaunchKernelGGL((conv_f16x3_kernel<NTB, true, false>), dim3((unsigned)nblk), dim3(256), 0, st, b);
-  }
-  else if (vec)
-    hipLaunchKernelGGL((conv_f16x3_kernel<NTB, true, true>), dim3((unsigned)nblk), dim3(256), 0, st, b);
-  else
-    hipLaunchKernelGGL((conv_f16x3_kernel<NTB, false, true>), dim3((unsigned)nblk), dim3(256), 0, st, b);
-  return hipGetLastError() == hipSuccess ? HCF_OK : HCF_ERR_HIP;
-}
-
-// stand-alone 1x1 conv (training): 16-byte addressable windows, no upsample, vector epilogue; anything else stays on the exact kernel
-template <int NTB>
-static int launch_k1(const ConvArgs& a, hipStream_t st) {
-  if (a.tC > 0 || a.w2 || getenv("HCF_NO_K1") != nullptr) return HCF_ERR_UNSUPPORTED;      // HCF_NO_K1: 1x1 convs on the exact kernel (A/B)
-  ConvArgs b = a;
-  b.any_up = 0; b.strip_w = 0; b.strip_magic = 0;
-  auto v4 = [](const View& v) { return !v.p || ((((v.cs | v.c0) & 3) == 0) && ((reinterpret_cast<uintptr_t>(v.p) & 15) == 0)); };
-  b.vec_epi = a.out.p && (a.out.n & 3) == 0 && v4(a.out) && v4(a.res1) && v4(a.res2);
-  if (!b.vec_epi) return HCF_ERR_UNSUPPORTED;
-  for (int i = 0; i < a.nsrc; ++i) {
-    if (a.src[i].up || ((a.src[i].cs | a.src[i].c0) & 3) || (reinterpret_cast<uintptr_t>(a.src[i].p) & 15)) return HCF_ERR_UNSUPPORTED;
-    if ((long long)a.B * a.H * a.W * a.src[i].cs >= 0x7fffffffLL) return HCF_ERR_UNSUPPORTED;
-  }
-  if (a.fb_y.p) {
-    auto v4b = [](const View& v) { return (((v.cs | v.c0) & 3) == 0) && ((reinterpret_cast<uintptr_t>(v.p) & 15) == 0); };
-    if (!a.in_max || a.fb_max2 == a.in_max || !a.fb_part || !v4b(a.fb_y) || a.out.n > 32 * NTB ||
-        (a.fb_scale && (reinterpret_cast<uintptr_t>(a.fb_scale) & 15))) return HCF_ERR_UNSUPPORTED;
-  }
-  const int tiles_x = (a.W + TW - 1) / TW;
-  long long nblk = (long long)a.B * tiles_x * ((a.H + 7) / 8);
-  if (nblk <= 0 || nblk > 0x7fffffffLL) return HCF_ERR_ARG;
-  if (a.in_max) {
-    int th = 8;
-    nblk = conv_f16x3_scaled_blocks(a.B, a.H, a.W, &b.strip_w, &th);
-    b.strip_magic = b.strip_w ? (unsigned)(0x100000000ull / (unsigned)b.strip_w) + 1u : 0u;
-    if (th == 4) hipLaunchKernelGGL((conv_f16x3_kernel<NTB, true, false, false, 0, 4, true, true>), dim3((unsigned)nblk), dim3(256), 0, st, b);
-    else hipLaunchKernelGGL((conv_f16x3_kernel<NTB, true, false, false, 0, 8, true, true>), dim3((unsigned)nblk), dim3(256), 0, st, b);
-  } else {
-    const long long nblk4 = (long long)a.B * tiles_x * ((a.H + 3) / 4);
-    if (nblk4 <= 256 && getenv("HCF_NO_TH4") == nullptr)
-      hipLaunchKernelGGL((conv_f16x3_kernel<NTB, true, false, false, 0, 4, false, true>), dim3((unsigned)nblk4), dim3(256), 0, st, b);
-    else
-      hipLaunchKernelGGL((conv_f16x3_kernel<NTB, true, false, false, 0, 8, false, true>), dim3((unsigned)nblk), dim3(256), 0, st, b);
-  }
-  return hipGetLastError() == hipSuccess ? HCF_OK : HCF_ERR_HIP;
-}
+// Every instantiation of the kernel there is: a variant the plan asks for and this table lacks is refused, never substituted.
+// (The rows' order is the order of instantiation, i.e. of the kernels in the code object.)
+// Columns of every HCF_ROW, = the template parameters in order: NTB, VEC, UP, FUSE2, TAILC, TH, SCALED, K1, N16.
+#define HCF_ROW(...) {{__VA_ARGS__}, conv_f16x3_kernel<__VA_ARGS__>}
+#define HCF_ROWS_3X3(N) /* NTB = N; VEC, UP, no FUSE2, no TAILC, TH 16 / 4 / 8, SCALED, not K1, not N16 */                  \
+  HCF_ROW(N, true, false, false, 0, 16, false, false, false), HCF_ROW(N, true, true, false, 0, 16, false, false, false),     /* tall */ \
+  HCF_ROW(N, false, true, false, 0, 16, false, false, false),                                                                \
+  HCF_ROW(N, true, false, false, 0, 4, true, false, false), HCF_ROW(N, true, false, false, 0, 8, true, false, false),        /* scaled */ \
+  HCF_ROW(N, true, false, false, 0, 4, false, false, false), HCF_ROW(N, true, false, false, 0, 8, false, false, false),      /* plain */ \
+  HCF_ROW(N, true, true, false, 0, 8, false, false, false), HCF_ROW(N, false, true, false, 0, 8, false, false, false)
+#define HCF_ROWS_1X1(N) /* NTB = N; VEC, no UP, no FUSE2, no TAILC, TH 4 / 8, SCALED or not, K1, not N16 */                  \
+  HCF_ROW(N, true, false, false, 0, 4, true, true, false), HCF_ROW(N, true, false, false, 0, 8, true, true, false),          /* scaled */ \
+  HCF_ROW(N, true, false, false, 0, 4, false, true, false), HCF_ROW(N, true, false, false, 0, 8, false, true, false)
+static const struct { F16x3Variant v; void (*kernel)(const ConvArgs); } kVariants[] = {
+  //      NTB VEC   UP     FUSE2  TAILC TH SCALED K1    N16
+  HCF_ROW(1, true, false, false, 8, 4, false, false, true), HCF_ROW(1, true, false, false, 12, 4, false, false, true),      // fused tail, <= 16 channels
+  HCF_ROW(1, true, false, false, 8, 8, false, false, true), HCF_ROW(1, true, false, false, 12, 8, false, false, true),
+  HCF_ROW(1, true, false, false, 8, 4, false, false, false), HCF_ROW(1, true, false, false, 12, 4, false, false, false),    // fused tail
+  HCF_ROW(1, true, false, false, 24, 4, false, false, false), HCF_ROW(1, true, false, false, 8, 8, false, false, false),
+  HCF_ROW(1, true, false, false, 12, 8, false, false, false), HCF_ROW(1, true, false, false, 24, 8, false, false, false),
+  HCF_ROWS_3X3(1),
+  HCF_ROW(2, true, true, true, 0, 8, false, false, false), HCF_ROW(2, true, false, true, 0, 4, false, false, false),        // fused FCN conv1 + conv2
+  HCF_ROW(2, true, false, true, 0, 8, false, false, false),
+  HCF_ROWS_3X3(2), HCF_ROWS_1X1(1), HCF_ROWS_1X1(2),
+};
+#undef HCF_ROWS_3X3
+#undef HCF_ROWS_1X1
+#undef HCF_ROW
 
 }  // namespace f16x3
 
+F16x3Plan plan_conv_f16x3(const ConvArgs& a, int taps) {
+  F16x3Plan p = {};
+  auto refuse = [](int status) { F16x3Plan r = {}; r.status = status; return r; };
+  if (a.nsrc < 1 || a.nsrc > kMaxSrc || a.H >= 32768 || a.W >= 32768 || a.H < 1 || a.W < 1 || !a.ovf) return refuse(HCF_ERR_ARG);
+  for (int i = 0; i < a.nsrc; ++i)
+    if (!up_divides(a.H, a.W, a.src[i].up)) return refuse(HCF_ERR_ARG);
+  const int ntb = (a.out.n + 31) / 32;
+  const bool k1 = taps == 1;      // stand-alone 1x1 conv (training): 16-byte addressable windows, no upsample, vector epilogue
+  if ((taps != 9 && !k1) || ntb < 1 || ntb > 2) return refuse(HCF_ERR_UNSUPPORTED);      // > 64 output channels stay on the exact kernel
+  if (k1 && (a.tC > 0 || a.w2 || getenv("HCF_NO_K1") != nullptr)) return refuse(HCF_ERR_UNSUPPORTED);      // HCF_NO_K1: 1x1 convs on the exact kernel (A/B)
+  const bool plain = !(a.tC > 0) && !a.w2 && !a.in_max;
+  const bool tall = !k1 && plain && (((f16x3::g_f16x3_tall ^ g_f16x3_ablation) >> (ntb - 1)) & 1) && a.H >= 16;   // --ablate 1/2/3 turns it off
+  const int tiles_x = (a.W + f16x3::TW - 1) / f16x3::TW;
+  long long nblk = (long long)a.B * tiles_x * ((a.H + (tall ? 15 : 7)) / (tall ? 16 : 8));
+  const long long nblk4 = (long long)a.B * tiles_x * ((a.H + 3) / 4);
+  // small grids: 4-row tiles while even they stay within one block per CU (bit-identical to the 8-row form; HCF_NO_TH4: A/B knob)
+  auto th4_small = [&] { return nblk4 <= 256 && getenv("HCF_NO_TH4") == nullptr; };
+  const bool grid_bad = nblk <= 0 || nblk > 0x7fffffffLL;
+  if (!k1 && grid_bad) return refuse(HCF_ERR_ARG);      // (the 3x3 form tests its grid first, the 1x1 form last: their statuses as they always were)
+  p.vec_epi = a.out.p && (a.out.n & 3) == 0 && view_vec16_or_null(a.out) && view_vec16_or_null(a.res1) && view_vec16_or_null(a.res2) &&
+              (k1 || (!tall && !(a.tC > 0) && !(g_f16x3_ablation & 64)));                                   // --ablate 64: scalar epilogue
+  if (k1 && !p.vec_epi) return refuse(HCF_ERR_UNSUPPORTED);
+  // fused epilogue backward: the scaled, vector-epilogue variant only, 16-byte addressable y, whole channel quads
+  if (a.fb_y.p && (!a.in_max || a.fb_max2 == a.in_max || !p.vec_epi || !a.fb_part || !view_vec16(a.fb_y) || (a.out.n & 3) ||
+                   a.out.n > 32 * ntb || (a.fb_scale && !ptr16(a.fb_scale)))) return refuse(HCF_ERR_UNSUPPORTED);
+  bool vec = true;
+  for (int i = 0; i < a.nsrc; ++i) {
+    vec = vec && view_vec16(a.src[i]);
+    if (a.src[i].up) p.any_up = 1;
+    // 32-bit element offsets inside the kernel
+    if ((long long)a.B * (a.H >> a.src[i].up) * (a.W >> a.src[i].up) * a.src[i].cs >= 0x7fffffffLL) return refuse(HCF_ERR_UNSUPPORTED);
+  }
+  if (k1 && (!vec || p.any_up)) return refuse(HCF_ERR_UNSUPPORTED);
+  if (k1 && grid_bad) return refuse(HCF_ERR_ARG);
+  int th = tall ? 16 : 8;
+  p.v = F16x3Variant{ntb, vec, p.any_up || !vec, 0, 0, 8, 0, k1, 0};
+  if (a.tC > 0) {  // fused inverse flow-step tail
+    if (!vec || p.any_up || a.w2 || a.res1.p || a.res2.p || a.act != ACT_NONE || a.out.n > ((ntb == 1) ? 32 : 48)) return refuse(HCF_ERR_ARG);
+    const int cm = step_cmax(a.tC);
+    // 45/48-channel steps (x8 level 2) keep the stand-alone tail kernel
+    if (ntb != 1 || (cm != 8 && cm != 12 && cm != 24)) return refuse(HCF_ERR_UNSUPPORTED);
+    static const bool n16_off = getenv("HCF_NO_N16") != nullptr;              // A/B knob: the 16-wide channel tile (<= 16 output channels)
+    p.v.n16 = a.out.n <= 16 && !n16_off && !(g_f16x3_ablation & 2048) && cm != 24;
+    p.v.tailc = cm;
+    if (th4_small()) th = 4;
+  } else if (a.w2) {      // fused FCN conv1 + conv2
+    if (ntb != 2 || !vec || a.out.n != 64 || !a.bias2 || !a.scale2 || a.res1.p || a.res2.p) return refuse(HCF_ERR_ARG);
+    p.v.fuse2 = 1;
+    if (!p.any_up && p.vec_epi && th4_small()) th = 4;
+  } else if (a.in_max) {      // scaled (training) variant
+    if (!vec || p.any_up) return refuse(HCF_ERR_UNSUPPORTED);
+    p.v.scaled = 1;
+    // strips on narrow images (the vector epilogue maps pixels back per image)
+    if (p.vec_epi) nblk = conv_f16x3_scaled_blocks(a.B, a.H, a.W, &p.strip_w, &th);
+    p.strip_magic = strip_magic(p.strip_w);
+  } else if (!tall && vec && !p.any_up && p.vec_epi && th4_small()) {
+    th = 4;
+  }
+  p.v.th = th;
+  p.grid = (unsigned)((th == 4 && !p.v.scaled) ? nblk4 : nblk);
+  p.block = th == 16 ? 512 : 256;
+  return p;
+}
+
 // a.wpack must point at the f16x3 pack (pack_conv_weights_f16x3), a.ovf at a device int
 int launch_conv_f16x3(const ConvArgs& a, int taps, hipStream_t st) {
-  if (a.nsrc < 1 || a.nsrc > kMaxSrc || a.H >= 32768 || a.W >= 32768 || a.H < 1 || a.W < 1 || !a.ovf) return HCF_ERR_ARG;
-  for (int i = 0; i < a.nsrc; ++i)
-    if ((a.H >> a.src[i].up) << a.src[i].up != a.H || (a.W >> a.src[i].up) << a.src[i].up != a.W) return HCF_ERR_ARG;
-  const int nt = (a.out.n + 31) / 32;
-  if (taps == 9 && nt == 1) return f16x3::launch_t<1>(a, st);
-  if (taps == 9 && nt == 2) return f16x3::launch_t<2>(a, st);
-  if (taps == 1 && nt == 1) return f16x3::launch_k1<1>(a, st);
-  if (taps == 1 && nt == 2) return f16x3::launch_k1<2>(a, st);
-  // > 64 output channels stay on the exact kernel
+  const F16x3Plan p = plan_conv_f16x3(a, taps);
+  if (p.status != HCF_OK) return p.status;
+  ConvArgs b = a;
+  b.any_up = p.any_up; b.vec_epi = p.vec_epi; b.strip_w = p.strip_w; b.strip_magic = p.strip_magic;
+  for (const auto& row : f16x3::kVariants)
+    if (!memcmp(&row.v, &p.v, sizeof(p.v))) {
+      hipLaunchKernelGGL(row.kernel, dim3(p.grid), dim3(p.block), 0, st, b);
+      return hipGetLastError() == hipSuccess ? HCF_OK : HCF_ERR_HIP;
+    }
   return HCF_ERR_UNSUPPORTED;
 }
 

@@ -834,52 +834,83 @@ int launch_absmax(const View& g, int B, int H, int W, float* out, hipStream_t st
   return hipGetLastError() == hipSuccess ? HCF_OK : HCF_ERR_HIP;
 }
 
-// Tiles the kernels walk; *strip_w: WgradArgs::strip_w of the f16x3 kernel (strips when they save >= 10 % of the tiles).
-static int wgrad_tiles(const WgradArgs& a0, int* strip_w) {
-  const int tiles_y = (a0.H + 7) / 8, per_image = a0.B * ((a0.W + 31) / 32) * tiles_y;
-  if (strip_w) *strip_w = 0;
-  const bool off = getenv("HCF_NO_WG_STRIP") != nullptr;             // A/B knob
-  if (!a0.g_max || off || a0.B < 2 || (long long)a0.B * (a0.W + 1) >= 65536) return per_image;
-  const int strips = ((a0.B * (a0.W + 1) + 31) / 32) * tiles_y;
-  if (strips * 10 > per_image * 9) return per_image;
-  if (strip_w) *strip_w = a0.W + 1;
-  return strips;
-}
+// every instantiation of the one-conv kernels (fp32: f16 = false, db unused) and of the batched kernel, in the order of the code object
+namespace wgrad {
+#define HCF_ROW16(TAPS, VEC, DB) {true, TAPS, VEC, DB, conv_wgrad_f16x3_kernel<TAPS, VEC, DB>, {}}
+#define HCF_ROW32(TAPS, VEC) {false, TAPS, VEC, 0, conv_wgrad_kernel<TAPS, VEC>, {}}
+static struct { bool f16; int taps; bool vec; int db; void (*kernel)(const WgradArgs); bool lds_done[64]; } kVariants[] = {
+  HCF_ROW16(9, true, 2), HCF_ROW16(9, false, 2), HCF_ROW16(1, true, 2), HCF_ROW16(1, false, 2),
+  HCF_ROW16(9, true, 1), HCF_ROW16(9, false, 1), HCF_ROW16(1, true, 1), HCF_ROW16(1, false, 1),
+  HCF_ROW16(9, true, 0), HCF_ROW16(9, false, 0), HCF_ROW16(1, true, 0), HCF_ROW16(1, false, 0),
+  HCF_ROW32(9, true), HCF_ROW32(9, false), HCF_ROW32(1, true), HCF_ROW32(1, false),
+};
+static struct { int db; void (*kernel)(const WgradBatchArgs); bool lds_done[64]; } kBatchVariants[] = {
+  {1, conv_wgrad_f16x3_batch_kernel<true, 1>, {}}, {0, conv_wgrad_f16x3_batch_kernel<true, 0>, {}}, {2, conv_wgrad_f16x3_batch_kernel<true, 2>, {}},
+};
+#undef HCF_ROW16
+#undef HCF_ROW32
+}  // namespace wgrad
 
-size_t conv_wgrad_scratch_floats(const WgradArgs& a0, int* out_nblk_x, int* out_tpb) {
-  int nicb = 0;
-  for (int i = 0; i < a0.nsrc; ++i) nicb += (a0.src[i].n + 31) >> 5;
-  const int nocb = (a0.g.n + 31) >> 5;
-  const int tiles = wgrad_tiles(a0, nullptr);
-  const int pairs = nicb * nocb;
+WgradPlan plan_conv_wgrad(const WgradArgs& a) {
+  WgradPlan p = {};
+  p.status = HCF_ERR_ARG;
+  if (a.nsrc < 1 || a.nsrc > kMaxSrc || a.g.n < 1) return p;      // nothing to size
+  if (a.taps == 9 || a.taps == 1) p.status = HCF_OK;
+  p.vec = view_vec16(a.g);
+  for (int i = 0; i < a.nsrc; ++i) {
+    if (!up_divides(a.H, a.W, a.src[i].up)) p.status = HCF_ERR_ARG;
+    p.nicb += (a.src[i].n + 31) >> 5;
+    p.cin_total += a.src[i].n;
+    p.vec = p.vec && view_vec16(a.src[i]);
+  }
+  p.f16 = a.g_max != nullptr;      // f16 matrix cores
+  p.taps = a.taps;
+  p.nocb = (a.g.n + 31) >> 5;
+  // Tiles the kernel walks. f16x3 kernel: STRIPS (WgradArgs::strip_w) when they save >= 10 % of the tiles; HCF_NO_WG_STRIP: A/B knob
+  const int tiles_y = (a.H + 7) / 8;
+  int tiles = a.B * ((a.W + 31) / 32) * tiles_y;
+  if (p.f16 && getenv("HCF_NO_WG_STRIP") == nullptr && a.B >= 2 && (long long)a.B * (a.W + 1) < 65536) {
+    const int strips = ((a.B * (a.W + 1) + 31) / 32) * tiles_y;
+    if (strips * 10 <= tiles * 9) { tiles = strips; p.strip_w = a.W + 1; }
+  }
+  p.strip_magic = strip_magic(p.strip_w);
+  const int pairs = p.nicb * p.nocb;
   // fp32 kernel: one resident round of 256 CUs x 2 blocks (measured best of 512 / 768 / 1024 / 2048; phase-aligned rounds do
   // not overlap). The f16x3 kernel holds one 8-wave block per CU (92 KB of LDS).
   static const int wg_blocks = getenv("HCF_WG_BLOCKS") ? atoi(getenv("HCF_WG_BLOCKS")) : 0;   // experiment knob, read once
-  int nblk_x;
-  if (a0.g_max) {                                   // at most one full round of 256 blocks (264 blocks would cost two)
-    const int target = wg_blocks > 0 ? wg_blocks : (a0.blocks_hint > 0 ? a0.blocks_hint : 256);
-    nblk_x = target / pairs;
-  } else {
-    nblk_x = ((wg_blocks > 0 ? wg_blocks : 512) + pairs - 1) / pairs;
+  if (p.f16)                                        // at most one full round of 256 blocks (264 blocks would cost two)
+    p.nblk_x = (wg_blocks > 0 ? wg_blocks : (a.blocks_hint > 0 ? a.blocks_hint : 256)) / pairs;
+  else
+    p.nblk_x = ((wg_blocks > 0 ? wg_blocks : 512) + pairs - 1) / pairs;
+  p.nblk_x = std::max(1, std::min(p.nblk_x, tiles));
+  p.tpb = (tiles + p.nblk_x - 1) / p.nblk_x;
+  p.nblk_x = (tiles + p.tpb - 1) / p.tpb;
+  p.scratch_floats = (size_t)p.nblk_x * pairs * a.taps * 1024;
+  p.nbx = (a.taps * 1024 + 255) / 256;
+  // LDS form of the f16x3 kernels: 2 = double-buffered, interleaved, four threads per pixel (the default; same box,
+  // profiles/r05_ab_wgrad_lds_forms.txt: batched launch 263.4 -> 229.2 us, one-conv 3x3 launch 56.3 -> 49.1 us, 1x1 launch
+  // 25.3 -> 21.0 us), 1 = double-buffered with one block store per tile (HCF_WG_DB_BLOCK=1), 0 = single buffer (HCF_WG_SINGLE_BUF=1).
+  // Read per launch: the tests compare the forms inside one process. All three are bit-identical.
+  if (p.f16) {
+    const char* const e = getenv("HCF_WG_SINGLE_BUF");
+    const char* const b = getenv("HCF_WG_DB_BLOCK");
+    p.db = (e && atoi(e) != 0) ? 0 : (b && atoi(b) != 0) ? 1 : 2;
   }
-  if (nblk_x > tiles) nblk_x = tiles;
-  if (nblk_x < 1) nblk_x = 1;
-  const int tpb = (tiles + nblk_x - 1) / nblk_x;
-  nblk_x = (tiles + tpb - 1) / tpb;
-  if (out_nblk_x) *out_nblk_x = nblk_x;
-  if (out_tpb) *out_tpb = tpb;
-  return (size_t)nblk_x * pairs * a0.taps * 1024;
+  p.block = p.f16 ? 512 : 256;
+  if (p.f16 && p.status == HCF_OK)      // (> 64 KB: opted in to per kernel, lds_opt_in)
+    p.lds_bytes = p.taps == 9 ? (p.db ? wgrad::Wg16<9>::LDS2_BYTES : wgrad::Wg16<9>::LDS_BYTES) : (p.db ? wgrad::Wg16<1>::LDS2_BYTES : wgrad::Wg16<1>::LDS_BYTES);
+  return p;
 }
 
-// LDS form of the f16x3 weight-gradient kernels: 2 = double-buffered, interleaved, four threads per pixel (the default; same box,
-// profiles/r05_ab_wgrad_lds_forms.txt: batched launch 263.4 -> 229.2 us, one-conv 3x3 launch 56.3 -> 49.1 us, 1x1 launch
-// 25.3 -> 21.0 us), 1 = double-buffered with one block store per tile (HCF_WG_DB_BLOCK=1), 0 = single buffer (HCF_WG_SINGLE_BUF=1).
-// Read per launch: the tests compare the forms inside one process. All three are bit-identical.
-static int wgrad_lds_form() {
-  const char* const e = getenv("HCF_WG_SINGLE_BUF");
-  if (e && atoi(e) != 0) return 0;
-  const char* const b = getenv("HCF_WG_DB_BLOCK");
-  return (b && atoi(b) != 0) ? 1 : 2;
+size_t conv_wgrad_scratch_floats(const WgradArgs& a) { return plan_conv_wgrad(a).scratch_floats; }
+
+// the launcher's part of a job's arguments, and its reduce step
+static WgradReduceJob planned_job(const WgradArgs& a0, const WgradPlan& p, int dbg) {
+  WgradReduceJob j;
+  j.a = a0;
+  j.a.dbg = dbg; j.a.cin_total = p.cin_total; j.a.tpb = p.tpb; j.a.strip_w = p.strip_w; j.a.strip_magic = p.strip_magic;
+  j.nx = p.nblk_x; j.nicb = p.nicb; j.nocb = p.nocb; j.nbx = p.nbx; j.blk0 = 0;
+  return j;
 }
 
 int launch_wgrad_reduce_batch(const WgradReduceJob* jobs_dev, int njobs, long long nblocks, hipStream_t st) {
@@ -889,72 +920,22 @@ int launch_wgrad_reduce_batch(const WgradReduceJob* jobs_dev, int njobs, long lo
 }
 
 int launch_conv_wgrad(const WgradArgs& a0, hipStream_t st, WgradReduceJob* defer) {
-  if (a0.nsrc < 1 || a0.nsrc > kMaxSrc || (a0.taps != 9 && a0.taps != 1) || !a0.dw || !a0.g.p || a0.g.n < 1 || !a0.part)
-    return HCF_ERR_ARG;
-  WgradArgs a = a0;
+  if (!a0.dw || !a0.g.p || !a0.part) return HCF_ERR_ARG;
+  const WgradPlan p = plan_conv_wgrad(a0);
+  if (p.status != HCF_OK) return p.status;
+  if (p.scratch_floats > a0.part_cap) return HCF_ERR_NOMEM;
   static const int wg_dbg = getenv("HCF_WG_DBG") ? atoi(getenv("HCF_WG_DBG")) : 0;   // read once
-  a.dbg = wg_dbg;
-  int nicb = 0, cin = 0;
-  for (int i = 0; i < a.nsrc; ++i) {
-    if ((a.H >> a.src[i].up) << a.src[i].up != a.H || (a.W >> a.src[i].up) << a.src[i].up != a.W) return HCF_ERR_ARG;
-    nicb += (a.src[i].n + 31) >> 5;
-    cin += a.src[i].n;
-  }
-  a.cin_total = cin;
-  int nblk_x = 0;
-  const size_t need = conv_wgrad_scratch_floats(a, &nblk_x, &a.tpb);
-  (void)wgrad_tiles(a, &a.strip_w);
-  a.strip_magic = a.strip_w ? (unsigned)(0x100000000ull / (unsigned)a.strip_w) + 1u : 0u;
-  if (need > a.part_cap) return HCF_ERR_NOMEM;
-  const int nocb = (a.g.n + 31) >> 5;
-  const dim3 grid((unsigned)nblk_x, (unsigned)nicb, (unsigned)nocb);
-  bool vec = (((a.g.cs | a.g.c0) & 3) == 0) && ((reinterpret_cast<uintptr_t>(a.g.p) & 15) == 0);
-  for (int i = 0; i < a.nsrc; ++i)
-    vec = vec && (((a.src[i].cs | a.src[i].c0) & 3) == 0) && ((reinterpret_cast<uintptr_t>(a.src[i].p) & 15) == 0);
-  if (a.g_max) {
-    // f16 matrix cores (one-time opt-in to > 64 KB of dynamic LDS per instantiation)
-    static bool attr_dev[64][12] = {};    // per device: several GPUs in one process (nn.DataParallel replicas)
-    int dev_ = 0;
-    if (hipGetDevice(&dev_) != hipSuccess || dev_ < 0 || dev_ >= 64) return HCF_ERR_HIP;
-    bool (&attr)[12] = attr_dev[dev_];
-    const int db = wgrad_lds_form();
-    auto go = [&](auto fn, int idx, int ldsb) {
-      if (!attr[idx]) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, ldsb) != hipSuccess) return false;
-        attr[idx] = true;
-      }
-      hipLaunchKernelGGL(fn, grid, dim3(512), ldsb, st, a);
-      return true;
-    };
-    bool ok;
-    if (db == 2) {
-      if (a.taps == 9 && vec) ok = go(wgrad::conv_wgrad_f16x3_kernel<9, true, 2>, 8, wgrad::Wg16<9>::LDS2_BYTES);
-      else if (a.taps == 9) ok = go(wgrad::conv_wgrad_f16x3_kernel<9, false, 2>, 9, wgrad::Wg16<9>::LDS2_BYTES);
-      else if (vec) ok = go(wgrad::conv_wgrad_f16x3_kernel<1, true, 2>, 10, wgrad::Wg16<1>::LDS2_BYTES);
-      else ok = go(wgrad::conv_wgrad_f16x3_kernel<1, false, 2>, 11, wgrad::Wg16<1>::LDS2_BYTES);
-    } else if (db == 1) {
-      if (a.taps == 9 && vec) ok = go(wgrad::conv_wgrad_f16x3_kernel<9, true, 1>, 4, wgrad::Wg16<9>::LDS2_BYTES);
-      else if (a.taps == 9) ok = go(wgrad::conv_wgrad_f16x3_kernel<9, false, 1>, 5, wgrad::Wg16<9>::LDS2_BYTES);
-      else if (vec) ok = go(wgrad::conv_wgrad_f16x3_kernel<1, true, 1>, 6, wgrad::Wg16<1>::LDS2_BYTES);
-      else ok = go(wgrad::conv_wgrad_f16x3_kernel<1, false, 1>, 7, wgrad::Wg16<1>::LDS2_BYTES);
-    } else
-    if (a.taps == 9 && vec) ok = go(wgrad::conv_wgrad_f16x3_kernel<9, true, 0>, 0, wgrad::Wg16<9>::LDS_BYTES);
-    else if (a.taps == 9) ok = go(wgrad::conv_wgrad_f16x3_kernel<9, false, 0>, 1, wgrad::Wg16<9>::LDS_BYTES);
-    else if (vec) ok = go(wgrad::conv_wgrad_f16x3_kernel<1, true, 0>, 2, wgrad::Wg16<1>::LDS_BYTES);
-    else ok = go(wgrad::conv_wgrad_f16x3_kernel<1, false, 0>, 3, wgrad::Wg16<1>::LDS_BYTES);
-    if (!ok) return HCF_ERR_HIP;
-  } else
-  if (a.taps == 9 && vec) hipLaunchKernelGGL((wgrad::conv_wgrad_kernel<9, true>), grid, dim3(256), 0, st, a);
-  else if (a.taps == 9) hipLaunchKernelGGL((wgrad::conv_wgrad_kernel<9, false>), grid, dim3(256), 0, st, a);
-  else if (vec) hipLaunchKernelGGL((wgrad::conv_wgrad_kernel<1, true>), grid, dim3(256), 0, st, a);
-  else hipLaunchKernelGGL((wgrad::conv_wgrad_kernel<1, false>), grid, dim3(256), 0, st, a);
-  if (defer) {                                    // the caller batches the reduce steps (launch_wgrad_reduce_batch)
-    defer->a = a; defer->nx = nblk_x; defer->nicb = nicb; defer->nocb = nocb; defer->nbx = (a.taps * 1024 + 255) / 256; defer->blk0 = 0;
+  const WgradReduceJob job = planned_job(a0, p, wg_dbg);
+  const dim3 grid((unsigned)p.nblk_x, (unsigned)p.nicb, (unsigned)p.nocb);
+  for (auto& row : wgrad::kVariants) {
+    if (row.f16 != p.f16 || row.taps != p.taps || row.vec != p.vec || row.db != p.db) continue;
+    if (p.lds_bytes && !lds_opt_in(reinterpret_cast<const void*>(row.kernel), p.lds_bytes, row.lds_done)) return HCF_ERR_HIP;
+    hipLaunchKernelGGL(row.kernel, grid, dim3(p.block), p.lds_bytes, st, job.a);
+    if (defer) *defer = job;                        // the caller batches the reduce steps (launch_wgrad_reduce_batch)
+    else hipLaunchKernelGGL(wgrad::wgrad_reduce_kernel, dim3((unsigned)p.nbx, (unsigned)p.nicb, (unsigned)p.nocb), dim3(256), 0, st, job.a, p.nblk_x, p.taps);
     return hipGetLastError() == hipSuccess ? HCF_OK : HCF_ERR_HIP;
   }
-  const dim3 rgrid((unsigned)((a.taps * 1024 + 255) / 256), (unsigned)nicb, (unsigned)nocb);
-  hipLaunchKernelGGL(wgrad::wgrad_reduce_kernel, rgrid, dim3(256), 0, st, a, nblk_x, a.taps);
-  return hipGetLastError() == hipSuccess ? HCF_OK : HCF_ERR_HIP;
+  return HCF_ERR_UNSUPPORTED;
 }
 
 // f16x3 3x3 weight gradients of n <= kWgBatchMax convs as one launch; jobs[i].part / part_cap / blocks_hint set by the caller
@@ -965,49 +946,30 @@ int launch_conv_wgrad_batch(const WgradArgs* jobs, int n, hipStream_t st, WgradR
   WgradBatchArgs b;
   memset(&b, 0, sizeof(b));
   b.n = n;
-  int total = 0;
+  int total = 0, db = 0, ldsb = 0;
   for (int i = 0; i < n; ++i) {
-    WgradArgs a = jobs[i];
+    const WgradArgs& a = jobs[i];
     if (a.nsrc < 1 || a.nsrc > kMaxSrc || !a.dw || !a.g.p || a.g.n < 1 || !a.part) return HCF_ERR_ARG;
     if (a.taps != 9 || !a.g_max) return HCF_ERR_UNSUPPORTED;
-    int nicb = 0, cin = 0;
-    bool vec = (((a.g.cs | a.g.c0) & 3) == 0) && ((reinterpret_cast<uintptr_t>(a.g.p) & 15) == 0);
-    for (int k = 0; k < a.nsrc; ++k) {
-      if ((a.H >> a.src[k].up) << a.src[k].up != a.H || (a.W >> a.src[k].up) << a.src[k].up != a.W) return HCF_ERR_ARG;
-      nicb += (a.src[k].n + 31) >> 5;
-      cin += a.src[k].n;
-      vec = vec && (((a.src[k].cs | a.src[k].c0) & 3) == 0) && ((reinterpret_cast<uintptr_t>(a.src[k].p) & 15) == 0);
-    }
-    if (!vec) return HCF_ERR_UNSUPPORTED;
-    a.cin_total = cin;
-    a.dbg = 0;
-    int nblk_x = 0;
-    const size_t need = conv_wgrad_scratch_floats(a, &nblk_x, &a.tpb);
-    if (need > a.part_cap) return HCF_ERR_NOMEM;
-    (void)wgrad_tiles(a, &a.strip_w);
-    a.strip_magic = a.strip_w ? (unsigned)(0x100000000ull / (unsigned)a.strip_w) + 1u : 0u;
-    const int nocb = (a.g.n + 31) >> 5;
-    b.a[i] = a;
-    b.nicb[i] = nicb; b.nocb[i] = nocb;
+    const WgradPlan p = plan_conv_wgrad(a);
+    if (p.status != HCF_OK) return p.status;
+    if (!p.vec) return HCF_ERR_UNSUPPORTED;
+    if (p.scratch_floats > a.part_cap) return HCF_ERR_NOMEM;
+    defer[i] = planned_job(a, p, 0);
+    b.a[i] = defer[i].a;
+    b.nicb[i] = p.nicb; b.nocb[i] = p.nocb;
     b.blk0[i] = total;
-    total += nblk_x * nicb * nocb;
-    defer[i].a = a; defer[i].nx = nblk_x; defer[i].nicb = nicb; defer[i].nocb = nocb; defer[i].nbx = (9 * 1024 + 255) / 256; defer[i].blk0 = 0;
+    total += p.nblk_x * p.nicb * p.nocb;
+    db = p.db; ldsb = p.lds_bytes;
   }
   b.blk0[n] = total;
-  static bool attr_dev[64][3] = {};
-  int dev_ = 0;
-  if (hipGetDevice(&dev_) != hipSuccess || dev_ < 0 || dev_ >= 64) return HCF_ERR_HIP;
-  const int db = wgrad_lds_form();
-  auto fn = db == 2 ? wgrad::conv_wgrad_f16x3_batch_kernel<true, 2>
-          : db == 1 ? wgrad::conv_wgrad_f16x3_batch_kernel<true, 1> : wgrad::conv_wgrad_f16x3_batch_kernel<true, 0>;
-  const int ldsb = db ? wgrad::Wg16<9>::LDS2_BYTES : wgrad::Wg16<9>::LDS_BYTES;
-  if (!attr_dev[dev_][db]) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, ldsb) != hipSuccess)
-      return HCF_ERR_HIP;
-    attr_dev[dev_][db] = true;
-  }
-  hipLaunchKernelGGL(fn, dim3((unsigned)total), dim3(512), ldsb, st, b);
-  return hipGetLastError() == hipSuccess ? HCF_OK : HCF_ERR_HIP;
+  for (auto& row : wgrad::kBatchVariants)
+    if (row.db == db) {
+      if (!lds_opt_in(reinterpret_cast<const void*>(row.kernel), ldsb, row.lds_done)) return HCF_ERR_HIP;
+      hipLaunchKernelGGL(row.kernel, dim3((unsigned)total), dim3(512), ldsb, st, b);
+      return hipGetLastError() == hipSuccess ? HCF_OK : HCF_ERR_HIP;
+    }
+  return HCF_ERR_UNSUPPORTED;
 }
 
 }  // namespace hcf

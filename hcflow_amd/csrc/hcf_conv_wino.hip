@@ -155,14 +155,17 @@ static int wino_ncu() {
   return ncu_dev[dev];
 }
 // blocks of a launch of the 32- (ntile_n = 1) / 64-channel (2) kernel = rows of partial sums its fused epilogue backward leaves
+long long wino_units(int B, int H, int W, int ntile_n) {      // 16 x 32 pixels x 32 channels, or 8 x 32 x 64 for 64 output channels
+  return (long long)B * ((W + 31) / 32) * ((ntile_n == 2) ? (H + 7) / 8 : (H + 15) / 16);
+}
 int conv_wino_grid(int B, int H, int W, int ntile_n) {
-  const long long nunits = (ntile_n == 2) ? (long long)B * ((W + 31) / 32) * ((H + 7) / 8) : (long long)B * ((W + 31) / 32) * ((H + 15) / 16);
+  const long long nunits = wino_units(B, H, W, ntile_n);
   const int ncu = wino_ncu();
   return (int)(nunits < ncu ? nunits : ncu);
 }
 bool conv_wino_rounds_ok(int B, int H, int W, int ntile_n) {
   const int ncu = wino_ncu();
-  const long long nunits = (ntile_n == 2) ? (long long)B * ((W + 31) / 32) * ((H + 7) / 8) : (long long)B * ((W + 31) / 32) * ((H + 15) / 16);
+  const long long nunits = wino_units(B, H, W, ntile_n);
   const long long rounds = (nunits + ncu - 1) / ncu;
   return !(rounds >= 2 && nunits * 100 < rounds * ncu * 75) && (long long)B * H * W < (1LL << 24);
 }

@@ -237,13 +237,14 @@
     if (rdb_wg.empty() || rc != HCF_OK) { rdb_wg.clear(); return rc; }
     const int n = (int)rdb_wg.size();
     bool batch = n >= 2 && n <= kWgBatchMax && getenv("HCF_NO_WG_BATCH") == nullptr;
-    for (const WgradArgs& w : rdb_wg) {
+    int pairs[kWgBatchMax], total_pairs = 0;      // (input-channel block, output-channel block) pairs per conv
+    for (int i = 0; i < n && batch; ++i) {
+      const WgradArgs& w = rdb_wg[i];
       // the batched kernel's eligibility (launch_conv_wgrad_batch): 3x3, scaled, every view 16-byte addressable -- e.g. RRDB_gc not a
       // multiple of 4 gives slab windows with an unaligned c0, which the one-conv launches handle on their non-vector path
-      bool vec = (((w.g.cs | w.g.c0) & 3) == 0) && ((reinterpret_cast<uintptr_t>(w.g.p) & 15) == 0);
-      for (int k = 0; k < w.nsrc; ++k)
-        vec = vec && (((w.src[k].cs | w.src[k].c0) & 3) == 0) && ((reinterpret_cast<uintptr_t>(w.src[k].p) & 15) == 0);
-      batch = batch && vec && w.g_max != nullptr && w.taps == 9;
+      const WgradPlan p = plan_conv_wgrad(w);
+      batch = p.vec && p.f16 && w.taps == 9;
+      total_pairs += pairs[i] = p.nicb * p.nocb;
     }
     if (!batch) {
       for (WgradArgs& w : rdb_wg) {
@@ -254,13 +255,6 @@
       return rc;
     }
     static const int budget = getenv("HCF_WG_BATCH_BLOCKS") ? atoi(getenv("HCF_WG_BATCH_BLOCKS")) : 160;
-    int pairs[kWgBatchMax], total_pairs = 0;
-    for (int i = 0; i < n; ++i) {
-      int nicb = 0;
-      for (int k = 0; k < rdb_wg[i].nsrc; ++k) nicb += (rdb_wg[i].src[k].n + 31) >> 5;
-      pairs[i] = nicb * ((rdb_wg[i].g.n + 31) >> 5);
-      total_pairs += pairs[i];
-    }
     size_t need[kWgBatchMax], sum = 0;
     for (int i = 0; i < n; ++i) {
       rdb_wg[i].blocks_hint = std::max(pairs[i], (int)((long long)budget * pairs[i] / total_pairs));
@@ -882,7 +876,6 @@
   // rows of partial sums a fused epilogue backward leaves (= the scaled f16x3 conv's grid, its strip walk included); the
   // buffers are sized for the larger per-image grid
   static int conv_tile_blocks(int B, int H, int W) { int sw = 0, th = 8; return conv_f16x3_scaled_blocks(B, H, W, &sw, &th); }
-  static int conv_tile_blocks_max(int B, int H, int W) { return B * ((W + 31) / 32) * ((H + 3) / 4); }
   bool gen_fuse_ok(const Conv& consumer) const {
     return !tape->bwd.epi_fuse_off && !tape->bwd.fcn_fuse_off && tape->bwd.f16 && consumer.nsrc == 1 && consumer.tpacks.size() == 1 && consumer.tpacks[0].wpack16 &&
            (consumer.taps == 9 || consumer.taps == 1) && (consumer.src_n[0] & 3) == 0 && consumer.src_n[0] <= 64;
@@ -1100,7 +1093,7 @@
       TB h1 = talloc(B_, H, W, s.hid), h2 = talloc(B_, H, W, s.hid);
       // conv2's data gradient applies conv1's epilogue backward, conv3's applies conv2's (bwd_conv, gen_fuse_ok): conv1's and conv2's
       // partial rows and max slots up front, sized for either form's grid
-      const size_t rows = (size_t)std::max(conv_epilogue_bwd_blocks(B_, H, W), conv_tile_blocks_max(B_, H, W)) * 2;
+      const size_t rows = (size_t)std::max(conv_epilogue_bwd_blocks(B_, H, W), conv_f16x3_scaled_blocks_max(B_, H, W)) * 2;
       EpiLink l0, l1, l2;
       memset(&l0, 0, sizeof(l0)); memset(&l1, 0, sizeof(l1)); memset(&l2, 0, sizeof(l2));
       l0.own_part = tape->g.alloc(rows * s.c[0].cout); l0.own_gmax = tape->g.alloc(1); l0.next = &s.c[1];
@@ -1181,7 +1174,7 @@
     if (r.gather) {
       float* const gmax2 = tape->g.alloc(5);
       // every conv's max slot and partial-sum rows up front: the gather conv of x_m writes conv m's (fused epilogue backward)
-      const size_t rows = (size_t)std::max(conv_epilogue_bwd_blocks(B_, H, W), conv_tile_blocks_max(B_, H, W)) * 2;
+      const size_t rows = (size_t)std::max(conv_epilogue_bwd_blocks(B_, H, W), conv_f16x3_scaled_blocks_max(B_, H, W)) * 2;
       float *gm[5], *pt[5];
       for (int i = 0; i < 5; ++i) { gm[i] = tape->g.alloc(1); pt[i] = tape->g.alloc(rows * (i < 4 ? gc : nf)); }
       for (int m = 0; m < 5; ++m) {                    // ctx[m]: the record of conv index m (its output: x_{m+1}), which gathers dL/dx_m

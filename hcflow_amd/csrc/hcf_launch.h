@@ -1,0 +1,53 @@
+// Host-side predicates and launch plans shared by the conv launchers (included by hcf_common.h).
+//
+// A plan_* function is PURE (arguments, process-wide switches and environment in; no HIP call, no launch) and decides all a launcher
+// decides: the launcher is "plan, look the variant up in its table, launch", and hcf_debug_conv_plan pins the selection without a GPU.
+#pragma once
+
+namespace hcf {
+
+static inline bool ptr16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+// a channel window every pixel of which can be read / written as 16-byte quads
+static inline bool view_vec16(const View& v) { return ((v.cs | v.c0) & 3) == 0 && ptr16(v.p); }
+static inline bool view_vec16_or_null(const View& v) { return !v.p || view_vec16(v); }      // optional views (residuals)
+// ConvArgs / WgradArgs::strip_magic: 2^32 / strip_w + 1 (exact division of values < 2^16 by a multiply-high), 0 without strips
+static inline unsigned strip_magic(int strip_w) { return strip_w ? (unsigned)(0x100000000ull / (unsigned)strip_w) + 1u : 0u; }
+// an output of H x W can be read through a nearest upsample by 2^up
+static inline bool up_divides(int H, int W, int up) { return (H >> up) << up == H && (W >> up) << up == W; }
+
+// One-time opt-in of `kernel` to `bytes` (> 64 KB) of dynamic LDS on the current device; `done` = the kernel's per-device flags, kept
+// beside it in its launcher's table (several GPUs in one process: nn.DataParallel replicas). false: a HIP call failed.
+static inline bool lds_opt_in(const void* kernel, int bytes, bool (&done)[64]) {
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return false;
+  if (!done[dev] && hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess) return false;
+  return done[dev] = true;
+}
+
+// ---- f16x3 conv (hcf_conv_f16x3.hip) ----
+struct F16x3Variant { int ntb, vec, up, fuse2, tailc, th, scaled, k1, n16; };      // conv_f16x3_kernel's template arguments (no padding: rows compare bytewise)
+struct F16x3Plan {
+  int status;              // HCF_OK, or why launch_conv_f16x3 refuses the call (HCF_ERR_ARG / HCF_ERR_UNSUPPORTED); the rest is then zero
+  F16x3Variant v;
+  unsigned grid, block;
+  int any_up, vec_epi, strip_w; unsigned strip_magic;      // the ConvArgs fields "set by the launcher"
+};
+F16x3Plan plan_conv_f16x3(const ConvArgs& a, int taps);
+// rows of ConvArgs::fb_part no scaled launch on [B, H, W] exceeds, whatever tile height and walk conv_f16x3_scaled_blocks picks
+int conv_f16x3_scaled_blocks_max(int B, int H, int W);
+
+// ---- conv weight gradient (hcf_conv_wgrad.hip) ----
+struct WgradPlan {
+  int status;              // HCF_OK or HCF_ERR_ARG (the geometry is filled in all the same: workspaces are sized from half-filled arguments)
+  bool f16; int taps; bool vec; int db;      // kernel: f16x3 (a.g_max) or fp32; conv_wgrad_f16x3_kernel<taps, vec, db> / conv_wgrad_kernel<taps, vec>
+  int nblk_x, nicb, nocb;  // grid of the one-conv launch; the batched launch gives the job nblk_x * nicb * nocb blocks
+  int block, lds_bytes;
+  int tpb, cin_total, strip_w; unsigned strip_magic;      // the WgradArgs fields "set by the launcher"
+  size_t scratch_floats;   // partial tiles the launch leaves in WgradArgs::part
+  int nbx;                 // the reduce step runs on a grid of (nbx, nicb, nocb) over nblk_x partial tiles per element
+};
+WgradPlan plan_conv_wgrad(const WgradArgs& a);
+
+long long wino_units(int B, int H, int W, int ntile_n);      // units a Winograd launch walks (hcf_conv_wino.hip)
+
+}  // namespace hcf

@@ -300,6 +300,52 @@ int hcf_debug_clock_probe(int32_t enable) { return hcf::wino_clock_probe(enable)
 // timing ablations of the f16x3 kernel (tools/conv_bench.py --ablate); 0 = off
 int hcf_debug_set_ablation(int32_t bits) { hcf::g_f16x3_ablation = bits; return HCF_OK; }
 
+// launch selection without a GPU (layouts: include/hcflow.h). The views get made-up addresses: the plans test them, nothing reads them
+static float* plan_case_ptr(int base, int aligned) { return reinterpret_cast<float*>((uintptr_t)(base * 0x1000 + (aligned ? 0 : 4))); }
+static void plan_case_args(const int32_t* in, ConvArgs& c, WgradArgs& w) {
+  memset(&c, 0, sizeof(c));
+  memset(&w, 0, sizeof(w));
+  c.B = w.B = in[2]; c.H = w.H = in[3]; c.W = w.W = in[4];
+  c.nsrc = w.nsrc = in[5];
+  for (int i = 0; i < kMaxSrc; ++i) {
+    const int32_t* s = in + 6 + 5 * i;
+    if (s[1]) c.src[i] = w.src[i] = mkview(plan_case_ptr(1 + i, s[4]), s[1], s[2], s[0], s[3]);
+  }
+  c.out = w.g = mkview(plan_case_ptr(4, in[24]), in[22], in[23], in[21]);
+  if (in[39] & 1) c.out.p = nullptr;
+  if (in[25]) c.res1 = mkview(plan_case_ptr(5, in[25] == 1), in[26], in[27], in[21]);
+  if (in[28]) c.res2 = mkview(plan_case_ptr(6, in[28] == 1), in[29], in[30], in[21]);
+  c.tC = in[31]; w.blocks_hint = in[31];
+  if (in[32] & 1) c.w2 = plan_case_ptr(7, 1);
+  if (in[32] & 2) c.bias2 = plan_case_ptr(8, 1);
+  if (in[32] & 4) c.scale2 = plan_case_ptr(9, 1);
+  if (in[33]) c.in_max = w.g_max = plan_case_ptr(10, 1);
+  c.act = in[34];
+  if (in[35]) c.fb_y = mkview(plan_case_ptr(11, in[35] == 1), in[36], in[37], in[21]);
+  if (in[38] & 1) c.fb_part = plan_case_ptr(12, 1);
+  if (in[38] & 2) c.fb_scale = plan_case_ptr(13, !(in[38] & 4));
+  c.fb_max2 = (in[38] & 8) ? const_cast<float*>(c.in_max) : plan_case_ptr(14, 1);
+  if (!(in[39] & 2)) c.ovf = reinterpret_cast<int*>(plan_case_ptr(15, 1));
+  w.taps = in[1];
+  w.dw = plan_case_ptr(16, 1); w.part = plan_case_ptr(17, 1); w.part_cap = (size_t)1 << 40;
+}
+int hcf_debug_conv_plan(const int32_t* in, int32_t n_in, int64_t* out, int32_t n_out) {
+  if (!in || !out || n_in != HCF_PLAN_N_IN || n_out != HCF_PLAN_N_OUT || (in[0] != 0 && in[0] != 1)) return HCF_ERR_ARG;
+  ConvArgs c;
+  WgradArgs w;
+  plan_case_args(in, c, w);
+  int th = 8;
+  const F16x3Plan p = in[0] == 0 ? plan_conv_f16x3(c, in[1]) : F16x3Plan{};
+  const WgradPlan q = in[0] == 1 ? plan_conv_wgrad(w) : WgradPlan{};
+  const int64_t conv[HCF_PLAN_N_OUT] = {p.status, p.v.ntb, p.v.vec, p.v.up, p.v.fuse2, p.v.tailc, p.v.th, p.v.scaled, p.v.k1, p.v.n16, p.grid, p.block, p.any_up,
+                                        p.vec_epi, p.strip_w, p.strip_magic,      // then the partial-sum rows the engine plans for (conv_tile_blocks)
+                                        conv_f16x3_scaled_blocks(c.B, c.H, c.W, nullptr, &th), conv_f16x3_scaled_blocks_max(c.B, c.H, c.W)};
+  const int64_t wgrad[HCF_PLAN_N_OUT] = {q.status, q.f16, q.taps, q.vec, q.db, q.nblk_x, q.nicb, q.nocb, q.block, q.lds_bytes, q.tpb, q.cin_total, q.strip_w,
+                                         q.strip_magic, (int64_t)q.scratch_floats, q.nbx};
+  for (int i = 0; i < n_out; ++i) out[i] = in[0] == 0 ? conv[i] : wgrad[i];
+  return HCF_OK;
+}
+
 int hcf_op_set_precision(int32_t mode) {
   if (mode != PREC_EXACT && mode != PREC_F16X3) return HCF_ERR_ARG;
   g_op_precision = mode;

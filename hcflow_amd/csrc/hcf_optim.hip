@@ -68,8 +68,7 @@ extern "C" int hcf_adam_step(float* param, float* exp_avg, float* exp_avg_sq, co
   if (n_chunks == 0) return HCF_OK;
   if (!param || !exp_avg || !exp_avg_sq || !chunks_dev || n_chunks < 0 || step < 1) return HCF_ERR_ARG;
   if (!(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && eps >= 0.0 && lr >= 0.0 && weight_decay >= 0.0)) return HCF_ERR_ARG;
-  if (((reinterpret_cast<uintptr_t>(param) | reinterpret_cast<uintptr_t>(exp_avg) | reinterpret_cast<uintptr_t>(exp_avg_sq)) & 15) != 0)
-    return HCF_ERR_ARG;
+  if (!hcf::ptr16(param) || !hcf::ptr16(exp_avg) || !hcf::ptr16(exp_avg_sq)) return HCF_ERR_ARG;
   const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
   AdamK k;
   k.step_size = (float)(lr / bc1);

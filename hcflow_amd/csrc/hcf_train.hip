@@ -200,9 +200,8 @@ int launch_conv_epilogue_bwd(const EpiBwdArgs& a, hipStream_t st) {
   if (a.gy.n < 1 || a.gy.n > 256 || a.gpre.n != a.gy.n) return HCF_ERR_ARG;
   const long long npix = (long long)a.B * a.H * a.W;
   const int ppb = epi_bwd_ppb();
-  auto v4 = [](const View& v) { return !v.p || ((((v.cs | v.c0) & 3) == 0) && ((reinterpret_cast<uintptr_t>(v.p) & 15) == 0)); };
-  const bool vec = (a.gy.n & 3) == 0 && a.gy.n >= 4 && v4(a.gy) && v4(a.gpre) && v4(a.y) && v4(a.g1) && v4(a.g2) &&
-                   (!a.scale || (reinterpret_cast<uintptr_t>(a.scale) & 15) == 0);
+  const bool vec = (a.gy.n & 3) == 0 && a.gy.n >= 4 && view_vec16_or_null(a.gy) && view_vec16_or_null(a.gpre) && view_vec16_or_null(a.y) &&
+                   view_vec16_or_null(a.g1) && view_vec16_or_null(a.g2) && ptr16(a.scale);
   if (vec) hipLaunchKernelGGL(conv_epilogue_bwd_vec_kernel, dim3((unsigned)((npix + ppb - 1) / ppb)), dim3(256), 0, st, a, npix, ppb);
   else hipLaunchKernelGGL(conv_epilogue_bwd_kernel, dim3((unsigned)((npix + ppb - 1) / ppb)), dim3(256), 0, st, a, npix, ppb);
   HCF_RET_T();

@@ -452,6 +452,22 @@ int hcf_debug_clock_probe(int32_t enable);
 double hcf_debug_last_clock_mhz(void);
 /* tools/conv_bench.py --ablate: timing-only ablations of the f16x3 kernel (results invalid); 0 = off */
 int hcf_debug_set_ablation(int32_t bits);
+/* What the conv launchers would select for a call, WITHOUT a GPU (tests/test_conv_plan_cpu.py): plan_conv_f16x3 / plan_conv_wgrad on
+ * shapes and window strides given as integers; an "aligned" flag stands for a view's 16-byte addressability.
+ *   in[HCF_PLAN_N_IN]:  0 kind (0 f16x3 conv, 1 weight gradient), 1 taps, 2 B, 3 H, 4 W, 5 nsrc, 6 + 5 i .. : source i = {n, cs, c0, up,
+ *     aligned}, 21 .. 24 out (kind 1: g) = {n, cs, c0, aligned}, 25 .. 27 res1 = {0 none / 1 aligned / 2 unaligned, cs, c0}, 28 .. 30 res2
+ *     likewise, 31 tC (kind 1: blocks_hint), 32 bit0 w2, bit1 bias2, bit2 scale2, 33 in_max (kind 1: g_max) given, 34 act,
+ *     35 .. 37 fb_y = {0 none / 1 aligned / 2 unaligned, cs, c0}, 38 bit0 fb_part, bit1 fb_scale, bit2 fb_scale unaligned, bit3 fb_max2 is
+ *     in_max, 39 bit0 out.p null, bit1 ovf null
+ *   out[HCF_PLAN_N_OUT], kind 0: 0 status, 1 .. 9 the kernel's template arguments NTB, VEC, UP, FUSE2, TAILC, TH, SCALED, K1, N16,
+ *     10 grid, 11 block, 12 any_up, 13 vec_epi, 14 strip_w, 15 strip_magic (zeros when refused), 16 rows of per-block partial sums
+ *     the engine plans for a scaled launch on [B, H, W], 17 their bound over tile heights
+ *   kind 1: 0 status, 1 f16x3 kernel, 2 TAPS, 3 VEC, 4 DB (LDS form), 5 nblk_x, 6 nicb, 7 nocb, 8 block, 9 dynamic LDS bytes, 10 tpb,
+ *     11 cin_total, 12 strip_w, 13 strip_magic, 14 scratch floats, 15 blocks per channel-block pair of the reduce (the plan as it
+ *     is, also when refused: workspaces are sized from it before the arguments are complete) */
+#define HCF_PLAN_N_IN 40
+#define HCF_PLAN_N_OUT 18
+int hcf_debug_conv_plan(const int32_t* in, int32_t n_in, int64_t* out, int32_t n_out);
 /* precision used by the per-op entry points hcf_op_conv2d / hcf_bench_conv (process-wide test knob) */
 int hcf_op_set_precision(int32_t mode);
 /* tools/conv_bench.py: times `iters` back-to-back launches of the conv kernel on random NHWC slabs */
