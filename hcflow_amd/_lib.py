@@ -39,6 +39,7 @@ SYMBOLS = [
     "hcf_aux_bn_act_workspace", "hcf_aux_bn_act", "hcf_aux_bn_act_backward",
     "hcf_op_step_forward_backward", "hcf_op_step_inverse_backward", "hcf_op_prior_backward", "hcf_op_quant_logp_backward",
     "hcf_op_output_grad_backward", "hcf_op_conv_epilogue_backward", "hcf_op_lu_chain",
+    "hcf_train_backward_inverse_ex", "hcf_train_backward_counts", "hcf_op_prior_sample_backward",
 ]
 
 
@@ -111,6 +112,8 @@ def load() -> C.CDLL:
     lib.hcf_metric_imresize_down.argtypes = [fp, i32, i32, i32, i32, fp, vp]
     lib.hcf_train_inverse.argtypes = [vp, fp, C.POINTER(fp), i32, f32, u64, fp, i32, i32, i32, C.c_uint32, vp]
     lib.hcf_train_backward_inverse.argtypes = [vp, fp, fp, i64, fp, vp]
+    lib.hcf_train_backward_inverse_ex.argtypes = [vp, fp, fp, i64, fp, C.POINTER(fp), i32, vp]
+    lib.hcf_train_backward_counts.argtypes = [vp, C.POINTER(i64)]
     lib.hcf_train_select_tape.argtypes = [vp, i32]
     lib.hcf_train_forward_rescale.argtypes = [vp, fp, fp, fp, fp, i32, i32, i32, C.c_uint32, vp]
     lib.hcf_train_backward_rescale.argtypes = [vp, fp, fp, fp, fp, i64, vp]
@@ -152,6 +155,7 @@ def load() -> C.CDLL:
     lib.hcf_op_step_forward_backward.argtypes = [fp] * 8 + [i32] * 7 + [fp, fp, f32, vp]
     lib.hcf_op_step_inverse_backward.argtypes = [fp] * 10 + [i32] * 7 + [fp, fp, fp, vp]
     lib.hcf_op_prior_backward.argtypes = [i32, fp, fp, fp, fp, fp, i32, i32, i32, i32, i32, f32, vp]
+    lib.hcf_op_prior_sample_backward.argtypes = [fp, fp, fp, fp, fp, i32, i32, i32, i32, i32, vp]
     lib.hcf_op_quant_logp_backward.argtypes = [fp, fp, fp, i32, i32, i32, f32, vp]
     lib.hcf_op_output_grad_backward.argtypes = [i32, fp, fp, fp, i32, i32, i32, i32, vp]
     lib.hcf_op_conv_epilogue_backward.argtypes = [fp, fp, fp, i32, i32, f32, fp, i32, f32, fp, fp, fp, fp, f32, fp, fp, fp,

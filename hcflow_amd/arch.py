@@ -389,11 +389,14 @@ def _grad_nodes() -> int:
 
 class _SRReverseStep(torch.autograd.Function):
     """``fake_H = netG(lr=, eps_std=, reverse=True)`` with gradients w.r.t. the parameters (the HR pixel / feature /
-    GAN losses of the HCFlow+ / ++ recipes, HCFlow_SR_model.py:207-255): hcf_train_inverse keeps the tape,
-    hcf_train_backward_inverse turns dL/d fake_H into the flat parameter gradient."""
+    GAN losses of the HCFlow+ / ++ recipes, HCFlow_SR_model.py:207-255), ``lr`` and the injected ``eps`` tensors (optimising
+    in the latent space with the weights frozen): hcf_train_inverse keeps the tape, hcf_train_backward_inverse_ex turns
+    dL/d fake_H into the flat parameter gradient, dL/d lr and dL/d eps_l. ``mask``: which levels of ``eps`` were given (None:
+    no eps at all); the given tensors lead ``tensors``, the parameters follow. With no parameter requiring grad the backward
+    pass is the input-gradient-only one (no gradient buffer, no parameter-gradient work)."""
 
     @staticmethod
-    def forward(ctx, module, lr, tau, seed, clamp, eps, *params):
+    def forward(ctx, module, lr, tau, seed, clamp, mask, *tensors):
         dev = lr.device
         eng, idx = module._engine_for(dev)
         cfg = module.cfg
@@ -401,16 +404,20 @@ class _SRReverseStep(torch.autograd.Function):
         out = torch.empty(B, 3, h * cfg.scale, w * cfg.scale, device=dev, dtype=torch.float32)
         shapes = eps_shapes(cfg, B, h, w)
         arr = (C.c_void_p * len(shapes))()
-        keep = []
-        if eps is not None:
-            assert len(eps) == len(shapes)
-            for i, (e, s) in enumerate(zip(eps, shapes)):
-                if e is None:
+        n_given = sum(mask) if mask is not None else 0
+        given, params = tensors[:n_given], tensors[n_given:]
+        keep, slots = [], []
+        if mask is not None:
+            assert len(mask) == len(shapes)
+            it = iter(given)
+            for i, (m, s) in enumerate(zip(mask, shapes)):
+                if not m:
                     arr[i] = None
                     continue
-                e = module._prep(e, dev)
+                e = module._prep(next(it), dev)
                 assert tuple(e.shape) == tuple(s), (tuple(e.shape), s)
                 keep.append(e)
+                slots.append(i)
                 arr[i] = e.data_ptr()
         with torch.cuda.device(idx):
             _lib.check(eng.lib.hcf_train_select_tape(eng.handle, 1), eng.handle, "hcf_train_select_tape")
@@ -421,27 +428,35 @@ class _SRReverseStep(torch.autograd.Function):
         ctx.eng, ctx.idx = eng, idx
         ctx.keep = (lr, keep)
         ctx.lr_needs_grad = bool(lr.requires_grad)
+        ctx.eps_slots, ctx.n_levels = slots, len(shapes)
+        ctx.eps_needs_grad = [bool(e.requires_grad) for e in given]
         ctx.meta = [(tuple(p.shape), p.numel(), bool(p.requires_grad)) for p in params]
         return out
 
     @staticmethod
     def backward(ctx, g_out):
         eng, idx = ctx.eng, ctx.idx
-        total = sum(n for _, n, _ in ctx.meta)
         g_out = g_out.to(torch.float32).contiguous()
-        flat = torch.empty(total, device=g_out.device, dtype=torch.float32)
+        flat, total = None, 0
+        if any(need for _, _, need in ctx.meta):
+            total = sum(n for _, n, _ in ctx.meta)
+            flat = torch.empty(total, device=g_out.device, dtype=torch.float32)
         g_lr = torch.empty_like(ctx.keep[0]) if ctx.lr_needs_grad else None
+        g_eps = [torch.empty_like(e) if need else None for e, need in zip(ctx.keep[1], ctx.eps_needs_grad)]
+        arr = (C.c_void_p * ctx.n_levels)()
+        for slot, g in zip(ctx.eps_slots, g_eps):
+            arr[slot] = None if g is None else g.data_ptr()
         with torch.cuda.device(idx):
             _lib.check(eng.lib.hcf_train_select_tape(eng.handle, 1), eng.handle, "hcf_train_select_tape")
-            rc = eng.lib.hcf_train_backward_inverse(eng.handle, g_out.data_ptr(), flat.data_ptr(), total,
-                                                    None if g_lr is None else g_lr.data_ptr(),
-                                                    C.c_void_p(torch.cuda.current_stream(idx).cuda_stream))
-        _lib.check(rc, eng.handle, "hcf_train_backward_inverse")
+            rc = eng.lib.hcf_train_backward_inverse_ex(eng.handle, g_out.data_ptr(), None if flat is None else flat.data_ptr(),
+                                                       total, None if g_lr is None else g_lr.data_ptr(), arr, ctx.n_levels,
+                                                       C.c_void_p(torch.cuda.current_stream(idx).cuda_stream))
+        _lib.check(rc, eng.handle, "hcf_train_backward_inverse_ex")
         grads, off = [], 0
         for shape, n, need in ctx.meta:
             grads.append(flat[off:off + n].view(shape) if need else None)
             off += n
-        return (None, g_lr, None, None, None, None) + tuple(grads)
+        return (None, g_lr, None, None, None, None) + tuple(g_eps) + tuple(grads)
 
 
 class _RescaleForwardStep(torch.autograd.Function):
@@ -958,7 +973,8 @@ class _EngineModule(nn.Module):
         """``sample_offset``: this call is samples [offset, offset + B) of a larger (sharded) batch: the device draws are
         those of the global samples (hcf_inverse_ex). ``cache_cond``: keep / reuse the deepest level's conditional features
         while ``lr`` (same tensor, unchanged) and the parameters stay the same (tau sweeps, repeated sampling)."""
-        if self._wants_grad() or (torch.is_grad_enabled() and torch.is_tensor(lr) and lr.requires_grad):
+        eps_grad = eps is not None and any(torch.is_tensor(e) and e.requires_grad for e in eps)
+        if self._wants_grad() or (torch.is_grad_enabled() and ((torch.is_tensor(lr) and lr.requires_grad) or eps_grad)):
             if self.training and self._pending_actnorms():
                 raise NotImplementedError(
                     "un-initialised ActNorm layers in train() mode on the REVERSE path: run one forward (hr -> z) pass "
@@ -968,7 +984,12 @@ class _EngineModule(nn.Module):
                 seed = int(torch.randint(0, 2 ** 62, (1,)).item())
             tau = 0.0 if eps_std is None else float(eps_std)
             lr_t = lr.to(device=dev, dtype=torch.float32).contiguous()          # keeps the autograd link to the caller's lr
-            return _SRReverseStep.apply(self, lr_t, tau, seed, bool(clamp), eps, *self._params())
+            mask, given = None, []
+            if eps is not None:
+                mask = tuple(e is not None for e in eps)
+                # (as lr: converted here, so that the autograd link to the caller's eps tensors survives)
+                given = [e.to(device=dev, dtype=torch.float32).contiguous() for e in eps if e is not None]
+            return _SRReverseStep.apply(self, lr_t, tau, seed, bool(clamp), mask, *given, *self._params())
         self._check_inference(reverse=True)
         if seed is None:
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())     # follows torch.manual_seed

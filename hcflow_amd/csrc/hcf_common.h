@@ -286,9 +286,11 @@ struct PriorBwdArgs {
   float gobj;
   int rescale;             // 0: logs = s (SR); 1: logs = 0.318 atan(2 s) (rescaling net, ConditionalFlow.py:78,90)
   const float* gz_nchw;    // encode backward: dL/dz of z = (a - mean) e^-logs, NCHW [B,C,H,W] (nullptr: zero)
+  float* geps_nchw;        // sample backward, optional: receives dL/d eps = ga e^logs, NCHW [B,C,H,W] (nullptr: not wanted)
 };
 int launch_gauss_logp_bwd(const PriorBwdArgs& a, hipStream_t st);
-// a = mean + e^logs * eps (SR prior sample): gh[2c] = ga[c], gh[2c+1] = ga[c] * (a[c] - mean)   (ga in, gh out)
+// a = mean + e^logs * eps (SR prior sample): gh[2c] = ga[c], gh[2c+1] = ga[c] * (a[c] - mean)   (ga in, gh out);
+// with geps_nchw also dL/d eps = ga[c] * e^logs (gauss_sample_bwd_eps_kernel: the same gh, bit for bit)
 int launch_gauss_sample_bwd(const PriorBwdArgs& a, hipStream_t st);
 // z = (a - mean) e^-logs (rescaling forward, ConditionalFlow.py:76-80): ga (=), gh (=) from gz_nchw
 int launch_gauss_encode_bwd(const PriorBwdArgs& a, hipStream_t st);

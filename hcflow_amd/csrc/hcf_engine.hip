@@ -627,13 +627,13 @@ int hcf_train_forward_sr(hcf_engine* e, const float* hr, const float* lr, const 
 
 int hcf_train_backward(hcf_engine* e, float grad_nll, float* dparams, int64_t numel, hcf_stream_t stream) {
   if (!e || numel < 0) return HCF_ERR_ARG;
-  hcf_engine::BwdIn in = {1, grad_nll, nullptr, nullptr, nullptr, nullptr};
+  hcf_engine::BwdIn in = {1, grad_nll, nullptr, nullptr, nullptr, nullptr, nullptr, 0};
   return e->run_backward(in, dparams, (size_t)numel, (hipStream_t)stream);
 }
 
 int hcf_train_backward_phase(hcf_engine* e, int32_t phase, float grad_nll, float* dparams, int64_t numel, hcf_stream_t stream) {
   if (!e || numel < 0 || phase < 0 || phase > 1) return HCF_ERR_ARG;
-  hcf_engine::BwdIn in = {1, grad_nll, nullptr, nullptr, nullptr, nullptr};
+  hcf_engine::BwdIn in = {1, grad_nll, nullptr, nullptr, nullptr, nullptr, nullptr, 0};
   return e->run_backward(in, dparams, (size_t)numel, (hipStream_t)stream, phase);
 }
 
@@ -654,7 +654,7 @@ int hcf_train_forward_rescale(hcf_engine* e, const float* hr, float* out_lr, flo
 int hcf_train_backward_rescale(hcf_engine* e, const float* g_lr, const float* g_z1, const float* g_z2, float* dparams,
                                int64_t numel, hcf_stream_t stream) {
   if (!e || numel < 0) return HCF_ERR_ARG;
-  hcf_engine::BwdIn in = {3, 0.f, g_lr, nullptr, g_z1, g_z2};
+  hcf_engine::BwdIn in = {3, 0.f, g_lr, nullptr, g_z1, g_z2, nullptr, 0};
   return e->run_backward(in, dparams, (size_t)numel, (hipStream_t)stream);
 }
 
@@ -666,9 +666,20 @@ int hcf_train_inverse(hcf_engine* e, const float* lr, const float* const* eps, i
 
 int hcf_train_backward_inverse(hcf_engine* e, const float* grad_out, float* dparams, int64_t numel, float* grad_lr,
                                hcf_stream_t stream) {
-  if (!e || numel < 0) return HCF_ERR_ARG;
-  hcf_engine::BwdIn in = {2, 1.f, grad_out, grad_lr, nullptr, nullptr};
+  return hcf_train_backward_inverse_ex(e, grad_out, dparams, numel, grad_lr, nullptr, 0, stream);
+}
+
+int hcf_train_backward_inverse_ex(hcf_engine* e, const float* grad_out, float* dparams, int64_t numel, float* grad_lr,
+                                  float* const* grad_eps, int32_t n_eps, hcf_stream_t stream) {
+  if (!e || !grad_out || numel < 0 || n_eps < 0 || (n_eps > 0 && !grad_eps)) return HCF_ERR_ARG;
+  hcf_engine::BwdIn in = {2, 1.f, grad_out, grad_lr, nullptr, nullptr, grad_eps, n_eps};
   return e->run_backward(in, dparams, (size_t)numel, (hipStream_t)stream);
+}
+
+int hcf_train_backward_counts(const hcf_engine* e, int64_t out[4]) {
+  if (!e || !out) return HCF_ERR_ARG;
+  for (int i = 0; i < 4; ++i) out[i] = e->tape->bwd.counts[i];
+  return HCF_OK;
 }
 
 int hcf_bind_param_device(hcf_engine* e, const char* key, const float* dev_ptr) {

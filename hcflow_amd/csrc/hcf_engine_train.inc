@@ -54,6 +54,14 @@
       // this pass uses the side streams below (their `on` flags: per pass, a pass on the other slot ends with its own switched off)
       bool wg_async = false, dg_async = false;
       bool dg_dirty = false;                         // dg_stream has been given work that the caller's stream has not waited for
+      // Input-gradient-only pass (inverse pass with frozen weights: latent optimisation): no gradient buffer, and the four funnels of
+      // parameter-gradient work -- run_wgrad, the dense blocks' batched weight gradients, add_sum_job, add_axpy_job -- drop their jobs
+      bool inputs_only = false;
+      float* const* geps = nullptr;                  // inverse pass, optional: geps[draw] receives dL / d eps of that draw (entries nullable)
+      int n_geps = 0;
+      // parameter-gradient work of the last backward pass on this tape (hcf_train_backward_counts): launch_conv_wgrad calls, convs
+      // handed to launch_conv_wgrad_batch, sum jobs, axpy jobs
+      long long counts[4] = {0, 0, 0, 0};
     } bwd;
   };
   Tape slots[2];
@@ -91,12 +99,16 @@
   // partials in the gradient arena, ONE launch at the end of the pass reduces them in a fixed order (bit-reproducible)
   JobQueue<SumJob> sum_jobs;
   void add_sum_job(const float* part, int nblk, int n, int pstride, float* d0, float* d1, float mult1) {
+    if (tape->bwd.inputs_only) return;
+    ++tape->bwd.counts[2];
     SumJob j; j.part = part; j.nblk = nblk; j.n = n; j.pstride = pstride; j.dst0 = d0; j.dst1 = d1; j.mult1 = mult1;
     sum_jobs.host.push_back(j);
   }
   // data-independent log-det terms (logs += k, dW += k W^-T): queued, one launch at the end of the pass
   JobQueue<AxpyJob> axpy_jobs;
   void add_axpy_job(const float* x, float* y, int n, float alpha) {
+    if (tape->bwd.inputs_only) return;
+    ++tape->bwd.counts[3];
     AxpyJob j; j.x = x; j.y = y; j.n = n; j.alpha = alpha;
     axpy_jobs.host.push_back(j);
   }
@@ -151,7 +163,7 @@
   hipStream_t wgs() const { return tape->bwd.wg_async ? wg_stream.s : st; }
   void wg_begin_pass() {
     static const bool off = getenv("HCF_NO_WGRAD_STREAM") != nullptr;
-    tape->bwd.wg_async = !off && wg_stream.open(0);
+    tape->bwd.wg_async = !off && !tape->bwd.inputs_only && wg_stream.open(0);      // (nothing to fork for without weight gradients)
   }
   // the caller's stream waits for everything the weight-gradient stream has been given so far
   void wg_join() {
@@ -209,6 +221,8 @@
     return HCF_OK;
   }
   int run_wgrad(WgradArgs& w) {
+    if (tape->bwd.inputs_only) return HCF_OK;
+    ++tape->bwd.counts[0];
     // beside the data-gradient chain (105 .. 160 blocks per launch at the training sizes) a full round of 256 blocks shares CUs
     // with it and slows both: 160 measured best (backward 45.0 / 43.3 / 42.4 / 42.7 / 43.9 / 50.0 ms at 256 / 192 / 160 / 144 /
     // 128 / 96, profiles/r04_notes.md); alone on the stream 256 stays best
@@ -267,6 +281,7 @@
     if (tape->bwd.wg_async && !wg_stream.fork(st)) { rdb_wg.clear(); return fail(HCF_ERR_HIP, "event on the weight-gradient stream failed"); }
     WgradReduceJob jobs[kWgBatchMax];
     const int r = launch_conv_wgrad_batch(rdb_wg.data(), n, wgs(), jobs);
+    tape->bwd.counts[1] += n;
     ++launch_seq;
     rdb_wg.clear();
     if (r != HCF_OK) return fail(r, "batched weight-gradient launch failed");
@@ -302,6 +317,7 @@
     HCF_LAUNCH(launch_lu_chain(a, st));
   }
   float* gp(const std::string& key) {
+    if (tape->bwd.inputs_only) return nullptr;         // no gradient buffer: whoever asks drops the work or brings scratch
     auto it = poff.find(key);
     if (it == poff.end()) { fail(HCF_ERR_KEY, "training: no gradient slot for " + key); return tape->bwd.gparams; }
     return tape->bwd.gparams + it->second;
@@ -916,7 +932,7 @@
     // inputs were never checked -> fp32 weight-gradient kernel
     if (tape->bwd.f16 && tape->f16 && (cv.taps == 9 || cv.taps == 1) && cv.wpack16) w.g_max = r.gmax;
     if (r.rdb) {
-      rdb_wg.push_back(w);                             // the block's five weight gradients go out as one launch (flush_rdb_wgrad)
+      if (!tape->bwd.inputs_only) rdb_wg.push_back(w); // the block's five weight gradients go out as one launch (flush_rdb_wgrad)
       if (r.rdb_m == 0 && flush_rdb_wgrad() != HCF_OK) return;
     } else {
       HCF_LAUNCH(run_wgrad(w));
@@ -1374,18 +1390,20 @@
     a.z = zin.v.all(); a.h = ho.v.v(0, s.f_out); a.out = x.v.all(); a.aux = zc.v.all();
     HCF_LAUNCH(launch_step_tail_inv(a, st));
     float* const spart = tape->g.alloc((size_t)B_ * step_blocks_per_sample(H, W) * 2 * s.cmax);
-    if (!dry()) tape->recs.push_back([this, sp, zin, zc, x, y, ho, H, W, spart]() {
+    float* const gscr = tape->g.alloc(2 * (size_t)s.cmax);      // ActNorm sums of an input-gradient-only pass (the launcher wants a destination)
+    if (!dry()) tape->recs.push_back([this, sp, zin, zc, x, y, ho, H, W, spart, gscr]() {
       const Step& s = *sp;
       StepInvBwdArgs b = step_dims<StepInvBwdArgs>(s, H, W);
       b.gx = x.g.all(); b.x = x.v.all(); b.zc = zc.v.all(); b.h = ho.v.v(0, s.f_out);
       b.gz = zin.g.all(); b.gh = ho.g.v(0, s.f_out); b.gzc = zc.g.all(); b.y = y.all();
       b.matInvT = s.has_mat ? s.mat_invT : nullptr;
       b.an_bias = s.bias; b.mul_fwd = s.mul_fwd; b.mul_inv = s.mul_inv;
-      b.g_bias = gp(s.an_key + ".bias"); b.g_logs = gp(s.an_key + ".logs");
+      const bool io = tape->bwd.inputs_only;
+      b.g_bias = io ? gscr : gp(s.an_key + ".bias"); b.g_logs = io ? gscr + s.cmax : gp(s.an_key + ".logs");
       b.part = spart;
       HCF_LAUNCH(launch_step_inv_bwd(b, st));
       add_sum_job(spart, B_ * step_blocks_per_sample(H, W), s.C, s.cmax, b.g_bias, b.g_logs, 1.f);
-      if (s.has_mat) {                                   // y = W^-1 zc  ->  dW = -sum (W^-T gy) y^T = -sum gzc y^T
+      if (s.has_mat && !io) {                            // y = W^-1 zc  ->  dW = -sum (W^-T gy) y^T = -sum gzc y^T
         WgradArgs w;
         memset(&w, 0, sizeof(w));
         w.src[0] = y.all(); w.nsrc = 1; w.g = zc.g.all(); w.B = B_; w.H = H; w.W = W; w.taps = 1;
@@ -1442,8 +1460,11 @@
         HCF_LAUNCH(launch_gauss_sample(g, st));
         const TB a0 = a;
         const int Ca = cf.Ca;
-        if (!dry()) tape->recs.push_back([this, a0, ho, Ca, H, W]() {
-          HCF_LAUNCH(launch_gauss_sample_bwd(prior_bwd_args(a0, ho, Ca, H, W), st));
+        if (!dry()) tape->recs.push_back([this, a0, ho, Ca, H, W, draw]() {
+          PriorBwdArgs p = prior_bwd_args(a0, ho, Ca, H, W);
+          // dL / d eps of this draw, whether the caller injected it or the device drew it (then: w.r.t. the drawn N(0, tau) values)
+          p.geps_nchw = (tape->bwd.geps && draw < tape->bwd.n_geps) ? tape->bwd.geps[draw] : nullptr;
+          HCF_LAUNCH(launch_gauss_sample_bwd(p, st));
         });
       }
       for (int k = (int)cf.steps.size() - 1; k >= 0; --k) a = t_step_inverse(cf.steps[k], a, &cfv, H, W);
@@ -1554,6 +1575,8 @@
     const float* gout;              // kind 2: dL / d out_hr;  kind 3: dL / d out_lr (nullable)
     float* gin;                     // kind 2: receives dL / d lr (nullable)
     const float* gz1; const float* gz2;   // kind 3: dL / d z1, z2 (nullable)
+    float* const* geps; int n_geps;       // kind 2: receive dL / d eps, one per draw in sampling order (deepest level first, as
+                                          // hcf_inverse's eps); the array and its entries are nullable
   };
   // phase: -1 the whole pass; 0 records [mark, end) + a flush of every pending parameter-gradient job; 1 the rest
   int run_backward(const BwdIn& in, float* dparams, size_t n, hipStream_t stream, int phase = -1) {
@@ -1566,7 +1589,10 @@
     if (!tape->valid || tape->kind != in.kind)
       return fail(HCF_ERR_STATE, "backward without a matching taped pass on the selected tape slot before it");
     if (in.kind == 2 && !in.gout) return fail(HCF_ERR_ARG, "hcf_train_backward_inverse: null output gradient");
-    if (n != ptotal || !dparams) return fail(HCF_ERR_ARG, "backward: gradient buffer size mismatch");
+    // inverse pass only: no gradient buffer at all = the gradients of the inputs (lr, eps) alone, no parameter-gradient work
+    const bool inputs_only = in.kind == 2 && !dparams && n == 0;
+    if (!inputs_only && (n != ptotal || !dparams)) return fail(HCF_ERR_ARG, "backward: gradient buffer size mismatch");
+    if (in.n_geps < 0 || (in.n_geps > 0 && !in.geps)) return fail(HCF_ERR_ARG, "backward: n_geps without the eps gradient array");
     if (phase >= 0 && in.kind != 1) return fail(HCF_ERR_UNSUPPORTED, "two-phase backward: NLL pass only");
     if (phase == 1 && (!tape->mid || dparams != tape->bwd.gparams)) return fail(HCF_ERR_STATE, "backward phase 1 without phase 0 on this tape (same gradient buffer) before it");
     if (phase != 1 && tape->mid) return fail(HCF_ERR_STATE, "backward: phase 1 of a two-phase backward is pending on this tape");
@@ -1586,6 +1612,10 @@
     if (tape->bwd.f16) { ovf_latch(); ovf_clear = false; }
     if (tape->bwd.f16 && hipMemsetAsync(ovf_flag, 0, 256, st) != hipSuccess) return fail(HCF_ERR_HIP, "hipMemsetAsync failed (backward)");
     tape->bwd.gparams = dparams;
+    tape->bwd.inputs_only = inputs_only;
+    tape->bwd.geps = (in.kind == 2) ? in.geps : nullptr;
+    tape->bwd.n_geps = (in.kind == 2) ? in.n_geps : 0;
+    for (long long& c : tape->bwd.counts) c = 0;
     tape->bwd.g_out_nchw = (in.kind == 2) ? in.gout : nullptr;
     tape->bwd.g_in_nchw = (in.kind == 2) ? in.gin : nullptr;
     tape->bwd.g_fwd_lr = (in.kind == 3) ? in.gout : nullptr;
@@ -1594,7 +1624,7 @@
     // nll = mean_b( -objective_b / (ln 2 * pixels) ); the other objectives have no log-det term
     tape->bwd.gobj = (in.kind == 1) ? -in.gscale / (float)((double)B_ * log(2.0) * tape->pixels) : 0.f;
     if (hipMemsetAsync(tape->g.base, 0, tape->g.top, st) != hipSuccess ||
-        hipMemsetAsync(dparams, 0, ptotal * sizeof(float), st) != hipSuccess)
+        (dparams && hipMemsetAsync(dparams, 0, ptotal * sizeof(float), st) != hipSuccess))
       return fail(HCF_ERR_HIP, "hipMemsetAsync failed (backward)");
     sum_jobs.host.clear();
     wg_jobs.host.clear();
@@ -1631,5 +1661,7 @@
     flush_sum_jobs();
     tape->valid = false;          // the epilogue backward overwrote the gradient buffers in place: one backward per forward
     tape->bwd.gparams = nullptr;
+    tape->bwd.geps = nullptr;     // (the caller's array)
+    tape->bwd.n_geps = 0;
     return rc;
   }

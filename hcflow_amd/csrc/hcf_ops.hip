@@ -680,6 +680,27 @@ int hcf_op_prior_backward(int32_t kind, const float* a, const float* h, float* g
   return rc;
 }
 
+int hcf_op_prior_sample_backward(const float* a, const float* h, const float* ga, float* gh, float* geps_nchw, int32_t B,
+                                 int32_t C, int32_t H, int32_t W, int32_t rescale, hcf_stream_t stream) {
+  if (!a || !h || !ga || !gh || B < 1 || C < 1 || H < 1 || W < 1) return HCF_ERR_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  Tmp t;
+  int rc = HCF_OK;
+  PriorBwdArgs p;
+  memset(&p, 0, sizeof(p));
+  p.B = B; p.H = H; p.W = W; p.C = C;
+  p.a = nhwc_from_nchw(t, a, B, C, H, W, st, rc);
+  p.h = nhwc_from_nchw(t, h, B, 2 * C, H, W, st, rc);
+  p.ga = nhwc_window(t, ga, B, C, H, W, ru4(C), 0, st, rc);
+  p.gh = nhwc_window(t, nullptr, B, 2 * C, H, W, ru4(2 * C), 0, st, rc);
+  p.rescale = rescale; p.geps_nchw = geps_nchw;         // straight into the caller's NCHW tensor, as the engine's pass does
+  if (!t.ok) return HCF_ERR_NOMEM;
+  if (rc == HCF_OK) rc = launch_gauss_sample_bwd(p, st);
+  if (rc == HCF_OK) rc = launch_nhwc_to_nchw(p.gh, gh, B, 2 * C, H, W, 0, st);
+  if (hipStreamSynchronize(st) != hipSuccess) return HCF_ERR_HIP;
+  return rc;
+}
+
 int hcf_op_quant_logp_backward(const float* z, const float* lr, float* gz, int32_t B, int32_t H, int32_t W, float gobj,
                                hcf_stream_t stream) {
   if (!z || !lr || !gz || B < 1 || H < 1 || W < 1) return HCF_ERR_ARG;

@@ -508,9 +508,56 @@ int launch_mask_flat(const float* g, const float* raw, float* out, size_t n, hip
   hipLaunchKernelGGL(mask_flat_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, g, raw, out, n);
   HCF_RET_T();
 }
+// The same with dL/d eps = ga e^logs as an NCHW caller tensor (latent optimisation: the weights are frozen, eps moves). gh: the
+// expressions of gauss_sample_bwd_kernel, element by element (bit-identical). A block owns 256 pixels of one sample, as
+// gauss_encode_logp_kernel (hcf_flow.hip): the NHWC records are read and gh is written channel fastest (consecutive lanes =
+// consecutive floats of a record), dL/d eps crosses an LDS tile [channel][row] and goes out pixel fastest (consecutive lanes =
+// consecutive floats of a channel plane); latents wider than the tile pass through it in slices of GEPS_TILE_C channels.
+// Row length: ds_write_b32 is banked mod 32 over each 32-lane half. Channel-fastest lanes (pixel i, channel c) store to c * row + i,
+// and a half covers ceil(32 / nc) pixels (+ 1 when it starts inside a record): with row = 257 the bank is (c + i) mod 32 and the
+// pixels of a half land on each other (6 channels: 32 lanes on 11 banks, up to 6 on one). row = 256 + ceil(32 / nc) gives bank
+// (c * ceil(32 / nc) + i) mod 32: the channels of a half are ceil(32 / nc) banks apart and its pixels fill the gaps -- at most 2
+// lanes per bank, which a 4-cycle ds_write_b32 hides. The pixel-fastest reads are consecutive dwords for any row length.
+constexpr int GEPS_TILE_C = 24;
+constexpr int GEPS_TILE_FLOATS = GEPS_TILE_C * 256 + 64;       // nc * geps_row(nc) <= 256 nc + 31 + nc for every nc <= GEPS_TILE_C
+__device__ __forceinline__ int geps_row(int nc) { return 256 + (32 + nc - 1) / nc; }
+__global__ __launch_bounds__(256) void gauss_sample_bwd_eps_kernel(const PriorBwdArgs a) {
+  __shared__ float tile[GEPS_TILE_FLOATS];
+  const int hw = a.H * a.W;
+  const int b = blockIdx.y;
+  const int p0 = blockIdx.x * 256;
+  const int np = min(256, hw - p0);                       // pixels of this block (>= 1: the grid is ceil(hw / 256))
+  for (int c0 = 0; c0 < a.C; c0 += GEPS_TILE_C) {
+    const int nc = min(GEPS_TILE_C, a.C - c0);
+    const int row = geps_row(nc);
+    const int n = np * nc;
+    for (int t = threadIdx.x; t < n; t += 256) {
+      const int i = t / nc, c = c0 + (t - i * nc);
+      const size_t pix = (size_t)b * hw + p0 + i;
+      const float* ap = a.a.p + pix * a.a.cs + a.a.c0;
+      const float* hp = a.h.p + pix * a.h.cs + a.h.c0;
+      const float* ga = a.ga.p + pix * a.ga.cs + a.ga.c0;
+      float* gh = a.gh.p + pix * a.gh.cs + a.gh.c0;
+      gh[2 * c] = ga[c];                               // a = mean + e^logs eps
+      float gl = ga[c] * (ap[c] - hp[2 * c]);          // d a / d logs = e^logs eps = a - mean
+      const float s = hp[2 * c + 1];
+      if (a.rescale) gl *= 0.636f / (1.f + 4.f * s * s);   // logs = 0.318 atan(2 s)
+      gh[2 * c + 1] = gl;
+      tile[(c - c0) * row + i] = ga[c] * expf(a.rescale ? logscale_of(s) : s);   // d a / d eps = e^logs
+    }
+    __syncthreads();
+    for (int t = threadIdx.x; t < n; t += 256) {
+      const int c = t / np, i = t - c * np;
+      a.geps_nchw[((size_t)b * a.C + c0 + c) * hw + p0 + i] = tile[c * row + i];
+    }
+    __syncthreads();
+  }
+}
 int launch_gauss_sample_bwd(const PriorBwdArgs& a, hipStream_t st) {
+  if (a.C < 1 || a.H < 1 || a.W < 1 || a.B < 1) return HCF_ERR_ARG;
   const dim3 grid((unsigned)step_blocks_per_sample(a.H, a.W), (unsigned)a.B);
-  hipLaunchKernelGGL(gauss_sample_bwd_kernel, grid, dim3(256), 0, st, a);
+  if (a.geps_nchw) hipLaunchKernelGGL(gauss_sample_bwd_eps_kernel, grid, dim3(256), 0, st, a);
+  else hipLaunchKernelGGL(gauss_sample_bwd_kernel, grid, dim3(256), 0, st, a);
   HCF_RET_T();
 }
 

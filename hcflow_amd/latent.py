@@ -81,3 +81,42 @@ def get_sr_with_z(net, lq, heat=None, seed=None, eps=None):
         eps = [torch.randn(s, generator=g, device=lq.device) * tau for s in eps_shapes(net.cfg, B, h, w)]
     sr = net(lr=lq, eps_std=1.0 if heat is None else float(heat), reverse=True, eps=eps)
     return sr, eps
+
+
+def optimise(net, z_lr, eps, loss_fn, steps, lr=0.02, optimise_lr=False, optimizer=None):
+    """Gradient descent in the latent space with the weights frozen: ``steps`` iterations of ``loss_fn(net.decode(z_lr, eps))``
+    (a scalar) over clones of ``eps`` -- and of ``z_lr`` when ``optimise_lr`` -- with ``torch.optim.Adam(tensors, lr=lr)``, or
+    with ``optimizer(tensors)`` when a factory is given. Returns ``(z_lr, eps, losses)``: the moved latents, detached, and the
+    loss of every step (evaluated BEFORE that step's update) as floats. The caller's tensors are not written.
+
+    Every parameter of ``net`` has ``requires_grad`` switched off for the duration, so each backward pass is the engine's
+    input-gradient-only one (no weight-gradient work at all), and gets its flag back afterwards, also on an error; no parameter
+    is written. ``eps`` entries that are None (levels left to the device sampler) stay None and are not optimised. ``decode`` is
+    unclamped: a clamp would zero the gradient of every saturated pixel."""
+    steps = int(steps)
+    assert steps >= 0
+    eps_v = [None if e is None else e.detach().clone().float().requires_grad_(True) for e in eps]
+    z_v = z_lr.detach().clone().float()
+    if optimise_lr:
+        z_v.requires_grad_(True)
+    moved = [e for e in eps_v if e is not None] + ([z_v] if optimise_lr else [])
+    assert moved, "nothing to optimise: every eps entry is None and optimise_lr is off"
+    opt = torch.optim.Adam(moved, lr=float(lr)) if optimizer is None else optimizer(moved)
+    params = list(net.parameters())
+    flags = [p.requires_grad for p in params]
+    history = []
+    try:
+        for p in params:
+            p.requires_grad_(False)
+        with torch.enable_grad():
+            for _ in range(steps):
+                opt.zero_grad(set_to_none=True)
+                loss = loss_fn(net.decode(z_v, eps_v))
+                loss.backward()
+                opt.step()
+                history.append(loss.detach())
+    finally:
+        for p, f in zip(params, flags):
+            p.requires_grad_(f)
+    losses = [float(v) for v in torch.stack(history).cpu()] if history else []
+    return z_v.detach(), [None if e is None else e.detach() for e in eps_v], losses

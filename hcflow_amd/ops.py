@@ -226,6 +226,19 @@ def prior_backward(kind: str, a, h, ga=None, gz=None, rescale: bool = False, gob
     return ga, gh
 
 
+def prior_sample_backward(a, h, ga, rescale: bool = False, want_geps: bool = True):
+    """Backward of the prior sample a = mean + e^logs eps given ``ga`` = dL/da: (gh, geps) with geps = dL/d eps (None when
+    ``want_geps`` is off: the entry then runs the kernel of ``prior_backward("sample", ...)``)."""
+    lib = _lib.load()
+    a, h, ga = _dev(a), _dev(h), _dev(ga)
+    B, Cc, H, W = a.shape
+    gh = torch.empty_like(h)
+    geps = torch.empty_like(a) if want_geps else None
+    _lib.check(lib.hcf_op_prior_sample_backward(a.data_ptr(), h.data_ptr(), ga.data_ptr(), gh.data_ptr(), _ptr(geps), B, Cc, H, W,
+                                                int(rescale), _stream(a)), None, "hcf_op_prior_sample_backward")
+    return gh, geps
+
+
 def quant_logp_backward(z, lr, gobj: float, gz=None) -> torch.Tensor:
     """gz (zeros when None) + gobj * d logp(lr; Quant(z), logs = -6) / dz with the straight-through Quant."""
     lib = _lib.load()

@@ -215,6 +215,22 @@ int hcf_train_inverse(hcf_engine* e, const float* lr, const float* const* eps, i
                       float* out_hr, int32_t B, int32_t h, int32_t w, uint32_t flags, hcf_stream_t stream);
 int hcf_train_backward_inverse(hcf_engine* e, const float* grad_out, float* dparams, int64_t numel, float* grad_lr,
                                hcf_stream_t stream);     /* grad_lr: optional device [B,3,h,w], receives dL/d lr */
+/* The same with the gradients of the latents (optimising in the latent space with the weights frozen: editing, projection onto
+ * a constraint, refining a sample against a metric). grad_eps: n_eps device tensors in sampling order, deepest level first and
+ * shaped as hcf_inverse's eps (the array and each entry nullable): grad_eps[i] receives dL/d eps_i of a = mean + e^logs eps
+ * (GaussianDiag.sample, Basic.py:96-101; logs = s for the SR prior, 0.318 atan(2 s) for the rescaling prior,
+ * ConditionalFlow.py:59-69,86-96). A level whose eps the taped pass drew on the device has a gradient too: w.r.t. the drawn
+ * N(0, tau) values. hcf_train_backward_inverse = this call with grad_eps = NULL, n_eps = 0.
+ * dparams = NULL with numel = 0 asks for the gradients of the inputs alone: the pass launches no weight-gradient kernel, no
+ * per-channel sum and no log-det update, touches no parameter-gradient slot and does not fork the weight-gradient stream; the
+ * data-gradient chain (direct and Winograd convs, fused epilogue backward) is the one of the full pass. Every other backward
+ * entry refuses a null dparams. */
+int hcf_train_backward_inverse_ex(hcf_engine* e, const float* grad_out, float* dparams, int64_t numel, float* grad_lr,
+                                  float* const* grad_eps, int32_t n_eps, hcf_stream_t stream);
+/* Parameter-gradient work of the LAST backward pass on the selected tape slot (hcf_train_select_tape): out[0] = weight-gradient
+ * launches of one conv, out[1] = convs handed to the batched weight-gradient launches of the dense blocks, out[2] = per-channel
+ * sum jobs, out[3] = axpy (log-det) jobs. All zero after an input-gradient-only pass. */
+int hcf_train_backward_counts(const hcf_engine* e, int64_t out[4]);
 
 /* Rescaling net (reference: one generator step of HCFlow_Rescaling_model.optimize_parameters, :212-256 --
  * `fake_LR, z1, z2 = netG(hr, reverse=False)`; losses on all three; `fake_H = netG(lr=Quant(fake_LR), reverse=True)`;
@@ -355,6 +371,11 @@ int hcf_op_step_inverse_backward(const float* gx, const float* x, const float* z
  *   kind 2 (encode): z = (a - mean) e^-logs, gz_nchw = dL/dz (NULL: zero) -> ga, gh out */
 int hcf_op_prior_backward(int32_t kind, const float* a, const float* h, float* ga, float* gh, const float* gz_nchw,
                           int32_t B, int32_t C, int32_t H, int32_t W, int32_t rescale, float gobj, hcf_stream_t stream);
+/* kind 1 of the above that also returns the gradient of the latent (GaussianDiag.sample, Basic.py:96-101, as the conditional
+ * priors call it, ConditionalFlow.py:59-69 SR, :86-96 rescaling): a = mean + e^logs eps, ga = dL/da IN -> gh out (the same
+ * values as kind 1, bit for bit) and geps_nchw [B,C,H,W] = dL/d eps = ga e^logs out (NULL: not wanted, the call is kind 1). */
+int hcf_op_prior_sample_backward(const float* a, const float* h, const float* ga, float* gh, float* geps_nchw, int32_t B,
+                                 int32_t C, int32_t H, int32_t W, int32_t rescale, hcf_stream_t stream);
 /* Dirac-LR term with the straight-through Quant: gz [B,3,H,W] += gobj * d logp(lr; mean = Quant(z), logs = -6) / dz */
 int hcf_op_quant_logp_backward(const float* z, const float* lr, float* gz, int32_t B, int32_t H, int32_t W, float gobj,
                                hcf_stream_t stream);
