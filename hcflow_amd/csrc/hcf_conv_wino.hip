@@ -5,6 +5,7 @@
 #include "hcf_common.h"
 #include <cstdlib>
 #include "hcf_conv_wino.h"
+#include "hcf_pack_index.h"
 #include <atomic>
 
 namespace hcf {
@@ -60,15 +61,7 @@ __device__ __forceinline__ void repack_wino_one(const RepackWinoJob& jb, int idx
   if (idx >= kn * cout) return;
   const int oc = idx / kn, ic = idx - oc * kn + (jb.tr ? jb.k0 : 0);
   float g[9];
-  if (jb.tr) {
-    const float* src = jb.w + (size_t)(ic - jb.k0) * jb.ld + (size_t)(jb.tr_off + oc) * 9;
-    for (int t = 0; t < 9; ++t) g[t] = src[8 - t];
-  } else {
-    const int ld = jb.ld ? jb.ld : cin * 9, ld2 = jb.ld2 ? jb.ld2 : cin * 9;
-    const float* row = (!jb.w2 || oc < jb.split) ? jb.w + (size_t)oc * ld : jb.w2 + (size_t)(oc - jb.split) * ld2;
-    const int col = jb.z1_pad == 0 ? ic : (ic < jb.z1_n ? ic : ic < jb.z1_pad ? -1 : ic - jb.z1_pad + jb.z1_n);
-    for (int t = 0; t < 9; ++t) g[t] = col >= 0 ? row[(size_t)col * 9 + t] : 0.f;
-  }
+  wino_taps(jb, oc, ic, g);
   const double G[4][3] = {{1, 0, 0}, {.5, .5, .5}, {.5, -.5, .5}, {0, 0, 1}};
   double t[4][3], U[4][4];
   for (int i = 0; i < 4; ++i)

@@ -20,6 +20,7 @@
 
 #include "../../include/hcflow.h"
 #include "hcf_common.h"
+#include "hcf_pack_index.h"
 
 namespace hcf {
 int step_cmax(int C);
@@ -243,7 +244,6 @@ struct hcf_engine {
   // Winograd packs of the eligible convs (built by hcf_finalize, rebuilt on the device by hcf_refresh_from_device);
   // HCF_NO_WINO=1 keeps them from being built at all.
   bool wino_enabled = getenv("HCF_NO_WINO") == nullptr;
-  bool wino_stale = false;
   // ActNorm data-dependent initialisation (ActNorms.py:29-43), armed for ONE forward pass by hcf_actnorm_init_request
   std::set<std::string> an_pending, an_fitted;
   bool an_active = false;
@@ -303,7 +303,8 @@ struct hcf_engine {
     return d;
   }
 
-#include "hcf_engine_build.inc"      // planning: packs, derived packs, the module-tree walk
+#include "hcf_engine_packs.inc"      // the derived packs and tables, each described once: recipes, host execution, device jobs
+#include "hcf_engine_build.inc"      // planning: which packs every layer gets, the module-tree walk
 #include "hcf_engine_run.inc"        // routing + execution: run_conv, blocks, pass_inverse / pass_forward
 #include "hcf_engine_train.inc"
 
@@ -523,8 +524,6 @@ int hcf_finalize(hcf_engine* e, int device) {
   e->cc_valid = false;
   e->invalidate_tapes();
   e->host_stale = false;
-  e->wino_stale = false;       // build() re-packs the Winograd form from the host weights
-  e->fat_stale = false;
   e->device = device;
   e->spec_mode = false;
   e->rc = HCF_OK;

@@ -1,10 +1,14 @@
-// hcf_engine_build.inc -- included INSIDE struct hcf_engine (hcf_engine.hip). PLANNING: how every layer of the reference module tree
-// is packed for the kernels (direct f16x3 / fp32 packs, Winograd packs, the derived packs of the fat dense-block pairs and of the
-// padded-z1 coupling nets, ActNorm epilogue vectors, fp64 inverses of the invertible 1x1 convs) and the walk over the tree in the
-// reference's registration order (build()). Nothing here launches a kernel of the path.
+// hcf_engine_build.inc -- included INSIDE struct hcf_engine (hcf_engine.hip). PLANNING: which packs every layer of the reference
+// module tree gets (direct f16x3 / fp32 packs, Winograd packs, the derived packs of the fat dense-block pairs and of the padded-z1
+// coupling nets, ActNorm epilogue vectors, fp64 inverses of the invertible 1x1 convs) and the walk over the tree in the reference's
+// registration order (build()). Each pack is stated as a recipe and executed through hcf_engine_packs.inc, which also derives the
+// device-side refresh from the same recipes: nothing here assembles a weight by hand. Nothing here launches a kernel of the path.
 
   // ---------------------------------------------------------------- conv packing
-  void pack_conv(Conv& cv, const float* w, const float* bias, const float* scale, int cin, int cout, int k,
+  // The packs of one conv layer and their recipes. Its [cout][cin][k][k] weight is the parameter `wkey`, or, for a conv the engine
+  // composes from slices of parameters (the fat dense-block pairs), what `composed` describes; such a conv's direct packs are built
+  // here and have no device job (no kernel reads them: a fat launch only ever takes the Winograd pack; the f16x3 one is its range gate).
+  void pack_conv(Conv& cv, const std::string& wkey, const WinoPart* composed, EpiRecipe epi, int cin, int cout, int k,
                  std::vector<int> srcs, int act) {
     cv.taps = k * k;
     cv.cout = cout;
@@ -24,71 +28,61 @@
       fail(HCF_ERR_SHAPE, "internal: conv source channels do not add up");
       return;
     }
-    if (!w) return;
-    std::vector<float> pk;
-    pack_conv_weights(w, cin, cout, cv.taps, srcs.data(), cv.nsrc, pk, cv.nchunk, cv.npad);
-    std::vector<float> b(cv.npad, 0.f), s(cv.npad, 1.f);
-    for (int n = 0; n < cout; ++n) {
-      if (bias) b[n] = bias[n];
-      if (scale) s[n] = scale[n];
-    }
-    cv.wpack = upload(pk);
-    cv.bias = upload(b);
-    cv.scale = upload(s);
-    cv.wpack16 = nullptr;
-    if (cv.npad <= 64) {      // 1x1 packs are only used fused into a preceding 3x3 (FCN conv1 + conv2)
-      std::vector<float> pk16;
-      int nc = 0, np = 0;
-      if (pack_conv_weights_f16x3(w, cin, cout, cv.taps, srcs.data(), cv.nsrc, pk16, nc, np)) cv.wpack16 = upload(pk16);
-    }
+    if (rc != HCF_OK) return;
+    DirectRecipe d = direct_recipe(cin, cout, cv.taps, srcs.data(), cv.nsrc);
+    if (!composed) d.parts.push_back(direct_part(wkey, cin, cv.taps, cout, srcs.data(), cv.nsrc));
+    const WinoPart wp = composed ? *composed : wino_part(wkey, cin, cout);
+    const std::vector<float> L = composed ? wino_logical({wp}, cin, cout) : direct_logical(d);
+    if (rc != HCF_OK) return;
+    keep_direct(d, L.data(), cv.npad <= 64);      // 1x1 packs are only used fused into a preceding 3x3 (FCN conv1 + conv2)
+    cv.wpack = d.pk;
+    cv.wpack16 = d.pk16;
+    if (!epi.cout) epi.cout = cout;
+    run_epi(epi, cv.npad);
+    cv.bias = epi.bias;
+    cv.scale = epi.scale;
     cv.wpack_wino = nullptr;
     cv.wino_ntile = 0;
     if (cv.wpack16 && cv.taps == 9 && wino_enabled) {
-      std::vector<float> pkw;
-      if (pack_conv_weights_wino(w, cin, cout, srcs.data(), cv.nsrc, pkw)) cv.wpack_wino = upload(pkw);
-      else if (wino_pad_ok && cout >= 8 && cout < 64 && cout != 32 && (cout & 3) == 0 && !getenv("HCF_NO_WINO_PAD")) {       // (A/B knob)
+      WinoRecipe w = wino_recipe({wp}, cin, cout, srcs.data(), cv.nsrc, -1);
+      if ((cv.wpack_wino = run_wino(w))) return;
+      if (wino_pad_ok && cout >= 8 && cout < 64 && cout != 32 && (cout & 3) == 0 && !getenv("HCF_NO_WINO_PAD")) {       // (A/B knob)
         // other widths of the dense-block growth convs (the rescaling trunk's 16 channels): a zero-padded 32 / 64-channel tile
         // (the prior heads, 12 / 24 output channels at K = 128, measured even-to-slower in that form and keep the direct kernel)
-        const int cout_t = cout < 32 ? 32 : 64;
-        std::vector<float> wp((size_t)cout_t * cin * 9, 0.f);
-        memcpy(wp.data(), w, (size_t)cout * cin * 9 * sizeof(float));
-        if (pack_conv_weights_wino(wp.data(), cin, cout_t, srcs.data(), cv.nsrc, pkw)) {
-          cv.wpack_wino = upload(pkw);
-          cv.wino_ntile = cout_t / 32;
-        }
+        w.cout_tile = cout < 32 ? 32 : 64;
+        if ((cv.wpack_wino = run_wino(w))) cv.wino_ntile = w.cout_tile / 32;
       }
     }
   }
 
+  static EpiRecipe epi_recipe(const std::string& bkey, const std::string& lkey, int kind) {
+    EpiRecipe e;
+    e.bkey = bkey; e.lkey = lkey; e.kind = kind;
+    return e;
+  }
   // nn.Conv2d(cin, cout, 3, 1, 1, bias=True)
   void build_conv(Conv& cv, const std::string& p, int cin, int cout, std::vector<int> srcs, int act) {
-    const float* w = P(p + ".weight", {cout, cin, 3, 3});
-    const float* b = P(p + ".bias", {cout});
-    pack_conv(cv, w, b, nullptr, cin, cout, 3, srcs, act);
+    P(p + ".weight", {cout, cin, 3, 3});
+    P(p + ".bias", {cout});
     cv.wkey = p + ".weight"; cv.bkey = p + ".bias"; cv.lkey.clear(); cv.l_mult = 0.f;
+    pack_conv(cv, cv.wkey, nullptr, epi_recipe(cv.bkey, cv.lkey, 0), cin, cout, 3, srcs, act);
   }
-  // Basic.Conv2d with ActNorm (Basic.py:14-53) + ReLU
+  // Basic.Conv2d with ActNorm (Basic.py:14-53) + ReLU: scale = exp(logs)
   void build_conv_an(Conv& cv, const std::string& p, int cin, int cout, int k, std::vector<int> srcs) {
-    const float* w = P(p + ".weight", {cout, cin, k, k});
-    const float* ab = P(p + ".actnorm.bias", {1, cout, 1, 1});
-    const float* al = P(p + ".actnorm.logs", {1, cout, 1, 1});
-    std::vector<float> sc(cout, 1.f);
-    if (al)
-      for (int i = 0; i < cout; ++i) sc[i] = expf(al[i]);
-    pack_conv(cv, w, ab, al ? sc.data() : nullptr, cin, cout, k, srcs, ACT_RELU);
+    P(p + ".weight", {cout, cin, k, k});
+    P(p + ".actnorm.bias", {1, cout, 1, 1});
+    P(p + ".actnorm.logs", {1, cout, 1, 1});
     cv.an_key = p + ".actnorm";
     cv.wkey = p + ".weight"; cv.bkey = p + ".actnorm.bias"; cv.lkey = p + ".actnorm.logs"; cv.l_mult = 1.f;
+    pack_conv(cv, cv.wkey, nullptr, epi_recipe(cv.bkey, cv.lkey, 1), cin, cout, k, srcs, ACT_RELU);
   }
   // Basic.Conv2dZeros (Basic.py:57-72): (conv + bias) * exp(logs * 3)
   void build_conv_zeros(Conv& cv, const std::string& p, int cin, int cout, std::vector<int> srcs) {
-    const float* w = P(p + ".weight", {cout, cin, 3, 3});
-    const float* b = P(p + ".bias", {cout});
-    const float* lg = P(p + ".logs", {cout, 1, 1});
-    std::vector<float> sc(cout, 1.f);
-    if (lg)
-      for (int i = 0; i < cout; ++i) sc[i] = expf(lg[i] * 3.f);
-    pack_conv(cv, w, b, lg ? sc.data() : nullptr, cin, cout, 3, srcs, ACT_NONE);
+    P(p + ".weight", {cout, cin, 3, 3});
+    P(p + ".bias", {cout});
+    P(p + ".logs", {cout, 1, 1});
     cv.wkey = p + ".weight"; cv.bkey = p + ".bias"; cv.lkey = p + ".logs"; cv.l_mult = 3.f;
+    pack_conv(cv, cv.wkey, nullptr, epi_recipe(cv.bkey, cv.lkey, 2), cin, cout, 3, srcs, ACT_NONE);
   }
 
   static std::vector<int> srcs2(int a, int b) {
@@ -149,19 +143,14 @@
     const float* al = P(p + ".actnorm.logs", {1, C, 1, 1});
     const float* W = nullptr;
     s.has_mat = (perm == HCF_PERM_INVCONV);
-    std::vector<float> lu_w, lu_l, lu_u;
-    double lu_sumlogs = 0;
+    const float *pl = nullptr, *ps = nullptr, *pu = nullptr;
     if (s.lu) {
       // state_dict order of the module: parameters l, log_s, u, then the buffers p, sign_s (Permutations.py:51-55)
-      const float* pl = P(s.lu_pre + ".l", {C, C});
-      const float* ps = P(s.lu_pre + ".log_s", {C});
-      const float* pu = P(s.lu_pre + ".u", {C, C});
-      const float* pp = P(s.lu_pre + ".p", {C, C});
-      const float* pg = P(s.lu_pre + ".sign_s", {C});
-      if (!spec_mode && rc == HCF_OK) {
-        compose_lu(pl, ps, pu, pp, pg, C, lu_w, lu_l, lu_u, lu_sumlogs);
-        W = lu_w.data();
-      }
+      pl = P(s.lu_pre + ".l", {C, C});
+      ps = P(s.lu_pre + ".log_s", {C});
+      pu = P(s.lu_pre + ".u", {C, C});
+      P(s.lu_pre + ".p", {C, C});
+      P(s.lu_pre + ".sign_s", {C});
     } else if (s.has_mat) W = P(p + ".permute.weight", {C, C});
     // coupling geometry (AffineCouplings.py:18-19, 101-106)
     int z1_n;
@@ -183,21 +172,19 @@
       static const bool no_w4f = getenv("HCF_NO_W4F") != nullptr;      // A/B knob, read once
       if (!spec_mode && rc == HCF_OK && wino_enabled && !no_w4f && cond >= 16 && (cond & 15) == 0 && z1_n <= 16 && hid == 64 &&
           s.c[0].wpack16 && s.c[1].wpack16) {
-        const std::vector<float>& w1 = params[f + ".conv1.weight"].data;
-        const std::vector<float>& w2 = params[f + ".conv2.weight"].data;
-        const int cin_p = 16 + cond;
-        std::vector<float> wp((size_t)hid * cin_p * 9, 0.f), pk, fr;
-        for (int oc = 0; oc < hid; ++oc)
-          for (int ic = 0; ic < s.f_in; ++ic)
-            memcpy(&wp[((size_t)oc * cin_p + (ic < z1_n ? ic : ic - z1_n + 16)) * 9], &w1[((size_t)oc * s.f_in + ic) * 9], 9 * sizeof(float));
+        // conv1 over [z1 zero-padded to 16 | features] + the lane-order pack of conv2 (1x1) for its fused epilogue
+        WinoPart p1 = wino_part(s.c[0].wkey, 16 + cond, hid), p2 = wino_part(s.c[1].wkey, 64, 64);
+        p1.job.ld = s.f_in * 9; p1.job.z1_n = z1_n; p1.job.z1_pad = 16;
+        p2.job.frag1x1 = 1; p2.job.split = 0;
         const int sp[2] = {16, cond};
-        if (w1.size() == (size_t)hid * s.f_in * 9 && w2.size() == (size_t)hid * hid &&
-            pack_conv_weights_wino(wp.data(), cin_p, hid, sp, 2, pk, 16) && pack_conv_weights_1x1_frag(w2.data(), fr)) {
+        WinoRecipe r1 = wino_recipe({p1}, 16 + cond, hid, sp, 2, 16), r2 = wino_recipe({p2}, 64, 64, sp, 0, -1);
+        std::vector<float> pk, fr;
+        if (host_wino(r1, pk) && host_wino(r2, fr)) {
           s.c1w = s.c[0];
           s.c1w.src_n[0] = 16;
-          s.c1w.wpack_wino = upload(pk);
+          s.c1w.wpack_wino = keep_wino(r1, pk);
           s.c1w.tpacks.clear();
-          s.w4f_frag = upload(fr);
+          s.w4f_frag = keep_wino(r2, fr);
         }
       }
     } else {
@@ -220,17 +207,15 @@
         bool any = false;
         for (int i = 1; i < 5; ++i) {
           const int cin = s.f_in + i * hid, cin_p = npad + i * hid, cout = i < 4 ? hid : s.f_out, cout_t = cout <= 32 ? 32 : 64;
-          const std::vector<float>& w = params[f + ".conv" + std::to_string(i + 1) + ".weight"].data;
-          if (cin_p < 48 || !s.c[i].wpack16 || w.size() != (size_t)cout * cin * 9) continue;
-          std::vector<float> wp((size_t)cout_t * cin_p * 9, 0.f), pk;
-          for (int oc = 0; oc < cout; ++oc)
-            for (int ic = 0; ic < cin; ++ic)
-              memcpy(&wp[((size_t)oc * cin_p + (ic < z1_n ? ic : ic - z1_n + npad)) * 9], &w[((size_t)oc * cin + ic) * 9], 9 * sizeof(float));
+          if (cin_p < 48 || !s.c[i].wpack16) continue;
+          WinoPart pt = wino_part(s.c[i].wkey, cin_p, cout);            // conv i + 1 over [z1 zero-padded to npad | growth]
+          pt.job.ld = cin * 9; pt.job.z1_n = z1_n; pt.job.z1_pad = npad;
           const int sp[2] = {npad, i * hid};
-          if (!pack_conv_weights_wino(wp.data(), cin_p, cout_t, sp, 2, pk, 48)) continue;
+          WinoRecipe rw = wino_recipe({pt}, cin_p, cout_t, sp, 2, 48);
+          if (!run_wino(rw)) continue;
           s.cw[i] = s.c[i];
           s.cw[i].src_n[0] = npad;
-          s.cw[i].wpack_wino = upload(pk);
+          s.cw[i].wpack_wino = rw.pk;
           s.cw[i].wino_ntile = (cout == 32 || cout == 64) ? 0 : cout_t / 32;
           s.cw[i].tpacks.clear();
           any = true;
@@ -239,54 +224,17 @@
       }
     }
     if (spec_mode || rc != HCF_OK) return;
-    const int M = s.cmax;
-    std::vector<float> bias(M, 0.f), mi(M, 0.f), mf(M, 0.f);
-    double sumlogs = 0;
-    for (int c = 0; c < C; ++c) {
-      bias[c] = ab[c];
-      mi[c] = expf(-al[c]);
-      mf[c] = expf(al[c]);
-      sumlogs += (double)al[c];
+    // the step's tables (step_tables): one allocation each
+    std::vector<float> tab(step_scatter_n(s), 0.f);
+    if (!step_tables(s, ab, al, W, pl, ps, pu, tab.data())) { fail(HCF_ERR_ARG, "singular invertible-conv weight: " + p); return; }
+    const float* q = tab.data();
+    for (const auto& slot : step_table_slots(s)) {
+      *slot.first = upload(std::vector<float>(q, q + slot.second));
+      q += slot.second;
     }
-    s.bias = upload(bias);
-    s.mul_inv = upload(mi);
-    s.mul_fwd = upload(mf);
-    s.ld_const = sumlogs;
-    if (s.has_mat) {
-      std::vector<double> A((size_t)C * C), inv;
-      for (int i = 0; i < C * C; ++i) A[i] = (double)W[i];
-      double lad = 0;
-      if (!invert(A, C, inv, lad)) { fail(HCF_ERR_ARG, "singular invertible-conv weight: " + p); return; }
-      std::vector<float> wi((size_t)M * M, 0.f), wf((size_t)M * M, 0.f);
-      for (int r = 0; r < C; ++r)
-        for (int c = 0; c < C; ++c) {
-          wi[(size_t)r * M + c] = (float)inv[(size_t)r * C + c];    // inverse(W.double()).float(), Permutations.py:74
-          wf[(size_t)r * M + c] = W[(size_t)r * C + c];
-        }
-      s.mat_inv = upload(wi);
-      s.mat_fwd = upload(wf);
-      {
-        std::vector<float> wt((size_t)M * M, 0.f), it((size_t)C * C, 0.f), itp((size_t)M * M, 0.f);
-        for (int r = 0; r < C; ++r)
-          for (int c = 0; c < C; ++c) {
-            wt[(size_t)c * M + r] = W[(size_t)r * C + c];
-            it[(size_t)c * C + r] = (float)inv[(size_t)r * C + c];
-            itp[(size_t)c * M + r] = (float)inv[(size_t)r * C + c];
-          }
-        s.mat_fwdT = upload(wt);
-        s.winvT = upload(it);
-        s.mat_invT = upload(itp);
-      }
-      if (s.lu) {
-        lad = lu_sumlogs;                              // dlogdet = sum(log_s) * pixels (Permutations.py:84)
-        std::vector<float> pm(s_lu_p(s), s_lu_p(s) + (size_t)C * C);
-        s.lu_P = upload(pm);
-        s.lu_L = upload(lu_l);
-        s.lu_U = upload(lu_u);
-        s.lu_dw = upload(std::vector<float>((size_t)C * C, 0.f));
-      }
-      s.lad = lad;
-      s.ld_const += lad;
+    if (s.lu) {
+      s.lu_P = upload(std::vector<float>(s_lu_p(s), s_lu_p(s) + (size_t)C * C));
+      s.lu_dw = upload(std::vector<float>((size_t)C * C, 0.f));
     }
   }
   const float* s_lu_p(const Step& s) { return params[s.lu_pre + ".p"].data.data(); }
@@ -338,34 +286,27 @@
     if (spec_mode || rc != HCF_OK || !wino_enabled || no_fat || (gc != 32 && gc != 16) || (nf & 15) || nf < 32) return;
     for (int j = 0; j < 2 && rc == HCF_OK; ++j) {
       const std::string pa = p + ".conv" + std::to_string(2 * j + 1), pb = p + ".conv" + std::to_string(2 * j + 2);
-      auto wa = params.find(pa + ".weight"), wb = params.find(pb + ".weight");
-      auto ba = params.find(pa + ".bias"), bb = params.find(pb + ".bias");
-      if (wa == params.end() || wb == params.end() || ba == params.end() || bb == params.end()) return;
       const int ka = nf + 2 * j * gc, kb = ka + gc;            // input channels of the two convs
-      std::vector<float> wab((size_t)2 * gc * ka * 9), biasab(2 * gc, 0.f), wc((size_t)gc * gc * 9);
-      for (int oc = 0; oc < gc; ++oc) {
-        memcpy(&wab[(size_t)oc * ka * 9], &wa->second.data[(size_t)oc * ka * 9], sizeof(float) * ka * 9);
-        memcpy(&wab[(size_t)(gc + oc) * ka * 9], &wb->second.data[(size_t)oc * kb * 9], sizeof(float) * ka * 9);
-        memcpy(&wc[(size_t)oc * gc * 9], &wb->second.data[((size_t)oc * kb + ka) * 9], sizeof(float) * gc * 9);
-        biasab[oc] = ba->second.data[oc];
-      }
-      pack_conv(r.ca[j], wab.data(), biasab.data(), nullptr, ka, 2 * gc, 3, srcs2(nf, 2 * j * gc), ACT_LRELU);
+      const size_t nw = wino_recipes.size(), ne = epi_recipes.size();
+      // ca = [conv 2j+1 ; conv 2j+2's old-input columns] with the bias [bias of conv 2j+1 ; zeros (the raw partial)]
+      WinoPart a = wino_part(pa + ".weight", ka, 2 * gc);
+      a.key2 = pb + ".weight"; a.job.split = gc; a.job.ld = ka * 9; a.job.ld2 = kb * 9;
+      EpiRecipe ea = epi_recipe(pa + ".bias", "", 0);
+      ea.cout = gc;
+      pack_conv(r.ca[j], "", &a, ea, ka, 2 * gc, 3, srcs2(nf, 2 * j * gc), ACT_LRELU);
+      // cb = the completion: conv 2j+2's new-input columns, its bias
+      WinoPart b = wino_part(pb + ".weight", gc, gc);
+      b.woff = (size_t)ka * 9; b.job.ld = kb * 9;
       std::vector<int> s1(1, gc);
-      pack_conv(r.cb[j], wc.data(), bb->second.data.data(), nullptr, gc, gc, 3, s1, ACT_LRELU);
+      pack_conv(r.cb[j], "", &b, epi_recipe(pb + ".bias", "", 0), gc, gc, 3, s1, ACT_LRELU);
       if (rc == HCF_OK && !r.cb[j].wpack_wino) {         // 32 / 16 input channels: below the general Winograd threshold, wanted here
-        std::vector<float> pkw;
-        int one = gc;
-        if (gc == 32) {
-          if (pack_conv_weights_wino(wc.data(), gc, gc, &one, 1, pkw, 16)) r.cb[j].wpack_wino = upload(pkw);
-        } else {                                          // 16 -> 16 in a zero-padded 32-channel tile
-          std::vector<float> wp((size_t)32 * gc * 9, 0.f);
-          memcpy(wp.data(), wc.data(), wc.size() * sizeof(float));
-          if (pack_conv_weights_wino(wp.data(), gc, 32, &one, 1, pkw, 16)) { r.cb[j].wpack_wino = upload(pkw); r.cb[j].wino_ntile = 1; }
-        }
+        WinoRecipe w = wino_recipe({b}, gc, 32, &gc, 1, 16);        // (16 -> 16 in a zero-padded 32-channel tile)
+        if ((r.cb[j].wpack_wino = run_wino(w)) && gc != 32) r.cb[j].wino_ntile = 1;
       }
       r.ca[j].wkey = pa + ".weight+" + pb + ".weight[:, :" + std::to_string(ka) + "]";
       r.cb[j].wkey = pb + ".weight[:, " + std::to_string(ka) + ":]";
       r.fat[j] = rc == HCF_OK && r.ca[j].wpack_wino && r.cb[j].wpack_wino;
+      if (!r.fat[j]) { wino_recipes.resize(nw); epi_recipes.resize(ne); }       // a pair that is not run is not refreshed either
     }
   }
 
@@ -441,6 +382,7 @@
   void free_weights() {
     for (float* p : dev_allocs) hipFree(p);
     dev_allocs.clear();
+    direct_recipes.clear(); wino_recipes.clear(); epi_recipes.clear();      // (their packs are gone)
     ++refresh_gen;                           // the cached refresh job tables point into these allocations
     unit_dev = nullptr;
     weight_bytes = 0;

@@ -87,7 +87,7 @@
     ++launch_seq;
     int r = HCF_ERR_UNSUPPORTED;
     const bool w4f = fat && fat->w4f_frag && fuse2;    // Winograd conv1 + the 1x1 layer in its epilogue
-    if (use_f16 && cv.wpack_wino && (!fuse2 || w4f) && !tail && !wino_stale && !(g_f16x3_ablation & 256)) {
+    if (use_f16 && cv.wpack_wino && (!fuse2 || w4f) && !tail && !(g_f16x3_ablation & 256)) {
       a.ovf = ovf_flag;
       a.zeros = reinterpret_cast<const float*>(ovf_flag) + 16;
       if (w4f) { a.wf1x1 = fat->w4f_frag; a.bias2 = fuse2->bias; a.scale2 = fuse2->scale; a.act2 = fuse2->act; }
@@ -265,7 +265,7 @@
   // that cannot fall back per launch (fat dense-block pairs, the FCN form with the 1x1 epilogue) must know beforehand
   bool wino_offsets_ok(int H, int W, int cs) const { return (long long)B_ * H * W * cs * 4 < 0x7fffe000LL; }
   bool w4f_ok(const Step& s, const View* u, int H, int W, const Scratch& sc) const {
-    return s.fcn && s.w4f_frag && u && wino_offsets_ok(H, W, std::max(u->cs, 16)) && s.w4f_frag && s.cond > 0 && u && s.mode == CPL_AFFINE && can_fuse_fcn(s.c[0], s.c[1]) && !fat_stale && !wino_stale &&
+    return s.fcn && s.w4f_frag && u && wino_offsets_ok(H, W, std::max(u->cs, 16)) && s.w4f_frag && s.cond > 0 && u && s.mode == CPL_AFFINE && can_fuse_fcn(s.c[0], s.c[1]) &&
            !(g_f16x3_ablation & (256 | 512)) && u->up == 0 && sc.zpad.p && conv_wino_rounds_ok(B_, H, W, 2);
   }
 
@@ -297,7 +297,7 @@
       // DenseBlock: conv i >= 1 in Winograd form over [z1 padded | growth] where that form exists and this level qualifies
       bool need64 = false;
       for (int i = 1; i < 5; ++i) need64 = need64 || (s.cw[i].wpack_wino && (s.cw[i].wino_ntile == 2 || s.cw[i].cout == 64));
-      const bool dw = s.dw_pad > 0 && s.cond == 0 && use_f16 && !taping && !fat_stale && !wino_stale && !(g_f16x3_ablation & (256 | 1024)) &&
+      const bool dw = s.dw_pad > 0 && s.cond == 0 && use_f16 && !taping && !(g_f16x3_ablation & (256 | 1024)) &&
                       sc.zpadd.p && sc.zpadd.C >= s.dw_pad && conv_wino_rounds_ok(B_, H, W, 1) && (!need64 || conv_wino_rounds_ok(B_, H, W, 2)) &&
                       wino_offsets_ok(H, W, std::max(sc.grow.cs, sc.zpadd.cs));
       if (dw) HCF_LAUNCH(launch_copy_pad(z1, sc.zpadd.v(0, s.dw_pad), B_, H, W, st));
@@ -371,7 +371,6 @@
   }
 
   // ResidualDenseBlock (Basic.py:379-385) with optional second residual (RRDB tail, :394-398)
-  bool fat_stale = false;        // (never set since round 6: hcf_refresh_from_device rebuilds the fat packs too)
   bool tape_fat = false;         // the taped forward of a training pass takes the fat schedule as well (t_rdb; HCF_NO_TAPE_FAT: A/B knob)
   void run_rdb(const Rdb& r, View xin, const Buf& grow, int H, int W, View out, View res2, float rs2, const Buf* fatp = nullptr) {
     const int gc = cfg.rrdb_gc;
@@ -379,7 +378,7 @@
     // launches are short (the 64-channel kernel's fixed cost: 350 + 146 us against 199 + 267 at 16 x 320^2, 82 + 43 against
     // 61 + 79 at 16 x 160^2) -> up to 200 x 200 pixels per sample. The rule looks at the SAMPLE size, not at the batch: a sample's
     // bits must not depend on how many others share its launch (tests/test_gpu_nets.py: batch independence).
-    const bool fat_ok = fatp && fatp->p && use_f16 && (!taping || tape_fat) && !fat_stale && !wino_stale && !(g_f16x3_ablation & 256) &&
+    const bool fat_ok = fatp && fatp->p && use_f16 && (!taping || tape_fat) && !(g_f16x3_ablation & 256) &&
                         (gc == 16 || conv_wino_rounds_ok(B_, H, W, 2)) && conv_wino_rounds_ok(B_, H, W, 1) &&
                         wino_offsets_ok(H, W, std::max(std::max(xin.cs, grow.cs), fatp->cs));
     static const long long fat12_pixels = getenv("HCF_FAT12_PIXELS") ? atoll(getenv("HCF_FAT12_PIXELS")) : 40000;   // experiment knob

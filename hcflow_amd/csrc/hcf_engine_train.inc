@@ -13,6 +13,9 @@
 // Precision: hcf_set_precision(F16X3) puts the forward and the 3x3 data-gradient convs on the split kernels (the latter
 // with per-tensor power-of-two scaling: gradients of 1e-8 are below the split's absolute floor); the weight gradient
 // always runs on fp32 MFMA.
+// The data-gradient packs (make_tpacks, make_rdb_gather_packs) are recipes of hcf_engine_packs.inc like every other pack; the
+// device-side refresh (build_refresh_tables, refresh_from_device) only lays out the jobs those recipes give and the flow-step
+// tables of step_tables().
 
   struct TB { Buf v, g; };
   struct VG { View v, g; };
@@ -366,96 +369,55 @@
     const int nf = cfg.rrdb_nf, gc = cfg.rrdb_gc;
     r.gather = false;
     if (rdb_gather_off() || (nf & 15) || (gc & 15)) return;
-    for (int j = 0; j < 5; ++j) {
-      auto it = params.find(r.c[j].wkey);
-      if (it == params.end() || !it->second.set || it->second.data.size() != (size_t)(j < 4 ? gc : nf) * (nf + j * gc) * 9) return;
-    }
     for (int m = 0; m < 5 && rc == HCF_OK; ++m) {
       const int N = m == 0 ? nf : gc, nA = (4 - m) * gc, K = nA + nf, choff = m == 0 ? 0 : nf + (m - 1) * gc;
-      std::vector<float> wt((size_t)N * K * 9, 0.f);
-      int koff = 0;
-      for (int j = m; j < 5; ++j) {                    // r.c[j] = conv j + 1
-        const std::vector<float>& w = params[r.c[j].wkey].data;
-        const int cin = nf + j * gc, cout = j < 4 ? gc : nf;
-        for (int n = 0; n < N; ++n)
-          for (int oc = 0; oc < cout; ++oc)
-            for (int t = 0; t < 9; ++t)
-              wt[((size_t)n * K + koff + oc) * 9 + t] = w[((size_t)oc * cin + choff + n) * 9 + (8 - t)];
-        koff += cout;
-      }
-      Conv::TPack tp;
       int srcs[2] = {nA, nf};
       const int* sp = nA > 0 ? srcs : srcs + 1;
       const int ns = nA > 0 ? 2 : 1;
-      std::vector<float> pk, pk16;
-      pack_conv_weights(wt.data(), K, N, 9, sp, ns, pk, tp.nchunk, tp.npad);
-      tp.wpack = upload(pk);
-      tp.wpack16 = nullptr;
-      int nc = 0, np = 0;
-      if (pack_conv_weights_f16x3(wt.data(), K, N, 9, sp, ns, pk16, nc, np)) tp.wpack16 = upload(pk16);
+      DirectRecipe d = direct_recipe(K, N, 9, sp, ns);
+      WinoRecipe w = wino_recipe({}, K, N, sp, ns, -1);
+      int koff = 0;
+      for (int j = m; j < 5; ++j) {                    // r.c[j] = conv j + 1: its slice is input channels [koff, koff + cout) of the pack
+        const int cin = nf + j * gc, cout = j < 4 ? gc : nf;
+        DirectPart dp = direct_part(r.c[j].wkey, cin, 9, N, &cout, 1);
+        dp.k0 = koff; dp.job.transposed = 1; dp.job.off = choff;
+        d.parts.push_back(dp);
+        WinoPart wp = wino_part(r.c[j].wkey, K, N);
+        wp.job.tr = 1; wp.job.k0 = koff; wp.job.kn = cout; wp.job.tr_off = choff; wp.job.ld = cin * 9;
+        w.parts.push_back(wp);
+        koff += cout;
+      }
+      const std::vector<float> L = direct_logical(d);
+      if (rc != HCF_OK) return;
+      keep_direct(d, L.data(), true);
+      Conv::TPack tp;
+      tp.wpack = d.pk; tp.wpack16 = d.pk16; tp.nchunk = d.nchunk; tp.npad = d.npad;
       tp.src = 0; tp.c0 = 0; tp.n = N;
       r.gt[m] = tp;
       // the same logical weight in Winograd form (round 6): the gather conv of x_m has the shape of the forward conv 5 - m, and at
       // the 80 x 80 level of the training patches the Winograd kernels run it in 30-65 us where the direct scaled kernel takes 60-150
-      r.gtw[m] = nullptr;
-      std::vector<float> pkw;
-      if (!rdb_dgrad_wino_off() && pack_conv_weights_wino(wt.data(), K, N, sp, ns, pkw, -1) > 0) r.gtw[m] = upload(pkw);
+      r.gtw[m] = rdb_dgrad_wino_off() ? nullptr : run_wino(w);
     }
     r.gather = (rc == HCF_OK);
     if (r.gather) for (int j = 0; j < 5; ++j) r.c[j].tpacks.clear();      // (none are built for a gathered block)
   }
-  // device-side refresh of the gather packs: conv j's slice rewrites chunks [koff_j / 16, (koff_j + cout_j) / 16) of pack m
-  void add_rdb_gather_jobs(Rdb& r, std::vector<RepackArgs>& jobs) {
-    if (!r.gather || rc != HCF_OK) return;
-    const int nf = cfg.rrdb_nf, gc = cfg.rrdb_gc;
-    for (int m = 0; m < 5; ++m) {
-      const Conv::TPack& tp = r.gt[m];
-      const int N = m == 0 ? nf : gc, choff = m == 0 ? 0 : nf + (m - 1) * gc;
-      const size_t chunk_f = (size_t)9 * 2 * tp.npad * 8, chunk_h = (size_t)9 * 2 * 2 * tp.npad * 8;
-      int koff = 0;
-      for (int j = m; j < 5; ++j) {
-        const int cin = nf + j * gc, cout = j < 4 ? gc : nf;
-        const float* w = dsrc(r.c[j].wkey);
-        if (rc != HCF_OK) return;
-        RepackArgs t;
-        memset(&t, 0, sizeof(t));
-        t.w = w; t.cin_w = cin; t.taps = 9; t.transposed = 1; t.off = choff; t.cout = N;
-        t.srcs[0] = cout; t.nsrc = 1; t.nchunk = cout / 16; t.npad = tp.npad;
-        t.pk = tp.wpack + (size_t)(koff / 16) * chunk_f;
-        t.pk16 = tp.wpack16 ? reinterpret_cast<_Float16*>(tp.wpack16) + (size_t)(koff / 16) * chunk_h : nullptr;
-        jobs.push_back(t);
-        koff += cout;
-      }
-    }
-  }
 
   void make_tpacks(Conv& cv) {
     if (!cv.tpacks.empty() || cv.wkey.empty() || cv.gathered) return;
-    auto it = params.find(cv.wkey);
-    if (it == params.end() || !it->second.set) { fail(HCF_ERR_KEY, "training: missing " + cv.wkey); return; }
-    const float* w = it->second.data.data();
     int cin = 0;
     for (int i = 0; i < cv.nsrc; ++i) cin += cv.src_n[i];
-    const int taps = cv.taps, cout = cv.cout;
     int off = 0;
     for (int i = 0; i < cv.nsrc; ++i) {
-      for (int c0 = 0; c0 < cv.src_n[i]; c0 += 64) {
-        const int nb = std::min(64, cv.src_n[i] - c0);
-        std::vector<float> wt((size_t)nb * cout * taps);
-        for (int ic = 0; ic < nb; ++ic)
-          for (int oc = 0; oc < cout; ++oc)
-            for (int t = 0; t < taps; ++t)
-              wt[((size_t)ic * cout + oc) * taps + t] = w[((size_t)oc * cin + off + c0 + ic) * taps + (taps - 1 - t)];
+      for (int c0 = 0; c0 < cv.src_n[i] && rc == HCF_OK; c0 += 64) {       // the data gradient of input channels [off + c0, + nb): a conv over
+        const int nb = std::min(64, cv.src_n[i] - c0);                     // the cout gradient channels with w transposed and flipped
+        DirectRecipe d = direct_recipe(cv.cout, nb, cv.taps, &cv.cout, 1);
+        d.parts.push_back(direct_part(cv.wkey, cin, cv.taps, nb, &cv.cout, 1));
+        d.parts[0].job.transposed = 1; d.parts[0].job.off = off + c0;
+        const std::vector<float> L = direct_logical(d);
+        if (rc != HCF_OK) return;
+        keep_direct(d, L.data(), true);
         Conv::TPack tp;
-        std::vector<float> pk;
-        pack_conv_weights(wt.data(), cout, nb, taps, &cout, 1, pk, tp.nchunk, tp.npad);
-        tp.wpack = upload(pk);
-        tp.wpack16 = nullptr;
-        if (taps == 9 || taps == 1) {
-          std::vector<float> pk16;
-          int nc = 0, np = 0;
-          if (pack_conv_weights_f16x3(wt.data(), cout, nb, taps, &cout, 1, pk16, nc, np)) tp.wpack16 = upload(pk16);
-        }
+        tp.wpack = d.pk; tp.wpack16 = d.pk16; tp.nchunk = d.nchunk; tp.npad = d.npad;
         tp.src = i; tp.c0 = c0; tp.n = nb;
         cv.tpacks.push_back(tp);
       }
@@ -518,37 +480,6 @@
   } rt;
   unsigned refresh_gen = 0;                // bumped whenever a bound pointer or a destination table may have changed
 
-  void add_conv_jobs(Conv& cv, std::vector<RepackArgs>& jobs, std::vector<RepackEpiJob>& epi) {
-    if (rc != HCF_OK || cv.wkey.empty()) return;
-    const float* w = dsrc(cv.wkey);
-    const float* b = dsrc(cv.bkey);
-    const float* l = cv.lkey.empty() ? nullptr : dsrc(cv.lkey);
-    if (rc != HCF_OK) return;
-    int cin = 0;
-    for (int i = 0; i < cv.nsrc; ++i) cin += cv.src_n[i];
-    RepackArgs a;
-    memset(&a, 0, sizeof(a));
-    a.w = w; a.cin_w = cin; a.taps = cv.taps; a.cout = cv.cout;
-    for (int i = 0; i < cv.nsrc; ++i) a.srcs[i] = cv.src_n[i];
-    a.nsrc = cv.nsrc; a.nchunk = cv.nchunk; a.npad = cv.npad;
-    a.pk = cv.wpack; a.pk16 = reinterpret_cast<_Float16*>(cv.wpack16);
-    jobs.push_back(a);
-    for (const Conv::TPack& tp : cv.tpacks) {
-      int off = 0;
-      for (int i = 0; i < tp.src; ++i) off += cv.src_n[i];
-      RepackArgs t;
-      memset(&t, 0, sizeof(t));
-      t.w = w; t.cin_w = cin; t.taps = cv.taps; t.transposed = 1; t.off = off + tp.c0; t.cout = tp.n;
-      t.srcs[0] = cv.cout; t.nsrc = 1; t.nchunk = tp.nchunk; t.npad = tp.npad; t.pk = tp.wpack;
-      t.pk16 = reinterpret_cast<_Float16*>(tp.wpack16);
-      jobs.push_back(t);
-    }
-    RepackEpiJob e;
-    e.kind = cv.lkey.empty() ? 0 : (cv.l_mult == 1.f ? 1 : 2);
-    e.cout = cv.cout; e.b = b; e.l = l; e.bias = cv.bias; e.scale = cv.scale;
-    epi.push_back(e);
-  }
-
   std::vector<Step*> all_steps() {
     std::vector<Step*> steps;
     for (Level& lv : levels) {
@@ -561,28 +492,12 @@
   static size_t step_gather_n(const Step& s) {
     return 2 * (size_t)s.C + (s.lu ? 2 * (size_t)s.C * s.C + s.C : (s.has_mat ? (size_t)s.C * s.C : 0));
   }
-  static size_t step_scatter_n(const Step& s) {
-    return 3 * (size_t)s.cmax + (s.has_mat ? 4 * (size_t)s.cmax * s.cmax + (size_t)s.C * s.C : 0) + (s.lu ? 2 * (size_t)s.C * s.C : 0);
-  }
   int build_refresh_tables() {
     std::vector<RepackArgs> jobs;
     std::vector<RepackEpiJob> epi;
-    for_each_conv([&](Conv& c) { add_conv_jobs(c, jobs, epi); });
-    for_each_rdb([&](Rdb& r) { add_rdb_gather_jobs(r, jobs); });
-    for_each_rdb([&](Rdb& r) {                     // epilogue vectors of the fat pairs: ca = [bias of conv 2j+1 ; zeros (the raw partial)], cb = bias of conv 2j+2
-      for (int jj = 0; jj < 2 && rc == HCF_OK; ++jj) {
-        if (!r.fat[jj]) continue;
-        const float* ba = dsrc(r.c[2 * jj].bkey);
-        const float* bb = dsrc(r.c[2 * jj + 1].bkey);
-        if (rc != HCF_OK) return;
-        RepackEpiJob e;
-        e.kind = 0; e.cout = cfg.rrdb_gc; e.l = nullptr;
-        e.b = ba; e.bias = r.ca[jj].bias; e.scale = r.ca[jj].scale;
-        epi.push_back(e);
-        e.b = bb; e.bias = r.cb[jj].bias; e.scale = r.cb[jj].scale;
-        epi.push_back(e);
-      }
-    });
+    std::vector<RepackWinoJob> wj;
+    long long wino_blocks = 0;
+    recipe_jobs(jobs, epi, wj, wino_blocks);
     if (rc != HCF_OK) return rc;
     std::vector<long long> prefix(jobs.size() + 1, 0);
     for (size_t j = 0; j < jobs.size(); ++j)
@@ -599,110 +514,11 @@
                  o_scatter = o_gather + al(steps.size() * 5 * sizeof(CopyJob)), o_gbuf = o_scatter + al(steps.size() * 10 * sizeof(CopyJob)),
                  o_sbuf = o_gbuf + al(gn * sizeof(float)), total = o_sbuf + al(sn * sizeof(float));
     if (rt.blob) { hipStreamSynchronize(st); hipFree(rt.blob); if (rt.wino) hipFree(rt.wino); rt = RefreshTables(); }
-    {
-      std::vector<RepackWinoJob> wj;
-      long long nb = 0;
-      for_each_conv([&](Conv& c) {
-        if (!c.wpack_wino || c.wkey.empty() || rc != HCF_OK) return;
-        int cin = 0;
-        for (int i = 0; i < c.nsrc; ++i) cin += c.src_n[i];
-        const float* w = dsrc(c.wkey);
-        if (!w) return;
-        RepackWinoJob j;
-        memset(&j, 0, sizeof(j));
-        j.w = w; j.pk = c.wpack_wino; j.cin = cin; j.cout = c.cout; j.cout_tile = c.wino_ntile ? 32 * c.wino_ntile : c.cout; j.blk0 = nb;
-        j.split = c.cout;
-        nb += ((long long)cin * c.cout + 255) / 256;
-        wj.push_back(j);
-      });
-      if (rc != HCF_OK) return rc;
-      // The DERIVED Winograd packs (round 6: until now only hcf_finalize built them, and a device-side refresh switched their
-      // schedules off until the next finalize -- the validation passes of a training run, train_HCFlow.py:208-305, ran the slower
-      // per-conv form). Same arithmetic as the host packs: bit-identical to a freshly finalised engine.
-      auto push = [&](RepackWinoJob j) { j.blk0 = nb; nb += j.frag1x1 ? 16 : ((long long)(j.tr ? j.kn : j.cin) * j.cout + 255) / 256; wj.push_back(j); };
-      // (a) fat dense-block pairs: ca = [conv 2j+1 ; conv 2j+2's old-input columns], cb = conv 2j+2's new-input columns
-      for_each_rdb([&](Rdb& r) {
-        const int nf = cfg.rrdb_nf, gc = cfg.rrdb_gc;
-        for (int jj = 0; jj < 2 && rc == HCF_OK; ++jj) {
-          if (!r.fat[jj]) continue;
-          const float* wa = dsrc(r.c[2 * jj].wkey);
-          const float* wb = dsrc(r.c[2 * jj + 1].wkey);
-          if (rc != HCF_OK) return;
-          const int ka = nf + 2 * jj * gc, kb = ka + gc;
-          RepackWinoJob j;
-          memset(&j, 0, sizeof(j));
-          j.w = wa; j.w2 = wb; j.split = gc; j.ld = ka * 9; j.ld2 = kb * 9;
-          j.pk = r.ca[jj].wpack_wino; j.cin = ka; j.cout = 2 * gc; j.cout_tile = r.ca[jj].wino_ntile ? 32 * r.ca[jj].wino_ntile : 2 * gc;
-          push(j);
-          memset(&j, 0, sizeof(j));
-          j.w = wb + (size_t)ka * 9; j.ld = kb * 9; j.split = gc;
-          j.pk = r.cb[jj].wpack_wino; j.cin = gc; j.cout = gc; j.cout_tile = r.cb[jj].wino_ntile ? 32 * r.cb[jj].wino_ntile : gc;
-          push(j);
-        }
-      });
-      // (a') the gather-form data-gradient packs in Winograd form (Rdb::gtw): conv j's slice of pack m, transposed and flipped
-      for_each_rdb([&](Rdb& r) {
-        if (!r.gather || rc != HCF_OK) return;
-        const int nf = cfg.rrdb_nf, gc = cfg.rrdb_gc;
-        for (int m = 0; m < 5; ++m) {
-          if (!r.gtw[m]) continue;
-          const int N = m == 0 ? nf : gc, K = (4 - m) * gc + nf, choff = m == 0 ? 0 : nf + (m - 1) * gc;
-          int koff = 0;
-          for (int jj = m; jj < 5; ++jj) {
-            const int cin = nf + jj * gc, cout = jj < 4 ? gc : nf;
-            const float* w = dsrc(r.c[jj].wkey);
-            if (rc != HCF_OK) return;
-            RepackWinoJob j;
-            memset(&j, 0, sizeof(j));
-            j.w = w; j.pk = r.gtw[m]; j.cin = K; j.cout = N; j.cout_tile = N; j.split = N;
-            j.tr = 1; j.k0 = koff; j.kn = cout; j.tr_off = choff; j.ld = cin * 9;
-            push(j);
-            koff += cout;
-          }
-        }
-      });
-      // (b) conditional FCN conv1 over [z1 padded to 16 | features] + the lane-order pack of conv2 (1x1) of its fused epilogue;
-      // (c) DenseBlock convs of the rescaling nets over [z1 padded | growth]
-      for (Step* sp : all_steps()) {
-        Step& s = *sp;
-        if (rc != HCF_OK) break;
-        if (s.fcn && s.w4f_frag && s.c1w.wpack_wino) {
-          const float* w1 = dsrc(s.c[0].wkey);
-          const float* w2 = dsrc(s.c[1].wkey);
-          if (rc != HCF_OK) break;
-          RepackWinoJob j;
-          memset(&j, 0, sizeof(j));
-          const int z1n = s.c[0].src_n[0], cond = s.f_in - z1n;
-          j.w = w1; j.ld = s.f_in * 9; j.z1_n = z1n; j.z1_pad = 16; j.cin = 16 + cond; j.cout = s.c[0].cout; j.cout_tile = s.c[0].cout;
-          j.split = j.cout; j.pk = s.c1w.wpack_wino;
-          push(j);
-          memset(&j, 0, sizeof(j));
-          j.w = w2; j.pk = s.w4f_frag; j.frag1x1 = 1; j.cin = 64; j.cout = 64; j.cout_tile = 64;
-          push(j);
-        }
-        if (!s.fcn && s.dw_pad > 0) {
-          for (int i = 1; i < 5; ++i) {
-            if (!s.cw[i].wpack_wino) continue;
-            const float* w = dsrc(s.c[i].wkey);
-            if (rc != HCF_OK) break;
-            int cin = 0;
-            for (int k = 0; k < s.c[i].nsrc; ++k) cin += s.c[i].src_n[k];
-            const int z1n = s.c[i].src_n[0];
-            RepackWinoJob j;
-            memset(&j, 0, sizeof(j));
-            j.w = w; j.ld = cin * 9; j.z1_n = z1n; j.z1_pad = s.dw_pad; j.cin = cin - z1n + s.dw_pad; j.cout = s.c[i].cout;
-            j.cout_tile = s.c[i].cout <= 32 ? 32 : 64; j.split = j.cout; j.pk = s.cw[i].wpack_wino;
-            push(j);
-          }
-        }
-      }
-      if (rc != HCF_OK) return rc;
-      if (!wj.empty()) {
-        RepackWinoJob* d = nullptr;
-        if (hipMalloc((void**)&d, wj.size() * sizeof(RepackWinoJob)) != hipSuccess) return fail(HCF_ERR_NOMEM, "hipMalloc failed for the Winograd refresh table");
-        if (hipMemcpy(d, wj.data(), wj.size() * sizeof(RepackWinoJob), hipMemcpyHostToDevice) != hipSuccess) { hipFree(d); return fail(HCF_ERR_HIP, "refresh tables: H2D copy failed"); }
-        rt.wino = d; rt.nwino = (int)wj.size(); rt.wino_blocks = nb;
-      }
+    if (!wj.empty()) {
+      RepackWinoJob* d = nullptr;
+      if (hipMalloc((void**)&d, wj.size() * sizeof(RepackWinoJob)) != hipSuccess) return fail(HCF_ERR_NOMEM, "hipMalloc failed for the Winograd refresh table");
+      if (hipMemcpy(d, wj.data(), wj.size() * sizeof(RepackWinoJob), hipMemcpyHostToDevice) != hipSuccess) { hipFree(d); return fail(HCF_ERR_HIP, "refresh tables: H2D copy failed"); }
+      rt.wino = d; rt.nwino = (int)wj.size(); rt.wino_blocks = wino_blocks;
     }
     char* blob = nullptr;
     if (hipMalloc(&blob, total) != hipSuccess) return fail(HCF_ERR_NOMEM, "hipMalloc failed for the refresh tables");
@@ -713,7 +529,7 @@
     rt.gather_buf = reinterpret_cast<float*>(blob + o_gbuf); rt.scatter_buf = reinterpret_cast<float*>(blob + o_sbuf);
     size_t o = 0, q = 0;
     for (Step* s : steps) {
-      const int C = s->C, M = s->cmax;
+      const int C = s->C;
       const float* b = dsrc(s->an_key + ".bias");
       const float* l = dsrc(s->an_key + ".logs");
       const float* W = (s->has_mat && !s->lu) ? dsrc(s->wkey) : nullptr;
@@ -729,25 +545,9 @@
         gather.push_back({ls, rt.gather_buf + o + 2 * C + 2 * (size_t)C * C, C});
       }
       o += step_gather_n(*s);
-      const float* sb = rt.scatter_buf + q;
-      scatter.push_back({sb, s->bias, M});
-      scatter.push_back({sb + M, s->mul_inv, M});
-      scatter.push_back({sb + 2 * M, s->mul_fwd, M});
-      q += 3 * (size_t)M;
-      if (s->has_mat) {
-        const float* m = rt.scatter_buf + q;
-        const int MM = M * M;
-        scatter.push_back({m, s->mat_inv, MM});
-        scatter.push_back({m + MM, s->mat_fwd, MM});
-        scatter.push_back({m + 2 * (size_t)MM, s->mat_fwdT, MM});
-        scatter.push_back({m + 3 * (size_t)MM, s->winvT, C * C});
-        scatter.push_back({m + 3 * (size_t)MM + (size_t)C * C, s->mat_invT, MM});
-        q += 4 * (size_t)MM + (size_t)C * C;
-        if (s->lu) {
-          scatter.push_back({rt.scatter_buf + q, s->lu_L, C * C});
-          scatter.push_back({rt.scatter_buf + q + (size_t)C * C, s->lu_U, C * C});
-          q += 2 * (size_t)C * C;
-        }
+      for (const auto& slot : step_table_slots(*s)) {
+        scatter.push_back({rt.scatter_buf + q, *slot.first, (int)slot.second});
+        q += slot.second;
       }
     }
     bool ok = hipMemcpy(rt.jobs, jobs.data(), jobs.size() * sizeof(RepackArgs), hipMemcpyHostToDevice) == hipSuccess &&
@@ -789,56 +589,26 @@
     o = 0;
     size_t q = 0;
     for (Step* s : steps) {
-      const int C = s->C, M = s->cmax;
+      const int C = s->C;
       const float* b = &in[o];
       const float* l = &in[o + C];
       const float* W = (s->has_mat && !s->lu) ? &in[o + 2 * C] : nullptr;
-      std::vector<float> lu_w, lu_l, lu_u;
-      double lu_sumlogs = 0;
+      const float *ll = nullptr, *uu = nullptr, *ls = nullptr;
       if (s->lu) {
-        const float* ll = &in[o + 2 * C];
-        const float* uu = ll + (size_t)C * C;
-        const float* ls = uu + (size_t)C * C;
+        ll = &in[o + 2 * C];
+        uu = ll + (size_t)C * C;
+        ls = uu + (size_t)C * C;
         memcpy(params[s->lu_pre + ".l"].data.data(), ll, sizeof(float) * C * C);
         memcpy(params[s->lu_pre + ".u"].data.data(), uu, sizeof(float) * C * C);
         memcpy(params[s->lu_pre + ".log_s"].data.data(), ls, sizeof(float) * C);
-        compose_lu(ll, ls, uu, s_lu_p(*s), params[s->lu_pre + ".sign_s"].data.data(), C, lu_w, lu_l, lu_u, lu_sumlogs);
-        W = lu_w.data();
       }
       o += step_gather_n(*s);
-      float* bias = &refresh_stage[q]; float* mi = bias + M; float* mf = mi + M;
-      q += 3 * (size_t)M;
-      double sumlogs = 0;
-      for (int c = 0; c < C; ++c) { bias[c] = b[c]; mi[c] = expf(-l[c]); mf[c] = expf(l[c]); sumlogs += (double)l[c]; }
       memcpy(params[s->an_key + ".bias"].data.data(), b, sizeof(float) * C);
       memcpy(params[s->an_key + ".logs"].data.data(), l, sizeof(float) * C);
-      s->lad = 0;
-      if (W) {
-        if (!s->lu) memcpy(params[s->wkey].data.data(), W, sizeof(float) * C * C);
-        std::vector<double> A((size_t)C * C), inv;
-        for (int i = 0; i < C * C; ++i) A[i] = (double)W[i];
-        double lad = 0;
-        if (!invert(A, C, inv, lad)) return fail(HCF_ERR_ARG, "singular invertible-conv weight after update: " + s->lu_pre);
-        float* wi = &refresh_stage[q]; float* wf = wi + (size_t)M * M; float* wt = wf + (size_t)M * M; float* it = wt + (size_t)M * M;
-        float* itp = it + (size_t)C * C;
-        q += 4 * (size_t)M * M + (size_t)C * C;
-        for (int r = 0; r < C; ++r)
-          for (int c = 0; c < C; ++c) {
-            wi[(size_t)r * M + c] = (float)inv[(size_t)r * C + c];
-            wf[(size_t)r * M + c] = W[(size_t)r * C + c];
-            wt[(size_t)c * M + r] = W[(size_t)r * C + c];
-            it[(size_t)c * C + r] = (float)inv[(size_t)r * C + c];
-            itp[(size_t)c * M + r] = (float)inv[(size_t)r * C + c];
-          }
-        if (s->lu) {
-          lad = lu_sumlogs;
-          memcpy(&refresh_stage[q], lu_l.data(), sizeof(float) * C * C);
-          memcpy(&refresh_stage[q + (size_t)C * C], lu_u.data(), sizeof(float) * C * C);
-          q += 2 * (size_t)C * C;
-        }
-        s->lad = lad;
-      }
-      s->ld_const = sumlogs + s->lad;
+      if (W) memcpy(params[s->wkey].data.data(), W, sizeof(float) * C * C);
+      if (!step_tables(*s, b, l, W, ll, ls, uu, &refresh_stage[q]))
+        return fail(HCF_ERR_ARG, "singular invertible-conv weight after update: " + s->lu_pre);
+      q += step_scatter_n(*s);
     }
     // one upload of all derived tables (same layout as the scatter jobs), then one scatter launch
     if (q != rt.scatter_n || o != rt.gather_n) return fail(HCF_ERR_STATE, "internal: refresh table layout");
@@ -847,7 +617,6 @@
     HCF_LAUNCH(launch_copy_jobs(rt.scatter, rt.nscatter, st));
     host_stale = true;
     cc_valid = false;
-    fat_stale = false;             // (round 6: the fat / padded-z1 packs are rebuilt by the same launch as every other Winograd pack)
     return rc;
   }
 

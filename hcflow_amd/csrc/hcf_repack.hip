@@ -2,16 +2,9 @@
 // 8f rank 2 "repack cache ... device-side repack"). Rewrites the conv packs of hcf_conv.hip / hcf_conv_f16x3.hip and
 // the epilogue tables straight from the PyTorch-layout parameter tensors in device memory.
 #include "hcf_common.h"
+#include "hcf_pack_index.h"      // logical_weight: the index mapping, shared with the host execution of the same jobs
 
 namespace hcf {
-
-// logical weight L[n][ci][t]:
-//   forward packs     L = w[n][ci][t]                          (w: [cout][cin][taps])
-//   transposed packs  L = w[ci][off + n][taps - 1 - t]         (data gradient of channel block [off, off + nb))
-__device__ __forceinline__ float logical_weight(const RepackArgs& a, int n, int ci, int t) {
-  if (!a.transposed) return a.w[((size_t)n * a.cin_w + ci) * a.taps + t];
-  return a.w[((size_t)ci * a.cin_w + a.off + n) * a.taps + (a.taps - 1 - t)];
-}
 
 // one thread per (chunk, tap, n, e in 0..15) of one pack
 __device__ __forceinline__ void repack_one(const RepackArgs& a, long long i) {

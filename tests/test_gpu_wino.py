@@ -341,3 +341,73 @@ def test_in_place_updates_of_a_rescaling_net_keep_its_winograd_schedules():
         assert mix(ref) == after
     for x, y in zip(a, b):
         assert maxdiff(x, y) <= 2e-5 * max(1.0, float(y.abs().max()))
+
+
+@pytest.mark.parametrize("name", ["SR_4X_tiny", "Rescaling_4X_tiny"])
+def test_device_refresh_reproduces_the_finalised_engine_bit_for_bit(name):
+    """Every derived pack and flow-step table has ONE description, executed on the host by hcf_finalize and as device jobs by
+    hcf_refresh_from_device. With every `logs` tensor at zero (exp(0) is exactly 1 under libm and on the GPU: the one documented
+    host / device difference is absent) a refresh that changes no value must leave the outputs of both precisions bit-identical,
+    on the fat / fused-FCN schedules of the SR net (kinds 7 / 6) and the padded-z1 / fat schedules of the rescaling net (4 / 7)."""
+    from hcflow_amd import HCFlowNet_Rescaling
+    from hcflow_amd.config import eps_shapes, preset
+    from tests.test_gpu_backward import _fresh_sr
+    from tests.util import cached_params
+    sr = name == "SR_4X_tiny"
+    g = torch.Generator().manual_seed(29)
+    if sr:
+        cfg, net = _fresh_sr(name, 11)
+        lr = torch.rand(2, 3, 40, 40, generator=g).cuda()
+        eps = [torch.randn(s, generator=g).cuda() * 0.8 for s in eps_shapes(cfg, 2, 40, 40)]
+        kinds = (7, 6)
+
+        def run(n):
+            return (n.reverse_flow_diracLR(lr, None, None, eps_std=0.8, eps=eps, clamp=False),)
+    else:
+        cfg = preset(name)
+        net = HCFlowNet_Rescaling(opt=cfg.to_opt(), step=0)
+        net.load_state_dict(cached_params(name, 13), strict=True)
+        for m in net.modules():
+            if "ActNorm" in type(m).__name__:
+                m.inited = True
+        net = net.to("cuda:0")
+        hr = torch.rand(2, 3, 96, 128, generator=g).cuda()
+        kinds = (4, 7)
+
+        def run(n):
+            lr_hat = n(hr=hr, reverse=False)[0]
+            lrq = (torch.clamp(lr_hat, 0, 1) * 255.).round() / 255.
+            return lr_hat, n(lr=lrq, eps_std=0.0, reverse=True)
+    net.eval()
+
+    def both(n):
+        out = {}
+        for prec in ("exact", "f16x3"):
+            n.set_precision(prec)
+            out[prec] = [x.clone() for x in run(n)]
+        e = n.engine()                                   # (f16x3 is still set: the launch mix of the derived packs)
+        e.profile_convs(True)
+        run(n)
+        mix = tuple(e.conv_time(9, 0, kind=k)[1] for k in kinds)
+        e.conv_time(9, 0, kind=kinds[0], reset=True)
+        e.profile_convs(False)
+        return out, mix
+    try:
+        with torch.no_grad():
+            for key, p in net.named_parameters():
+                if key.endswith(".logs"):
+                    p.zero_()
+            a, mix_a = both(net)                         # host path (hcf_finalize), binds pointers
+            for p in net.parameters():
+                if p.requires_grad:
+                    p.mul_(1.0)                          # only _version moves -> hcf_refresh_from_device
+            b, mix_b = both(net)
+        assert net._engines[0]["ptrs"] is not None       # (the device-side path, not a host re-finalise)
+        assert min(mix_a) > 0 and mix_a == mix_b, (mix_a, mix_b)
+        for prec in ("exact", "f16x3"):
+            for x, y in zip(a[prec], b[prec]):
+                print(name, prec, "max|refreshed - finalised| =", float((x - y).abs().max()), "|ref|max =", float(x.abs().max()))
+                assert torch.isfinite(x).all()
+                assert torch.equal(x, y), (name, prec)
+    finally:
+        net.set_precision("exact")
