@@ -40,6 +40,8 @@ SYMBOLS = [
     "hcf_op_step_forward_backward", "hcf_op_step_inverse_backward", "hcf_op_prior_backward", "hcf_op_quant_logp_backward",
     "hcf_op_output_grad_backward", "hcf_op_conv_epilogue_backward", "hcf_op_lu_chain",
     "hcf_train_backward_inverse_ex", "hcf_train_backward_counts", "hcf_op_prior_sample_backward",
+    "hcf_aux_input_norm", "hcf_aux_input_norm_backward", "hcf_aux_maxpool2", "hcf_aux_maxpool2_act_backward",
+    "hcf_aux_act_backward", "hcf_aux_feature_loss_workspace", "hcf_aux_feature_loss",
 ]
 
 
@@ -128,6 +130,14 @@ def load() -> C.CDLL:
                                    i32, fp, i32, fp, fp, vp, C.c_size_t, vp]
     lib.hcf_aux_bn_act_backward.argtypes = [fp, i32, i32, i32, i32, i32, i32, i32, i32, i32, fp, fp, fp, fp, i32, i32, fp, i32, fp,
                                             i32, fp, fp, vp, C.c_size_t, vp]
+    lib.hcf_aux_input_norm.argtypes = [fp, fp, fp, i32, i32, i32, fp, vp]
+    lib.hcf_aux_input_norm_backward.argtypes = [fp, fp, i32, i32, i32, fp, vp]
+    lib.hcf_aux_maxpool2.argtypes = [fp, i32, i32, i32, i32, i32, fp, i32, vp]
+    lib.hcf_aux_maxpool2_act_backward.argtypes = [fp, i32, fp, i32, i32, i32, i32, i32, i32, fp, i32, vp]
+    lib.hcf_aux_act_backward.argtypes = [fp, fp, i32, i64, fp, vp]
+    lib.hcf_aux_feature_loss_workspace.argtypes = [i64]
+    lib.hcf_aux_feature_loss_workspace.restype = C.c_size_t
+    lib.hcf_aux_feature_loss.argtypes = [fp, fp, i64, i32, fp, fp, vp, C.c_size_t, vp]
     lib.hcf_lpips_workspace.argtypes = [i32, i32, i32]
     lib.hcf_lpips_workspace.restype = C.c_size_t
     lib.hcf_lpips_alex.argtypes = [fp, fp, i32, i32, i32, i32, C.POINTER(fp), fp, fp, vp, C.c_size_t, vp]
@@ -165,7 +175,7 @@ def load() -> C.CDLL:
         fn = getattr(lib, name)
         if name not in ("hcf_destroy", "hcf_last_error", "hcf_workspace_bytes", "hcf_weight_bytes",
                         "hcf_fallback_count", "hcf_debug_last_clock_mhz", "hcf_aux_conv2d_workspace", "hcf_lpips_workspace",
-                        "hcf_aux_bn_act_workspace"):
+                        "hcf_aux_bn_act_workspace", "hcf_aux_feature_loss_workspace"):
             fn.restype = C.c_int
     _lib = lib
     return lib

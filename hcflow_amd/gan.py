@@ -20,7 +20,11 @@ f16x3 / Winograd forward, fp32-MFMA data gradient, fixed-order weight gradient):
   eval(), the module's own buffers updated on the device); PatchGAN's padding-0 convs are the interior window of the
   same-padded conv, which those kernels read (forward) and zero-border (backward);
 * in ``Discriminator_VGG_160`` and ``VGGFeatureExtractor``, BatchNorm stays on stock PyTorch ops; the Linear layers,
-  max-pooling and the losses are a few elementwise / reduction ops per layer and stay on stock PyTorch ops everywhere.
+  max-pooling and the losses are a few elementwise / reduction ops per layer and stay on stock PyTorch ops in these modules;
+* ``PerceptualLoss`` is the generator step's whole feature loss ``cri_fea(netF(fake_H), netF(real_H).detach())`` as one autograd
+  node: netF's convs, with input normalisation, max-pooling, the fused max-pool + ReLU backward and the L1 / MSE criterion on the
+  kernels of ``hcf_vgg.hip`` (``hcf_aux_input_norm``, ``hcf_aux_maxpool2``, ``hcf_aux_maxpool2_act_backward``,
+  ``hcf_aux_act_backward``, ``hcf_aux_feature_loss``).
 
 ``VGGFeatureExtractor`` needs torchvision's pretrained VGG19 weights, which cannot be downloaded here: the layer stack is
 rebuilt from the VGG19 configuration with the same ``features.N`` keys, so a torchvision ``vgg19().features`` state dict loads
@@ -463,3 +467,180 @@ class PatchGANDiscriminator(_AuxNet):
             raise ValueError("PatchGANDiscriminator(n_layers=%d): its %d padding-0 3x3 convs need an input larger than %d x %d, "
                              "got %s" % (self.n_layers, self.n_layers + 2, shrink, shrink, tuple(x.shape)))
         return self._run(self._body, x)
+
+
+_CRITERIA = {"l1": 0, "l2": 1, "mse": 1}                    # feature_criterion of the recipes (HCFlow_SR_model.py:62-66)
+
+
+def _vgg_plan(netF):
+    """VGGFeatureExtractor.features as [(conv, act, pooled)]: each conv with its fused ReLU (act 1) and whether a MaxPool2d follows."""
+    mods, plan, i = list(netF.features), [], 0
+    while i < len(mods):
+        m = mods[i]
+        if isinstance(m, nn.BatchNorm2d):
+            raise ValueError("PerceptualLoss: use_bn=True (BatchNorm VGG) has no fused path here; networks.define_F builds "
+                             "VGGFeatureExtractor(use_bn=False)")
+        if not isinstance(m, nn.Conv2d):
+            raise ValueError("PerceptualLoss: unexpected %s at features.%d" % (type(m).__name__, i))
+        act = 1 if i + 1 < len(mods) and isinstance(mods[i + 1], nn.ReLU) else 0
+        i += 1 + act
+        pooled = i < len(mods) and isinstance(mods[i], nn.MaxPool2d)
+        i += int(pooled)
+        plan.append((m, act, pooled))
+    if not plan or plan[-1][2]:
+        raise ValueError("PerceptualLoss: feature_layer must end on a conv or a ReLU (a trailing MaxPool2d is not supported)")
+    return plan
+
+
+class _PerceptualLossFn(torch.autograd.Function):
+    """cri_fea(netF(fake), netF(real).detach()) as ONE node: convs through hcf_aux_conv2d / hcf_aux_conv2d_backward (dw = NULL,
+    VGG is frozen), everything between them through the kernels of hcf_vgg.hip. The real pass keeps nothing; the fake pass keeps
+    each conv's input and post-activation output; the loss kernel leaves dloss/dfeature, which backward scales and walks down."""
+
+    @staticmethod
+    def _pass(lib, netF, plan, x, prec, flags, keep):
+        B, _, H, W = x.shape
+        dev = x.device
+        st = torch.cuda.current_stream(dev).cuda_stream
+        stream = C.c_void_p(st)
+        y = torch.empty(B, H, W, 4, device=dev, dtype=torch.float32)
+        norm = netF.use_input_norm
+        rc = lib.hcf_aux_input_norm(x.data_ptr(), netF.mean.data_ptr() if norm else None, netF.std.data_ptr() if norm else None,
+                                    B, H, W, y.data_ptr(), stream)
+        _lib.check(rc, None, "hcf_aux_input_norm")
+        tape = []
+        for conv, act, pooled in plan:
+            cout, cin = conv.out_channels, conv.in_channels
+            w, b = conv.weight.contiguous(), conv.bias
+            z = torch.empty(B, H, W, cout, device=dev, dtype=torch.float32)       # VGG19 widths are multiples of 4
+            need = lib.hcf_aux_conv2d_workspace(cin, cout, 3, B, H, W)
+            key = (dev.index, st, cin, cout, 3, B, H, W)                           # _ConvNHWC's key: the two paths share workspaces
+            wk = netF._work.get(key)
+            if wk is None or wk.numel() < need or wk.device != dev:
+                wk = torch.zeros(need, dtype=torch.uint8, device=dev)
+                netF._work[key] = wk
+            flags.append(wk)
+            rc = lib.hcf_aux_conv2d(y.data_ptr(), y.shape[3], cin, B, H, W, w.data_ptr(), None if b is None else b.contiguous().data_ptr(),
+                                    cout, 3, act, z.data_ptr(), cout, C.c_void_p(wk.data_ptr()), wk.numel(), prec, stream)
+            _lib.check(rc, None, "hcf_aux_conv2d")
+            if keep:
+                tape.append((y, z if (act or pooled) else None, w, wk))
+            y = z
+            if pooled:
+                if H < 2 or W < 2:
+                    raise ValueError("PerceptualLoss: the input is too small for the %d max-pools of this feature_layer"
+                                     % sum(p for _, _, p in plan))
+                p = torch.empty(B, H // 2, W // 2, cout, device=dev, dtype=torch.float32)
+                rc = lib.hcf_aux_maxpool2(y.data_ptr(), cout, cout, B, H, W, p.data_ptr(), cout, stream)
+                _lib.check(rc, None, "hcf_aux_maxpool2")
+                y, H, W = p, H // 2, W // 2
+        return y, tape
+
+    @staticmethod
+    def forward(ctx, fake, real, netF, plan, kind):
+        lib = _lib.load()
+        need_grad = ctx.needs_input_grad[0]
+        xf, xr = fake.detach().to(torch.float32).contiguous(), real.detach().to(torch.float32).contiguous()
+        prec = _PREC[netF._prec[0]]
+        with torch.cuda.device(fake.device):
+            stream = C.c_void_p(torch.cuda.current_stream(fake.device).cuda_stream)
+            while True:
+                flags = []
+                fr, _ = _PerceptualLossFn._pass(lib, netF, plan, xr, prec, flags, False)
+                ff, tape = _PerceptualLossFn._pass(lib, netF, plan, xf, prec, flags, need_grad)
+                if prec != 1:
+                    break
+                uniq = list({id(f): f for f in flags}.values())
+                if not bool(torch.stack([f[:4].view(torch.int32)[0] for f in uniq]).any()):    # the one sync of an f16x3 call
+                    break
+                for f in uniq:                                # an activation left the f16 range: redo both passes exactly
+                    f[:4].zero_()
+                prec = 0
+            n = ff.numel()
+            need = lib.hcf_aux_feature_loss_workspace(n)
+            key = ("fea", fake.device.index, stream.value)
+            wk = netF._work.get(key)
+            if wk is None or wk.numel() < need:
+                wk = torch.empty(need, dtype=torch.uint8, device=fake.device)
+                netF._work[key] = wk
+            loss = torch.empty((), device=fake.device, dtype=torch.float32)
+            gfea = torch.empty_like(ff) if need_grad else None
+            rc = lib.hcf_aux_feature_loss(ff.data_ptr(), fr.data_ptr(), n, kind, loss.data_ptr(),
+                                          None if gfea is None else gfea.data_ptr(), C.c_void_p(wk.data_ptr()), wk.numel(), stream)
+            _lib.check(rc, None, "hcf_aux_feature_loss")
+        ctx.tape, ctx.gfea, ctx.plan, ctx.netF = tape, gfea, plan, netF
+        ctx.in_meta = (tuple(fake.shape), fake.dtype)
+        return loss
+
+    @staticmethod
+    def backward(ctx, gout):
+        lib = _lib.load()
+        plan, netF = ctx.plan, ctx.netF
+        (B, _, H0, W0), dtype = ctx.in_meta
+        g = ctx.gfea * gout                                    # a fresh tensor: the in-place activation backward below owns it
+        dev = g.device
+        with torch.cuda.device(dev):
+            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            for (conv, act, pooled), (x, y, w, wk) in zip(reversed(plan), reversed(ctx.tape)):
+                _, H, W, cs = x.shape
+                cout, cin = conv.out_channels, conv.in_channels
+                if pooled:
+                    gpre = torch.empty(B, H, W, cout, device=dev, dtype=torch.float32)
+                    rc = lib.hcf_aux_maxpool2_act_backward(g.data_ptr(), cout, y.data_ptr(), cout, cout, B, H, W, act, gpre.data_ptr(),
+                                                           cout, stream)
+                    _lib.check(rc, None, "hcf_aux_maxpool2_act_backward")
+                    g = gpre
+                elif act:
+                    rc = lib.hcf_aux_act_backward(g.data_ptr(), y.data_ptr(), act, g.numel(), g.data_ptr(), stream)
+                    _lib.check(rc, None, "hcf_aux_act_backward")
+                dx = torch.empty_like(x)                       # channels [0, cin) written; the 4th channel of the image layer is never read
+                rc = lib.hcf_aux_conv2d_backward(x.data_ptr(), cs, cin, B, H, W, w.data_ptr(), cout, 3, g.data_ptr(), cout,
+                                                 dx.data_ptr(), cs, None, C.c_void_p(wk.data_ptr()), wk.numel(), 0, stream)
+                _lib.check(rc, None, "hcf_aux_conv2d_backward")
+                g = dx
+            gx = torch.empty(B, 3, H0, W0, device=dev, dtype=torch.float32)
+            rc = lib.hcf_aux_input_norm_backward(g.data_ptr(), netF.std.data_ptr() if netF.use_input_norm else None, B, H0, W0,
+                                                 gx.data_ptr(), stream)
+            _lib.check(rc, None, "hcf_aux_input_norm_backward")
+        return gx.to(dtype), None, None, None, None
+
+
+class PerceptualLoss(nn.Module):
+    """The feature loss of the HCFlow++ generator step (HCFlow_SR_model.py:229-232, HCFlow_Rescaling_model.py:237-240) as one call:
+
+        cri = PerceptualLoss(netF, criterion="l1")           # netF: VGGFeatureExtractor, or nn.DataParallel around one
+        l_g_fea = l_fea_w * cri(fake_H, real_H)              # == cri_fea(netF(fake_H), netF(real_H).detach())
+
+    ``criterion``: the recipe's ``feature_criterion``, "l1" or "l2" ("mse"). Only ``fake_H`` receives a gradient. The convs are
+    netF's own (``hcf_aux_conv2d`` at netF's ``set_precision``, ``hcf_aux_conv2d_backward`` without the weight gradient); input
+    normalisation, max-pooling, the ReLU / max-pool backward and the criterion run on the kernels of ``hcf_vgg.hip``. Supports
+    ``use_bn=False`` stacks whose ``feature_layer`` ends on a conv or a ReLU, ``use_input_norm`` either way. No CPU fallback."""
+
+    def __init__(self, netF, criterion: str = "l1"):
+        super().__init__()
+        if isinstance(netF, (nn.DataParallel, nn.parallel.DistributedDataParallel)):
+            netF = netF.module                                # the loss runs on the device of its inputs, keyed workspaces per device
+        if not isinstance(netF, VGGFeatureExtractor):
+            raise TypeError("PerceptualLoss: netF must be a hcflow_amd.gan.VGGFeatureExtractor, got %s" % type(netF).__name__)
+        if criterion not in _CRITERIA:
+            raise ValueError("PerceptualLoss: criterion must be one of %s, got %r" % (sorted(_CRITERIA), criterion))
+        _vgg_plan(netF)                                       # raises ValueError for use_bn=True
+        self.netF = netF
+        self.kind = _CRITERIA[criterion]
+
+    def forward(self, fake_H, real_H):
+        if real_H.requires_grad:
+            raise ValueError("PerceptualLoss: real_H requires grad, but the target features are detached (netF(real_H).detach()): "
+                             "pass real_H.detach()")
+        if not (fake_H.is_cuda and real_H.is_cuda):
+            raise _lib.HcfError("hcflow_amd.gan runs on MI355X only (no CPU fallback): move the module and its inputs to a GPU")
+        if fake_H.dim() != 4 or fake_H.shape[1] != 3 or fake_H.shape != real_H.shape or fake_H.device != real_H.device:
+            raise ValueError("PerceptualLoss: fake_H and real_H must be [B,3,H,W] of one shape on one device, got %s and %s"
+                             % (tuple(fake_H.shape), tuple(real_H.shape)))
+        plan = _vgg_plan(self.netF)                           # per call: a DataParallel replica has its own conv modules
+        convs = [c for c, _, _ in plan]
+        if any(c.weight.requires_grad or (c.bias is not None and c.bias.requires_grad) for c in convs):
+            raise ValueError("PerceptualLoss: the VGG weights must be frozen (requires_grad=False), no weight gradient is computed")
+        if convs[0].weight.device != fake_H.device:
+            raise ValueError("PerceptualLoss: netF is on %s, the inputs on %s" % (convs[0].weight.device, fake_H.device))
+        return _PerceptualLossFn.apply(fake_H, real_H, self.netF, plan, self.kind)

@@ -439,6 +439,45 @@ int hcf_aux_bn_act_backward(const float* x, int32_t cs_x, int32_t C, int32_t B, 
                             const float* save_invstd, int32_t mode, int32_t act, const float* dy, int32_t cs_dy, float* dx,
                             int32_t cs_dx, float* dgamma, float* dbeta, void* work, size_t work_bytes, hcf_stream_t stream);
 
+/* ---- VGG19 perceptual loss of the HCFlow++ generator step: the memory-bound ops BETWEEN the aux convs of
+ * l_g_fea = l_fea_w * cri_fea(netF(fake_H), netF(real_H).detach())  (HCFlow_SR_model.py:229-232, HCFlow_Rescaling_model.py:237-240;
+ * netF = VGGFeatureExtractor(feature_layer=34, use_bn=False), networks.py:60-68). hcflow_amd/gan.py: PerceptualLoss chains them
+ * with hcf_aux_conv2d / hcf_aux_conv2d_backward; none of these entries launches a convolution. Activations are dense NHWC fp32
+ * (cs % 4 == 0, 16-byte aligned), act is 0 none / 1 relu / 2 leaky relu 0.2; no host synchronisation, no atomics.
+ *
+ * hcf_aux_input_norm: `x = (x - self.mean) / self.std` (discriminator_vgg_arch.py:153-154) and the layout change in one pass:
+ *   x device NCHW [B][3][H][W] -> y device NHWC [B][H][W][4], y[..., c] = (x[c] - mean[c]) / stdev[c], y[..., 3] = 0.
+ *   mean, stdev: device [3] (the module's buffers, :139-145); both NULL: the layout change only (use_input_norm=False).
+ * hcf_aux_input_norm_backward: g NHWC [B][H][W][4] -> dx NCHW [B][3][H][W], dx[c] = g[..., c] / stdev[c] (stdev NULL: the copy). */
+int hcf_aux_input_norm(const float* x, const float* mean, const float* stdev, int32_t B, int32_t H, int32_t W, float* y,
+                       hcf_stream_t stream);
+int hcf_aux_input_norm_backward(const float* g, const float* stdev, int32_t B, int32_t H, int32_t W, float* dx,
+                                hcf_stream_t stream);
+/* hcf_aux_maxpool2: nn.MaxPool2d(kernel_size=2, stride=2) of torchvision's VGG19 `features` (discriminator_vgg_arch.py:137,146),
+ * floor mode: x [B][H][W][cs_x] -> y [B][H/2][W/2][cs_y]; an odd last row / column is not read; channels >= C of y written 0.
+ * A NaN wins its window, as in PyTorch.
+ * hcf_aux_maxpool2_act_backward: the pool's and the preceding activation's backward in one pass. gp [B][H/2][W/2][cs_gp] is
+ * the gradient of the pooled tensor, y [B][H][W][cs_y] the pool's input = the conv's output AFTER its fused activation;
+ * gpre [B][H][W][cs_g] = gradient w.r.t. the conv's pre-activation: in each 2x2 window gp goes to the FIRST maximum in row-major
+ * order (PyTorch's rule: a strict > while scanning), kept only where y > 0 when act is relu (act 0 or 1 only); every other
+ * element, an odd last row / column and channels >= C are written 0. */
+int hcf_aux_maxpool2(const float* x, int32_t cs_x, int32_t C, int32_t B, int32_t H, int32_t W, float* y, int32_t cs_y,
+                     hcf_stream_t stream);
+int hcf_aux_maxpool2_act_backward(const float* gp, int32_t cs_gp, const float* y, int32_t cs_y, int32_t C, int32_t B, int32_t H,
+                                  int32_t W, int32_t act, float* gpre, int32_t cs_g, hcf_stream_t stream);
+/* hcf_aux_act_backward: gpre = g * act'(y) over n floats (n % 4 == 0), y the activation's OUTPUT: relu g * (y > 0), leaky relu
+ * g * (y > 0 ? 1 : 0.2), none the copy -- the expressions of hcflow_amd/gan.py _ConvNHWC.backward (nn.ReLU(inplace=True) of the
+ * VGG19 stack). gpre may alias g. */
+int hcf_aux_act_backward(const float* g, const float* y, int32_t act, int64_t n, float* gpre, hcf_stream_t stream);
+/* hcf_aux_feature_loss: cri_fea = nn.L1Loss() (kind 0) / nn.MSELoss() (kind 1) with the default mean reduction
+ * (HCFlow_SR_model.py:62-66): loss[0] = mean over n floats of |a - b| or (a - b)^2 (device float), and, when grad is not NULL,
+ * grad[i] = dloss/da[i] = sign(a - b) / n (0 where equal) or 2 (a - b) / n. a, b, grad: device [n], 16-byte aligned, any n >= 1.
+ * The sum runs in fp64 through per-block partials of a grid fixed by n and one fixed-order final block: bit-reproducible.
+ * work: device scratch of hcf_aux_feature_loss_workspace(n) bytes. */
+size_t hcf_aux_feature_loss_workspace(int64_t n);
+int hcf_aux_feature_loss(const float* a, const float* b, int64_t n, int32_t kind, float* loss, float* grad, void* work,
+                         size_t work_bytes, hcf_stream_t stream);
+
 /* ---- LPIPS v0.1, AlexNet (the LPIPS column of the reference's test log: test_HCFlow.py:48 builds lpips.LPIPS(net='alex'),
  * :132 evaluates it on (2 gt - 1, 2 sr - 1)); hcflow_amd/lpips.py is the module around it. One call runs the whole network on
  * both inputs and the LPIPS head, in exact fp32 (fp32 MFMA), on `stream`, without host synchronisation; the result for an image
