@@ -30,7 +30,7 @@ static AuxPlan aux_plan(int cin, int cout, int k, int B, int H, int W) {
   p.nchunk_f = (aux_ru4(cin) + 15) / 16;                  // forward: K = cin
   p.nchunk_t = (aux_ru4(cout) + 15) / 16;                 // data gradient: K = cout
   const int nch = std::max(p.nchunk_f, p.nchunk_t);
-  const size_t pk = ((size_t)nch * p.taps * 2 + 1) * 64 * 8 * sizeof(float);
+  const size_t pk = conv_pack_bytes(nch, p.taps, 64);
   const size_t pk16 = ((size_t)nch + 1) * p.taps * 2 * 2 * 64 * 8 * sizeof(_Float16);
   const size_t wino = (k == 3) ? ((size_t)(cin / 16) + 1) * 65536 : 0;
   p.o_bias = 256; p.o_scale = p.o_bias + 256; p.o_pk = p.o_scale + 256;
@@ -46,6 +46,36 @@ static AuxPlan aux_plan(int cin, int cout, int k, int B, int H, int W) {
   part = std::max(part, conv_wgrad_scratch_floats(w) * sizeof(float));
   p.total = p.o_part + al256(part);
   return p;
+}
+
+// the launch of one output-channel block: one source window, bias / scale vectors of the block, no residuals (wpack: the caller's)
+static ConvArgs conv_block_args(View src, int nchunk, View out, int act, int B, int H, int W, const float* bvec, const float* svec) {
+  ConvArgs a;
+  memset(&a, 0, sizeof(a));
+  a.src[0] = a.src[1] = a.src[2] = src;
+  a.nsrc = 1; a.B = B; a.H = H; a.W = W;
+  a.nchunk = nchunk; a.bias = bvec; a.scale = svec; a.act = act;
+  a.out = out;
+  a.res1 = mkview(nullptr, 0, 0, 0);
+  a.res2 = mkview(nullptr, 0, 0, 0);
+  return a;
+}
+
+int launch_conv_block(const float* w, int cin_w, int taps, int transposed, int off, const float* bias, int nb, int npad, View src,
+                      int nchunk, View out, int act, int B, int H, int W, float* bvec, float* svec, float* pk, hipStream_t st) {
+  int rc = launch_repack_epilogue(0, bias, nullptr, nb, bvec, svec, st);
+  if (rc != HCF_OK) return rc;
+  RepackArgs r;
+  memset(&r, 0, sizeof(r));
+  r.w = w; r.cin_w = cin_w; r.taps = taps; r.transposed = transposed; r.off = off; r.cout = nb;
+  r.srcs[0] = src.n; r.nsrc = 1; r.nchunk = nchunk; r.npad = npad; r.pk = pk;
+  // (the pack has zero K-padding lanes beyond src.n and zero n-padding beyond nb: clear, then fill the live entries)
+  if (hipMemsetAsync(pk, 0, conv_pack_bytes(nchunk, taps, npad), st) != hipSuccess) return HCF_ERR_HIP;
+  rc = launch_repack_conv(r, st);
+  if (rc != HCF_OK) return rc;
+  ConvArgs a = conv_block_args(src, nchunk, out, act, B, H, W, bvec, svec);
+  a.wpack = pk;
+  return launch_conv(a, taps, st);
 }
 }  // namespace hcf
 
@@ -72,53 +102,46 @@ int hcf_aux_conv2d(const float* x, int32_t cs_in, int32_t cin, int32_t B, int32_
   char* wk = (char*)work;
   const bool f16 = (precision == PREC_F16X3) && k == 3;
   int rc = HCF_OK;
+  float* bvec = (float*)(wk + p.o_bias);
+  float* svec = (float*)(wk + p.o_scale);
+  const View src = mkview(const_cast<float*>(x), cs_in, 0, cin);
   for (int oc0 = 0; oc0 < cout && rc == HCF_OK; oc0 += 64) {
     const int nb = std::min(64, cout - oc0);
     const int npad = ((nb + 31) / 32) * 32;
-    float* bvec = (float*)(wk + p.o_bias);
-    float* svec = (float*)(wk + p.o_scale);
-    rc = launch_repack_epilogue(0, bias ? bias + oc0 : nullptr, nullptr, nb, bvec, svec, st);
-    if (rc != HCF_OK) break;
-    RepackArgs r;
-    memset(&r, 0, sizeof(r));
-    r.w = w + (size_t)oc0 * cin * p.taps; r.cin_w = cin; r.taps = p.taps; r.cout = nb;
-    r.srcs[0] = cin; r.nsrc = 1; r.nchunk = p.nchunk_f; r.npad = npad;
-    r.pk = f16 ? nullptr : (float*)(wk + p.o_pk);
-    r.pk16 = f16 ? (_Float16*)(wk + p.o_pk16) : nullptr;
-    // (the packs have zero K-padding lanes beyond cin and zero n-padding beyond nb: clear, then fill the live entries)
-    const size_t pkb = f16 ? ((size_t)p.nchunk_f + 1) * p.taps * 2 * 2 * npad * 8 * sizeof(_Float16)
-                           : ((size_t)p.nchunk_f * p.taps * 2 + 1) * npad * 8 * sizeof(float);
-    if (hipMemsetAsync(f16 ? (void*)r.pk16 : (void*)r.pk, 0, pkb, st) != hipSuccess) return HCF_ERR_HIP;
-    rc = launch_repack_conv(r, st);
-    if (rc != HCF_OK) break;
-    ConvArgs a;
-    memset(&a, 0, sizeof(a));
-    a.src[0] = mkview(const_cast<float*>(x), cs_in, 0, cin);
-    a.src[1] = a.src[2] = a.src[0];
-    a.nsrc = 1; a.B = B; a.H = H; a.W = W;
-    a.nchunk = p.nchunk_f; a.bias = bvec; a.scale = svec; a.act = act;
-    a.out = mkview(y, cs_out, oc0, nb);
-    a.res1 = mkview(nullptr, 0, 0, 0);
-    a.res2 = mkview(nullptr, 0, 0, 0);
-    if (f16) {
+    const float* wb = w + (size_t)oc0 * cin * p.taps;
+    const float* bb = bias ? bias + oc0 : nullptr;
+    const View out = mkview(y, cs_out, oc0, nb);
+    if (!f16) {
+      rc = launch_conv_block(wb, cin, p.taps, 0, 0, bb, nb, npad, src, p.nchunk_f, out, act, B, H, W, bvec, svec,
+                             (float*)(wk + p.o_pk), st);
+    } else {                                                             // the only user of the f16x3 and Winograd pack layouts
+      rc = launch_repack_epilogue(0, bb, nullptr, nb, bvec, svec, st);
+      if (rc != HCF_OK) break;
+      RepackArgs r;
+      memset(&r, 0, sizeof(r));
+      r.w = wb; r.cin_w = cin; r.taps = p.taps; r.cout = nb;
+      r.srcs[0] = cin; r.nsrc = 1; r.nchunk = p.nchunk_f; r.npad = npad;
+      r.pk16 = (_Float16*)(wk + p.o_pk16);
+      // (the pack has zero K-padding lanes beyond cin and zero n-padding beyond nb: clear, then fill the live entries)
+      const size_t pkb = ((size_t)p.nchunk_f + 1) * p.taps * 2 * 2 * npad * 8 * sizeof(_Float16);
+      if (hipMemsetAsync(r.pk16, 0, pkb, st) != hipSuccess) return HCF_ERR_HIP;
+      rc = launch_repack_conv(r, st);
+      if (rc != HCF_OK) break;
+      ConvArgs a = conv_block_args(src, p.nchunk_f, out, act, B, H, W, bvec, svec);
       a.ovf = (int*)wk;
       a.zeros = reinterpret_cast<const float*>(wk) + 16;
-      int r2 = HCF_ERR_UNSUPPORTED;
+      rc = HCF_ERR_UNSUPPORTED;
       if ((cin & 15) == 0 && cin >= 64 && (nb == 32 || nb == 64)) {      // the dense 3x3 layers take the Winograd form
         // the kernels over-read ONE chunk behind the pack, which must be zero: the region is shared by the 64- and the 32-wide
         // layouts of successive output-channel blocks (cout = 96, 160 ...), whose chunk sizes and hence "behind the pack" differ
         const size_t chunk_b = (nb == 64) ? 65536 : 32768;
         if (hipMemsetAsync(wk + p.o_wino + (size_t)(cin / 16) * chunk_b, 0, chunk_b, st) != hipSuccess) return HCF_ERR_HIP;
-        if (launch_repack_wino(r.w, cin, nb, nb, wk + p.o_wino, st) == HCF_OK) r2 = launch_conv_wino(a, wk + p.o_wino, st);
+        if (launch_repack_wino(wb, cin, nb, nb, wk + p.o_wino, st) == HCF_OK) rc = launch_conv_wino(a, wk + p.o_wino, st);
       }
-      if (r2 == HCF_ERR_UNSUPPORTED) {
+      if (rc == HCF_ERR_UNSUPPORTED) {
         a.wpack = (const float*)(wk + p.o_pk16);
-        r2 = launch_conv_f16x3(a, p.taps, st);
+        rc = launch_conv_f16x3(a, p.taps, st);
       }
-      rc = r2;
-    } else {
-      a.wpack = (const float*)(wk + p.o_pk);
-      rc = launch_conv(a, p.taps, st);
     }
   }
   return rc;
@@ -142,27 +165,8 @@ int hcf_aux_conv2d_backward(const float* x, int32_t cs_in, int32_t cin, int32_t 
   // ---- data gradient: the same conv kernel on transposed, tap-flipped packs, <= 64 input channels per launch (exact fp32)
   for (int ic0 = 0; dx && ic0 < cin && rc == HCF_OK; ic0 += 64) {
     const int nb = std::min(64, cin - ic0);
-    const int npad = ((nb + 31) / 32) * 32;
-    float* bvec = (float*)(wk + p.o_bias);
-    float* svec = (float*)(wk + p.o_scale);
-    rc = launch_repack_epilogue(0, nullptr, nullptr, nb, bvec, svec, st);
-    if (rc != HCF_OK) break;
-    RepackArgs r;
-    memset(&r, 0, sizeof(r));
-    r.w = w; r.cin_w = cin; r.taps = p.taps; r.transposed = 1; r.off = ic0; r.cout = nb;
-    r.srcs[0] = cout; r.nsrc = 1; r.nchunk = p.nchunk_t; r.npad = npad; r.pk = (float*)(wk + p.o_pk);
-    if (hipMemsetAsync(r.pk, 0, ((size_t)p.nchunk_t * p.taps * 2 + 1) * npad * 8 * sizeof(float), st) != hipSuccess) return HCF_ERR_HIP;
-    rc = launch_repack_conv(r, st);
-    if (rc != HCF_OK) break;
-    ConvArgs a;
-    memset(&a, 0, sizeof(a));
-    a.src[0] = a.src[1] = a.src[2] = gv;
-    a.nsrc = 1; a.B = B; a.H = H; a.W = W;
-    a.wpack = r.pk; a.nchunk = p.nchunk_t; a.bias = bvec; a.scale = svec; a.act = ACT_NONE;
-    a.out = mkview(dx, cs_dx, ic0, nb);
-    a.res1 = mkview(nullptr, 0, 0, 0);
-    a.res2 = mkview(nullptr, 0, 0, 0);
-    rc = launch_conv(a, p.taps, st);
+    rc = launch_conv_block(w, cin, p.taps, 1, ic0, nullptr, nb, ((nb + 31) / 32) * 32, gv, p.nchunk_t, mkview(dx, cs_dx, ic0, nb),
+                           ACT_NONE, B, H, W, (float*)(wk + p.o_bias), (float*)(wk + p.o_scale), (float*)(wk + p.o_pk), st);
   }
   // ---- weight gradient (fp32 MFMA, fixed-order split-K reduce: bit-reproducible)
   if (rc == HCF_OK && dw) {

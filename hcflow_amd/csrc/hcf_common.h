@@ -186,6 +186,18 @@ int launch_repack_epilogue_batch(const RepackEpiJob* jobs, int njobs, hipStream_
 int launch_copy_jobs(const CopyJob* jobs, int njobs, hipStream_t st);      // dst[0..n) = src[0..n) per job (gather / scatter of small tables)
 int launch_repack_epilogue(int kind, const float* b, const float* l, int cout, float* bias, float* scale, hipStream_t st);
 
+// ---- one output-channel block of a stride-1 "same" conv, fp32 kernel, straight from a device weight (hcf_aux.hip) ----------
+// bytes of the fp32 pack [nchunk][taps][2][npad][8] AND the one zero K-step behind it, which the conv kernel reads
+static inline size_t conv_pack_bytes(int nchunk, int taps, int npad) {
+  return ((size_t)nchunk * taps * 2 + 1) * npad * 8 * sizeof(float);
+}
+// out = act(conv(src, W) + bias) for the nb <= npad <= 64 output channels of `out`: bias / scale vectors, the cleared pack and its
+// live entries are rebuilt in (bvec, svec, pk: 64, 64 and conv_pack_bytes(nchunk, taps, npad) / 4 floats), then the conv runs.
+// W = rows [0, nb) of w ([..][cin_w][taps]), or with `transposed` the tap-flipped transpose of w's input channels [off, off + nb)
+// (the data gradient); src.n = K of the conv, nchunk = ceil(K / 16); bias null: none.
+int launch_conv_block(const float* w, int cin_w, int taps, int transposed, int off, const float* bias, int nb, int npad, View src,
+                      int nchunk, View out, int act, int B, int H, int W, float* bvec, float* svec, float* pk, hipStream_t st);
+
 // ---- flow-step glue --------------------------------------------------------------------------
 enum { CPL_AFFINE = 0, CPL_SHIFT3 = 1 };
 

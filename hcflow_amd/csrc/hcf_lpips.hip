@@ -62,7 +62,7 @@ static bool lpips_plan(int B, int H, int W, LpipsPlan& p) {
   p.o_f4 = take(g3 * 256 * f);
   p.o_f5 = take(g3 * 256 * f);
   // fp32 conv pack [chunk][tap][2][64][8] + one zero K-step: conv1 3 chunks, conv2 4 chunks of 16 input channels
-  p.o_pk = take(((size_t)4 * 25 * 2 + 1) * 64 * 8 * f);
+  p.o_pk = take(conv_pack_bytes(4, 25, 64));
   p.o_bias = take(64 * f);
   p.o_scale = take(64 * f);
   p.o_part = take((size_t)B * p.nchunk_total * f);
@@ -241,28 +241,9 @@ static int lpips_grid(long long total, unsigned* g) {
 // conv 5x5 pad 2 (TAPS = 25) of x [N][H][W][cin] (cin % 16 == 0) into y[..., oc0 .. oc0+64) of a cs_out-channel slab, bias + ReLU
 static int lpips_conv5(const float* x, int cin, int N, int H, int W, const float* w, const float* bias, float* y, int cs_out,
                        int oc0, char* wk, const LpipsPlan& p, hipStream_t st) {
-  float* bvec = (float*)(wk + p.o_bias);
-  float* svec = (float*)(wk + p.o_scale);
-  int rc = launch_repack_epilogue(0, bias + oc0, nullptr, 64, bvec, svec, st);
-  if (rc != HCF_OK) return rc;
-  RepackArgs r;
-  memset(&r, 0, sizeof(r));
-  r.w = w + (size_t)oc0 * cin * 25; r.cin_w = cin; r.taps = 25; r.cout = 64;
-  r.srcs[0] = cin; r.nsrc = 1; r.nchunk = cin / 16; r.npad = 64;
-  r.pk = (float*)(wk + p.o_pk);
-  if (hipMemsetAsync(r.pk, 0, ((size_t)r.nchunk * 25 * 2 + 1) * 64 * 8 * sizeof(float), st) != hipSuccess) return HCF_ERR_HIP;
-  rc = launch_repack_conv(r, st);
-  if (rc != HCF_OK) return rc;
-  ConvArgs a;
-  memset(&a, 0, sizeof(a));
-  a.src[0] = mkview(const_cast<float*>(x), cin, 0, cin);
-  a.src[1] = a.src[2] = a.src[0];
-  a.nsrc = 1; a.B = N; a.H = H; a.W = W;
-  a.wpack = r.pk; a.nchunk = r.nchunk; a.bias = bvec; a.scale = svec; a.act = ACT_RELU;
-  a.out = mkview(y, cs_out, oc0, 64);
-  a.res1 = mkview(nullptr, 0, 0, 0);
-  a.res2 = mkview(nullptr, 0, 0, 0);
-  return launch_conv(a, 25, st);
+  return launch_conv_block(w + (size_t)oc0 * cin * 25, cin, 25, 0, 0, bias + oc0, 64, 64, mkview(const_cast<float*>(x), cin, 0, cin),
+                           cin / 16, mkview(y, cs_out, oc0, 64), ACT_RELU, N, H, W, (float*)(wk + p.o_bias), (float*)(wk + p.o_scale),
+                           (float*)(wk + p.o_pk), st);
 }
 
 static int lpips_pool(const float* in, int N, int Hst, int Wst, int C, int Ho, int Wo, float* out, hipStream_t st) {

@@ -76,6 +76,72 @@ def _w4s2_as_3x3(w: torch.Tensor) -> torch.Tensor:
     return w3.reshape(O, 4 * Cc, 3, 3)
 
 
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def _stream(device):
+    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def _workspace(work, key, need, device, zeroed):
+    """The scratch buffer work[key] of at least `need` bytes on `device` (re)allocated when missing or too small. Every key names
+    its DEVICE and STREAM: nn.DataParallel replicas share the dict (replicate() shallow-copies __dict__), one replica thread per
+    device (HCFlow_SR_model.py:76,94 wrap netD / netF); calls on a stream run in order, and a buffer holds state of the call in
+    flight only."""
+    wk = work.get(key)
+    if wk is None or wk.numel() < need or wk.device != device:
+        wk = (torch.zeros if zeroed else torch.empty)(need, dtype=torch.uint8, device=device)
+        work[key] = wk
+    return wk
+
+
+def _conv_forward(x, w, bias, act, prec, work, flags):
+    """y = act(conv_k(x, w) + bias): NHWC x, contiguous w [cout,cin,k,k]; y has cout rounded up to 4 channels (the padding zero).
+    Returns (y, wk); wk, the call's workspace (packs, the range flag, weight-gradient partials), also joins `flags`."""
+    lib = _lib.load()
+    B, H, W, cs = x.shape
+    cout, cin, k, _ = w.shape
+    y = torch.empty(B, H, W, (cout + 3) & ~3, device=x.device, dtype=torch.float32)
+    if y.shape[3] != cout:
+        y.zero_()
+    st = torch.cuda.current_stream(x.device).cuda_stream
+    wk = _workspace(work, (x.device.index, st, cin, cout, k, B, H, W), lib.hcf_aux_conv2d_workspace(cin, cout, k, B, H, W),
+                    x.device, zeroed=True)                                  # [0, 256): range flag + zero page
+    flags.append(wk)
+    b = None if bias is None else bias.contiguous()
+    rc = lib.hcf_aux_conv2d(x.data_ptr(), cs, cin, B, H, W, w.data_ptr(), _ptr(b), cout, k, act, y.data_ptr(), y.shape[3],
+                            wk.data_ptr(), wk.numel(), prec, C.c_void_p(st))
+    _lib.check(rc, None, "hcf_aux_conv2d")
+    return y, wk
+
+
+def _conv_backward(x, w, g, dx, dw, wk, prec):
+    """Gradients of conv_k(x, w) given g = dL/d(pre-activation) into the caller's dx (channels [0, cin)) and dw; None: skipped."""
+    B, H, W, cs = x.shape
+    cout, cin, k, _ = w.shape
+    rc = _lib.load().hcf_aux_conv2d_backward(x.data_ptr(), cs, cin, B, H, W, w.data_ptr(), cout, k, g.data_ptr(), g.shape[3],
+                                             _ptr(dx), cs, _ptr(dw), wk.data_ptr(), wk.numel(), prec, _stream(x.device))
+    _lib.check(rc, None, "hcf_aux_conv2d_backward")
+
+
+def _range_redo(run, prec, restore=None):
+    """run(prec, flags) speculatively at the requested precision. Under f16x3 the convs raise the flag word of their workspace
+    when an activation leaves the f16 range (the pass then holds inf / NaN): every flag is cleared, `restore` undoes what the
+    pass left behind, and the pass is redone exactly. The flag read is the one stream sync of an f16x3 call."""
+    flags = []
+    out = run(prec, flags)
+    if prec == 1 and flags:
+        uniq = list({id(f): f for f in flags}.values())
+        if bool(torch.stack([f[:4].view(torch.int32)[0] for f in uniq]).any()):
+            for f in uniq:
+                f[:4].zero_()
+            if restore is not None:
+                restore()
+            out = run(0, [])
+    return out
+
+
 class _ConvNHWC(torch.autograd.Function):
     """y = act(conv_k(x, w) + bias) on NHWC device tensors through the C ABI; act in {0 none, 1 relu, 2 lrelu 0.2}."""
 
@@ -83,54 +149,28 @@ class _ConvNHWC(torch.autograd.Function):
     def forward(ctx, x, w, bias, act, prec, work, flag_owner):
         if not x.is_cuda:
             raise _lib.HcfError("hcflow_amd.gan runs on MI355X only (no CPU fallback): move the module and its inputs to a GPU")
-        lib = _lib.load()
-        B, H, W, cs = x.shape
-        cout, cin, k, _ = w.shape
-        assert cs % 4 == 0 and cs >= cin and x.is_contiguous() and x.dtype == torch.float32
+        assert x.shape[3] % 4 == 0 and x.shape[3] >= w.shape[1] and x.is_contiguous() and x.dtype == torch.float32
         w = w.contiguous()
-        y = torch.empty(B, H, W, (cout + 3) & ~3, device=x.device, dtype=torch.float32)
-        if y.shape[3] != cout:
-            y.zero_()
-        need = lib.hcf_aux_conv2d_workspace(cin, cout, k, B, H, W)
-        # keyed by DEVICE and STREAM too: nn.DataParallel replicas share this dict (replicate() shallow-copies __dict__), one
-        # replica thread per device (HCFlow_SR_model.py:76,94 wrap netD / netF), and a workspace holds packs, the range flag and
-        # weight-gradient partials of the call in flight
-        key = (x.device.index, torch.cuda.current_stream(x.device).cuda_stream, cin, cout, k, B, H, W)
-        wk = work.get(key)
-        if wk is None or wk.numel() < need or wk.device != x.device:
-            wk = torch.zeros(need, dtype=torch.uint8, device=x.device)          # [0, 256): range flag + zero page
-            work[key] = wk
-        flag_owner.append(wk)
         with torch.cuda.device(x.device):
-            rc = lib.hcf_aux_conv2d(x.data_ptr(), cs, cin, B, H, W, w.data_ptr(), None if bias is None else bias.contiguous().data_ptr(),
-                                    cout, k, act, y.data_ptr(), y.shape[3], C.c_void_p(wk.data_ptr()), wk.numel(), prec,
-                                    C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream))
-        _lib.check(rc, None, "hcf_aux_conv2d")
+            y, wk = _conv_forward(x, w, bias, act, prec, work, flag_owner)
         ctx.save_for_backward(x, w, y if act else None)
-        ctx.meta = (cin, cout, k, act, prec, bias is not None, wk)
+        ctx.meta = (act, prec, bias is not None, wk)
         return y
 
     @staticmethod
     def backward(ctx, g):
-        lib = _lib.load()
         x, w, y = ctx.saved_tensors
-        cin, cout, k, act, prec, has_bias, wk = ctx.meta
-        B, H, W, cs = x.shape
+        act, prec, has_bias, wk = ctx.meta
         g = g.contiguous()
         if act == 1:
             g = g * (y > 0)
         elif act == 2:
             g = g * torch.where(y > 0, torch.ones_like(y), torch.full_like(y, 0.2))
-        need_dx = ctx.needs_input_grad[0]
-        dx = torch.zeros_like(x) if need_dx else None
+        dx = torch.zeros_like(x) if ctx.needs_input_grad[0] else None
         dw = torch.empty_like(w) if ctx.needs_input_grad[1] else None       # frozen weights (VGG; netD during the G step): skipped
         with torch.cuda.device(x.device):
-            rc = lib.hcf_aux_conv2d_backward(x.data_ptr(), cs, cin, B, H, W, w.data_ptr(), cout, k, g.data_ptr(), g.shape[3],
-                                             None if dx is None else dx.data_ptr(), cs, None if dw is None else dw.data_ptr(),
-                                             C.c_void_p(wk.data_ptr()),
-                                             wk.numel(), prec, C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream))
-        _lib.check(rc, None, "hcf_aux_conv2d_backward")
-        db = g[..., :cout].sum(dim=(0, 1, 2)) if (has_bias and ctx.needs_input_grad[2]) else None
+            _conv_backward(x, w, g, dx, dw, wk, prec)
+        db = g[..., :w.shape[0]].sum(dim=(0, 1, 2)) if (has_bias and ctx.needs_input_grad[2]) else None
         return dx, dw, db, None, None, None, None
 
 
@@ -143,13 +183,9 @@ def _interior(y: torch.Tensor):
 
 
 def _bn_workspace(work, x, need):
-    # one scratch per device and stream: calls on a stream run in order, and nothing in it outlives a call
-    key = ("bn", x.device.index, torch.cuda.current_stream(x.device).cuda_stream)
-    wk = work.get(key)
-    if wk is None or wk.numel() < need:
-        wk = torch.empty(max(need, 256), dtype=torch.uint8, device=x.device)
-        work[key] = wk
-    return wk
+    # not inlined: the forward and the backward pass must name the same key
+    return _workspace(work, ("bn", x.device.index, torch.cuda.current_stream(x.device).cuda_stream), max(need, 256), x.device,
+                      zeroed=False)
 
 
 class _BnActNHWC(torch.autograd.Function):
@@ -166,7 +202,6 @@ class _BnActNHWC(torch.autograd.Function):
         B, H, W, cs = x.shape
         y0, x0, Ho, Wo = window
         assert cs % 4 == 0 and cs >= Cc and x.is_contiguous() and x.dtype == torch.float32
-        stream = torch.cuda.current_stream(x.device).cuda_stream
         y = torch.empty(B, Ho, Wo, (Cc + 3) & ~3, device=x.device, dtype=torch.float32)
         smean = sinv = rmean = rvar = wk = None
         momentum, eps = 0.0, 1e-5
@@ -195,12 +230,10 @@ class _BnActNHWC(torch.autograd.Function):
             smean = torch.empty(Cc, device=x.device, dtype=torch.float32)
             sinv = torch.empty(Cc, device=x.device, dtype=torch.float32)
             gamma, beta = gamma.contiguous(), beta.contiguous()
-        ptr = lambda t: None if t is None else t.data_ptr()
         with torch.cuda.device(x.device):
-            rc = lib.hcf_aux_bn_act(x.data_ptr(), cs, Cc, B, H, W, y0, x0, Ho, Wo, ptr(gamma), ptr(beta), ptr(rmean), ptr(rvar),
-                                    mode, momentum, eps, act, y.data_ptr(), y.shape[3], ptr(smean), ptr(sinv),
-                                    None if wk is None else C.c_void_p(wk.data_ptr()), 0 if wk is None else wk.numel(),
-                                    C.c_void_p(stream))
+            rc = lib.hcf_aux_bn_act(x.data_ptr(), cs, Cc, B, H, W, y0, x0, Ho, Wo, _ptr(gamma), _ptr(beta), _ptr(rmean), _ptr(rvar),
+                                    mode, momentum, eps, act, y.data_ptr(), y.shape[3], _ptr(smean), _ptr(sinv),
+                                    _ptr(wk), 0 if wk is None else wk.numel(), _stream(x.device))
         _lib.check(rc, None, "hcf_aux_bn_act")
         ctx.save_for_backward(x, gamma, beta, smean, sinv)
         ctx.meta = (Cc, window, act, mode, work)
@@ -220,13 +253,10 @@ class _BnActNHWC(torch.autograd.Function):
         wk = None
         if mode == _BN_TRAIN or need_p:
             wk = _bn_workspace(work, x, lib.hcf_aux_bn_act_workspace(Cc, B, Ho, Wo))
-        ptr = lambda t: None if t is None else t.data_ptr()
         with torch.cuda.device(x.device):
-            rc = lib.hcf_aux_bn_act_backward(x.data_ptr(), cs, Cc, B, H, W, y0, x0, Ho, Wo, ptr(gamma), ptr(beta), ptr(smean),
-                                             ptr(sinv), mode, act, g.data_ptr(), g.shape[3], dx.data_ptr(), cs, ptr(dgamma),
-                                             ptr(dbeta), None if wk is None else C.c_void_p(wk.data_ptr()),
-                                             0 if wk is None else wk.numel(),
-                                             C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream))
+            rc = lib.hcf_aux_bn_act_backward(x.data_ptr(), cs, Cc, B, H, W, y0, x0, Ho, Wo, _ptr(gamma), _ptr(beta), _ptr(smean),
+                                             _ptr(sinv), mode, act, g.data_ptr(), g.shape[3], dx.data_ptr(), cs, _ptr(dgamma),
+                                             _ptr(dbeta), _ptr(wk), 0 if wk is None else wk.numel(), _stream(x.device))
         _lib.check(rc, None, "hcf_aux_bn_act_backward")
         return (dx, dgamma if ctx.needs_input_grad[1] else None, dbeta if ctx.needs_input_grad[2] else None,
                 None, None, None, None, None)
@@ -262,33 +292,28 @@ class _AuxNet(nn.Module):
 
     def _run(self, body, x):
         prec = _PREC[self._prec[0]]
-        flags = []
         # a speculative f16x3 pass in train() mode updates every BatchNorm's running statistics; if it is thrown away (range
         # overflow: its activations were inf / NaN) the exact re-run must start from the statistics BEFORE it
-        bn_state = None
+        restore = None
         if prec == 1 and self.training:
             bn_state = [(m, m.running_mean.clone(), m.running_var.clone(), m.num_batches_tracked.clone())
                         for m in self.modules() if isinstance(m, nn.BatchNorm2d) and m.track_running_stats and m.running_mean is not None]
-        out = body(x, flags, prec)
-        if prec == 1 and flags:
-            hit = torch.stack([f[:4].view(torch.int32)[0] for f in {id(f): f for f in flags}.values()]).any()
-            if bool(hit):                                     # an activation left the f16 range: redo the pass exactly
-                for f in flags:
-                    f[:4].zero_()
-                for m, mean, var, cnt in (bn_state or []):
-                    with torch.no_grad():
-                        m.running_mean.copy_(mean)
-                        m.running_var.copy_(var)
-                        m.num_batches_tracked.copy_(cnt)
-                out = body(x, [], 0)
-        return out
+
+            @torch.no_grad()
+            def restore():
+                for m, mean, var, cnt in bn_state:
+                    m.running_mean.copy_(mean)
+                    m.running_var.copy_(var)
+                    m.num_batches_tracked.copy_(cnt)
+        return _range_redo(lambda p, flags: body(x, flags, p), prec, restore)
 
 
-class Discriminator_VGG_128(_AuxNet):
-    """Drop-in for discriminator_vgg_arch.Discriminator_VGG_128 (:6-65): same modules / state_dict (128 x 128 input,
-    ``linear1`` on 512 * 4 * 4 features); convs on our conv kernels, every BatchNorm + LeakyReLU on the fused BN kernels."""
+class _DiscriminatorVGG(_AuxNet):
+    """The VGG-style discriminators of discriminator_vgg_arch.py (:6-65, :68-107): ten convs (every second one 4x4 stride 2),
+    BatchNorm + LeakyReLU after all but the first, two Linear layers on the fc_side x fc_side map that is left. Same modules /
+    state_dict as the reference; convs on our conv kernels, BatchNorm + LeakyReLU as the subclass runs it (_bn_lrelu)."""
 
-    def __init__(self, in_nc, nf):
+    def __init__(self, in_nc, nf, fc_side):
         super().__init__()
         self.conv0_0 = nn.Conv2d(in_nc, nf, 3, 1, 1, bias=True)
         self.conv0_1 = nn.Conv2d(nf, nf, 4, 2, 1, bias=False)
@@ -299,56 +324,13 @@ class Discriminator_VGG_128(_AuxNet):
             setattr(self, "bn%d_0" % i, nn.BatchNorm2d(co, affine=True))
             setattr(self, "conv%d_1" % i, nn.Conv2d(co, co, 4, 2, 1, bias=False))
             setattr(self, "bn%d_1" % i, nn.BatchNorm2d(co, affine=True))
-        self.linear1 = nn.Linear(512 * 4 * 4, 100)
-        self.linear2 = nn.Linear(100, 1)
-        self.lrelu = nn.LeakyReLU(negative_slope=0.2, inplace=True)
-        self._aux_init()
-
-    def _conv_bn(self, fea, conv, bn, flags, prec):
-        return self._bn_act(self._conv(fea, conv, 0, flags, prec), bn, bn.num_features)
-
-    def _body(self, x, flags, prec):
-        fea = self._conv(_nhwc(x), self.conv0_0, 2, flags, prec)                       # bias + LeakyReLU fused
-        fea = self._conv_bn(fea, self.conv0_1, self.bn0_1, flags, prec)
-        for i in range(1, 5):
-            fea = self._conv_bn(fea, getattr(self, "conv%d_0" % i), getattr(self, "bn%d_0" % i), flags, prec)
-            fea = self._conv_bn(fea, getattr(self, "conv%d_1" % i), getattr(self, "bn%d_1" % i), flags, prec)
-        fea = fea.permute(0, 3, 1, 2).reshape(fea.size(0), -1)                         # the reference flattens NCHW
-        fea = self.lrelu(self.linear1(fea))
-        return self.linear2(fea)
-
-    def forward(self, x):
-        return self._run(self._body, x)
-
-    def reset_parameters(self):
-        for layer in self.children():
-            if hasattr(layer, "reset_parameters"):
-                layer.reset_parameters()
-
-
-class Discriminator_VGG_160(_AuxNet):
-    """Drop-in for discriminator_vgg_arch.Discriminator_VGG_160 (:68-107): same modules / state_dict, convs on our kernels."""
-
-    def __init__(self, in_nc, nf):
-        super().__init__()
-        self.conv0_0 = nn.Conv2d(in_nc, nf, 3, 1, 1, bias=True)
-        self.conv0_1 = nn.Conv2d(nf, nf, 4, 2, 1, bias=False)
-        self.bn0_1 = nn.BatchNorm2d(nf, affine=True)
-        chans = [(nf, nf * 2), (nf * 2, nf * 4), (nf * 4, nf * 8), (nf * 8, nf * 8)]
-        for i, (ci, co) in enumerate(chans, start=1):
-            setattr(self, "conv%d_0" % i, nn.Conv2d(ci, co, 3, 1, 1, bias=False))
-            setattr(self, "bn%d_0" % i, nn.BatchNorm2d(co, affine=True))
-            setattr(self, "conv%d_1" % i, nn.Conv2d(co, co, 4, 2, 1, bias=False))
-            setattr(self, "bn%d_1" % i, nn.BatchNorm2d(co, affine=True))
-        self.linear1 = nn.Linear(512 * 5 * 5, 100)
+        self.linear1 = nn.Linear(512 * fc_side * fc_side, 100)
         self.linear2 = nn.Linear(100, 1)
         self.lrelu = nn.LeakyReLU(negative_slope=0.2, inplace=True)
         self._aux_init()
 
     def _bn_lrelu(self, y, bn: nn.BatchNorm2d):
-        Cc = bn.num_features
-        v = bn(y[..., :Cc].permute(0, 3, 1, 2))               # channels-last view: no copy; batch / running statistics as nn.BatchNorm2d
-        return F.leaky_relu(v, 0.2).permute(0, 2, 3, 1).contiguous()
+        raise NotImplementedError
 
     def _body(self, x, flags, prec):
         fea = self._conv(_nhwc(x), self.conv0_0, 2, flags, prec)                       # bias + LeakyReLU fused
@@ -369,6 +351,30 @@ class Discriminator_VGG_160(_AuxNet):
                 layer.reset_parameters()
 
 
+class Discriminator_VGG_128(_DiscriminatorVGG):
+    """Drop-in for discriminator_vgg_arch.Discriminator_VGG_128 (:6-65): 128 x 128 input, ``linear1`` on 512 * 4 * 4 features;
+    every BatchNorm + LeakyReLU on the fused BN kernels."""
+
+    def __init__(self, in_nc, nf):
+        super().__init__(in_nc, nf, fc_side=4)
+
+    def _bn_lrelu(self, y, bn: nn.BatchNorm2d):
+        return self._bn_act(y, bn, bn.num_features)
+
+
+class Discriminator_VGG_160(_DiscriminatorVGG):
+    """Drop-in for discriminator_vgg_arch.Discriminator_VGG_160 (:68-107): 160 x 160 input, ``linear1`` on 512 * 5 * 5 features;
+    BatchNorm + LeakyReLU on stock PyTorch ops."""
+
+    def __init__(self, in_nc, nf):
+        super().__init__(in_nc, nf, fc_side=5)
+
+    def _bn_lrelu(self, y, bn: nn.BatchNorm2d):
+        Cc = bn.num_features
+        v = bn(y[..., :Cc].permute(0, 3, 1, 2))               # channels-last view: no copy; batch / running statistics as nn.BatchNorm2d
+        return F.leaky_relu(v, 0.2).permute(0, 2, 3, 1).contiguous()
+
+
 _VGG19 = [64, 64, "M", 128, 128, "M", 256, 256, 256, 256, "M", 512, 512, 512, 512, "M", 512, 512, 512, 512, "M"]
 
 
@@ -384,6 +390,28 @@ def _vgg19_features(use_bn):
             layers.append(nn.ReLU(inplace=True))
             cin = v
     return layers
+
+
+def _vgg_plan(netF, who="VGGFeatureExtractor"):
+    """VGGFeatureExtractor.features as [(conv, bn, relu, pooled)]: each conv with the BatchNorm2d (or None), the ReLU and the
+    MaxPool2d that follow it, in that order. The ReLU is fused into the conv where no BatchNorm sits between them."""
+    mods, plan, i = list(netF.features), [], 0
+
+    def take(kind):                                          # the next module if it is a `kind` (consumed), else None
+        nonlocal i
+        if i < len(mods) and isinstance(mods[i], kind):
+            i += 1
+            return mods[i - 1]
+        return None
+
+    while i < len(mods):
+        conv = take(nn.Conv2d)
+        if conv is None:
+            raise ValueError("%s: unexpected %s at features.%d" % (who, type(mods[i]).__name__, i))
+        bn = take(nn.BatchNorm2d)
+        relu = take(nn.ReLU) is not None
+        plan.append((conv, bn, relu, take(nn.MaxPool2d) is not None))
+    return plan
 
 
 class VGGFeatureExtractor(_AuxNet):
@@ -406,24 +434,15 @@ class VGGFeatureExtractor(_AuxNet):
         if self.use_input_norm:
             x = (x - self.mean) / self.std
         y, Cc = _nhwc(x), 3
-        mods = list(self.features)
-        i = 0
-        while i < len(mods):
-            m = mods[i]
-            if isinstance(m, nn.Conv2d):
-                fuse = i + 1 < len(mods) and isinstance(mods[i + 1], nn.ReLU)
-                y = _ConvNHWC.apply(y, m.weight, m.bias, 1 if fuse else 0, prec, self._work, flags)
-                Cc = m.out_channels
-                i += 2 if fuse else 1
-            elif isinstance(m, nn.MaxPool2d):
+        for conv, bn, relu, pooled in _vgg_plan(self):
+            Cc = conv.out_channels
+            y = _ConvNHWC.apply(y, conv.weight, conv.bias, int(relu and bn is None), prec, self._work, flags)
+            if bn is not None:
+                y = bn(y[..., :Cc].permute(0, 3, 1, 2)).permute(0, 2, 3, 1).contiguous()
+                if relu:
+                    y = F.relu(y)
+            if pooled:
                 y = F.max_pool2d(y[..., :Cc].permute(0, 3, 1, 2), 2, 2).permute(0, 2, 3, 1).contiguous()
-                i += 1
-            elif isinstance(m, nn.BatchNorm2d):
-                y = m(y[..., :Cc].permute(0, 3, 1, 2)).permute(0, 2, 3, 1).contiguous()
-                i += 1
-            else:                                             # a ReLU that follows a BatchNorm
-                y = F.relu(y)
-                i += 1
         return _nchw(y, Cc).contiguous()
 
     def forward(self, x):
@@ -472,22 +491,13 @@ class PatchGANDiscriminator(_AuxNet):
 _CRITERIA = {"l1": 0, "l2": 1, "mse": 1}                    # feature_criterion of the recipes (HCFlow_SR_model.py:62-66)
 
 
-def _vgg_plan(netF):
-    """VGGFeatureExtractor.features as [(conv, act, pooled)]: each conv with its fused ReLU (act 1) and whether a MaxPool2d follows."""
-    mods, plan, i = list(netF.features), [], 0
-    while i < len(mods):
-        m = mods[i]
-        if isinstance(m, nn.BatchNorm2d):
-            raise ValueError("PerceptualLoss: use_bn=True (BatchNorm VGG) has no fused path here; networks.define_F builds "
-                             "VGGFeatureExtractor(use_bn=False)")
-        if not isinstance(m, nn.Conv2d):
-            raise ValueError("PerceptualLoss: unexpected %s at features.%d" % (type(m).__name__, i))
-        act = 1 if i + 1 < len(mods) and isinstance(mods[i + 1], nn.ReLU) else 0
-        i += 1 + act
-        pooled = i < len(mods) and isinstance(mods[i], nn.MaxPool2d)
-        i += int(pooled)
-        plan.append((m, act, pooled))
-    if not plan or plan[-1][2]:
+def _perceptual_plan(netF):
+    """_vgg_plan(netF), if PerceptualLoss has kernels for all of it."""
+    plan = _vgg_plan(netF, "PerceptualLoss")
+    if any(bn is not None for _, bn, _, _ in plan):
+        raise ValueError("PerceptualLoss: use_bn=True (BatchNorm VGG) has no fused path here; networks.define_F builds "
+                         "VGGFeatureExtractor(use_bn=False)")
+    if not plan or plan[-1][3]:
         raise ValueError("PerceptualLoss: feature_layer must end on a conv or a ReLU (a trailing MaxPool2d is not supported)")
     return plan
 
@@ -501,35 +511,23 @@ class _PerceptualLossFn(torch.autograd.Function):
     def _pass(lib, netF, plan, x, prec, flags, keep):
         B, _, H, W = x.shape
         dev = x.device
-        st = torch.cuda.current_stream(dev).cuda_stream
-        stream = C.c_void_p(st)
+        stream = _stream(dev)
         y = torch.empty(B, H, W, 4, device=dev, dtype=torch.float32)
         norm = netF.use_input_norm
         rc = lib.hcf_aux_input_norm(x.data_ptr(), netF.mean.data_ptr() if norm else None, netF.std.data_ptr() if norm else None,
                                     B, H, W, y.data_ptr(), stream)
         _lib.check(rc, None, "hcf_aux_input_norm")
         tape = []
-        for conv, act, pooled in plan:
-            cout, cin = conv.out_channels, conv.in_channels
-            w, b = conv.weight.contiguous(), conv.bias
-            z = torch.empty(B, H, W, cout, device=dev, dtype=torch.float32)       # VGG19 widths are multiples of 4
-            need = lib.hcf_aux_conv2d_workspace(cin, cout, 3, B, H, W)
-            key = (dev.index, st, cin, cout, 3, B, H, W)                           # _ConvNHWC's key: the two paths share workspaces
-            wk = netF._work.get(key)
-            if wk is None or wk.numel() < need or wk.device != dev:
-                wk = torch.zeros(need, dtype=torch.uint8, device=dev)
-                netF._work[key] = wk
-            flags.append(wk)
-            rc = lib.hcf_aux_conv2d(y.data_ptr(), y.shape[3], cin, B, H, W, w.data_ptr(), None if b is None else b.contiguous().data_ptr(),
-                                    cout, 3, act, z.data_ptr(), cout, C.c_void_p(wk.data_ptr()), wk.numel(), prec, stream)
-            _lib.check(rc, None, "hcf_aux_conv2d")
+        for conv, _, relu, pooled in plan:
+            cout, w = conv.out_channels, conv.weight.contiguous()
+            z, wk = _conv_forward(y, w, conv.bias, int(relu), prec, netF._work, flags)       # VGG19 widths are multiples of 4
             if keep:
-                tape.append((y, z if (act or pooled) else None, w, wk))
+                tape.append((y, z if (relu or pooled) else None, w, wk))
             y = z
             if pooled:
                 if H < 2 or W < 2:
                     raise ValueError("PerceptualLoss: the input is too small for the %d max-pools of this feature_layer"
-                                     % sum(p for _, _, p in plan))
+                                     % sum(p for _, _, _, p in plan))
                 p = torch.empty(B, H // 2, W // 2, cout, device=dev, dtype=torch.float32)
                 rc = lib.hcf_aux_maxpool2(y.data_ptr(), cout, cout, B, H, W, p.data_ptr(), cout, stream)
                 _lib.check(rc, None, "hcf_aux_maxpool2")
@@ -541,32 +539,21 @@ class _PerceptualLossFn(torch.autograd.Function):
         lib = _lib.load()
         need_grad = ctx.needs_input_grad[0]
         xf, xr = fake.detach().to(torch.float32).contiguous(), real.detach().to(torch.float32).contiguous()
-        prec = _PREC[netF._prec[0]]
+
+        def both(prec, flags):                                 # the real pass keeps nothing
+            fr, _ = _PerceptualLossFn._pass(lib, netF, plan, xr, prec, flags, False)
+            return (fr,) + _PerceptualLossFn._pass(lib, netF, plan, xf, prec, flags, need_grad)
+
         with torch.cuda.device(fake.device):
-            stream = C.c_void_p(torch.cuda.current_stream(fake.device).cuda_stream)
-            while True:
-                flags = []
-                fr, _ = _PerceptualLossFn._pass(lib, netF, plan, xr, prec, flags, False)
-                ff, tape = _PerceptualLossFn._pass(lib, netF, plan, xf, prec, flags, need_grad)
-                if prec != 1:
-                    break
-                uniq = list({id(f): f for f in flags}.values())
-                if not bool(torch.stack([f[:4].view(torch.int32)[0] for f in uniq]).any()):    # the one sync of an f16x3 call
-                    break
-                for f in uniq:                                # an activation left the f16 range: redo both passes exactly
-                    f[:4].zero_()
-                prec = 0
+            stream = _stream(fake.device)
+            fr, ff, tape = _range_redo(both, _PREC[netF._prec[0]])
             n = ff.numel()
-            need = lib.hcf_aux_feature_loss_workspace(n)
-            key = ("fea", fake.device.index, stream.value)
-            wk = netF._work.get(key)
-            if wk is None or wk.numel() < need:
-                wk = torch.empty(need, dtype=torch.uint8, device=fake.device)
-                netF._work[key] = wk
+            wk = _workspace(netF._work, ("fea", fake.device.index, stream.value), lib.hcf_aux_feature_loss_workspace(n),
+                            fake.device, zeroed=False)
             loss = torch.empty((), device=fake.device, dtype=torch.float32)
             gfea = torch.empty_like(ff) if need_grad else None
             rc = lib.hcf_aux_feature_loss(ff.data_ptr(), fr.data_ptr(), n, kind, loss.data_ptr(),
-                                          None if gfea is None else gfea.data_ptr(), C.c_void_p(wk.data_ptr()), wk.numel(), stream)
+                                          _ptr(gfea), wk.data_ptr(), wk.numel(), stream)
             _lib.check(rc, None, "hcf_aux_feature_loss")
         ctx.tape, ctx.gfea, ctx.plan, ctx.netF = tape, gfea, plan, netF
         ctx.in_meta = (tuple(fake.shape), fake.dtype)
@@ -580,10 +567,10 @@ class _PerceptualLossFn(torch.autograd.Function):
         g = ctx.gfea * gout                                    # a fresh tensor: the in-place activation backward below owns it
         dev = g.device
         with torch.cuda.device(dev):
-            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            for (conv, act, pooled), (x, y, w, wk) in zip(reversed(plan), reversed(ctx.tape)):
-                _, H, W, cs = x.shape
-                cout, cin = conv.out_channels, conv.in_channels
+            stream = _stream(dev)
+            for (conv, _, relu, pooled), (x, y, w, wk) in zip(reversed(plan), reversed(ctx.tape)):
+                _, H, W, _ = x.shape
+                cout, act = conv.out_channels, int(relu)
                 if pooled:
                     gpre = torch.empty(B, H, W, cout, device=dev, dtype=torch.float32)
                     rc = lib.hcf_aux_maxpool2_act_backward(g.data_ptr(), cout, y.data_ptr(), cout, cout, B, H, W, act, gpre.data_ptr(),
@@ -594,9 +581,7 @@ class _PerceptualLossFn(torch.autograd.Function):
                     rc = lib.hcf_aux_act_backward(g.data_ptr(), y.data_ptr(), act, g.numel(), g.data_ptr(), stream)
                     _lib.check(rc, None, "hcf_aux_act_backward")
                 dx = torch.empty_like(x)                       # channels [0, cin) written; the 4th channel of the image layer is never read
-                rc = lib.hcf_aux_conv2d_backward(x.data_ptr(), cs, cin, B, H, W, w.data_ptr(), cout, 3, g.data_ptr(), cout,
-                                                 dx.data_ptr(), cs, None, C.c_void_p(wk.data_ptr()), wk.numel(), 0, stream)
-                _lib.check(rc, None, "hcf_aux_conv2d_backward")
+                _conv_backward(x, w, g, dx, None, wk, 0)
                 g = dx
             gx = torch.empty(B, 3, H0, W0, device=dev, dtype=torch.float32)
             rc = lib.hcf_aux_input_norm_backward(g.data_ptr(), netF.std.data_ptr() if netF.use_input_norm else None, B, H0, W0,
@@ -624,7 +609,7 @@ class PerceptualLoss(nn.Module):
             raise TypeError("PerceptualLoss: netF must be a hcflow_amd.gan.VGGFeatureExtractor, got %s" % type(netF).__name__)
         if criterion not in _CRITERIA:
             raise ValueError("PerceptualLoss: criterion must be one of %s, got %r" % (sorted(_CRITERIA), criterion))
-        _vgg_plan(netF)                                       # raises ValueError for use_bn=True
+        _perceptual_plan(netF)                                # raises ValueError for use_bn=True
         self.netF = netF
         self.kind = _CRITERIA[criterion]
 
@@ -637,8 +622,8 @@ class PerceptualLoss(nn.Module):
         if fake_H.dim() != 4 or fake_H.shape[1] != 3 or fake_H.shape != real_H.shape or fake_H.device != real_H.device:
             raise ValueError("PerceptualLoss: fake_H and real_H must be [B,3,H,W] of one shape on one device, got %s and %s"
                              % (tuple(fake_H.shape), tuple(real_H.shape)))
-        plan = _vgg_plan(self.netF)                           # per call: a DataParallel replica has its own conv modules
-        convs = [c for c, _, _ in plan]
+        plan = _perceptual_plan(self.netF)                    # per call: a DataParallel replica has its own conv modules
+        convs = [c for c, _, _, _ in plan]
         if any(c.weight.requires_grad or (c.bias is not None and c.bias.requires_grad) for c in convs):
             raise ValueError("PerceptualLoss: the VGG weights must be frozen (requires_grad=False), no weight gradient is computed")
         if convs[0].weight.device != fake_H.device:

@@ -119,6 +119,37 @@ def test_vgg_features_match_stock_pytorch_ops(precision):
     assert float(err.norm()) <= 5e-2 * float(xd.grad.norm()), (float(err.norm()), float(xd.grad.norm()))
 
 
+@pytest.mark.parametrize("precision", ["exact", "f16x3"])
+@pytest.mark.parametrize("use_bn,feature_layer", [(True, 6), (True, 8), (True, 9), (False, 4)])
+def test_vgg_stacks_with_batchnorm_or_a_trailing_pool_match_stock_pytorch_ops(use_bn, feature_layer, precision):
+    """The branches of VGGFeatureExtractor's walk that feature_layer=34, use_bn=False never takes: BatchNorm between a conv and
+    its ReLU (eval() mode, so the ReLU is NOT fused into the conv), and a stack that ends on a max-pool (use_bn=True: 6,
+    use_bn=False: 4), on a BatchNorm (8) or on the ReLU behind one (9). Features and the gradient that reaches the input."""
+    torch.manual_seed(13)
+    net = gan.VGGFeatureExtractor(feature_layer=feature_layer, use_bn=use_bn, use_input_norm=True, device=torch.device("cuda")).cuda().eval()
+    net.set_precision(precision)
+    with torch.no_grad():
+        for m in net.features:
+            if isinstance(m, nn.Conv2d):                    # variance-preserving weights, as in the test above
+                nn.init.kaiming_normal_(m.weight, nonlinearity="relu")
+                m.bias.normal_(0, 0.05)
+            elif isinstance(m, nn.BatchNorm2d):             # non-trivial running statistics
+                m.running_mean.normal_(0, 0.1)
+                m.running_var.uniform_(0.5, 1.5)
+    assert type(net.features[feature_layer]) is {6: nn.MaxPool2d, 8: nn.BatchNorm2d, 9: nn.ReLU, 4: nn.MaxPool2d}[feature_layer]
+    ref = copy.deepcopy(net).double()
+    x = torch.rand(2, 3, 16, 24, device="cuda", requires_grad=True)
+    xd = x.detach().double().requires_grad_(True)
+    fea = net(x)
+    want = ref.features((xd - ref.mean) / ref.std)
+    assert fea.shape == want.shape
+    assert maxdiff(fea, want) <= 1e-4 * max(1.0, float(want.abs().max()))
+    fea.square().sum().backward()
+    want.square().sum().backward()
+    err = (x.grad.double() - xd.grad)
+    assert float(err.norm()) <= 5e-2 * float(xd.grad.norm()), (float(err.norm()), float(xd.grad.norm()))
+
+
 @pytest.mark.parametrize("cin,cout,H,W,act", [(64, 64, 64, 96, 0), (64, 64, 64, 96, 1), (128, 128, 32, 48, 2), (3, 64, 64, 96, 1),
                                                (512, 512, 8, 12, 1), (64, 128, 33, 47, 1), (256, 64, 16, 24, 0)])
 def test_aux_conv_op_matches_torch(cin, cout, H, W, act):
