@@ -10,6 +10,9 @@
 //   conv backward = epilogue backward in place on the output gradient (-> d pre-activation, bias / logs sums)
 //                 + weight gradient (hcf_conv_wgrad.hip) + data gradient = the forward conv kernel on transposed,
 //                   tap-flipped weight packs, accumulating through the residual slot of its epilogue.
+// A data-gradient conv whose output is the complete dL/dy of ONE producer conv (dense blocks in gather form, the FCN chains) may
+// apply that conv's epilogue backward in its own epilogue (ConvArgs::fb_y). Its record runs before the producer's, so it decides
+// alone and writes down what it did (Tape::epi_done); the producer's record reads that and does whatever is left.
 // Precision: hcf_set_precision(F16X3) puts the forward and the 3x3 data-gradient convs on the split kernels (the latter
 // with per-tensor power-of-two scaling: gradients of 1e-8 are below the split's absolute floor); the weight gradient
 // always runs on fp32 MFMA.
@@ -29,6 +32,10 @@
   struct Tape {
     Arena a, g;                                      // activations; gradients (one memset clears them before the backward pass)
     std::vector<std::function<void()>> recs;         // one closure per taped op, run in reverse by the backward pass
+    // One slot per taped conv: the rows of partial sums its epilogue backward has already left in this backward pass, written by the
+    // record whose data-gradient conv applied it in its own epilogue (ConvLink; that record runs first). 0: not done, the conv's own
+    // record launches conv_epilogue_bwd.
+    std::vector<int> epi_done;
     std::vector<const float*> late_bufs;             // gradient buffers of the conditional features taped in this pass
     bool valid = false;
     bool f16 = false;                                // the taped pass completed on the f16x3 kernels (slot 0 may have fallen back to the exact ones while slot 1 did not)
@@ -353,17 +360,14 @@
   // K order = the gradient slab's channel order [conv m+1 .. conv 4] followed by conv 5's gradient tensor.
   static bool rdb_gather_off() { return getenv("HCF_NO_DGRAD_GATHER") != nullptr; }     // A/B knob, read when an engine prepares for training
   static bool rdb_dgrad_wino_off() { return getenv("HCF_NO_DGRAD_WINO") != nullptr; }    // likewise: gather convs stay on the direct scaled kernel
-  // Does the gather conv of x_m of this block run on the Winograd kernels at this size? Decided identically by the record that launches
-  // it and by the record whose epilogue backward it fuses (the rows of partial sums differ: one per block of the launch).
-  // HCF_DGRAD_WINO_MIN_PIX (default 4 096 = 64 x 64: at 40 x 40 both forms are one 24 us round) = smallest H * W that takes it.
-  bool rdb_dgrad_wino(const Rdb* rdb, int m, int H, int W) const {
-    if (!rdb || m < 0 || m > 4 || !tape->bwd.f16 || !rdb->gtw[m] || (long long)H * W < tape->bwd.dgrad_wino_min_pix) return false;
+  // Policy of the record that launches the gather conv of x_m of this block: the Winograd pack it should try first at this size, or
+  // null. HCF_DGRAD_WINO_MIN_PIX (default 4 096 = 64 x 64: at 40 x 40 both forms are one 24 us round) = smallest H * W that takes it.
+  const float* rdb_dgrad_wino(const Rdb& rdb, int m, int H, int W) const {
+    if (!tape->bwd.f16 || !rdb.gtw[m] || (long long)H * W < tape->bwd.dgrad_wino_min_pix) return nullptr;
     // (the Winograd kernels address their sources with 31-bit byte offsets: the widest one is the block's 4 gc-channel gradient slab)
-    if ((long long)B_ * H * W * std::max(4 * cfg.rrdb_gc, cfg.rrdb_nf) * 4 >= 0x7fffe000LL) return false;
-    return conv_wino_rounds_ok(B_, H, W, m == 0 ? cfg.rrdb_nf / 32 : cfg.rrdb_gc / 32);
-  }
-  int rdb_dgrad_rows(const Rdb* rdb, int m, int H, int W) const {
-    return rdb_dgrad_wino(rdb, m, H, W) ? conv_wino_grid(B_, H, W, 1) : conv_tile_blocks(B_, H, W);
+    if ((long long)B_ * H * W * std::max(4 * cfg.rrdb_gc, cfg.rrdb_nf) * 4 >= 0x7fffe000LL) return nullptr;
+    // (launch_conv_wino refuses a ragged grid itself, but only after it has flipped its walk direction for the launch after it)
+    return conv_wino_rounds_ok(B_, H, W, m == 0 ? cfg.rrdb_nf / 32 : cfg.rrdb_gc / 32) ? rdb.gtw[m] : nullptr;
   }
   void make_rdb_gather_packs(Rdb& r) {
     const int nf = cfg.rrdb_nf, gc = cfg.rrdb_gc;
@@ -621,6 +625,28 @@
   }
 
   // ---- conv: forward + tape ---------------------------------------------------------------------------------------
+  // What a conv's record knows about its neighbours in the backward pass: the one declaration, filled by t_rdb and t_coupling_net,
+  // handed to t_conv (TConvOpt::link) and embedded in the record.
+  struct ConvLink {
+    // The producer of this conv's input, where that input has no other reader (an FCN's conv k-1 for conv k; conv m of a dense block
+    // for the gather conv of x_m): this conv's data gradient is its complete dL/dy, and in the f16x3 backward may apply its epilogue
+    // backward -- activation, learned scale, both partial sums, max -- in its own epilogue. It then writes the rows it left in
+    // prev_part into Tape::epi_done[prev_slot], and prev's record, which runs later, skips its own launch. null: no such producer.
+    const Conv* prev;
+    View prev_y;               // its forward output
+    float *prev_part, *prev_gmax;
+    int prev_slot;
+    float* gmax;               // max |dL/d pre-activation| of this conv (gradient arena: cleared with the gradients)
+    float* part;               // per-block partial sums of its epilogue backward (gradient arena). The caller allocates both where a
+                               // later conv names them as prev_*, sized for the grid of any form; null: t_conv does
+    // conv m + 1 of a dense block whose data gradients run in gather form (struct Rdb): after this conv's epilogue backward the
+    // gradient of x_m is complete -> ONE conv over gA = slab gradient channels [m gc, 4 gc) and gB = conv 5's gradient tensor
+    const Rdb* rdb;
+    int m;
+    View gA, gB, gT;           // gT: where dL/dx_m accumulates
+    float* gmax2;              // the block's five slots; [m]: max |dL/d pre-activation| over this conv and the block's later ones (= what
+                               // gA / gB hold when dL/dx_m is gathered), each folding in [m + 1]; a fused gather conv carries on [m - 1]
+  };
   struct ConvRec {
     const Conv* cv;
     View src[kMaxSrc], gsrc[kMaxSrc];
@@ -629,45 +655,83 @@
     View y, gy, g1, g2;
     bool has1, has2;
     float rs1, rs2;
-    float* gmax;               // max |dL/d pre-activation| of this conv (gradient arena: cleared with the gradients)
-    float* part;               // per-block partial sums of the epilogue backward (gradient arena)
-    // conv m + 1 of a dense block whose data gradients run in gather form (struct Rdb): after this conv's epilogue backward the
-    // gradient of x_m is complete -> ONE conv over gA = slab gradient channels [m gc, 4 gc) and gB = conv 5's gradient tensor
-    const Rdb* rdb;
-    int rdb_m;
-    View gA, gB, gT;           // gT: where dL/dx_m accumulates
-    float* gmax2;              // max |dL/d pre-activation| over this conv and the block's later ones (= what gA / gB hold when
-                               // dL/dx_m is gathered): one slot per conv, each folding in the next conv's (gmax2_next)
-    float* gmax2_next;         // nullptr for the block's last conv
-    float* gmax2_prev;         // the slot of the conv before (nullptr for the first)
-    // f16x3 backward: the gather conv of x_m (m >= 1) also applies the epilogue backward of the conv that produced x_m (conv m:
-    // LeakyReLU, no residuals) in its epilogue -- prev_* are that conv's forward output, partial-sum rows and max slot -- and conv m's
-    // own record then skips its epilogue-backward launch (own_fused). Both records evaluate rdb_fuse_ok() to the same answer.
-    View prev_y;
-    float *prev_part, *prev_gmax;
-    int own_fused;             // this conv's output is a growth tensor of a gathered block (conv index 0..3)
     int late_mask;             // bit i: source i's gradient is a conditional-feature buffer read in front of its net's backward (dg_stream)
-    // FCN chain (t_coupling_net): conv k's data gradient w.r.t. its single input completes dL/dy of conv k-1 (next_cv of that record),
-    // whose epilogue backward -- activation, ActNorm scale, both partial sums, max -- it applies in its own epilogue (prev_cv, prev_y,
-    // prev_part, prev_gmax above). Both records evaluate gen_fuse_ok(consumer conv).
-    const Conv* next_cv;
-    const Conv* prev_cv;
+    int slot;                  // this conv's entry of Tape::epi_done
+    ConvLink k;                // k.gmax, k.part: always set (t_conv allocates what the caller did not)
   };
-  bool rdb_fuse_ok(const Rdb* rdb, int m) const {
-    if (tape->bwd.epi_fuse_off || !rdb || m < 1 || m > 4 || !tape->bwd.f16 || !rdb->gt[m].wpack16 || (cfg.rrdb_gc & 3)) return false;
-    const Conv& pc = rdb->c[m - 1];                    // the producer of x_m: LeakyReLU(conv + bias), no learned output scale
+  // Policy, evaluated by the consumer's record alone: should the gather conv of x_m (m >= 1) also apply the epilogue backward of the
+  // conv that produced x_m? HCF_NO_EPI_FUSE: no (A/B knob). Whether a launch takes the fused form is the launchers' business.
+  bool rdb_fuse_ok(const Rdb& rdb, int m) const {
+    if (tape->bwd.epi_fuse_off || m < 1 || !tape->bwd.f16 || !rdb.gt[m].wpack16 || (cfg.rrdb_gc & 3)) return false;
+    const Conv& pc = rdb.c[m - 1];                     // the producer of x_m: LeakyReLU(conv + bias), no learned output scale
     return pc.act == ACT_LRELU && pc.lkey.empty();      // (no logs key: its scale array is all ones)
   }
-  // rows of partial sums a fused epilogue backward leaves (= the scaled f16x3 conv's grid, its strip walk included); the
-  // buffers are sized for the larger per-image grid
+  // rows of partial sums a fused epilogue backward on the scaled f16x3 kernel leaves (= its grid, the strip walk included)
   static int conv_tile_blocks(int B, int H, int W) { int sw = 0, th = 8; return conv_f16x3_scaled_blocks(B, H, W, &sw, &th); }
+  // Likewise for an FCN conv's data gradient and the conv before it (HCF_NO_FCN_FUSE: the second A/B knob): the input has one
+  // reader and one <= 64-channel pack.
   bool gen_fuse_ok(const Conv& consumer) const {
     return !tape->bwd.epi_fuse_off && !tape->bwd.fcn_fuse_off && tape->bwd.f16 && consumer.nsrc == 1 && consumer.tpacks.size() == 1 && consumer.tpacks[0].wpack16 &&
            (consumer.taps == 9 || consumer.taps == 1) && (consumer.src_n[0] & 3) == 0 && consumer.src_n[0] <= 64;
   }
 
+  // One data-gradient conv: a conv over dL/dpre (`src`) with a transposed, tap-flipped pack -- `tp`, `wino`: the same pack in
+  // Winograd form where the caller wants that tried first, else null -- unit bias and scale, no activation, into `out` (`acc`: added
+  // to it through the residual slot) on stream `s`. f16x3 backward: the scaled kernels, `in_max` = the slot of max |src|; the exact
+  // kernel where they refuse. `k` non-null: the caller wants the epilogue backward of k->prev, whose dL/dy `out` then is (no other
+  // writer: plain store), done in this launch's epilogue. Forms in order: fused Winograd, fused scaled, Winograd, scaled, exact.
+  // Returns the rows of partial sums a fused launch left in k->prev_part (= its grid); 0: not fused, k->prev's record does its own.
+  int launch_dgrad(const View* src, int nsrc, int H, int W, int taps, const Conv::TPack& tp, const float* wino, View out, bool acc,
+                   float* in_max, const ConvLink* k, hipStream_t s) {
+    ConvArgs a;
+    memset(&a, 0, sizeof(a));
+    for (int i = 0; i < 3; ++i) a.src[i] = src[std::min(i, nsrc - 1)];
+    a.nsrc = nsrc;
+    a.B = B_; a.H = H; a.W = W;
+    a.wpack = tp.wpack; a.nchunk = tp.nchunk;
+    a.bias = unit_dev; a.scale = unit_dev + 256; a.act = ACT_NONE;
+    a.out = out;
+    if (acc) { a.res1 = out; a.rs1 = 1.f; }
+    int lr_ = HCF_ERR_UNSUPPORTED, rows = 0;
+    if (tape->bwd.f16 && tp.wpack16 && (taps == 9 || taps == 1) && rc == HCF_OK) {
+      ConvArgs f = a;
+      f.wpack = tp.wpack16;
+      f.ovf = ovf_flag;
+      f.zeros = reinterpret_cast<const float*>(ovf_flag) + 16;
+      f.in_max = in_max;
+      // the scaled forms of `c`; *grid (optional): the blocks of the one that answered
+      auto scaled = [&](const ConvArgs& c, int* grid) {
+        if (wino) {
+          ConvArgs wv = c;
+          wv.wpack = nullptr;
+          const int r = launch_conv_wino(wv, wino, s);
+          if (grid) *grid = conv_wino_grid(B_, H, W, 1);      // (the fused epilogue backward: the 32-channel kernel only)
+          if (r != HCF_ERR_UNSUPPORTED) return r;
+        }
+        if (grid) *grid = conv_tile_blocks(B_, H, W);
+        return launch_conv_f16x3(c, taps, s);
+      };
+      if (k) {
+        ConvArgs fb = f;
+        fb.res1 = mkview(nullptr, 0, 0, 0); fb.rs1 = 0.f;
+        fb.fb_y = k->prev_y; fb.fb_act = k->prev->act; fb.fb_part = k->prev_part; fb.fb_max = k->prev_gmax;
+        fb.fb_max2 = k->rdb ? k->gmax2 + k->m - 1 : nullptr;
+        if (!k->prev->lkey.empty()) { fb.fb_scale = k->prev->scale; fb.fb_zy = 1; }      // (no logs key: the scale array is all ones)
+        int grid = 0;
+        lr_ = scaled(fb, &grid);
+        if (lr_ == HCF_OK) rows = grid;
+      }
+      if (lr_ == HCF_ERR_UNSUPPORTED) lr_ = scaled(f, nullptr);
+    }
+    if (lr_ == HCF_ERR_UNSUPPORTED) { HCF_LAUNCH(launch_conv(a, taps, s)); }
+    else if (lr_ != HCF_OK) fail(lr_, "data-gradient conv launch failed");
+    return rows;
+  }
+
   void bwd_conv(const ConvRec& r) {
     const Conv& cv = *r.cv;
+    const ConvLink& k = r.k;
+    float* const gmax2 = k.rdb ? k.gmax2 + k.m : nullptr;
     EpiBwdArgs e;
     memset(&e, 0, sizeof(e));
     e.B = B_; e.H = r.H; e.W = r.W;
@@ -677,20 +741,18 @@
     e.sum_pre = gp(cv.bkey);
     e.sum_zy = cv.lkey.empty() ? nullptr : gp(cv.lkey);
     e.zy_mult = cv.l_mult;
-    e.absmax = r.gmax;
-    e.absmax2 = r.rdb ? r.gmax2 : nullptr;
-    e.carry2 = r.rdb ? r.gmax2_next : nullptr;
-    e.part = r.part;
-    if ((r.own_fused && rdb_fuse_ok(r.rdb, r.rdb_m + 1)) || (r.next_cv && gen_fuse_ok(*r.next_cv))) {
-      // dL/dpre, the partial sums and the maxima were left by the conv that completed this conv's dL/dy (the gather conv of conv
-      // index + 1's record; the FCN's next conv's data gradient)
-      const bool own = r.own_fused && rdb_fuse_ok(r.rdb, r.rdb_m + 1);
-      add_sum_job(r.part, own ? rdb_dgrad_rows(r.rdb, r.rdb_m + 1, r.H, r.W) : conv_tile_blocks(B_, r.H, r.W), cv.cout, cv.cout, e.sum_pre,
-                  e.sum_zy, cv.l_mult);
-    } else {
+    e.absmax = k.gmax;
+    e.absmax2 = gmax2;
+    e.carry2 = (k.rdb && k.m < 4) ? gmax2 + 1 : nullptr;
+    e.part = k.part;
+    int rows = tape->epi_done[r.slot];
+    if (!rows) {
+      // (else: dL/dpre, the partial sums and the maxima were left by the conv that completed this conv's dL/dy -- the gather conv of
+      //  conv index + 1's record; the FCN's next conv's data gradient)
       HCF_LAUNCH(launch_conv_epilogue_bwd(e, st));
-      add_sum_job(r.part, conv_epilogue_bwd_blocks(B_, r.H, r.W), cv.cout, cv.cout, e.sum_pre, e.sum_zy, cv.l_mult);
+      rows = conv_epilogue_bwd_blocks(B_, r.H, r.W);
     }
+    add_sum_job(k.part, rows, cv.cout, cv.cout, e.sum_pre, e.sum_zy, cv.l_mult);
     WgradArgs w;
     memset(&w, 0, sizeof(w));
     for (int i = 0; i < r.nsrc; ++i) w.src[i] = r.src[i];
@@ -699,49 +761,20 @@
     // weight gradient on the f16 matrix cores: only where the taped FORWARD of this very layer ran on the f16x3 kernels, whose
     // range check then covered X (run_conv: 3x3 / stand-alone 1x1 with an f16x3 pack); > 64 output channels ran exactly, their
     // inputs were never checked -> fp32 weight-gradient kernel
-    if (tape->bwd.f16 && tape->f16 && (cv.taps == 9 || cv.taps == 1) && cv.wpack16) w.g_max = r.gmax;
-    if (r.rdb) {
+    if (tape->bwd.f16 && tape->f16 && (cv.taps == 9 || cv.taps == 1) && cv.wpack16) w.g_max = k.gmax;
+    if (k.rdb) {
       if (!tape->bwd.inputs_only) rdb_wg.push_back(w); // the block's five weight gradients go out as one launch (flush_rdb_wgrad)
-      if (r.rdb_m == 0 && flush_rdb_wgrad() != HCF_OK) return;
+      if (k.m == 0 && flush_rdb_wgrad() != HCF_OK) return;
     } else {
       HCF_LAUNCH(run_wgrad(w));
     }
-    if (r.rdb) {                                       // gather form: dL/dx_m from every later conv of the block in one launch
-      const Conv::TPack& tp = r.rdb->gt[r.rdb_m];
-      if (!r.gT.p) return;
-      ConvArgs a;
-      memset(&a, 0, sizeof(a));
-      const bool hasA = r.gA.n > 0;
-      a.src[0] = hasA ? r.gA : r.gB; a.src[1] = r.gB; a.src[2] = r.gB;
-      a.nsrc = hasA ? 2 : 1;
-      a.B = B_; a.H = r.H; a.W = r.W;
-      a.wpack = tp.wpack; a.nchunk = tp.nchunk;
-      a.bias = unit_dev; a.scale = unit_dev + 256; a.act = ACT_NONE;
-      a.out = r.gT;
-      a.res1 = a.out; a.rs1 = 1.f;                      // accumulate (x_0 also feeds the block's residual path)
-      int lr_ = HCF_ERR_UNSUPPORTED;
-      const bool fuse = rdb_fuse_ok(r.rdb, r.rdb_m);
-      if (tape->bwd.f16 && tp.wpack16 && rc == HCF_OK) {
-        ConvArgs f = a;
-        f.wpack = tp.wpack16;
-        f.ovf = ovf_flag;
-        f.zeros = reinterpret_cast<const float*>(ovf_flag) + 16;
-        f.in_max = r.gmax2;
-        if (fuse) {                                    // x_m (m >= 1) has no other consumer: plain store + conv m's epilogue backward
-          f.res1 = mkview(nullptr, 0, 0, 0); f.rs1 = 0.f;
-          f.fb_y = r.prev_y; f.fb_act = ACT_LRELU; f.fb_part = r.prev_part; f.fb_max = r.prev_gmax; f.fb_max2 = r.gmax2_prev;
-        }
-        if (rdb_dgrad_wino(r.rdb, r.rdb_m, r.H, r.W)) {  // Winograd form of the same conv (scaled split, the fused epilogue backward in
-          ConvArgs wv = f;                             //  the 32-channel kernel's epilogue); refused launches fall through to the direct form
-          wv.wpack = nullptr;
-          lr_ = launch_conv_wino(wv, r.rdb->gtw[r.rdb_m], st);
-          if (lr_ == HCF_ERR_UNSUPPORTED && fuse) { fail(HCF_ERR_STATE, "internal: the Winograd gather conv refused a launch its partial-sum rows were planned for"); return; }
-        }
-        if (lr_ == HCF_ERR_UNSUPPORTED) lr_ = launch_conv_f16x3(f, 9, st);
-      }
-      if (fuse && lr_ != HCF_OK) { fail(HCF_ERR_STATE, "internal: the fused epilogue-backward form of a gather data-gradient conv was refused"); return; }
-      if (lr_ == HCF_ERR_UNSUPPORTED) { HCF_LAUNCH(launch_conv(a, 9, st)); }
-      else if (lr_ != HCF_OK) fail(lr_, "gather-form data-gradient conv launch failed");
+    if (k.rdb) {                                       // gather form: dL/dx_m from every later conv of the block in one launch,
+      if (!k.gT.p) return;                             //  accumulated (x_0 also feeds the block's residual path) unless fused
+      const View gs[2] = {k.gA, k.gB};
+      const int ns = k.gA.n > 0 ? 2 : 1;
+      const int done = launch_dgrad(gs + 2 - ns, ns, r.H, r.W, 9, k.rdb->gt[k.m], rdb_dgrad_wino(*k.rdb, k.m, r.H, r.W), k.gT, true, gmax2,
+                                    rdb_fuse_ok(*k.rdb, k.m) ? &k : nullptr, st);
+      if (done) tape->epi_done[k.prev_slot] = done;
       return;
     }
     bool dg_waits = false;
@@ -758,38 +791,12 @@
         ls = dg_stream.s;
         tape->bwd.dg_dirty = true;
       }
-      ConvArgs a;
-      memset(&a, 0, sizeof(a));
-      a.src[0] = r.gy; a.src[1] = r.gy; a.src[2] = r.gy;
-      a.src[0].up = 0;
-      a.nsrc = 1;
-      a.B = B_; a.H = r.H; a.W = r.W;
-      a.wpack = tp.wpack; a.nchunk = tp.nchunk;
-      a.bias = unit_dev; a.scale = unit_dev + 256; a.act = ACT_NONE;
-      if (up == 0) {
-        a.out = mkview(gs.p, gs.cs, gs.c0 + tp.c0, tp.n);
-        a.res1 = a.out; a.rs1 = 1.f;                // accumulate
-      } else {
-        a.out = mkview(r.uptmp[tp.src], ru4(r.src[tp.src].n), tp.c0, tp.n);
-      }
-      int lr_ = HCF_ERR_UNSUPPORTED;
-      if (tape->bwd.f16 && tp.wpack16 && (cv.taps == 9 || cv.taps == 1) && rc == HCF_OK) {
-        ConvArgs f = a;
-        f.wpack = tp.wpack16;
-        f.ovf = ovf_flag;
-        f.zeros = reinterpret_cast<const float*>(ovf_flag) + 16;
-        f.in_max = r.gmax;
-        const bool gfuse = r.prev_cv && gen_fuse_ok(cv);
-        if (gfuse) {                                   // the input has no other reader: plain store + the producer's epilogue backward
-          f.res1 = mkview(nullptr, 0, 0, 0); f.rs1 = 0.f;
-          f.fb_y = r.prev_y; f.fb_act = r.prev_cv->act; f.fb_part = r.prev_part; f.fb_max = r.prev_gmax; f.fb_max2 = nullptr;
-          f.fb_scale = r.prev_cv->scale; f.fb_zy = r.prev_cv->lkey.empty() ? 0 : 1;
-        }
-        lr_ = launch_conv_f16x3(f, cv.taps, ls);
-        if (gfuse && lr_ != HCF_OK) { fail(HCF_ERR_STATE, "internal: the fused epilogue-backward form of an FCN data-gradient conv was refused"); return; }
-      }
-      if (lr_ == HCF_ERR_UNSUPPORTED) { HCF_LAUNCH(launch_conv(a, cv.taps, ls)); }
-      else if (lr_ != HCF_OK) fail(lr_, "data-gradient conv launch failed");
+      View gy = r.gy;
+      gy.up = 0;
+      // accumulated into the source's gradient; an upsampled source: stored into its full-size scratch, pooled below
+      const View out = up == 0 ? mkview(gs.p, gs.cs, gs.c0 + tp.c0, tp.n) : mkview(r.uptmp[tp.src], ru4(r.src[tp.src].n), tp.c0, tp.n);
+      const int done = launch_dgrad(&gy, 1, r.H, r.W, cv.taps, tp, nullptr, out, up == 0, k.gmax, (k.prev && gen_fuse_ok(cv)) ? &k : nullptr, ls);
+      if (done) tape->epi_done[k.prev_slot] = done;
     }
     for (int i = 0; i < r.nsrc; ++i) {
       const int up = r.src[i].up;
@@ -801,25 +808,18 @@
     }
   }
 
-  struct RdbCtx { const Rdb* rdb; int m; View gA, gB, gT; float *gmax2, *gmax2_next, *gmax2_prev; View prev_y; float *prev_part, *prev_gmax, *own_part, *own_gmax; int own_fused; };
-  struct EpiLink {                                   // FCN chain, see ConvRec::next_cv
-    float *own_part, *own_gmax;                       // this conv's partial rows / max slot, allocated by the caller (null: t_conv allocates)
-    const Conv* next;                                 // the only reader of this conv's output
-    const Conv* prev; View prev_y; float *prev_part, *prev_gmax;      // the producer of this conv's single input
-  };
   struct TConvOpt {                                  // t_conv's optionals
     const VG* res1 = nullptr; float rs1 = 0.f;        // the residuals of the conv's epilogue (ConvOpt) with their gradient buffers
     const VG* res2 = nullptr; float rs2 = 0.f;
-    const RdbCtx* ctx = nullptr;
-    const EpiLink* link = nullptr;
+    const ConvLink* link = nullptr;
     bool already_run = false;                        // the caller has launched the forward conv (t_rdb): the record only
   };
-  void t_conv(const Conv& cv, std::vector<VG> in, int H, int W, VG out) { t_conv(cv, std::move(in), H, W, out, TConvOpt()); }
-  void t_conv(const Conv& cv, std::vector<VG> in, int H, int W, VG out, const TConvOpt& o) {
-    if (rc != HCF_OK) return;
+  // returns the conv's slot of Tape::epi_done: what the next conv's ConvLink::prev_slot wants (-1: a sizing run, nothing is taped)
+  int t_conv(const Conv& cv, std::vector<VG> in, int H, int W, VG out) { return t_conv(cv, std::move(in), H, W, out, TConvOpt()); }
+  int t_conv(const Conv& cv, std::vector<VG> in, int H, int W, VG out, const TConvOpt& o) {
+    if (rc != HCF_OK) return -1;
     const VG *const res1 = o.res1, *const res2 = o.res2;
     const float rs1 = o.rs1, rs2 = o.rs2;
-    const RdbCtx* const ctx = o.ctx; const EpiLink* const link = o.link;
     std::vector<View> srcs;
     for (const VG& s : in) srcs.push_back(s.v);
     ConvOpt fo;
@@ -843,22 +843,16 @@
     r.has1 = res1 != nullptr; r.has2 = res2 != nullptr;
     r.g1 = res1 ? res1->g : View(); r.g2 = res2 ? res2->g : View();
     r.rs1 = rs1; r.rs2 = rs2;
-    if (ctx) {
-      r.rdb = ctx->rdb; r.rdb_m = ctx->m; r.gA = ctx->gA; r.gB = ctx->gB; r.gT = ctx->gT; r.gmax2 = ctx->gmax2;
-      r.gmax2_next = ctx->gmax2_next; r.gmax2_prev = ctx->gmax2_prev;
-      r.prev_y = ctx->prev_y; r.prev_part = ctx->prev_part; r.prev_gmax = ctx->prev_gmax; r.own_fused = ctx->own_fused;
-      r.gmax = ctx->own_gmax; r.part = ctx->own_part;
-    } else if (link && link->own_part) {
-      r.gmax = link->own_gmax; r.part = link->own_part;
-    } else {
-      r.gmax = tape->g.alloc(1);
-      r.part = tape->g.alloc((size_t)conv_epilogue_bwd_blocks(B_, H, W) * 2 * cv.cout);
+    if (o.link) r.k = *o.link;
+    if (!r.k.part) {
+      r.k.gmax = tape->g.alloc(1);
+      r.k.part = tape->g.alloc((size_t)conv_epilogue_bwd_blocks(B_, H, W) * 2 * cv.cout);
     }
-    if (link) {
-      r.next_cv = link->next; r.prev_cv = link->prev;
-      if (link->prev) { r.prev_y = link->prev_y; r.prev_part = link->prev_part; r.prev_gmax = link->prev_gmax; }
-    }
-    if (!dry()) tape->recs.push_back([this, r]() { bwd_conv(r); });
+    if (dry()) return -1;
+    r.slot = (int)tape->epi_done.size();
+    tape->epi_done.push_back(0);
+    tape->recs.push_back([this, r]() { bwd_conv(r); });
+    return r.slot;
   }
 
   // ---- flow step --------------------------------------------------------------------------------------------------
@@ -876,19 +870,20 @@
     }
     if (s.fcn) {
       TB h1 = talloc(B_, H, W, s.hid), h2 = talloc(B_, H, W, s.hid);
-      // conv2's data gradient applies conv1's epilogue backward, conv3's applies conv2's (bwd_conv, gen_fuse_ok): conv1's and conv2's
-      // partial rows and max slots up front, sized for either form's grid
+      // conv2's data gradient may apply conv1's epilogue backward, conv3's conv2's (ConvLink): conv1's and conv2's partial rows and
+      // max slots up front, sized for either form's grid
       const size_t rows = (size_t)std::max(conv_epilogue_bwd_blocks(B_, H, W), conv_f16x3_scaled_blocks_max(B_, H, W)) * 2;
-      EpiLink l0, l1, l2;
-      memset(&l0, 0, sizeof(l0)); memset(&l1, 0, sizeof(l1)); memset(&l2, 0, sizeof(l2));
-      l0.own_part = tape->g.alloc(rows * s.c[0].cout); l0.own_gmax = tape->g.alloc(1); l0.next = &s.c[1];
-      l1.own_part = tape->g.alloc(rows * s.c[1].cout); l1.own_gmax = tape->g.alloc(1); l1.next = &s.c[2];
-      l1.prev = &s.c[0]; l1.prev_y = h1.v.v(0, s.hid); l1.prev_part = l0.own_part; l1.prev_gmax = l0.own_gmax;
-      l2.prev = &s.c[1]; l2.prev_y = h2.v.v(0, s.hid); l2.prev_part = l1.own_part; l2.prev_gmax = l1.own_gmax;
+      const TB* const hs[2] = {&h1, &h2};
+      ConvLink k[3];
+      memset(k, 0, sizeof(k));
+      for (int i = 0; i < 2; ++i) {
+        k[i].part = tape->g.alloc(rows * s.c[i].cout); k[i].gmax = tape->g.alloc(1);
+        k[i + 1].prev = &s.c[i]; k[i + 1].prev_y = hs[i]->v.v(0, s.hid); k[i + 1].prev_part = k[i].part; k[i + 1].prev_gmax = k[i].gmax;
+      }
       TConvOpt o;
-      o.link = &l0; t_conv(s.c[0], in, H, W, vg(h1, 0, s.hid), o);
-      o.link = &l1; t_conv(s.c[1], {vg(h1, 0, s.hid)}, H, W, vg(h2, 0, s.hid), o);
-      o.link = &l2; t_conv(s.c[2], {vg(h2, 0, s.hid)}, H, W, vg(ho, 0, s.f_out), o);
+      o.link = &k[0]; k[1].prev_slot = t_conv(s.c[0], in, H, W, vg(h1, 0, s.hid), o);
+      o.link = &k[1]; k[2].prev_slot = t_conv(s.c[1], {vg(h1, 0, s.hid)}, H, W, vg(h2, 0, s.hid), o);
+      o.link = &k[2]; t_conv(s.c[2], {vg(h2, 0, s.hid)}, H, W, vg(ho, 0, s.f_out), o);
     } else {
       TB grow = talloc(B_, H, W, 4 * s.hid);
       for (int i = 0; i < 5; ++i) {
@@ -955,23 +950,20 @@
   void t_rdb(const Rdb& r, VG xin, int H, int W, VG out, const VG* res2, float rs2) {
     const int gc = cfg.rrdb_gc, nf = cfg.rrdb_nf;
     TB grow = talloc(B_, H, W, 4 * gc);
-    RdbCtx ctx[5];
+    ConvLink k[5];
+    memset(k, 0, sizeof(k));
     if (r.gather) {
       float* const gmax2 = tape->g.alloc(5);
-      // every conv's max slot and partial-sum rows up front: the gather conv of x_m writes conv m's (fused epilogue backward)
+      // every conv's max slot and partial-sum rows up front, sized for the grid of any form: the gather conv of x_m may write conv m's
       const size_t rows = (size_t)std::max(conv_epilogue_bwd_blocks(B_, H, W), conv_f16x3_scaled_blocks_max(B_, H, W)) * 2;
-      float *gm[5], *pt[5];
-      for (int i = 0; i < 5; ++i) { gm[i] = tape->g.alloc(1); pt[i] = tape->g.alloc(rows * (i < 4 ? gc : nf)); }
-      for (int m = 0; m < 5; ++m) {                    // ctx[m]: the record of conv index m (its output: x_{m+1}), which gathers dL/dx_m
-        ctx[m].rdb = &r; ctx[m].m = m;
-        ctx[m].gmax2 = gmax2 + m; ctx[m].gmax2_next = m < 4 ? gmax2 + m + 1 : nullptr; ctx[m].gmax2_prev = m >= 1 ? gmax2 + m - 1 : nullptr;
-        ctx[m].gA = grow.g.v(m * gc, (4 - m) * gc);
-        ctx[m].gB = out.g; ctx[m].gB.n = nf;
-        ctx[m].gT = (m == 0) ? xin.g : grow.g.v((m - 1) * gc, gc);
-        ctx[m].own_part = pt[m]; ctx[m].own_gmax = gm[m]; ctx[m].own_fused = m < 4 ? 1 : 0;
-        ctx[m].prev_y = m >= 1 ? grow.v.v((m - 1) * gc, gc) : View();
-        ctx[m].prev_part = m >= 1 ? pt[m - 1] : nullptr;
-        ctx[m].prev_gmax = m >= 1 ? gm[m - 1] : nullptr;
+      for (int m = 0; m < 5; ++m) {                    // k[m]: the record of conv index m (its output: x_{m+1}), which gathers dL/dx_m
+        k[m].rdb = &r; k[m].m = m; k[m].gmax2 = gmax2;
+        k[m].gA = grow.g.v(m * gc, (4 - m) * gc);
+        k[m].gB = out.g; k[m].gB.n = nf;
+        k[m].gT = (m == 0) ? xin.g : grow.g.v((m - 1) * gc, gc);
+        k[m].gmax = tape->g.alloc(1); k[m].part = tape->g.alloc(rows * (m < 4 ? gc : nf));
+        if (m == 0) continue;
+        k[m].prev = &r.c[m - 1]; k[m].prev_y = grow.v.v((m - 1) * gc, gc); k[m].prev_part = k[m - 1].part; k[m].prev_gmax = k[m - 1].gmax;
       }
     }
     // forward: the block as the inference pass runs it (run_rdb: the fat pairs where they pay -- conv 2j+1 and the old-input part of
@@ -984,10 +976,10 @@
       std::vector<VG> in;
       in.push_back(xin);
       if (i > 0) in.push_back(vg(grow, 0, i * gc));
-      o.ctx = r.gather ? &ctx[i] : nullptr;
-      t_conv(r.c[i], in, H, W, vg(grow, i * gc, gc), o);
+      o.link = r.gather ? &k[i] : nullptr;
+      k[i + 1].prev_slot = t_conv(r.c[i], in, H, W, vg(grow, i * gc, gc), o);
     }
-    o.ctx = r.gather ? &ctx[4] : nullptr;
+    o.link = r.gather ? &k[4] : nullptr;
     o.res1 = &xin; o.rs1 = 0.2f; o.res2 = res2; o.rs2 = rs2;
     t_conv(r.c[4], {xin, vg(grow, 0, 4 * gc)}, H, W, out, o);
   }
@@ -1280,7 +1272,7 @@
     B_ = B;
     arena.top = 0;
     tape->g.top = 0;
-    if (!dry()) { tape->recs.clear(); tape->late_bufs.clear(); tape->mark = 0; tape->mid = false; }
+    if (!dry()) { tape->recs.clear(); tape->epi_done.clear(); tape->late_bufs.clear(); tape->mark = 0; tape->mid = false; }
   }
 
   // A taped pass of kind `kind` (Tape::kind) on the selected slot: sizing run, arenas, real run (+ exact re-run when an activation left
@@ -1385,6 +1377,7 @@
     tape->bwd.geps = (in.kind == 2) ? in.geps : nullptr;
     tape->bwd.n_geps = (in.kind == 2) ? in.n_geps : 0;
     for (long long& c : tape->bwd.counts) c = 0;
+    std::fill(tape->epi_done.begin(), tape->epi_done.end(), 0);      // (phase 1 above goes on with what phase 0 wrote down)
     tape->bwd.g_out_nchw = (in.kind == 2) ? in.gout : nullptr;
     tape->bwd.g_in_nchw = (in.kind == 2) ? in.gin : nullptr;
     tape->bwd.g_fwd_lr = (in.kind == 3) ? in.gout : nullptr;

@@ -694,25 +694,36 @@ def test_winograd_gather_data_gradients_equal_the_direct_form(fused, monkeypatch
     kernels (scaled split of the transformed gradients, the producer's epilogue backward in the 32-channel kernel's epilogue,
     hcf_conv_wino.h SC variants; transposed packs rebuilt on the device after optimiser steps). Same sums, another order: against
     the direct scaled kernel on the same steps (knob read at the start of each backward pass), with and without the fused epilogue
-    backward, before and after an optimiser step; the Winograd form is reproducible run to run."""
-    import numpy as np
-    from hcflow_amd import HCFlowNet_SR
+    backward, before and after an optimiser step; the Winograd form is reproducible run to run.
+    Second net: RRDB_gc = 64, whose growth tensors are too wide for the 32-channel kernel that carries the fused epilogue backward --
+    their gather convs fuse it on the direct scaled kernel (or not at all), conv 1's unfused gather conv takes the 64-channel Winograd
+    kernel. B = 2 at 48 x 80: maps of 24 x 40 and 12 x 20, ragged Winograd tiles in both directions."""
+    import dataclasses
     from hcflow_amd.config import preset
-    from tests.util import cached_params, spec_grads
-    cfg = preset("SR_4X_tiny")
-    g = torch.Generator().manual_seed(29)
-    hr = torch.rand(3, 3, 96, 160, generator=g).cuda()
-    lr = F.interpolate(hr, scale_factor=0.25, mode="bicubic", align_corners=False).clamp(0, 1)
-    noise = torch.rand(hr.shape, generator=g).cuda()
+    from tests.util import cached_params, make_params
     if fused:
         monkeypatch.delenv("HCF_NO_EPI_FUSE", raising=False)
     else:
         monkeypatch.setenv("HCF_NO_EPI_FUSE", "1")
+    cfg = preset("SR_4X_tiny")
+    _winograd_gather_against_direct(cfg, cached_params("SR_4X_tiny", 11), (3, 3, 96, 160), monkeypatch)
+    cfg = dataclasses.replace(cfg, rrdb_gc=64)
+    _winograd_gather_against_direct(cfg, make_params(cfg, 11), (2, 3, 48, 80), monkeypatch)
+
+
+def _winograd_gather_against_direct(cfg, params, hr_shape, monkeypatch):
+    import numpy as np
+    from hcflow_amd import HCFlowNet_SR
+    from tests.util import spec_grads
+    g = torch.Generator().manual_seed(29)
+    hr = torch.rand(*hr_shape, generator=g).cuda()
+    lr = F.interpolate(hr, scale_factor=0.25, mode="bicubic", align_corners=False).clamp(0, 1)
+    noise = torch.rand(hr.shape, generator=g).cuda()
     res = {}
     for form, minpix in (("wino", "0"), ("direct", "1000000000")):
         monkeypatch.setenv("HCF_DGRAD_WINO_MIN_PIX", minpix)
         net = HCFlowNet_SR(opt=cfg.to_opt(), step=0)
-        net.load_state_dict(cached_params("SR_4X_tiny", 11), strict=True)
+        net.load_state_dict(params, strict=True)
         for m in net.modules():
             if "ActNorm" in type(m).__name__:
                 m.inited = True
