@@ -42,6 +42,8 @@ SYMBOLS = [
     "hcf_train_backward_inverse_ex", "hcf_train_backward_counts", "hcf_op_prior_sample_backward",
     "hcf_aux_input_norm", "hcf_aux_input_norm_backward", "hcf_aux_maxpool2", "hcf_aux_maxpool2_act_backward",
     "hcf_aux_act_backward", "hcf_aux_feature_loss_workspace", "hcf_aux_feature_loss",
+    "hcf_train_backward_ex", "hcf_train_backward_rescale_ex", "hcf_train_encode_sr", "hcf_train_backward_encode",
+    "hcf_op_quant_logp_backward_lr", "hcf_op_prior_encode_logp_backward", "hcf_op_input_grad",
 ]
 
 
@@ -149,6 +151,13 @@ def load() -> C.CDLL:
     lib.hcf_train_forward_sr.argtypes = [vp, fp, fp, fp, fp, fp, fp, i32, i32, i32, vp]
     lib.hcf_train_backward.argtypes = [vp, f32, fp, i64, vp]
     lib.hcf_train_backward_phase.argtypes = [vp, i32, f32, fp, i64, vp]
+    lib.hcf_train_backward_ex.argtypes = [vp, f32, fp, i64, fp, fp, vp]
+    lib.hcf_train_backward_rescale_ex.argtypes = [vp, fp, fp, fp, fp, i64, fp, vp]
+    lib.hcf_train_encode_sr.argtypes = [vp, fp, fp, fp, C.POINTER(fp), i32, fp, i32, i32, i32, u32, vp]
+    lib.hcf_train_backward_encode.argtypes = [vp, fp, C.POINTER(fp), i32, fp, fp, i64, fp, vp]
+    lib.hcf_op_quant_logp_backward_lr.argtypes = [fp, fp, fp, fp, i32, i32, i32, f32, vp]
+    lib.hcf_op_prior_encode_logp_backward.argtypes = [fp, fp, fp, fp, fp, fp, i32, i32, i32, i32, i32, f32, vp]
+    lib.hcf_op_input_grad.argtypes = [fp, fp, i32, i32, i32, i32, i32, vp]
     lib.hcf_actnorm_init_request.argtypes = [vp, C.POINTER(C.c_char_p), i32]
     lib.hcf_get_param.argtypes = [vp, C.c_char_p, fp, i64]
     lib.hcf_op_conv2d.argtypes = [C.POINTER(fp), C.POINTER(i32), C.POINTER(i32), i32, i32, i32, i32, fp, fp, fp,

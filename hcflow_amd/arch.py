@@ -251,7 +251,9 @@ class FlowNet(nn.Module):
 class _SRNLLStep(torch.autograd.Function):
     """``_, nll = netG(hr=, lr=, reverse=False)`` with gradients (HCFlow_SR_model.py:195-199): the engine keeps the
     intermediate tensors of the forward pass in HBM (hcf_train_forward_sr) and produces d nll / d parameters for the
-    whole net in one call (hcf_train_backward); this Function only hands the flat gradient buffer to autograd."""
+    whole net in one call (hcf_train_backward_ex); this Function only hands the flat gradient buffer to autograd. An ``hr`` / ``lr``
+    that requires grad gets d nll / d hr, d nll / d lr beside the parameter gradients; with no parameter requiring grad the
+    backward pass is the input-gradient-only one (no gradient buffer, no parameter-gradient work)."""
 
     @staticmethod
     def forward(ctx, module, hr, lr, noise, *params):
@@ -270,6 +272,7 @@ class _SRNLLStep(torch.autograd.Function):
         _lib.check(rc, eng.handle, "hcf_train_forward_sr")
         ctx.eng, ctx.idx = eng, idx
         ctx.keep = (hr, lr, noise)                       # the engine's tape holds raw pointers to these
+        ctx.image_needs_grad = (bool(hr.requires_grad), bool(lr.requires_grad))
         ctx.meta = [(tuple(p.shape), p.numel(), bool(p.requires_grad)) for p in params]
         ctx.mark_non_differentiable(out_lr, logdet)
         return out_lr, nll.view(()), logdet
@@ -277,18 +280,75 @@ class _SRNLLStep(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_lr, g_nll, g_logdet):
         eng, idx = ctx.eng, ctx.idx
-        total = sum(n for _, n, _ in ctx.meta)
-        flat = torch.empty(total, device=ctx.keep[0].device, dtype=torch.float32)
+        hr, lr, _ = ctx.keep
+        flat, total = _flat_grad_buffer(ctx.meta, hr.device)
+        g_hr = torch.empty_like(hr) if ctx.image_needs_grad[0] else None
+        g_lq = torch.empty_like(lr) if ctx.image_needs_grad[1] else None
         with torch.cuda.device(idx):
             _lib.check(eng.lib.hcf_train_select_tape(eng.handle, 0), eng.handle, "hcf_train_select_tape")
-            rc = eng.lib.hcf_train_backward(eng.handle, float(g_nll), flat.data_ptr(), total,
-                                            C.c_void_p(torch.cuda.current_stream(idx).cuda_stream))
-        _lib.check(rc, eng.handle, "hcf_train_backward")
-        grads, off = [], 0
-        for shape, n, need in ctx.meta:
-            grads.append(flat[off:off + n].view(shape) if need else None)
-            off += n
-        return (None, None, None, None) + tuple(grads)
+            rc = eng.lib.hcf_train_backward_ex(eng.handle, float(g_nll), None if flat is None else flat.data_ptr(), total,
+                                               None if g_hr is None else g_hr.data_ptr(), None if g_lq is None else g_lq.data_ptr(),
+                                               C.c_void_p(torch.cuda.current_stream(idx).cuda_stream))
+        _lib.check(rc, eng.handle, "hcf_train_backward_ex")
+        return (None, g_hr, g_lq, None) + _split_flat(flat, ctx.meta)
+
+
+def _flat_grad_buffer(meta, device):
+    """(flat parameter-gradient buffer, its length) of a backward pass, or (None, 0) when no parameter requires grad: the engine
+    then runs its input-gradient-only pass."""
+    if not any(need for _, _, need in meta):
+        return None, 0
+    total = sum(n for _, n, _ in meta)
+    return torch.empty(total, device=device, dtype=torch.float32), total
+
+
+def _split_flat(flat, meta):
+    grads, off = [], 0
+    for shape, n, need in meta:
+        grads.append(flat[off:off + n].view(shape) if need else None)
+        off += n
+    return tuple(grads)
+
+
+class _SREncodeStep(torch.autograd.Function):
+    """``z, eps, logp = net.encode(hr)`` with the gradient w.r.t. ``hr`` (weights frozen): hcf_train_encode_sr keeps the tape,
+    hcf_train_backward_encode turns dL/d z, dL/d eps_l and dL/d logp (per sample) into dL/d hr. Outputs: (z, logp, *eps)."""
+
+    @staticmethod
+    def forward(ctx, module, hr, noise):
+        dev = hr.device
+        eng, idx = module._engine_for(dev)
+        cfg = module.cfg
+        B, _, H, W = hr.shape
+        h, w = H // cfg.scale, W // cfg.scale
+        z = torch.empty(B, 3, h, w, device=dev)
+        eps = [torch.empty(sh, device=dev) for sh in eps_shapes(cfg, B, h, w)]
+        logp = torch.empty(B, device=dev)
+        arr = (C.c_void_p * len(eps))(*[e.data_ptr() for e in eps])
+        with torch.cuda.device(idx):
+            _lib.check(eng.lib.hcf_train_select_tape(eng.handle, 0), eng.handle, "hcf_train_select_tape")
+            rc = eng.lib.hcf_train_encode_sr(eng.handle, hr.data_ptr(), None if noise is None else noise.data_ptr(), z.data_ptr(),
+                                             arr, len(eps), logp.data_ptr(), B, H, W, 0, module._stream(idx))
+        _lib.check(rc, eng.handle, "hcf_train_encode_sr")
+        ctx.eng, ctx.idx = eng, idx
+        ctx.keep = (hr, noise)                           # the engine's tape holds raw pointers to these
+        ctx.n_levels = len(eps)
+        return (z, logp) + tuple(eps)
+
+    @staticmethod
+    def backward(ctx, g_z, g_logp, *g_eps):
+        eng, idx = ctx.eng, ctx.idx
+        hr = ctx.keep[0]
+        gs = [None if g is None else g.to(torch.float32).contiguous() for g in (g_z, g_logp) + tuple(g_eps)]
+        arr = (C.c_void_p * ctx.n_levels)(*[None if g is None else g.data_ptr() for g in gs[2:]])
+        g_hr = torch.empty_like(hr)
+        with torch.cuda.device(idx):
+            _lib.check(eng.lib.hcf_train_select_tape(eng.handle, 0), eng.handle, "hcf_train_select_tape")
+            rc = eng.lib.hcf_train_backward_encode(eng.handle, None if gs[0] is None else gs[0].data_ptr(), arr, ctx.n_levels,
+                                                   None if gs[1] is None else gs[1].data_ptr(), None, 0, g_hr.data_ptr(),
+                                                   C.c_void_p(torch.cuda.current_stream(idx).cuda_stream))
+        _lib.check(rc, eng.handle, "hcf_train_backward_encode")
+        return None, g_hr, None
 
 
 # ---- the same step as TWO autograd nodes (gradient all-reduce overlapped with the backward pass) -----------------------------
@@ -437,10 +497,7 @@ class _SRReverseStep(torch.autograd.Function):
     def backward(ctx, g_out):
         eng, idx = ctx.eng, ctx.idx
         g_out = g_out.to(torch.float32).contiguous()
-        flat, total = None, 0
-        if any(need for _, _, need in ctx.meta):
-            total = sum(n for _, n, _ in ctx.meta)
-            flat = torch.empty(total, device=g_out.device, dtype=torch.float32)
+        flat, total = _flat_grad_buffer(ctx.meta, g_out.device)
         g_lr = torch.empty_like(ctx.keep[0]) if ctx.lr_needs_grad else None
         g_eps = [torch.empty_like(e) if need else None for e, need in zip(ctx.keep[1], ctx.eps_needs_grad)]
         arr = (C.c_void_p * ctx.n_levels)()
@@ -452,11 +509,7 @@ class _SRReverseStep(torch.autograd.Function):
                                                        total, None if g_lr is None else g_lr.data_ptr(), arr, ctx.n_levels,
                                                        C.c_void_p(torch.cuda.current_stream(idx).cuda_stream))
         _lib.check(rc, eng.handle, "hcf_train_backward_inverse_ex")
-        grads, off = [], 0
-        for shape, n, need in ctx.meta:
-            grads.append(flat[off:off + n].view(shape) if need else None)
-            off += n
-        return (None, g_lr, None, None, None, None) + tuple(g_eps) + tuple(grads)
+        return (None, g_lr, None, None, None, None) + tuple(g_eps) + _split_flat(flat, ctx.meta)
 
 
 class _RescaleForwardStep(torch.autograd.Function):
@@ -478,26 +531,24 @@ class _RescaleForwardStep(torch.autograd.Function):
                                                    B, H, W, 0 if clamp else _lib.FLAG_NO_CLAMP, module._stream(idx))
         _lib.check(rc, eng.handle, "hcf_train_forward_rescale")
         ctx.eng, ctx.idx, ctx.keep = eng, idx, hr
+        ctx.hr_needs_grad = bool(hr.requires_grad)
         ctx.meta = [(tuple(p.shape), p.numel(), bool(p.requires_grad)) for p in params]
         return out_lr, z1, z2
 
     @staticmethod
     def backward(ctx, g_lr, g_z1, g_z2):
         eng, idx = ctx.eng, ctx.idx
-        total = sum(n for _, n, _ in ctx.meta)
         gs = [None if g is None else g.to(torch.float32).contiguous() for g in (g_lr, g_z1, g_z2)]
-        flat = torch.empty(total, device=ctx.keep.device, dtype=torch.float32)
+        flat, total = _flat_grad_buffer(ctx.meta, ctx.keep.device)
+        g_hr = torch.empty_like(ctx.keep) if ctx.hr_needs_grad else None
         with torch.cuda.device(idx):
             _lib.check(eng.lib.hcf_train_select_tape(eng.handle, 0), eng.handle, "hcf_train_select_tape")
-            rc = eng.lib.hcf_train_backward_rescale(eng.handle, *[None if g is None else g.data_ptr() for g in gs],
-                                                    flat.data_ptr(), total,
-                                                    C.c_void_p(torch.cuda.current_stream(idx).cuda_stream))
-        _lib.check(rc, eng.handle, "hcf_train_backward_rescale")
-        grads, off = [], 0
-        for shape, n, need in ctx.meta:
-            grads.append(flat[off:off + n].view(shape) if need else None)
-            off += n
-        return (None, None, None) + tuple(grads)
+            rc = eng.lib.hcf_train_backward_rescale_ex(eng.handle, *[None if g is None else g.data_ptr() for g in gs],
+                                                       None if flat is None else flat.data_ptr(), total,
+                                                       None if g_hr is None else g_hr.data_ptr(),
+                                                       C.c_void_p(torch.cuda.current_stream(idx).cuda_stream))
+        _lib.check(rc, eng.handle, "hcf_train_backward_rescale_ex")
+        return (None, g_hr, None) + _split_flat(flat, ctx.meta)
 
 
 _POOL = []
@@ -798,6 +849,16 @@ class _EngineModule(nn.Module):
     def _wants_grad(self):
         return torch.is_grad_enabled() and any(p.requires_grad for _, p in self._tensors())
 
+    @staticmethod
+    def _image_wants_grad(*images):
+        """grad mode is on and one of the given image tensors requires grad: the taped path runs also with every weight frozen"""
+        return torch.is_grad_enabled() and any(torch.is_tensor(t) and t.requires_grad for t in images)
+
+    @staticmethod
+    def _link(t, device):
+        """as _prep, but the autograd link to the caller's tensor survives"""
+        return t.to(device=device, dtype=torch.float32).contiguous()
+
     def _params(self):
         return [p for _, p in self._tensors()]
 
@@ -1096,8 +1157,10 @@ class HCFlowNet_SR(_EngineModule):
     def normal_flow_diracLR(self, hr, lr, u=None, step=None, training=True, noise=None, return_internals=False):
         """hr -> (clamp(LR^), nll)   (HCFlowNet_SR_arch.py:47-67). ``noise``: optional injected U[0,1)
         tensor replacing the internal torch.rand draw (:52). With autograd enabled on trainable parameters the
-        pass runs through the engine's taped training path and ``nll.backward()`` works (HCFlow_SR_model.py:195-199)."""
-        if self._wants_grad() and not return_internals:
+        pass runs through the engine's taped training path and ``nll.backward()`` works (HCFlow_SR_model.py:195-199); so it
+        does when ``hr`` or ``lr`` requires grad, also with every weight frozen: ``nll.backward()`` then fills ``hr.grad`` /
+        ``lr.grad`` (the flow as a density over images), alone when no parameter requires grad."""
+        if (self._wants_grad() or self._image_wants_grad(hr, lr)) and not return_internals:
             return self._normal_flow_train(hr, lr, noise)
         self._check_inference()
         dev = self._device()
@@ -1128,7 +1191,8 @@ class HCFlowNet_SR(_EngineModule):
     def _normal_flow_train(self, hr, lr, noise):
         dev = self._device()
         assert lr is not None, "the NLL objective needs lr"
-        hr, lr = self._prep(hr, dev), self._prep(lr, dev)
+        image_grad = self._image_wants_grad(hr, lr)
+        hr, lr = (self._link(hr, dev), self._link(lr, dev)) if image_grad else (self._prep(hr, dev), self._prep(lr, dev))
         if noise is None:
             noise = torch.rand(hr.shape, device=dev)
         noise = self._prep(noise, dev)
@@ -1137,7 +1201,7 @@ class HCFlowNet_SR(_EngineModule):
             # that with one statistics pass on the same batch / noise, then run the differentiable pass
             with torch.no_grad():
                 self.normal_flow_diracLR(hr, lr, noise=noise)
-        if _grad_nodes() == 2:
+        if _grad_nodes() == 2 and not image_grad:          # (image gradients: the one-node step)
             params = self._params()
             early_idx = [i for i, k in enumerate(self._spec_keys) if k.startswith("flow.level0_condFlow.")]
             eset = set(early_idx)
@@ -1166,10 +1230,28 @@ class HCFlowNet_SR(_EngineModule):
         -ln(quant) * H * W (:53) is part of it whether or not noise is added. ``decode(z_lr, eps)`` returns hr + noise / quant.
 
         ``noise``: an explicit U[0,1) tensor; ``add_gt_noise=True`` draws it with torch.rand as the reference does (:52); by
-        default none is added, so that the decode target is ``hr`` itself. Always the inference path (as ``return_internals=True``
-        is): the outputs carry no autograd graph, whatever the grad mode, and un-initialised ActNorms are not fitted.
-        Per sample: a batch of >= 4 runs as two half batches on the two side streams (set_streams)."""
+        default none is added, so that the decode target is ``hr`` itself. Un-initialised ActNorms are not fitted.
+        With grad mode on, an ``hr`` that requires grad and every weight frozen the outputs are differentiable w.r.t. ``hr``
+        (one taped pass, the engine's input-gradient-only backward); with trainable weights beside such an ``hr`` the call raises
+        NotImplementedError (parameter gradients of the encode are not implemented: freeze the weights or detach ``hr``).
+        Otherwise the inference path (as ``return_internals=True`` is): no autograd graph, and a batch of >= 4 runs as two half
+        batches on the two side streams (set_streams)."""
         dev = self._device()
+        if self._image_wants_grad(hr):
+            if self._wants_grad():
+                raise NotImplementedError(
+                    "encode(hr) with hr.requires_grad and trainable weights: the encode is differentiable w.r.t. hr with the "
+                    "weights frozen only (requires_grad_(False) on the parameters), or detach hr.")
+            hr_t = self._link(hr, dev)
+            assert hr_t.dim() == 4 and hr_t.shape[1] == 3 and hr_t.shape[2] % self.cfg.scale == 0 and \
+                hr_t.shape[3] % self.cfg.scale == 0, "{}".format(tuple(hr_t.shape))
+            if noise is None and add_gt_noise:
+                noise = torch.rand(hr_t.shape, device=dev)
+            if noise is not None:
+                noise = self._prep(noise, dev)
+                assert noise.shape == hr_t.shape, (tuple(noise.shape), tuple(hr_t.shape))
+            outs = _SREncodeStep.apply(self, hr_t, noise)
+            return outs[0], list(outs[2:]), outs[1]
         B_ = int(hr.shape[0]) if torch.is_tensor(hr) and hr.dim() == 4 else 0
         eng, idx = self._engine_for(dev, twin_hint=self._nstreams[0] >= 2 and B_ >= 4)
         self._cond_key.pop(idx, None)
@@ -1223,13 +1305,17 @@ class HCFlowNet_Rescaling(_EngineModule):
                                          sample_offset=sample_offset, cache_cond=cache_cond)
 
     def normal_flow_diracLR(self, hr, lr=None, u=None, step=None, training=True, clamp=True):
-        """hr -> (clamp(LR^), z1, z2)   (HCFlowNet_Rescaling_arch.py:39-46)."""
-        if self._wants_grad():
+        """hr -> (clamp(LR^), z1, z2)   (HCFlowNet_Rescaling_arch.py:39-46). With grad mode on and an ``hr`` that requires grad the
+        taped path runs also with every weight frozen, and the backward pass returns d / d hr (alone when no parameter requires
+        grad)."""
+        image_grad = self._image_wants_grad(hr)
+        if self._wants_grad() or image_grad:
             dev = self._device()
             if self.training and self._pending_actnorms():
                 with torch.no_grad():                       # fit the ActNorms on this batch first (ActNorms.py:78-80)
                     self.normal_flow_diracLR(hr)
-            return _RescaleForwardStep.apply(self, self._prep(hr, dev), bool(clamp), *self._params())
+            return _RescaleForwardStep.apply(self, self._link(hr, dev) if image_grad else self._prep(hr, dev), bool(clamp),
+                                             *self._params())
         self._check_inference()
         if not self.training and not _capturing():      # (a stale pass is drained with a stream sync: never while capturing)
             try:

@@ -263,6 +263,7 @@ struct StepBwdArgs {
   // coupling backward: (gzout, zout, h) -> gzb (=), gh (=)
   View gzout, zout, h, gzb, gh;
   float gobj;              // dL/d(objective) of every sample (the sum-of-logscale term feeds the log-det)
+  const float* gobj_b;     // optional [B]: dL/d(objective_b) per sample, read instead of gobj (encode backward); nullptr: gobj
   // head backward: (gzb, za) -> gzin (=), sums for ActNorm bias / logs
   View za, gzin;
   const float* matT;       // [CMAX][CMAX] W^T (row c = column c of W) or nullptr (no permutation)
@@ -299,6 +300,7 @@ struct PriorBwdArgs {
   int rescale;             // 0: logs = s (SR); 1: logs = 0.318 atan(2 s) (rescaling net, ConditionalFlow.py:78,90)
   const float* gz_nchw;    // encode backward: dL/dz of z = (a - mean) e^-logs, NCHW [B,C,H,W] (nullptr: zero)
   float* geps_nchw;        // sample backward, optional: receives dL/d eps = ga e^logs, NCHW [B,C,H,W] (nullptr: not wanted)
+  const float* gobj_b;     // encode + logp backward, optional [B]: dL/d logp_b per sample, read instead of gobj (nullptr: gobj)
 };
 int launch_gauss_logp_bwd(const PriorBwdArgs& a, hipStream_t st);
 // a = mean + e^logs * eps (SR prior sample): gh[2c] = ga[c], gh[2c+1] = ga[c] * (a[c] - mean)   (ga in, gh out);
@@ -306,12 +308,22 @@ int launch_gauss_logp_bwd(const PriorBwdArgs& a, hipStream_t st);
 int launch_gauss_sample_bwd(const PriorBwdArgs& a, hipStream_t st);
 // z = (a - mean) e^-logs (rescaling forward, ConditionalFlow.py:76-80): ga (=), gh (=) from gz_nchw
 int launch_gauss_encode_bwd(const PriorBwdArgs& a, hipStream_t st);
+// SR encode (gauss_encode_logp_kernel): eps = (a - mean) e^-logs leaves the pass AND logp(a; mean, logs) joins the log-density
+// (ConditionalFlow.py:46-57, Basic.py:78-94). Seeds: gz_nchw = dL/d eps (nullptr: zero), gobj_b[b] (or gobj) = dL/d logp_b.
+// ga (=), gh (=): the sum of launch_gauss_encode_bwd's and launch_gauss_logp_bwd's values, each term in that kernel's own
+// arithmetic, so that one seed alone gives that kernel's output bit for bit.
+int launch_gauss_encode_logp_bwd(const PriorBwdArgs& a, hipStream_t st);
 // gz[pix][c] += g_nchw[b][c][pix] (masked where z is outside [0,1] when clamp01): backward of an NCHW (clamped) output
 int launch_add_nchw_grad(const float* g_nchw, View z, View gz, int B, int H, int W, int clamp01, hipStream_t st);
 // out = (0 <= raw <= 1) ? g : 0 over n floats (flat NCHW tensors)
 int launch_mask_flat(const float* g, const float* raw, float* out, size_t n, hipStream_t st);
-// d/dz of logp(lr; mean := Quant(z), logs = -6) with the straight-through Quant: gz += gobj * (lr - q(z)) * e^12
-int launch_quant_logp_bwd(View z, const float* lr_nchw, View gz, int B, int H, int W, float gobj, hipStream_t st);
+// d/dz of logp(lr; mean := Quant(z), logs = -6) with the straight-through Quant: gz += gobj * (lr - q(z)) * e^12;
+// glr_nchw (optional, NCHW [B,3,H,W]) = dL/d lr = gobj * (q(z) - lr) * e^12 in the same pass over the pixels
+int launch_quant_logp_bwd(View z, const float* lr_nchw, View gz, int B, int H, int W, float gobj, float* glr_nchw, hipStream_t st);
+// Input end of the taped forward passes: dL/d hr [B,C,2H,2W] NCHW (=) from the gradient gz [B,H,W,4C] NHWC of the level-0 tensor
+// z = squeeze2d(hr + noise / quant) (haar = 0: the transpose is unsqueeze2d, Basic.py:143-157) or z = Haar(hr) (haar = 1:
+// (Haar fwd)^T = Haar inv / 4, Basic.py:450-487). One read of gz, one write of dL/d hr.
+int launch_input_grad_emit(View gz, float* ghr_nchw, int B, int C, int H, int W, int haar, hipStream_t st);
 int launch_add_view(View in, View out, int B, int H, int W, float alpha, hipStream_t st);      // out += alpha * in
 int launch_add_const(float* p, size_t n, float v, hipStream_t st);                             // p[i] += v
 int launch_axpy(const float* x, float* y, size_t n, float alpha, hipStream_t st);              // y += alpha * x

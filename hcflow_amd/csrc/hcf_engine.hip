@@ -625,8 +625,38 @@ int hcf_train_forward_sr(hcf_engine* e, const float* hr, const float* lr, const 
 }
 
 int hcf_train_backward(hcf_engine* e, float grad_nll, float* dparams, int64_t numel, hcf_stream_t stream) {
+  return hcf_train_backward_ex(e, grad_nll, dparams, numel, nullptr, nullptr, stream);
+}
+
+int hcf_train_backward_ex(hcf_engine* e, float grad_nll, float* dparams, int64_t numel, float* grad_hr, float* grad_lr,
+                          hcf_stream_t stream) {
   if (!e || numel < 0) return HCF_ERR_ARG;
   hcf_engine::BwdIn in = {1, grad_nll, nullptr, nullptr, nullptr, nullptr, nullptr, 0};
+  in.ghr = grad_hr; in.glr = grad_lr;
+  return e->run_backward(in, dparams, (size_t)numel, (hipStream_t)stream);
+}
+
+int hcf_train_encode_sr(hcf_engine* e, const float* hr, const float* noise, float* out_z, float* const* out_eps, int32_t n_eps,
+                        float* out_logp, int32_t B, int32_t H, int32_t W, uint32_t flags, hcf_stream_t stream) {
+  if (!e || !hr || !out_z || !out_eps || !out_logp || B < 1 || H < 1 || W < 1) return HCF_ERR_ARG;
+  (void)flags;                        // (a taped pass reads its overflow flag itself and re-runs on the exact kernels: run_train)
+  if (e->sr()) {
+    if (n_eps != e->cfg.L) return e->fail(HCF_ERR_ARG, "hcf_train_encode_sr: n_eps must equal the number of levels (one eps tensor per split)");
+    for (int i = 0; i < n_eps; ++i)
+      if (!out_eps[i]) return e->fail(HCF_ERR_ARG, "hcf_train_encode_sr: null eps output");
+    const int m = 1 << e->cfg.L;
+    if (H % m || W % m) return e->fail(HCF_ERR_SHAPE, "H, W must be divisible by the scale (squeeze2d assert, Basic.py:136)");
+  }
+  return e->run_train(4, e->sr() ? nullptr : "hcf_train_encode_sr on a rescaling engine", (hipStream_t)stream,
+                      [&]() { e->pass_train_forward(hr, nullptr, noise, nullptr, nullptr, out_logp, nullptr, nullptr, B, H, W, 0, out_z, out_eps); });
+}
+
+int hcf_train_backward_encode(hcf_engine* e, const float* g_z, const float* const* g_eps, int32_t n_eps, const float* g_logp,
+                              float* dparams, int64_t numel, float* grad_hr, hcf_stream_t stream) {
+  if (!e || numel < 0 || n_eps < 0 || (n_eps > 0 && !g_eps)) return HCF_ERR_ARG;
+  hcf_engine::BwdIn in = {4, 0.f, nullptr, nullptr, nullptr, nullptr, nullptr, 0};
+  in.ghr = grad_hr;
+  in.enc_z = g_z; in.enc_eps = g_eps; in.n_enc_eps = n_eps; in.enc_logp = g_logp;
   return e->run_backward(in, dparams, (size_t)numel, (hipStream_t)stream);
 }
 
@@ -652,8 +682,14 @@ int hcf_train_forward_rescale(hcf_engine* e, const float* hr, float* out_lr, flo
 
 int hcf_train_backward_rescale(hcf_engine* e, const float* g_lr, const float* g_z1, const float* g_z2, float* dparams,
                                int64_t numel, hcf_stream_t stream) {
+  return hcf_train_backward_rescale_ex(e, g_lr, g_z1, g_z2, dparams, numel, nullptr, stream);
+}
+
+int hcf_train_backward_rescale_ex(hcf_engine* e, const float* g_lr, const float* g_z1, const float* g_z2, float* dparams,
+                                  int64_t numel, float* grad_hr, hcf_stream_t stream) {
   if (!e || numel < 0) return HCF_ERR_ARG;
   hcf_engine::BwdIn in = {3, 0.f, g_lr, nullptr, g_z1, g_z2, nullptr, 0};
+  in.ghr = grad_hr;
   return e->run_backward(in, dparams, (size_t)numel, (hipStream_t)stream);
 }
 

@@ -39,7 +39,7 @@
     std::vector<const float*> late_bufs;             // gradient buffers of the conditional features taped in this pass
     bool valid = false;
     bool f16 = false;                                // the taped pass completed on the f16x3 kernels (slot 0 may have fallen back to the exact ones while slot 1 did not)
-    int kind = 0;                                    // 1: NLL forward, 2: inverse (sampling) pass, 3: rescaling forward
+    int kind = 0;                                    // 1: NLL forward, 2: inverse (sampling) pass, 3: rescaling forward, 4: SR encode
     int B = 0;
     double pixels = 0;
     Buf tfat = {nullptr, 0, 0};                      // the fat launches' stored partial sum (consumed by the completion behind it): one per conditional net
@@ -64,9 +64,19 @@
       // this pass uses the side streams below (their `on` flags: per pass, a pass on the other slot ends with its own switched off)
       bool wg_async = false, dg_async = false;
       bool dg_dirty = false;                         // dg_stream has been given work that the caller's stream has not waited for
-      // Input-gradient-only pass (inverse pass with frozen weights: latent optimisation): no gradient buffer, and the four funnels of
-      // parameter-gradient work -- run_wgrad, the dense blocks' batched weight gradients, add_sum_job, add_axpy_job -- drop their jobs
+      // Input-gradient-only pass (frozen weights: latent optimisation on the inverse pass, image gradients of the NLL, the rescaling
+      // forward and the encode): no gradient buffer, and the four funnels of parameter-gradient work -- run_wgrad, the dense blocks'
+      // batched weight gradients, add_sum_job, add_axpy_job -- drop their jobs
       bool inputs_only = false;
+      // forward passes (kinds 1, 3, 4), optional: g_hr_nchw receives dL / d hr; NLL pass: g_lr_nchw receives dL / d lr (Dirac term)
+      float* g_hr_nchw = nullptr;
+      float* g_lr_nchw = nullptr;
+      // encode pass: the seeds dL / d z (nullable), dL / d eps of each level in sampling order (array and entries nullable) and
+      // dL / d logp_b, a device vector [B] (nullable) that stands where the NLL pass has the scalar gobj
+      const float* g_enc_z = nullptr;
+      const float* const* g_enc_eps = nullptr;
+      int n_enc_eps = 0;
+      const float* g_enc_logp = nullptr;
       float* const* geps = nullptr;                  // inverse pass, optional: geps[draw] receives dL / d eps of that draw (entries nullable)
       int n_geps = 0;
       // parameter-gradient work of the last backward pass on this tape (hcf_train_backward_counts): launch_conv_wgrad calls, convs
@@ -903,18 +913,20 @@
     a.z = zin.v.all(); a.out = zb.v.all(); a.aux = za.all();
     HCF_LAUNCH(launch_step_head_fwd(a, st));
     float* const spart = tape->g.alloc((size_t)B_ * step_blocks_per_sample(H, W) * 2 * s.cmax);
-    if (!dry()) tape->recs.push_back([this, sp, zin, zb, za, H, W, spart]() {
+    float* const gscr = tape->g.alloc(2 * (size_t)s.cmax);      // ActNorm sums of an input-gradient-only pass (the launcher wants a destination)
+    if (!dry()) tape->recs.push_back([this, sp, zin, zb, za, H, W, spart, gscr]() {
       const Step& s = *sp;
       StepBwdArgs b = step_dims<StepBwdArgs>(s, H, W);
       b.gzb = zb.g.all(); b.za = za.all(); b.gzin = zin.g.all();
       b.matT = s.has_mat ? s.mat_fwdT : nullptr; b.an_mul = s.mul_fwd;
-      b.g_bias = gp(s.an_key + ".bias"); b.g_logs = gp(s.an_key + ".logs");
+      const bool io = tape->bwd.inputs_only;
+      b.g_bias = io ? gscr : gp(s.an_key + ".bias"); b.g_logs = io ? gscr + s.cmax : gp(s.an_key + ".logs");
       b.part = spart;
       HCF_LAUNCH(launch_step_head_bwd(b, st));
       add_sum_job(spart, B_ * step_blocks_per_sample(H, W), s.C, s.cmax, b.g_bias, b.g_logs, 1.f);
       const float k = tape->bwd.gobj * (float)B_ * (float)H * (float)W;          // d(sum_b logdet_b): logs * pixels, slogdet W * pixels
       add_axpy_job(nullptr, b.g_logs, s.C, k);
-      if (s.has_mat) {
+      if (s.has_mat && !io) {
         WgradArgs w;
         memset(&w, 0, sizeof(w));
         w.src[0] = za.all(); w.nsrc = 1; w.g = zb.g.all(); w.B = B_; w.H = H; w.W = W; w.taps = 1;
@@ -941,6 +953,7 @@
       b.gzout = zout.g.all(); b.zout = zout.v.all(); b.h = ho.v.v(0, s.f_out);
       b.gzb = zb.g.all(); b.gh = ho.g.v(0, s.f_out);
       b.gobj = tape->bwd.gobj;
+      b.gobj_b = tape->bwd.g_enc_logp;                 // encode pass: dL / d logp per sample (else null: the scalar)
       HCF_LAUNCH(launch_step_couple_bwd(b, st));
     });
     return zout;
@@ -1042,8 +1055,11 @@
 
   // ---- the taped forward pass: HCFlowNet_SR.normal_flow_diracLR (HCFlowNet_SR_arch.py:47-67; lr, noise -> out_nll, out_logdet) and
   // HCFlowNet_Rescaling.normal_flow_diracLR (HCFlowNet_Rescaling_arch.py:39-46; -> out_z1, out_z2, flags). One walk, as pass_forward.
+  // `out_eps` non-null: the SR encode (hcf_encode_sr's outputs: out_z, out_eps deepest level first, out_logdet = logp without the
+  // Dirac term; lr, out_lr, out_nll null), its priors keep eps beside the log-density (ConditionalFlow.py:46-57).
   void pass_train_forward(const float* hr, const float* lr, const float* noise, float* out_lr, float* out_nll, float* out_logdet,
-                          float* out_z1, float* out_z2, int B, int H0, int W0, uint32_t flags) {
+                          float* out_z1, float* out_z2, int B, int H0, int W0, uint32_t flags, float* out_z = nullptr,
+                          float* const* out_eps = nullptr) {
     tape_begin(B);
     const int L = cfg.L;
     const bool haar = cfg.squeeze == HCF_SQUEEZE_HAAR;
@@ -1061,6 +1077,12 @@
       TB z = talloc(B, H, W, lv.C);
       if (level == 0) {
         HCF_LAUNCH(launch_nchw_squeeze(hr, noise, cfg.quant, z.v.all(), B, cfg.in_nc, H0, W0, haar ? 1 : 0, st));   // (quant: read with noise only)
+        // d / d hr (last to run): hr + noise / quant has an identity Jacobian, squeeze^T = unsqueeze, (Haar fwd)^T = Haar inv / 4 --
+        // the first step's head backward has left the complete gradient of z (=), one launch takes it to the caller's NCHW tensor
+        const int C0 = cfg.in_nc;
+        if (!dry()) tape->recs.push_back([this, z, C0, H, W, haar]() {
+          if (tape->bwd.g_hr_nchw) HCF_LAUNCH(launch_input_grad_emit(z.g.all(), tape->bwd.g_hr_nchw, B_, C0, H, W, haar ? 1 : 0, st));
+        });
       } else {
         const TB prev = zlev[level - 1];
         const int C4 = lv.C, ns = levels[level - 1].ns;
@@ -1101,16 +1123,25 @@
         g.partial = partial + pslot;
         g.partial_stride = nslots;
         pslot += step_blocks_per_sample(H, W);
-        HCF_LAUNCH(launch_gauss_logp(g, st));
+        if (out_eps) {
+          g.aux = out_eps[L - 1 - level];              // (hcf_inverse's eps order: deepest level first)
+          HCF_LAUNCH(launch_gauss_encode_logp(g, st));
+        } else {
+          HCF_LAUNCH(launch_gauss_logp(g, st));
+        }
       } else {
         g.aux = (level == 0) ? out_z1 : out_z2;
         if (g.aux) HCF_LAUNCH(launch_gauss_encode(g, st));
       }
       const TB af = a;
-      const int Ca = cf.Ca, zi = (level == 0) ? 0 : 1;
-      if (!dry()) tape->recs.push_back([this, af, ho, Ca, zi, H, W]() {
+      const int Ca = cf.Ca, zi = (level == 0) ? 0 : 1, draw = L - 1 - level;
+      if (!dry()) tape->recs.push_back([this, af, ho, Ca, zi, draw, H, W]() {
         PriorBwdArgs p = prior_bwd_args(af, ho, Ca, H, W);
-        if (sr()) {
+        if (tape->kind == 4) {                         // encode: eps left the pass and logp joined the log-density -- one fused kernel
+          p.gz_nchw = (tape->bwd.g_enc_eps && draw < tape->bwd.n_enc_eps) ? tape->bwd.g_enc_eps[draw] : nullptr;
+          p.gobj_b = tape->bwd.g_enc_logp;             // (null: gobj = 0, no seed on logp)
+          HCF_LAUNCH(launch_gauss_encode_logp_bwd(p, st));
+        } else if (sr()) {
           p.gobj = tape->bwd.gobj;
           HCF_LAUNCH(launch_gauss_logp_bwd(p, st));
         } else {
@@ -1121,12 +1152,20 @@
     }
     const int h = H0 >> L, w = W0 >> L;
     const TB zd = zlev[L - 1];
-    if (sr()) {
+    if (sr() && out_eps) {                               // encode: the unquantised LR latent leaves the pass, no Dirac term (its slot stays 0)
+      HCF_LAUNCH(launch_nhwc_to_nchw(zd.v.v(0, 3), out_z, B, 3, h, w, 0, st));
+      if (!dry()) tape->recs.push_back([this, zd, h, w]() {
+        if (tape->bwd.g_enc_z) HCF_LAUNCH(launch_add_nchw_grad(tape->bwd.g_enc_z, zd.v.v(0, 3), zd.g.v(0, 3), B_, h, w, 0, st));
+      });
+      pslot += step_blocks_per_sample(h, w);
+      if (pslot > nslots) fail(HCF_ERR_STATE, "internal: partial slot overflow (training)");
+      HCF_LAUNCH(launch_reduce_partials(partial, nslots, nslots, B, ld_const_sum(H0, W0), (double)H0 * W0, out_logdet, nullptr, st));
+    } else if (sr()) {
       float* pp = partial + pslot;
       pslot += step_blocks_per_sample(h, w);
       HCF_LAUNCH(launch_quant_logp(zd.v.v(0, 3), lr, out_lr, B, h, w, pp, nslots, st));
       if (!dry()) tape->recs.push_back([this, zd, lr, h, w]() {
-        HCF_LAUNCH(launch_quant_logp_bwd(zd.v.v(0, 3), lr, zd.g.v(0, 3), B_, h, w, tape->bwd.gobj, st));
+        HCF_LAUNCH(launch_quant_logp_bwd(zd.v.v(0, 3), lr, zd.g.v(0, 3), B_, h, w, tape->bwd.gobj, tape->bwd.g_lr_nchw, st));
       });
       if (pslot > nslots) fail(HCF_ERR_STATE, "internal: partial slot overflow (training)");
       HCF_LAUNCH(launch_reduce_partials(partial, nslots, nslots, B, ld_const_sum(H0, W0), (double)H0 * W0, out_logdet, out_nll, st));
@@ -1331,13 +1370,16 @@
 
   // d(gscale * nll) / d parameters into `dparams` (device, ptotal floats, state_dict order)
   struct BwdIn {
-    int kind;                       // 1 NLL forward, 2 inverse (sampling) pass, 3 rescaling forward
+    int kind;                       // 1 NLL forward, 2 inverse (sampling) pass, 3 rescaling forward, 4 SR encode
     float gscale;                   // kind 1: dL / d nll
     const float* gout;              // kind 2: dL / d out_hr;  kind 3: dL / d out_lr (nullable)
     float* gin;                     // kind 2: receives dL / d lr (nullable)
     const float* gz1; const float* gz2;   // kind 3: dL / d z1, z2 (nullable)
     float* const* geps; int n_geps;       // kind 2: receive dL / d eps, one per draw in sampling order (deepest level first, as
                                           // hcf_inverse's eps); the array and its entries are nullable
+    float* ghr;                           // kinds 1, 3, 4: receives dL / d hr (nullable)
+    float* glr;                           // kind 1: receives dL / d lr of the Dirac term (nullable)
+    const float* enc_z; const float* const* enc_eps; int n_enc_eps; const float* enc_logp;   // kind 4: the seeds (each nullable)
   };
   // phase: -1 the whole pass; 0 records [mark, end) + a flush of every pending parameter-gradient job; 1 the rest
   int run_backward(const BwdIn& in, float* dparams, size_t n, hipStream_t stream, int phase = -1) {
@@ -1350,10 +1392,15 @@
     if (!tape->valid || tape->kind != in.kind)
       return fail(HCF_ERR_STATE, "backward without a matching taped pass on the selected tape slot before it");
     if (in.kind == 2 && !in.gout) return fail(HCF_ERR_ARG, "hcf_train_backward_inverse: null output gradient");
-    // inverse pass only: no gradient buffer at all = the gradients of the inputs (lr, eps) alone, no parameter-gradient work
-    const bool inputs_only = in.kind == 2 && !dparams && n == 0;
+    // no gradient buffer at all = the gradients of the inputs (hr, lr, eps) alone, no parameter-gradient work: every whole pass; the
+    // two-phase NLL backward exists for the parameter gradients' all-reduce and keeps refusing
+    const bool inputs_only = phase < 0 && !dparams && n == 0;
+    // the encode's seed on logp is per sample: the log-det axpy jobs (logs += k, dW += k W^-T) would need a device-side sum of it
+    if (in.kind == 4 && !inputs_only)
+      return fail(HCF_ERR_UNSUPPORTED, "hcf_train_backward_encode: parameter gradients under per-sample logp seeds are not implemented (dparams must be NULL, numel 0)");
     if (!inputs_only && (n != ptotal || !dparams)) return fail(HCF_ERR_ARG, "backward: gradient buffer size mismatch");
     if (in.n_geps < 0 || (in.n_geps > 0 && !in.geps)) return fail(HCF_ERR_ARG, "backward: n_geps without the eps gradient array");
+    if (in.n_enc_eps < 0 || (in.n_enc_eps > 0 && !in.enc_eps)) return fail(HCF_ERR_ARG, "backward: n_eps without the eps seed array");
     if (phase >= 0 && in.kind != 1) return fail(HCF_ERR_UNSUPPORTED, "two-phase backward: NLL pass only");
     if (phase == 1 && (!tape->mid || dparams != tape->bwd.gparams)) return fail(HCF_ERR_STATE, "backward phase 1 without phase 0 on this tape (same gradient buffer) before it");
     if (phase != 1 && tape->mid) return fail(HCF_ERR_STATE, "backward: phase 1 of a two-phase backward is pending on this tape");
@@ -1383,6 +1430,12 @@
     tape->bwd.g_fwd_lr = (in.kind == 3) ? in.gout : nullptr;
     tape->bwd.g_fwd_z[0] = (in.kind == 3) ? in.gz1 : nullptr;
     tape->bwd.g_fwd_z[1] = (in.kind == 3) ? in.gz2 : nullptr;
+    tape->bwd.g_hr_nchw = (in.kind != 2) ? in.ghr : nullptr;
+    tape->bwd.g_lr_nchw = (in.kind == 1) ? in.glr : nullptr;
+    tape->bwd.g_enc_z = (in.kind == 4) ? in.enc_z : nullptr;
+    tape->bwd.g_enc_eps = (in.kind == 4) ? in.enc_eps : nullptr;
+    tape->bwd.n_enc_eps = (in.kind == 4) ? in.n_enc_eps : 0;
+    tape->bwd.g_enc_logp = (in.kind == 4) ? in.enc_logp : nullptr;
     // nll = mean_b( -objective_b / (ln 2 * pixels) ); the other objectives have no log-det term
     tape->bwd.gobj = (in.kind == 1) ? -in.gscale / (float)((double)B_ * log(2.0) * tape->pixels) : 0.f;
     if (hipMemsetAsync(tape->g.base, 0, tape->g.top, st) != hipSuccess ||
@@ -1423,7 +1476,9 @@
     flush_sum_jobs();
     tape->valid = false;          // the epilogue backward overwrote the gradient buffers in place: one backward per forward
     tape->bwd.gparams = nullptr;
-    tape->bwd.geps = nullptr;     // (the caller's array)
+    tape->bwd.geps = nullptr;     // (the caller's arrays)
     tape->bwd.n_geps = 0;
+    tape->bwd.g_enc_eps = nullptr;
+    tape->bwd.n_enc_eps = 0;
     return rc;
   }

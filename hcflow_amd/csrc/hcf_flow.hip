@@ -491,6 +491,39 @@ __global__ __launch_bounds__(256) void unsqueeze_nchw_kernel(View in, float* dst
   }
 }
 
+// ---- input end of the taped forward passes: dL/d hr (NCHW) from the gradient of the level-0 tensor (NHWC) -----------------
+// z = squeeze2d(hr + noise / quant) or Haar(hr): hr + noise / quant has an identity Jacobian w.r.t. hr, squeeze2d^T = unsqueeze2d
+// (a pure index map), (Haar fwd)^T = Haar inv / 4 (the sum order of unsqueeze_nchw_kernel, times a power of two: exact).
+// One thread per pixel of gz: it reads its record's 4 C consecutive floats once (consecutive lanes = consecutive records) and
+// writes, per channel, two float pairs, one in each of the two output rows -- consecutive lanes write consecutive pairs of a row
+// of the channel plane, 512 bytes per wave and row (the compiler makes each pair one global_store_dwordx2, which needs no more
+// than the floats' own alignment).
+__global__ __launch_bounds__(256) void input_grad_emit_kernel(View gz, float* dst, int C, int H, int W, int haar) {
+  const int hw = H * W;
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= hw) return;
+  const int b = blockIdx.y, h = i / W, w = i - h * W;
+  const float* ip = gz.p + ((size_t)b * hw + i) * gz.cs + gz.c0;
+  for (int c = 0; c < C; ++c) {
+    float v[2][2];
+#pragma unroll
+    for (int di = 0; di < 2; ++di)
+#pragma unroll
+      for (int dj = 0; dj < 2; ++dj) {
+        if (!haar) v[di][dj] = ip[c * 4 + di * 2 + dj];
+        else
+          v[di][dj] = (((ip[c] * haar_sign(0, di, dj) + ip[C + c] * haar_sign(1, di, dj)) + ip[2 * C + c] * haar_sign(2, di, dj)) +
+                       ip[3 * C + c] * haar_sign(3, di, dj)) * 0.25f;
+      }
+#pragma unroll
+    for (int di = 0; di < 2; ++di) {
+      float* op = dst + ((size_t)((size_t)b * C + c) * (2 * H) + 2 * h + di) * (2 * W) + 2 * w;
+      op[0] = v[di][0];
+      op[1] = v[di][1];
+    }
+  }
+}
+
 // one thread per (pixel, channel), channel fastest (coalesced within the NHWC records)
 __global__ __launch_bounds__(256) void copy_view_kernel(View in, View out, int hw) {
   const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -660,6 +693,14 @@ int launch_nchw_squeeze(const float* src, const float* noise, float quant, View 
 int launch_unsqueeze_nchw(View in, float* dst, int B, int C4, int H, int W, int haar, int clamp01, hipStream_t st) {
   if (C4 & 3) return HCF_ERR_SHAPE;
   hipLaunchKernelGGL(unsqueeze_nchw_kernel, pix_grid(B, H, W), dim3(256), 0, st, in, dst, C4, H, W, haar, clamp01);
+  HCF_RET();
+}
+
+int launch_input_grad_emit(View gz, float* ghr_nchw, int B, int C, int H, int W, int haar, hipStream_t st) {
+  if (!gz.p || !ghr_nchw || B < 1 || C < 1 || H < 1 || W < 1 || gz.n != 4 * C) return HCF_ERR_ARG;
+  if ((long long)H * W > 0x7fffff00LL) return HCF_ERR_UNSUPPORTED;
+  const dim3 grid((unsigned)step_blocks_per_sample(H, W), (unsigned)B);
+  hipLaunchKernelGGL(input_grad_emit_kernel, grid, dim3(256), 0, st, gz, ghr_nchw, C, H, W, haar);
   HCF_RET();
 }
 int launch_copy_view(View in, View out, int B, int H, int W, hipStream_t st) {

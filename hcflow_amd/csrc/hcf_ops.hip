@@ -703,6 +703,11 @@ int hcf_op_prior_sample_backward(const float* a, const float* h, const float* ga
 
 int hcf_op_quant_logp_backward(const float* z, const float* lr, float* gz, int32_t B, int32_t H, int32_t W, float gobj,
                                hcf_stream_t stream) {
+  return hcf_op_quant_logp_backward_lr(z, lr, gz, nullptr, B, H, W, gobj, stream);
+}
+
+int hcf_op_quant_logp_backward_lr(const float* z, const float* lr, float* gz, float* glr, int32_t B, int32_t H, int32_t W,
+                                  float gobj, hcf_stream_t stream) {
   if (!z || !lr || !gz || B < 1 || H < 1 || W < 1) return HCF_ERR_ARG;
   hipStream_t st = (hipStream_t)stream;
   Tmp t;
@@ -710,8 +715,44 @@ int hcf_op_quant_logp_backward(const float* z, const float* lr, float* gz, int32
   View zv = nhwc_from_nchw(t, z, B, 3, H, W, st, rc);
   View gv = nhwc_from_nchw(t, gz, B, 3, H, W, st, rc);
   if (!t.ok) return HCF_ERR_NOMEM;
-  if (rc == HCF_OK) rc = launch_quant_logp_bwd(zv, lr, gv, B, H, W, gobj, st);
+  if (rc == HCF_OK) rc = launch_quant_logp_bwd(zv, lr, gv, B, H, W, gobj, glr, st);      // glr: straight into the caller's NCHW tensor
   if (rc == HCF_OK) rc = launch_nhwc_to_nchw(gv, gz, B, 3, H, W, 0, st);
+  if (hipStreamSynchronize(st) != hipSuccess) return HCF_ERR_HIP;
+  return rc;
+}
+
+int hcf_op_prior_encode_logp_backward(const float* a, const float* h, float* ga, float* gh, const float* geps_nchw,
+                                      const float* glogp, int32_t B, int32_t C, int32_t H, int32_t W, int32_t rescale, float gobj,
+                                      hcf_stream_t stream) {
+  if (!a || !h || !ga || !gh || B < 1 || C < 1 || H < 1 || W < 1) return HCF_ERR_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  Tmp t;
+  int rc = HCF_OK;
+  PriorBwdArgs p;
+  memset(&p, 0, sizeof(p));
+  p.B = B; p.H = H; p.W = W; p.C = C;
+  p.a = nhwc_from_nchw(t, a, B, C, H, W, st, rc);
+  p.h = nhwc_from_nchw(t, h, B, 2 * C, H, W, st, rc);
+  p.ga = nhwc_window(t, nullptr, B, C, H, W, ru4(C), 0, st, rc);
+  p.gh = nhwc_window(t, nullptr, B, 2 * C, H, W, ru4(2 * C), 0, st, rc);
+  p.gobj = gobj; p.gobj_b = glogp; p.rescale = rescale; p.gz_nchw = geps_nchw;
+  if (!t.ok) return HCF_ERR_NOMEM;
+  if (rc == HCF_OK) rc = launch_gauss_encode_logp_bwd(p, st);
+  if (rc == HCF_OK) rc = launch_nhwc_to_nchw(p.ga, ga, B, C, H, W, 0, st);
+  if (rc == HCF_OK) rc = launch_nhwc_to_nchw(p.gh, gh, B, 2 * C, H, W, 0, st);
+  if (hipStreamSynchronize(st) != hipSuccess) return HCF_ERR_HIP;
+  return rc;
+}
+
+int hcf_op_input_grad(const float* gz, float* ghr, int32_t B, int32_t C, int32_t H, int32_t W, int32_t haar,
+                      hcf_stream_t stream) {
+  if (!gz || !ghr || B < 1 || C < 1 || H < 1 || W < 1 || haar < 0 || haar > 1) return HCF_ERR_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  Tmp t;
+  int rc = HCF_OK;
+  View gv = nhwc_from_nchw(t, gz, B, 4 * C, H, W, st, rc);
+  if (!t.ok) return HCF_ERR_NOMEM;
+  if (rc == HCF_OK) rc = launch_input_grad_emit(gv, ghr, B, C, H, W, haar, st);           // straight into the caller's NCHW tensor
   if (hipStreamSynchronize(st) != hipSuccess) return HCF_ERR_HIP;
   return rc;
 }

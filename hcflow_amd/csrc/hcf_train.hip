@@ -218,6 +218,7 @@ __global__ __launch_bounds__(256) void step_couple_bwd_kernel(const StepBwdArgs 
   const float* hp = a.h.p + pix * a.h.cs + a.h.c0;
   float* ob = a.gzb.p + pix * a.gzb.cs + a.gzb.c0;
   float* oh = a.gh.p + pix * a.gh.cs + a.gh.c0;
+  const float gobj = a.gobj_b ? a.gobj_b[blockIdx.y] : a.gobj;   // per-sample seed of the log-det (encode backward) or the pass's scalar
   if (a.mode == CPL_AFFINE) {
     for (int c = 0; c < a.ns; ++c) ob[c] = gp[c];
     for (int c = a.ns; c < a.C; ++c) {
@@ -227,7 +228,7 @@ __global__ __launch_bounds__(256) void step_couple_bwd_kernel(const StepBwdArgs 
       const float g = gp[c];
       ob[c] = g * e;                                             // z2' = (z2 + shift) e^ls
       oh[2 * j] = g * e;                                         // d shift
-      const float dls = g * zp[c] + a.gobj;                      // d z2'/d ls = z2';  logdet += ls
+      const float dls = g * zp[c] + gobj;                        // d z2'/d ls = z2';  logdet += ls
       oh[2 * j + 1] = dls * (0.636f / (1.f + 4.f * scale * scale));   // ls = 0.318 atan(2 scale)
     }
   } else {                                                       // z[:3] += h
@@ -346,7 +347,7 @@ int launch_gauss_logp_bwd(const PriorBwdArgs& a, hipStream_t st) {
 }
 
 // ---- Dirac term backward with the straight-through Quant (HCFlowNet_SR_arch.py:58-63, Basic.py:186-196) ----------
-__global__ __launch_bounds__(256) void quant_logp_bwd_kernel(View z, const float* lr, View gz, int hw, float gobj) {
+__global__ __launch_bounds__(256) void quant_logp_bwd_kernel(View z, const float* lr, View gz, int hw, float gobj, float* glr) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= hw) return;
   const size_t pix = (size_t)blockIdx.y * hw + i;
@@ -354,15 +355,18 @@ __global__ __launch_bounds__(256) void quant_logp_bwd_kernel(View z, const float
   for (int c = 0; c < 3; ++c) {
     const float v = z.p[pix * z.cs + z.c0 + c];
     const float q = rintf(fminf(fmaxf(v, 0.f), 1.f) * 255.f) / 255.f;
-    const float l = lr[((size_t)blockIdx.y * 3 + c) * hw + i];
+    const size_t e = ((size_t)blockIdx.y * 3 + c) * hw + i;
+    const float l = lr[e];
     // logp(x = q; mean = lr, logs = -6) = -1/2 (-12 + (q - lr)^2 e^12 + ln 2pi);  d/dq = -(q - lr) e^12
     gz.p[pix * gz.cs + gz.c0 + c] += gobj * (l - q) * e12;
+    if (glr) glr[e] = gobj * (q - l) * e12;                      // d/d lr = (q - lr) e^12: lr is the mean's other side
   }
 }
 
-int launch_quant_logp_bwd(View z, const float* lr_nchw, View gz, int B, int H, int W, float gobj, hipStream_t st) {
+int launch_quant_logp_bwd(View z, const float* lr_nchw, View gz, int B, int H, int W, float gobj, float* glr_nchw, hipStream_t st) {
+  if (B < 1 || H < 1 || W < 1 || z.n < 3 || gz.n < 3) return HCF_ERR_ARG;
   const dim3 grid((unsigned)step_blocks_per_sample(H, W), (unsigned)B);
-  hipLaunchKernelGGL(quant_logp_bwd_kernel, grid, dim3(256), 0, st, z, lr_nchw, gz, H * W, gobj);
+  hipLaunchKernelGGL(quant_logp_bwd_kernel, grid, dim3(256), 0, st, z, lr_nchw, gz, H * W, gobj, glr_nchw);
   HCF_RET_T();
 }
 
@@ -479,6 +483,48 @@ __global__ __launch_bounds__(256) void gauss_encode_bwd_kernel(const PriorBwdArg
 int launch_gauss_encode_bwd(const PriorBwdArgs& a, hipStream_t st) {
   const dim3 grid((unsigned)step_blocks_per_sample(a.H, a.W), (unsigned)a.B);
   hipLaunchKernelGGL(gauss_encode_bwd_kernel, grid, dim3(256), 0, st, a);
+  HCF_RET_T();
+}
+
+// Backward of the SR encode's prior (gauss_encode_logp_kernel): eps = (a - mean) e^-logs is an output of the pass AND
+// logp = -1/2 (2 logs + eps^2 + ln 2pi) joins its log-density, so `a` and `h` receive both gradients. The two kernels above write
+// with `=`: two launches cannot be summed, hence this one. It evaluates gauss_encode_bwd_kernel's terms from the seed gz = dL/d eps
+// (nullptr: zero) and gauss_logp_bwd_kernel's from the seed g = dL/d logp_b (gobj_b[sample], else gobj) expression by expression
+// and stores their sums: with one seed absent the other kernel's result comes out bit for bit (x + 0 = x). One read of a and h.
+// The log-density term in the rescaling prior's form (logs = 0.318 atan(2 s)) takes the chain factor of the encode term.
+__global__ __launch_bounds__(256) void gauss_encode_logp_bwd_kernel(const PriorBwdArgs a) {
+  const int hw = a.H * a.W;
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= hw) return;
+  const size_t pix = (size_t)blockIdx.y * hw + i;
+  const float* ap = a.a.p + pix * a.a.cs + a.a.c0;
+  const float* hp = a.h.p + pix * a.h.cs + a.h.c0;
+  float* ga = a.ga.p + pix * a.ga.cs + a.ga.c0;
+  float* gh = a.gh.p + pix * a.gh.cs + a.gh.c0;
+  const float g = a.gobj_b ? a.gobj_b[blockIdx.y] : a.gobj;
+  for (int c = 0; c < a.C; ++c) {
+    const float mean = hp[2 * c], s = hp[2 * c + 1];
+    const float logs = a.rescale ? logscale_of(s) : s;
+    const float d = ap[c] - mean;
+    // eps = d e^-logs  (gauss_encode_bwd_kernel)
+    const float e = expf(-logs);
+    const float gz = a.gz_nchw ? a.gz_nchw[((size_t)blockIdx.y * a.C + c) * hw + i] : 0.f;
+    const float z = d * e;
+    const float ea = gz * e, em = -gz * e, el = -gz * z;
+    // logp = -1/2 (2 logs + d^2 e^{-2 logs} + ln 2pi)  (gauss_logp_bwd_kernel)
+    const float iv = expf(-2.f * logs);
+    const float la = -g * d * iv, lm = g * d * iv, ll = g * (d * d * iv - 1.f);
+    ga[c] = ea + la;
+    gh[2 * c] = em + lm;
+    float gl = el + ll;
+    if (a.rescale) gl *= 0.636f / (1.f + 4.f * s * s);
+    gh[2 * c + 1] = gl;
+  }
+}
+int launch_gauss_encode_logp_bwd(const PriorBwdArgs& a, hipStream_t st) {
+  if (a.C < 1 || a.H < 1 || a.W < 1 || a.B < 1) return HCF_ERR_ARG;
+  const dim3 grid((unsigned)step_blocks_per_sample(a.H, a.W), (unsigned)a.B);
+  hipLaunchKernelGGL(gauss_encode_logp_bwd_kernel, grid, dim3(256), 0, st, a);
   HCF_RET_T();
 }
 

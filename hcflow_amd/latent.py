@@ -120,3 +120,50 @@ def optimise(net, z_lr, eps, loss_fn, steps, lr=0.02, optimise_lr=False, optimiz
             p.requires_grad_(f)
     losses = [float(v) for v in torch.stack(history).cpu()] if history else []
     return z_v.detach(), [None if e is None else e.detach() for e in eps_v], losses
+
+
+def refine_image(net, hr0, lq, data_loss=None, steps=20, lr=1e-4, weight=1.0, noise=None, optimizer=None):
+    """Gradient descent on the IMAGE with the weights frozen: ``steps`` iterations on
+    ``weight * nll(hr | lq) + data_loss(hr)`` over a clone of ``hr0``, where ``nll`` is ``net(hr=hr, lr=lq, reverse=False)``'s
+    (bits per dimension, HCFlowNet_SR_arch.py:47-67) -- the trained flow as an image prior: MAP restoration
+    (``data_loss`` = the degradation's data term), likelihood-guided refinement of an SR sample (``data_loss=None``). With
+    ``torch.optim.Adam([hr], lr=lr)``, or ``optimizer([hr])`` when a factory is given. Returns ``(hr, losses, nlls)``: the moved
+    image, detached, and the total loss and the NLL of every step (evaluated BEFORE that step's update) as floats. The caller's
+    tensors are not written.
+
+    ``noise``: the U[0,1) dequantisation tensor of the NLL (:52); None: drawn once with torch.rand and held for all steps, so that
+    every step descends the same function. ``lq`` is an 8-bit image in [0, 1] (values k / 255) in practice: the Dirac-LR term
+    (:58-63) is e^12 / 2 * (Quant(z) - lq)^2 per element with a straight-through Quant, so an ``lq`` off that grid contributes a
+    constant gradient that no step can reduce. ``lr`` is in image units (one grey level = 1 / 255 = 3.9e-3).
+
+    Every parameter of ``net`` has ``requires_grad`` switched off for the duration, so each backward pass is the engine's
+    input-gradient-only one, and gets its flag back afterwards, also on an error; no parameter is written."""
+    steps = int(steps)
+    assert steps >= 0
+    hr = hr0.detach().clone().float().requires_grad_(True)
+    lq = lq.detach()
+    if noise is None:
+        noise = torch.rand(hr.shape, device=hr.device)
+    opt = torch.optim.Adam([hr], lr=float(lr)) if optimizer is None else optimizer([hr])
+    params = list(net.parameters())
+    flags = [p.requires_grad for p in params]
+    losses, nlls = [], []
+    try:
+        for p in params:
+            p.requires_grad_(False)
+        with torch.enable_grad():
+            for _ in range(steps):
+                opt.zero_grad(set_to_none=True)
+                _, nll = net(hr=hr, lr=lq, reverse=False, noise=noise)
+                loss = float(weight) * nll
+                if data_loss is not None:
+                    loss = loss + data_loss(hr)
+                loss.backward()
+                opt.step()
+                losses.append(loss.detach())
+                nlls.append(nll.detach())
+    finally:
+        for p, f in zip(params, flags):
+            p.requires_grad_(f)
+    as_floats = lambda h: [float(v) for v in torch.stack(h).cpu()] if h else []
+    return hr.detach(), as_floats(losses), as_floats(nlls)

@@ -250,6 +250,46 @@ def quant_logp_backward(z, lr, gobj: float, gz=None) -> torch.Tensor:
     return out
 
 
+def quant_logp_backward_lr(z, lr, gobj: float, gz=None):
+    """``quant_logp_backward`` that also returns d / d lr = gobj * (Quant(z) - lr) * e^12: (gz, glr)."""
+    lib = _lib.load()
+    z, lr = _dev(z), _dev(lr)
+    B, _, H, W = z.shape
+    out = torch.zeros_like(z) if gz is None else _dev(gz).clone()
+    glr = torch.empty_like(lr)
+    _lib.check(lib.hcf_op_quant_logp_backward_lr(z.data_ptr(), lr.data_ptr(), out.data_ptr(), glr.data_ptr(), B, H, W, float(gobj),
+                                                 _stream(z)), None, "hcf_op_quant_logp_backward_lr")
+    return out, glr
+
+
+def prior_encode_logp_backward(a, h, geps=None, glogp=None, rescale: bool = False, gobj: float = 0.0):
+    """Prior backward of the SR encode (eps = (a - mean) e^-logs is an output and logp joins the log-density): (ga, gh) from the
+    seeds ``geps`` = dL/d eps (None: zero) and ``glogp`` = dL/d logp per sample, a [B] tensor (None: the scalar ``gobj``)."""
+    lib = _lib.load()
+    a, h = _dev(a), _dev(h)
+    B, Cc, H, W = a.shape
+    ga, gh = torch.empty_like(a), torch.empty_like(h)
+    ge = _dev(geps) if geps is not None else None
+    gl = _dev(glogp) if glogp is not None else None
+    assert gl is None or gl.numel() == B
+    _lib.check(lib.hcf_op_prior_encode_logp_backward(a.data_ptr(), h.data_ptr(), ga.data_ptr(), gh.data_ptr(), _ptr(ge), _ptr(gl),
+                                                     B, Cc, H, W, int(rescale), float(gobj), _stream(a)), None,
+               "hcf_op_prior_encode_logp_backward")
+    return ga, gh
+
+
+def input_grad(gz, haar: bool = False) -> torch.Tensor:
+    """dL/d hr [B,C,2H,2W] from gz = dL/d z [B,4C,H,W] of z = squeeze2d(hr) (or Haar(hr)): unsqueeze2d(gz), or Haar inv(gz) / 4."""
+    lib = _lib.load()
+    gz = _dev(gz)
+    B, C4, H, W = gz.shape
+    assert C4 % 4 == 0
+    out = torch.empty(B, C4 // 4, 2 * H, 2 * W, device=gz.device, dtype=torch.float32)
+    _lib.check(lib.hcf_op_input_grad(gz.data_ptr(), out.data_ptr(), B, C4 // 4, H, W, int(haar), _stream(gz)), None,
+               "hcf_op_input_grad")
+    return out
+
+
 GRAD_KIND = {"add": 0, "add_clamp01": 1, "mask_unit_range": 2, "mask_flat": 3}
 
 

@@ -223,10 +223,37 @@ int hcf_train_backward_inverse(hcf_engine* e, const float* grad_out, float* dpar
  * N(0, tau) values. hcf_train_backward_inverse = this call with grad_eps = NULL, n_eps = 0.
  * dparams = NULL with numel = 0 asks for the gradients of the inputs alone: the pass launches no weight-gradient kernel, no
  * per-channel sum and no log-det update, touches no parameter-gradient slot and does not fork the weight-gradient stream; the
- * data-gradient chain (direct and Winograd convs, fused epilogue backward) is the one of the full pass. Every other backward
- * entry refuses a null dparams. */
+ * data-gradient chain (direct and Winograd convs, fused epilogue backward) is the one of the full pass. The forward passes'
+ * backward entries take the same form (hcf_train_backward_ex below); the two-phase backward refuses a null dparams. */
 int hcf_train_backward_inverse_ex(hcf_engine* e, const float* grad_out, float* dparams, int64_t numel, float* grad_lr,
                                   float* const* grad_eps, int32_t n_eps, hcf_stream_t stream);
+/* The forward passes differentiated w.r.t. their IMAGES (the flow as a density over images: MAP restoration with the NLL as image
+ * prior, likelihood-guided refinement of a sample, training a network that feeds the rescaler or the encoder).
+ * hcf_train_backward_ex = hcf_train_backward that also returns d(grad_nll * nll) / d hr (grad_hr, device [B,3,H,W], nullable) and
+ * / d lr (grad_lr, device [B,3,H/scale,W/scale], nullable) of normal_flow_diracLR (HCFlowNet_SR_arch.py:47-67): hr + noise / quant
+ * (:52) has an identity Jacobian w.r.t. hr and squeeze2d's transpose is unsqueeze2d; lr enters through the Dirac term
+ * logp(lr; mean = Quant(z), logs = -6) (:58-63) alone, d / d lr = (Quant(z) - lr) e^12 per element. d / d noise is not returned.
+ * hcf_train_backward_rescale_ex = hcf_train_backward_rescale with grad_hr (device [B,3,H,W], nullable): the input end is the
+ * Haar transform's transpose, (Haar fwd)^T = Haar inv / 4 (Basic.py:450-487).
+ * Both: dparams = NULL with numel = 0 gives the image gradients alone, as hcf_train_backward_inverse_ex does for the latents (no
+ * weight-gradient kernel, no per-channel sum, no log-det update, no fork of the weight-gradient stream; the data-gradient
+ * launches of the full pass); hcf_train_backward_counts then reads 0/0/0/0. hcf_train_backward = hcf_train_backward_ex without
+ * the image gradients, likewise hcf_train_backward_rescale. */
+int hcf_train_backward_ex(hcf_engine* e, float grad_nll, float* dparams, int64_t numel, float* grad_hr, float* grad_lr,
+                          hcf_stream_t stream);
+int hcf_train_backward_rescale_ex(hcf_engine* e, const float* g_lr, const float* g_z1, const float* g_z2, float* dparams,
+                                  int64_t numel, float* grad_hr, hcf_stream_t stream);
+/* hcf_encode_sr with a tape (same arguments, same outputs: out_z, out_eps deepest level first, out_logp [B], here required;
+ * flags are accepted and ignored: a taped pass checks its own range and re-runs on the exact kernels), and its backward:
+ * seeds g_z = dL/d out_z, g_eps[i] = dL/d out_eps[i] (the array and each entry nullable; n_eps entries) and g_logp = dL/d out_logp
+ * as a device vector [B] (nullable) -> grad_hr = dL/d hr (device [B,3,H,W]). Each conditional prior contributes through both of
+ * its outputs, eps = (a - mean) e^-logs and its log-density (ConditionalFlow.py:46-57). The pass is input-gradient-only by
+ * definition: dparams must be NULL and numel 0; anything else is refused with HCF_ERR_UNSUPPORTED (a per-sample seed on the
+ * log-det terms would need a device-side sum in the parameter updates). d / d noise is not returned. */
+int hcf_train_encode_sr(hcf_engine* e, const float* hr, const float* noise, float* out_z, float* const* out_eps, int32_t n_eps,
+                        float* out_logp, int32_t B, int32_t H, int32_t W, uint32_t flags, hcf_stream_t stream);
+int hcf_train_backward_encode(hcf_engine* e, const float* g_z, const float* const* g_eps, int32_t n_eps, const float* g_logp,
+                              float* dparams, int64_t numel, float* grad_hr, hcf_stream_t stream);
 /* Parameter-gradient work of the LAST backward pass on the selected tape slot (hcf_train_select_tape): out[0] = weight-gradient
  * launches of one conv, out[1] = convs handed to the batched weight-gradient launches of the dense blocks, out[2] = per-channel
  * sum jobs, out[3] = axpy (log-det) jobs. All zero after an input-gradient-only pass. */
@@ -379,6 +406,21 @@ int hcf_op_prior_sample_backward(const float* a, const float* h, const float* ga
 /* Dirac-LR term with the straight-through Quant: gz [B,3,H,W] += gobj * d logp(lr; mean = Quant(z), logs = -6) / dz */
 int hcf_op_quant_logp_backward(const float* z, const float* lr, float* gz, int32_t B, int32_t H, int32_t W, float gobj,
                                hcf_stream_t stream);
+/* The same that also returns d / d lr: glr [B,3,H,W] = gobj * (Quant(z) - lr) * e^12 (NULL: not wanted; gz is then bit-identical to
+ * hcf_op_quant_logp_backward's). lr is the value the Dirac density is evaluated at (HCFlowNet_SR_arch.py:58-63). */
+int hcf_op_quant_logp_backward_lr(const float* z, const float* lr, float* gz, float* glr, int32_t B, int32_t H, int32_t W,
+                                  float gobj, hcf_stream_t stream);
+/* Prior backward of the SR encode, where eps = (a - mean) e^-logs leaves the pass and logp(a; mean, logs) joins its log-density
+ * (ConditionalFlow.py:46-57, Basic.py:78-94): seeds geps_nchw = dL/d eps (NULL: zero) and dL/d logp_b = glogp[b] (device [B]; NULL:
+ * the scalar gobj for every sample) -> ga, gh out = kind 2 + kind 0 of hcf_op_prior_backward, each term in that kernel's own
+ * arithmetic: with only one seed the other kind's output comes out bit for bit. */
+int hcf_op_prior_encode_logp_backward(const float* a, const float* h, float* ga, float* gh, const float* geps_nchw,
+                                      const float* glogp, int32_t B, int32_t C, int32_t H, int32_t W, int32_t rescale, float gobj,
+                                      hcf_stream_t stream);
+/* Input end of the taped forward passes: gz [B,4C,H,W] = dL/d z of z = squeeze2d(hr) (haar 0) or Haar(hr) (haar 1) ->
+ * ghr [B,C,2H,2W] = dL/d hr: unsqueeze2d(gz) (Basic.py:143-157), or Haar inv(gz) / 4 (Basic.py:450-487); exact. */
+int hcf_op_input_grad(const float* gz, float* ghr, int32_t B, int32_t C, int32_t H, int32_t W, int32_t haar,
+                      hcf_stream_t stream);
 /* Gradients of an NCHW (clamped) output: kind 0: gz += g;  1: gz += g where 0 <= z <= 1;  2: gz = 0 where z is outside
  * [0, 1] (g unused, may be NULL);  3: gz = (0 <= z <= 1) ? g : 0 on the flat tensors. */
 int hcf_op_output_grad_backward(int32_t kind, const float* g, const float* z, float* gz, int32_t B, int32_t C, int32_t H,

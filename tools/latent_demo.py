@@ -3,11 +3,14 @@
     recon.npy        decode(encode(hr)) of both images (the exact reconstruction) and its max |diff| to the inputs
     tau_sweep.npy    image 0 re-decoded at scale(eps, tau) for tau in --taus
     slerp_path.npy   decode along slerp(eps of image 0, eps of image 1, t), the LR latent interpolated linearly, for --steps values of t
+    refined.npy      latent.refine_image: a tau = 0.8 sample of image 0's 8-bit LR latent after --refine-steps gradient steps on its
+                     NLL with the weights frozen (the flow as an image prior), and the NLL before / after
 
 The images are crops of the bundled example pair (tests/golden/real_images.npz) or, with --seeded, seeded random inputs; the weights
 are the seeded recipe (a trained checkpoint loads with --state-dict PATH: a torch.save'd state dict). Not run by any test.
 
     python tools/latent_demo.py [--preset SR_DF2K_4X] [--size 160] [--out latent_demo_out] [--taus 0,0.5,0.8,1] [--steps 5]
+                                [--refine-steps 20]
 """
 import argparse
 import os
@@ -28,6 +31,7 @@ def main():
     ap.add_argument("--out", default="latent_demo_out")
     ap.add_argument("--taus", default="0,0.5,0.8,1")
     ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--refine-steps", type=int, default=20)
     ap.add_argument("--seeded", action="store_true")
     ap.add_argument("--state-dict", default="")
     args = ap.parse_args()
@@ -67,7 +71,15 @@ def main():
         ts = [i / max(1, args.steps - 1) for i in range(args.steps)]
         path = torch.cat([net.decode(torch.lerp(z[:1], z[1:2], tt), latent.slerp(e0, e1, tt), clamp=True) for tt in ts])
         np.save(os.path.join(args.out, "slerp_path.npy"), path.cpu().numpy())
-    print("wrote recon.npy, tau_sweep.npy %s, slerp_path.npy %s under %s" % (tuple(sweep.shape), tuple(path.shape), args.out))
+        # likelihood-guided refinement: an SR sample of the 8-bit LR latent, moved down its own NLL (weights frozen inside)
+        lq = (torch.clamp(z[:1], 0, 1) * 255.).round() / 255.
+        sample = net.decode(lq, latent.scale(e0, 0.8))
+    refined, _, nlls = latent.refine_image(net, sample, lq, steps=args.refine_steps)
+    if nlls:
+        print("refine_image: nll %.4f -> %.4f bits/dim over %d steps, max |move| %.3e" % (nlls[0], nlls[-1], len(nlls),
+                                                                                       float((refined - sample).abs().max())))
+    np.save(os.path.join(args.out, "refined.npy"), refined.cpu().numpy())
+    print("wrote refined.npy, recon.npy, tau_sweep.npy %s, slerp_path.npy %s under %s" % (tuple(sweep.shape), tuple(path.shape), args.out))
 
 
 if __name__ == "__main__":
