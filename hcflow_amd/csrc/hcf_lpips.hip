@@ -12,6 +12,8 @@
 //   head      per layer and pixel: n_i = sum_c f_i^2, d = sum_c w_c (f0 / (sqrt n0 + 1e-10) - f1 / (sqrt n1 + 1e-10))^2; per-block
 //             partial sums in a fixed order, then out[b] = sum_l (sum of layer l's partials) / (h_l w_l), in layer order.
 // Every reduction has a fixed order that depends only on (H, W): results are bit-reproducible and per image independent of B.
+// The call leaves the s2d input and every feature map in its workspace; hcf_lpips_alex_backward (below) walks back down from
+// there to the image gradients (hcflow_amd/lpips.py: LPIPSLoss).
 #include <algorithm>
 #include <cstring>
 
@@ -253,6 +255,218 @@ static int lpips_pool(const float* in, int N, int Hst, int Wst, int C, int Ho, i
   return hipGetLastError() == hipSuccess ? HCF_OK : HCF_ERR_HIP;
 }
 
+// ---- backward (hcf_lpips_alex_backward): dL/d in0, dL/d in1 from gout[b] = dL/d out[b], the forward's workspace as the tape.
+// The gradient slabs hold only the halves of the stacked batch that want a gradient: Nb = B or 2B images, gradient image m
+// belongs to forward image m + off. Every kernel below is a gather with a fixed summation order: no atomics.
+//   head      per layer and pixel, a_c = 2 w_c (f0_c / d0 - f1_c / d1) gout[b] / (h w), d_i = sqrt(n_i) + 1e-10:
+//             g_f0_c = a_c / d0 - f0_c (sum_k a_k f0_k) / (d0^2 sqrt n0), g_f1 likewise with -a; the term through the norm is
+//             DEFINED as 0 where n_i = 0 (autograd of the stock formulation gives 0 * inf = NaN there). Stored under the
+//             producer's ReLU mask (f > 0).
+//   conv5..3  data gradients through hcf_aux_conv2d_backward (dw = NULL); g_l = f_l > 0 ? g_l + dx : 0 joins the layer below
+//   pool      MaxPool 3 / 2 backward as a gather: an element takes the gradient of each window (at most 2 x 2) whose FIRST
+//             maximum in row-major order it is (PyTorch's rule), plus its head gradient, under the ReLU mask; the spare rows /
+//             cols of the conv1 slab are written 0
+//   conv2, 1  the 5x5 kernel on the tap-flipped transposed pack (launch_conv_block, transposed = 1)
+//   un-prep   s2d gradient [Nb][Hs][Ws][48] -> NCHW [B,3,H,W]: / scale[c], * 2 with normalize, cropped to H x W
+struct LpipsBwdPlan {
+  int Nb, off;
+  size_t o_g[kLpipsLayers], o_t, o_gp2, o_gp1, o_gs2d, o_pk, o_bias, o_scale, o_aux, aux_bytes, total;
+};
+
+static bool lpips_bwd_plan(int B, int which, const LpipsPlan& p, LpipsBwdPlan& q) {
+  memset(&q, 0, sizeof(q));
+  if (which < 1 || which > 3) return false;
+  q.Nb = (which == 3) ? 2 * B : B;
+  q.off = (which == 2) ? B : 0;
+  const size_t N = (size_t)q.Nb, f = sizeof(float);
+  const size_t gs = N * p.Hs * p.Ws, g2 = N * p.H2 * p.W2, g3 = N * p.H3 * p.W3;
+  const size_t pix[kLpipsLayers] = {gs, g2, g3, g3, g3};
+  size_t o = 256;
+  auto take = [&](size_t bytes) { const size_t r = o; o += lp_al256(bytes); return r; };
+  for (int l = 0; l < kLpipsLayers; ++l) q.o_g[l] = take(pix[l] * kAlexC[l] * f);
+  q.o_t = take(g3 * 384 * f);                                   // dx of conv5 / conv4 before it joins g4 / g3
+  q.o_gp2 = take(g3 * 192 * f);
+  q.o_gp1 = take(g2 * 64 * f);
+  q.o_gs2d = take(gs * 48 * f);
+  q.o_pk = take(conv_pack_bytes(12, 25, 64));                   // conv2's data gradient: K = 192 = 12 chunks
+  q.o_bias = take(64 * f);
+  q.o_scale = take(64 * f);
+  size_t aux = 0;
+  for (int l = 2; l < kLpipsLayers; ++l)
+    aux = std::max(aux, hcf_aux_conv2d_workspace(kAlexC[l - 1], kAlexC[l], 3, q.Nb, p.H3, p.W3));
+  q.aux_bytes = aux;
+  q.o_aux = take(aux);
+  q.total = o;
+  return aux > 0;
+}
+
+struct LpipsHeadBwdArgs {
+  LpipsLayer L[kLpipsLayers];
+  float* g[kLpipsLayers];   // [Nb][Hst][Wst][C], the layout of L[l].f
+  int B, which;
+  const float* gout;        // [B]
+};
+
+// the grid and the lane layout of lpips_head_kernel; n_i is summed in the same order as there
+__global__ __launch_bounds__(256) void lpips_head_bwd_kernel(const LpipsHeadBwdArgs a) {
+  const int b = blockIdx.y, blk = blockIdx.x;
+  int l = 0;
+#pragma unroll
+  for (int k = 1; k < kLpipsLayers; ++k) l = (blk >= a.L[k].chunk0) ? k : l;
+  const LpipsLayer L = a.L[l];
+  float* const gl = a.g[l];
+  const int g = threadIdx.x >> 4, j = threadIdx.x & 15;
+  const int hw = L.h * L.w, C = L.C, ni = C >> 6;
+  const float eps = 1e-10f;
+  const float s = a.gout[b] / (float)hw;
+  const int m1 = (a.which == 3) ? a.B + b : b;                  // gradient image of the in1 half
+  for (int k = 0; k < kHeadPix / 16; ++k) {
+    const int p = (blk - L.chunk0) * kHeadPix + k * 16 + g;
+    if (p >= hw) break;                                         // (uniform over the group)
+    const int y = p / L.w, x = p - y * L.w;
+    const size_t po = ((size_t)y * L.Wst + x) * C, img = (size_t)L.Hst * L.Wst * C;
+    const float* f0 = L.f + (size_t)b * img + po;
+    const float* f1 = L.f + (size_t)(a.B + b) * img + po;
+    f32x4 v0[6], v1[6], ac[6];
+    float n0 = 0.f, n1 = 0.f;
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+      if (i < ni) {
+        v0[i] = *reinterpret_cast<const f32x4*>(f0 + 4 * (j + 16 * i));
+        v1[i] = *reinterpret_cast<const f32x4*>(f1 + 4 * (j + 16 * i));
+        n0 += v0[i].x * v0[i].x + v0[i].y * v0[i].y + v0[i].z * v0[i].z + v0[i].w * v0[i].w;
+        n1 += v1[i].x * v1[i].x + v1[i].y * v1[i].y + v1[i].z * v1[i].z + v1[i].w * v1[i].w;
+      }
+    }
+    n0 = __shfl(group16_sum(n0), 0, 16);
+    n1 = __shfl(group16_sum(n1), 0, 16);
+    const float r0 = sqrtf(n0), r1 = sqrtf(n1);
+    const float d0 = r0 + eps, d1 = r1 + eps;
+    float s0 = 0.f, s1 = 0.f;
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+      if (i < ni) {
+        const float* w = L.lin + 4 * (j + 16 * i);
+        f32x4 t;
+        t.x = 2.f * w[0] * (v0[i].x / d0 - v1[i].x / d1) * s; t.y = 2.f * w[1] * (v0[i].y / d0 - v1[i].y / d1) * s;
+        t.z = 2.f * w[2] * (v0[i].z / d0 - v1[i].z / d1) * s; t.w = 2.f * w[3] * (v0[i].w / d0 - v1[i].w / d1) * s;
+        ac[i] = t;
+        s0 += t.x * v0[i].x + t.y * v0[i].y + t.z * v0[i].z + t.w * v0[i].w;
+        s1 += t.x * v1[i].x + t.y * v1[i].y + t.z * v1[i].z + t.w * v1[i].w;
+      }
+    }
+    s0 = __shfl(group16_sum(s0), 0, 16);
+    s1 = __shfl(group16_sum(s1), 0, 16);
+    const float k0 = (n0 > 0.f) ? s0 / (d0 * d0 * r0) : 0.f;   // n == 0: the term through the norm is defined as 0
+    const float k1 = (n1 > 0.f) ? s1 / (d1 * d1 * r1) : 0.f;
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+      if (i < ni) {
+        const f32x4 t = ac[i], u0 = v0[i], u1 = v1[i];
+        if (a.which & 1) {
+          f32x4 o;
+          o.x = u0.x > 0.f ? t.x / d0 - u0.x * k0 : 0.f; o.y = u0.y > 0.f ? t.y / d0 - u0.y * k0 : 0.f;
+          o.z = u0.z > 0.f ? t.z / d0 - u0.z * k0 : 0.f; o.w = u0.w > 0.f ? t.w / d0 - u0.w * k0 : 0.f;
+          *reinterpret_cast<f32x4*>(gl + (size_t)b * img + po + 4 * (j + 16 * i)) = o;
+        }
+        if (a.which & 2) {
+          f32x4 o;
+          o.x = u1.x > 0.f ? u1.x * k1 - t.x / d1 : 0.f; o.y = u1.y > 0.f ? u1.y * k1 - t.y / d1 : 0.f;
+          o.z = u1.z > 0.f ? u1.z * k1 - t.z / d1 : 0.f; o.w = u1.w > 0.f ? u1.w * k1 - t.w / d1 : 0.f;
+          *reinterpret_cast<f32x4*>(gl + (size_t)m1 * img + po + 4 * (j + 16 * i)) = o;
+        }
+      }
+    }
+  }
+}
+
+// g = f > 0 ? g + t : 0 over n4 float4 units (f: the forward slab from its image `off` on)
+__global__ __launch_bounds__(256) void lpips_relu_join_kernel(const float* __restrict__ f, const float* __restrict__ t,
+                                                              float* __restrict__ g, long long n4) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n4) return;
+  const f32x4 fv = reinterpret_cast<const f32x4*>(f)[i], tv = reinterpret_cast<const f32x4*>(t)[i];
+  f32x4 gv = reinterpret_cast<f32x4*>(g)[i];
+  gv.x = fv.x > 0.f ? gv.x + tv.x : 0.f; gv.y = fv.y > 0.f ? gv.y + tv.y : 0.f;
+  gv.z = fv.z > 0.f ? gv.z + tv.z : 0.f; gv.w = fv.w > 0.f ? gv.w + tv.w : 0.f;
+  reinterpret_cast<f32x4*>(g)[i] = gv;
+}
+
+// MaxPool 3 / 2 backward + the producer's ReLU mask + the head gradient already in g. One thread per float4 of the pool's INPUT
+// slab g [Nb][Hst][Wst][C] (valid Hin x Win; beyond: 0). f [.][Hst][Wst][C] and the pool output p [.][Ho][Wo][C] are the
+// forward's, read from image `off` on; gp [Nb][Ho][Wo][C] is the gradient of the pool output. An element with f > 0 that equals a
+// window's maximum takes that window's gradient unless an EARLIER element of the window (row-major) equals it too.
+__global__ __launch_bounds__(256) void lpips_pool_bwd_kernel(const float* __restrict__ f, const float* __restrict__ p,
+                                                             const float* __restrict__ gp, float* __restrict__ g, int Nb, int off,
+                                                             int Hst, int Wst, int Hin, int Win, int C, int Ho, int Wo) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  const int C4 = C >> 2;
+  const long long total = (long long)Nb * Hst * Wst * C4;
+  if (i >= total) return;
+  const int c4 = (int)(i % C4);
+  const long long pix = i / C4;
+  const int x = (int)(pix % Wst);
+  const int y = (int)((pix / Wst) % Hst);
+  const int m = (int)(pix / ((long long)Wst * Hst));
+  f32x4* gptr = reinterpret_cast<f32x4*>(g + (size_t)pix * C + 4 * c4);
+  f32x4 o = {0.f, 0.f, 0.f, 0.f};
+  if (y < Hin && x < Win) {
+    const float* fb = f + (size_t)(m + off) * Hst * Wst * C + 4 * c4;
+    const f32x4 me = *reinterpret_cast<const f32x4*>(fb + ((size_t)y * Wst + x) * C);
+    if (me.x > 0.f || me.y > 0.f || me.z > 0.f || me.w > 0.f) {
+      f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+      const int oy0 = max((y - 1) >> 1, 0), oy1 = min(y >> 1, Ho - 1);
+      const int ox0 = max((x - 1) >> 1, 0), ox1 = min(x >> 1, Wo - 1);
+      for (int oy = oy0; oy <= oy1; ++oy)
+        for (int ox = ox0; ox <= ox1; ++ox) {
+          const size_t wo = ((size_t)oy * Wo + ox) * C + 4 * c4;
+          const f32x4 pv = *reinterpret_cast<const f32x4*>(p + (size_t)(m + off) * Ho * Wo * C + wo);
+          bool cx = me.x > 0.f && me.x == pv.x, cy = me.y > 0.f && me.y == pv.y;
+          bool cz = me.z > 0.f && me.z == pv.z, cw = me.w > 0.f && me.w == pv.w;
+          if (!(cx || cy || cz || cw)) continue;
+          for (int yy = 2 * oy; yy <= y; ++yy) {                 // the elements of the window before (y, x)
+            const int xe = (yy < y) ? 2 * ox + 3 : x;
+            for (int xx = 2 * ox; xx < xe; ++xx) {
+              const f32x4 e = *reinterpret_cast<const f32x4*>(fb + ((size_t)yy * Wst + xx) * C);
+              cx = cx && e.x != pv.x; cy = cy && e.y != pv.y; cz = cz && e.z != pv.z; cw = cw && e.w != pv.w;
+            }
+          }
+          const f32x4 gv = *reinterpret_cast<const f32x4*>(gp + (size_t)m * Ho * Wo * C + wo);
+          acc.x += cx ? gv.x : 0.f; acc.y += cy ? gv.y : 0.f; acc.z += cz ? gv.z : 0.f; acc.w += cw ? gv.w : 0.f;
+        }
+      const f32x4 hg = *gptr;
+      o.x = me.x > 0.f ? hg.x + acc.x : 0.f; o.y = me.y > 0.f ? hg.y + acc.y : 0.f;
+      o.z = me.z > 0.f ? hg.z + acc.z : 0.f; o.w = me.w > 0.f ? hg.w + acc.w : 0.f;
+    }
+  }
+  *gptr = o;
+}
+
+// un-prep: one thread per (gradient image m, s2d row Y, unit q = c * 4 + a, s2d column X): the 4 image columns 4X .. 4X+3 of row
+// 4Y + a, channel c. Image m < B goes to ga, the others to gb.
+__global__ __launch_bounds__(256) void lpips_unprep_kernel(const float* __restrict__ gs, int Nb, int B, int H, int W, int Hs,
+                                                           int Ws, int normalize, const float* __restrict__ scale,
+                                                           float* __restrict__ ga, float* __restrict__ gb) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  const long long total = (long long)Nb * Hs * 12 * Ws;
+  if (i >= total) return;
+  const int X = (int)(i % Ws);
+  const int q = (int)((i / Ws) % 12);
+  const int Y = (int)((i / ((long long)Ws * 12)) % Hs);
+  const int m = (int)(i / ((long long)Ws * 12 * Hs));
+  const int c = q >> 2, y = 4 * Y + (q & 3);
+  if (y >= H) return;
+  const f32x4 v = *reinterpret_cast<const f32x4*>(gs + (((size_t)m * Hs + Y) * Ws + X) * 48 + q * 4);
+  const float sc = scale[c], mul = normalize ? 2.f : 1.f;
+  float* dst = ((m < B) ? ga + (size_t)m * 3 * H * W : gb + (size_t)(m - B) * 3 * H * W) + ((size_t)c * H + y) * W;
+  const float r[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int xx = 4 * X + k;
+    if (xx < W) dst[xx] = r[k] / sc * mul;
+  }
+}
+
 }  // namespace hcf
 
 using namespace hcf;
@@ -318,6 +532,93 @@ int hcf_lpips_alex(const float* in0, const float* in1, int32_t B, int32_t H, int
   if (hipGetLastError() != hipSuccess) return HCF_ERR_HIP;
   fa.nchunk_total = p.nchunk_total; fa.part = h.part; fa.out = out; fa.out_layers = out_layers;
   hipLaunchKernelGGL(lpips_final_kernel, dim3((unsigned)B), dim3(64), 0, st, fa);
+  return hipGetLastError() == hipSuccess ? HCF_OK : HCF_ERR_HIP;
+}
+
+size_t hcf_lpips_backward_workspace(int32_t B, int32_t H, int32_t W, int32_t which) {
+  LpipsPlan p;
+  LpipsBwdPlan q;
+  return (lpips_plan(B, H, W, p) && lpips_bwd_plan(B, which, p, q)) ? q.total : 0;
+}
+
+int hcf_lpips_alex_backward(int32_t B, int32_t H, int32_t W, int32_t normalize, const float* const* params, const float* gout,
+                            int32_t which, float* gin0, float* gin1, const void* fwd_work, size_t fwd_work_bytes, void* work,
+                            size_t work_bytes, hcf_stream_t stream) {
+  if (!params || !gout || !fwd_work || !work || which < 1 || which > 3 || ((which & 1) && !gin0) || ((which & 2) && !gin1))
+    return HCF_ERR_ARG;
+  for (int i = 0; i < HCF_LPIPS_NPARAMS; ++i)
+    if (!params[i]) return HCF_ERR_ARG;
+  LpipsPlan p;
+  LpipsBwdPlan q;
+  if (!lpips_plan(B, H, W, p) || !lpips_bwd_plan(B, which, p, q)) return HCF_ERR_SHAPE;
+  if (fwd_work_bytes < p.total || work_bytes < q.total) return HCF_ERR_NOMEM;
+  hipStream_t st = (hipStream_t)stream;
+  const char* fw = (const char*)fwd_work;
+  char* wk = (char*)work;
+  const int Nb = q.Nb, off = q.off;
+  const float* feat[kLpipsLayers] = {(const float*)(fw + p.o_f1), (const float*)(fw + p.o_f2), (const float*)(fw + p.o_f3),
+                                     (const float*)(fw + p.o_f4), (const float*)(fw + p.o_f5)};
+  const float *p1 = (const float*)(fw + p.o_p1), *p2 = (const float*)(fw + p.o_p2);
+  float* g[kLpipsLayers];
+  for (int l = 0; l < kLpipsLayers; ++l) g[l] = (float*)(wk + q.o_g[l]);
+  float *t = (float*)(wk + q.o_t), *gp2 = (float*)(wk + q.o_gp2), *gp1 = (float*)(wk + q.o_gp1), *gs2d = (float*)(wk + q.o_gs2d);
+  float *bvec = (float*)(wk + q.o_bias), *svec = (float*)(wk + q.o_scale), *pk = (float*)(wk + q.o_pk);
+  const float* cw[kLpipsLayers] = {params[2], params[4], params[6], params[8], params[10]};
+  const int hst[kLpipsLayers] = {p.Hs, p.H2, p.H3, p.H3, p.H3}, wst[kLpipsLayers] = {p.Ws, p.W2, p.W3, p.W3, p.W3};
+  const int hh[kLpipsLayers] = {p.H1, p.H2, p.H3, p.H3, p.H3}, ww[kLpipsLayers] = {p.W1, p.W2, p.W3, p.W3, p.W3};
+
+  // ---- head: the ReLU-masked head gradient of all five layers, for the halves asked for
+  LpipsHeadBwdArgs h;
+  memset(&h, 0, sizeof(h));
+  for (int l = 0; l < kLpipsLayers; ++l) {
+    h.L[l].f = feat[l]; h.L[l].C = kAlexC[l]; h.L[l].Hst = hst[l]; h.L[l].Wst = wst[l]; h.L[l].h = hh[l]; h.L[l].w = ww[l];
+    h.L[l].chunk0 = p.chunk0[l];
+    h.L[l].lin = params[12 + l];
+    h.g[l] = g[l];
+  }
+  h.B = B; h.which = which; h.gout = gout;
+  hipLaunchKernelGGL(lpips_head_bwd_kernel, dim3((unsigned)p.nchunk_total, (unsigned)B), dim3(256), 0, st, h);
+  if (hipGetLastError() != hipSuccess) return HCF_ERR_HIP;
+
+  // ---- conv5, conv4, conv3: g5 -> t -> g4 -> t -> g3 -> gp2
+  void* aux = wk + q.o_aux;
+  if (hipMemsetAsync(aux, 0, 256, st) != hipSuccess) return HCF_ERR_HIP;
+  const size_t img3 = (size_t)p.H3 * p.W3;
+  unsigned grid;
+  int rc = HCF_OK;
+  for (int l = 4; l >= 2; --l) {
+    const int cin = kAlexC[l - 1];
+    const float* xin = ((l == 2) ? p2 : feat[l - 1]) + (size_t)off * img3 * cin;   // conv l's input, from the first wanted image on
+    rc = hcf_aux_conv2d_backward(xin, cin, cin, Nb, p.H3, p.W3, cw[l], kAlexC[l], 3, g[l], kAlexC[l], (l == 2) ? gp2 : t, cin,
+                                 nullptr, aux, q.aux_bytes, HCF_PRECISION_EXACT, stream);
+    if (rc != HCF_OK) return rc;
+    if (l == 2) break;                                          // conv3's input is pool2's output: no ReLU, no head term
+    const long long n4 = (long long)Nb * (long long)img3 * (cin / 4);
+    if (lpips_grid(n4, &grid) != HCF_OK) return HCF_ERR_ARG;
+    hipLaunchKernelGGL(lpips_relu_join_kernel, dim3(grid), dim3(256), 0, st, xin, t, g[l - 1], n4);
+    if (hipGetLastError() != hipSuccess) return HCF_ERR_HIP;
+  }
+
+  // ---- pool2, conv2, pool1 (which also clears the spare rows / cols of the conv1 slab), conv1
+  if (lpips_grid((long long)Nb * p.H2 * p.W2 * (192 / 4), &grid) != HCF_OK) return HCF_ERR_ARG;
+  hipLaunchKernelGGL(lpips_pool_bwd_kernel, dim3(grid), dim3(256), 0, st, feat[1], p2, gp2, g[1], Nb, off, p.H2, p.W2, p.H2, p.W2,
+                     192, p.H3, p.W3);
+  if (hipGetLastError() != hipSuccess) return HCF_ERR_HIP;
+  rc = launch_conv_block(cw[1], 64, 25, 1, 0, nullptr, 64, 64, mkview(g[1], 192, 0, 192), 12, mkview(gp1, 64, 0, 64), ACT_NONE, Nb,
+                         p.H2, p.W2, bvec, svec, pk, st);
+  if (rc != HCF_OK) return rc;
+  if (lpips_grid((long long)Nb * p.Hs * p.Ws * (64 / 4), &grid) != HCF_OK) return HCF_ERR_ARG;
+  hipLaunchKernelGGL(lpips_pool_bwd_kernel, dim3(grid), dim3(256), 0, st, feat[0], p1, gp1, g[0], Nb, off, p.Hs, p.Ws, p.H1, p.W1,
+                     64, p.H2, p.W2);
+  if (hipGetLastError() != hipSuccess) return HCF_ERR_HIP;
+  rc = launch_conv_block(cw[0], 48, 25, 1, 0, nullptr, 48, 64, mkview(g[0], 64, 0, 64), 4, mkview(gs2d, 48, 0, 48), ACT_NONE, Nb,
+                         p.Hs, p.Ws, bvec, svec, pk, st);
+  if (rc != HCF_OK) return rc;
+
+  // ---- un-prep
+  if (lpips_grid((long long)Nb * p.Hs * 12 * p.Ws, &grid) != HCF_OK) return HCF_ERR_ARG;
+  hipLaunchKernelGGL(lpips_unprep_kernel, dim3(grid), dim3(256), 0, st, gs2d, Nb, B, H, W, p.Hs, p.Ws, normalize, params[1],
+                     (which & 1) ? gin0 : gin1, gin1);
   return hipGetLastError() == hipSuccess ? HCF_OK : HCF_ERR_HIP;
 }
 

@@ -25,8 +25,22 @@ weight); H, W >= 31 is AlexNet's minimum (conv1 gives >= 7 rows, pool1 >= 3, poo
 two files users keep offline: torchvision's AlexNet state dict (``features.{0,3,6,8,10}.*``, ``alexnet-owt-7be5be79.pth``) and
 lpips' ``weights/v0.1/alex.pth``. Nothing is ever downloaded: without weights the parameters are seeded random.
 
-No CPU fallback (off-GPU inputs raise ``HcfError``) and no backward (inputs that require grad raise). The call runs on the
-current stream without host synchronisation, is bit-reproducible, and an image's value does not depend on the rest of the batch.
+No CPU fallback (off-GPU inputs raise ``HcfError``). ``LPIPS`` is the frozen metric: it has no backward, and inputs that
+require grad raise. The call runs on the current stream without host synchronisation, is bit-reproducible, and an image's value
+does not depend on the rest of the batch.
+
+``LPIPSLoss(metric, reduction="mean")`` is the same measure as a loss (where a feature loss enters the generator step,
+``HCFlow_SR_model.py:229-232``): one ``autograd.Function`` node whose forward is the metric's own call, bit for bit, and whose
+backward is ONE call of ``hcf_lpips_alex_backward``, which walks back down the feature maps that the forward left in its
+workspace. Each of ``in0`` / ``in1`` that requires grad receives a gradient (the backward convolutions cover only those halves
+of the stacked batch); the parameters are frozen. Per layer and pixel, with ``n_i = sum_c f_i^2``, ``d_i = sqrt(n_i) + 1e-10``
+and ``a_c = 2 w_c (f0_c / d0 - f1_c / d1) gout[b] / (h_l w_l)``:
+
+    ``g_f0_c = a_c / d0 - f0_c (sum_k a_k f0_k) / (d0^2 sqrt(n0))``,  ``g_f1`` the same with ``-a``;
+
+the term through the norm is DEFINED as 0 where ``n_i == 0`` (PyTorch autograd of the formula gives ``0 * inf = NaN`` there).
+The max-pool backward gives a window's gradient to its first maximum in row-major order, as PyTorch does. No atomics: the
+gradient is bit-reproducible, and sample b's gradient does not depend on the rest of the batch. No double backward.
 """
 from __future__ import annotations
 
@@ -36,6 +50,7 @@ from typing import Mapping, Optional, Union
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
+from torch.autograd.function import once_differentiable
 
 from . import _lib
 
@@ -95,7 +110,8 @@ class AlexNetSlices(nn.Module):
 
 class LPIPS(nn.Module):
     """Drop-in for ``lpips.LPIPS(net='alex')`` (v0.1) on the MI355X kernels. ``pnet_path`` / ``model_path``: local files of
-    torchvision's AlexNet state dict and lpips' ``alex.pth`` (either may be omitted: those parameters stay seeded random)."""
+    torchvision's AlexNet state dict and lpips' ``alex.pth`` (either may be omitted: those parameters stay seeded random).
+    ``forward`` is the frozen metric and raises for inputs that require grad: ``LPIPSLoss(metric)`` is the differentiable form."""
 
     def __init__(self, pretrained: bool = True, net: str = "alex", version: str = "0.1", lpips: bool = True,
                  spatial: bool = False, pnet_rand: bool = False, pnet_tune: bool = False, use_dropout: bool = True,
@@ -203,3 +219,102 @@ class LPIPS(nn.Module):
         if retPerLayer:
             return val, [layers[:, l].reshape(B, 1, 1, 1) for l in range(5)]
         return val
+
+
+class _LPIPSLossFn(torch.autograd.Function):
+    """``metric(in0, in1)`` as ONE node. forward: the launch sequence of ``LPIPS.forward`` (``hcf_lpips_alex``); when an input
+    wants a gradient the workspace of that call -- the tape -- and the parameter tensors stay alive in ``ctx``. backward: one
+    ``hcf_lpips_alex_backward`` call over the halves of the stacked batch that want a gradient."""
+
+    @staticmethod
+    def forward(ctx, in0, in1, params, normalize):
+        B, _, H, W = in0.shape
+        dev = in0.device
+        x0 = in0.detach().to(torch.float32).contiguous()
+        x1 = in1.detach().to(torch.float32).contiguous()
+        lib = _lib.load()
+        need = lib.hcf_lpips_workspace(B, H, W)
+        work = torch.empty(need, dtype=torch.uint8, device=dev)
+        out = torch.empty(B, dtype=torch.float32, device=dev)
+        ptrs = (C.c_void_p * len(params))(*[t.data_ptr() for t in params])
+        with torch.cuda.device(dev):
+            rc = lib.hcf_lpips_alex(x0.data_ptr(), x1.data_ptr(), B, H, W, int(bool(normalize)), ptrs, out.data_ptr(), None,
+                                    C.c_void_p(work.data_ptr()), need, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+        _lib.check(rc, None, "hcf_lpips_alex")
+        which = int(ctx.needs_input_grad[0]) | (int(ctx.needs_input_grad[1]) << 1)
+        if which:                                                       # (under no_grad / detached inputs: no tape)
+            ctx.tape = (work, params)
+            ctx.meta = (which, B, H, W, int(bool(normalize)), in0.dtype, in1.dtype)
+        return out.view(B, 1, 1, 1)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gout):
+        work, params = ctx.tape
+        which, B, H, W, normalize, dt0, dt1 = ctx.meta
+        dev = work.device
+        lib = _lib.load()
+        g = gout.reshape(B).to(torch.float32).contiguous()
+        need = lib.hcf_lpips_backward_workspace(B, H, W, which)
+        bwork = torch.empty(need, dtype=torch.uint8, device=dev)
+        g0 = torch.empty(B, 3, H, W, dtype=torch.float32, device=dev) if which & 1 else None
+        g1 = torch.empty(B, 3, H, W, dtype=torch.float32, device=dev) if which & 2 else None
+        ptrs = (C.c_void_p * len(params))(*[t.data_ptr() for t in params])
+        with torch.cuda.device(dev):
+            rc = lib.hcf_lpips_alex_backward(B, H, W, normalize, ptrs, g.data_ptr(), which,
+                                             None if g0 is None else g0.data_ptr(), None if g1 is None else g1.data_ptr(),
+                                             C.c_void_p(work.data_ptr()), work.numel(), C.c_void_p(bwork.data_ptr()), need,
+                                             C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+        _lib.check(rc, None, "hcf_lpips_alex_backward")
+        return (None if g0 is None else g0.to(dt0), None if g1 is None else g1.to(dt1), None, None)
+
+
+class LPIPSLoss(nn.Module):
+    """LPIPS as a loss, next to the frozen metric (``PerceptualLoss`` sits next to ``VGGFeatureExtractor`` the same way):
+
+        metric = LPIPS(pnet_path=..., model_path=...).cuda()
+        crit = LPIPSLoss(metric, reduction="mean")            # "mean" | "sum" | "none" ("none": [B,1,1,1])
+        loss = crit(sr, gt, normalize=True)                   # the (in0, in1, normalize) convention of LPIPS.forward
+        loss.backward()                                       # sr.grad
+
+    Each of ``in0`` / ``in1`` that requires grad receives a gradient (in its own dtype); the parameters of ``metric`` must be
+    frozen (``ValueError`` otherwise). The values are those of ``metric(in0.detach(), in1.detach(), normalize=...)`` bit for
+    bit; "mean" / "sum" are torch reductions of that vector. Under ``no_grad``, or when neither input requires grad, only the
+    forward runs and nothing is kept. The input checks are ``LPIPS.forward``'s (``HcfError``). See the module docstring for the
+    math, the zero-norm convention and the max-pool tie rule."""
+
+    REDUCTIONS = ("mean", "sum", "none")
+
+    def __init__(self, metric: LPIPS, reduction: str = "mean"):
+        super().__init__()
+        if not isinstance(metric, LPIPS):
+            raise TypeError("LPIPSLoss: metric must be a hcflow_amd.lpips.LPIPS, got %s" % type(metric).__name__)
+        if reduction not in self.REDUCTIONS:
+            raise ValueError("LPIPSLoss: reduction must be one of %s, got %r" % (self.REDUCTIONS, reduction))
+        self.metric = metric
+        self.reduction = reduction
+
+    def forward(self, in0: torch.Tensor, in1: torch.Tensor, normalize: bool = False):
+        if any(p.requires_grad for p in self.metric.parameters()):
+            raise ValueError("LPIPSLoss: the parameters of the metric must be frozen (requires_grad=False), no parameter "
+                             "gradient is computed")
+        if not (in0.is_cuda and in1.is_cuda):
+            raise _lib.HcfError("hcflow_amd.lpips runs on MI355X only (no CPU fallback): move the module and its inputs to a GPU")
+        if in0.dim() != 4 or in0.shape[1] != 3 or in0.shape != in1.shape:
+            raise _lib.HcfError("LPIPSLoss expects two [B,3,H,W] tensors of the same shape, got %s and %s"
+                                % (tuple(in0.shape), tuple(in1.shape)))
+        H, W = in0.shape[2:]
+        if H < MIN_SIDE or W < MIN_SIDE:
+            raise _lib.HcfError("LPIPS (AlexNet) needs H, W >= %d, got %dx%d" % (MIN_SIDE, H, W))
+        dev = in0.device
+        if in1.device != dev:
+            raise _lib.HcfError("in0 and in1 are on different devices")
+        params = self.metric._params()
+        if any(t.device != dev for t in params):
+            raise _lib.HcfError("the LPIPS module's parameters are not on %s: call .to(%s) first" % (dev, dev))
+        d = _LPIPSLossFn.apply(in0, in1, params, normalize)
+        if self.reduction == "mean":
+            return d.mean()
+        if self.reduction == "sum":
+            return d.sum()
+        return d

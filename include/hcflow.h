@@ -537,6 +537,24 @@ int hcf_lpips_alex(const float* in0, const float* in1, int32_t B, int32_t H, int
                    const float* const* params, float* out, float* out_layers, void* work, size_t work_bytes,
                    hcf_stream_t stream);
 
+/* ---- LPIPS as a loss: the image gradients of the measure above (test_HCFlow.py:48,132), for use where a feature loss enters
+ * the generator step (HCFlow_SR_model.py:229-232); hcflow_amd/lpips.py: LPIPSLoss. No parameter gradients.
+ * GUARANTEE: a successful hcf_lpips_alex call leaves in `work` the space-to-depth input and the feature maps of every layer of
+ * both inputs, and they stay valid for as long as the caller keeps that buffer unchanged. The layout is private: the backward
+ * entry reads it through the plan the forward wrote it with, so pass the SAME (B, H, W, normalize, params) and the same buffer.
+ *   gout:      device [B], dL/d out[b]
+ *   which:     bit 0: in0 wants a gradient, bit 1: in1 (1, 2 or 3); the backward convolutions cover those halves only
+ *   gin0/gin1: device [B,3,H,W] fp32 NCHW, overwritten for the bits set (the other may be NULL)
+ *   fwd_work:  the work buffer of the forward call (fwd_work_bytes >= the forward's workspace size), read only
+ *   work:      device scratch of the backward's own workspace size for (B, H, W, which); 0: bad shape or `which`
+ * Exact fp32, on `stream`, no host synchronisation, no atomics: bit-reproducible, and sample b's gradient depends on that image
+ * pair and gout[b] only. Where a pixel's feature vector is all zero the gradient through its norm is defined as 0 (autograd of
+ * f / (sqrt(sum f^2) + 1e-10) yields NaN there). Max-pool ties go to the first maximum in row-major order, as in PyTorch. */
+size_t hcf_lpips_backward_workspace(int32_t B, int32_t H, int32_t W, int32_t which);
+int hcf_lpips_alex_backward(int32_t B, int32_t H, int32_t W, int32_t normalize, const float* const* params,
+                            const float* gout, int32_t which, float* gin0, float* gin1, const void* fwd_work,
+                            size_t fwd_work_bytes, void* work, size_t work_bytes, hcf_stream_t stream);
+
 /* Range-headroom probe of the f16x3 path (tools/range_headroom.py): while enabled, every conv launch of the following passes
  * also records max |x| over its input windows and -- for layers that own a Winograd pack -- max |B^T d B| over the F(2x2,3x3)
  * input patches, i.e. the values the split has to represent (f16 limit 65504). hcf_debug_range_probe_read returns record
