@@ -7,5 +7,8 @@ from .config import NetConfig, preset, param_spec, eps_shapes  # noqa: F401
 from .params import make_params  # noqa: F401
 from .arch import HCFlowNet_SR, HCFlowNet_Rescaling  # noqa: F401
 from . import latent  # noqa: F401
+from . import data  # noqa: F401
+from .data import ImageBank, BankLoader, draw_crops, prepare_batch, whole_image  # noqa: F401
 
-__all__ = ["NetConfig", "preset", "param_spec", "eps_shapes", "make_params", "HCFlowNet_SR", "HCFlowNet_Rescaling", "latent"]
+__all__ = ["NetConfig", "preset", "param_spec", "eps_shapes", "make_params", "HCFlowNet_SR", "HCFlowNet_Rescaling", "latent",
+           "data", "ImageBank", "BankLoader", "draw_crops", "prepare_batch", "whole_image"]

@@ -18,6 +18,7 @@ FLAG_NO_CLAMP = 1
 FLAG_NO_RANGE_CHECK = 2
 FLAG_KEEP_COND = 4
 FLAG_REUSE_COND = 8
+DATA_LAUNCH_BATCH = 64      # HCF_DATA_LAUNCH_BATCH: samples per launch of hcf_data_prepare_batch
 
 # every symbol include/hcflow.h declares (tests/test_cabi_cpu.py checks the .so exports them all)
 SYMBOLS = [
@@ -44,6 +45,7 @@ SYMBOLS = [
     "hcf_aux_act_backward", "hcf_aux_feature_loss_workspace", "hcf_aux_feature_loss",
     "hcf_train_backward_ex", "hcf_train_backward_rescale_ex", "hcf_train_encode_sr", "hcf_train_backward_encode",
     "hcf_op_quant_logp_backward_lr", "hcf_op_prior_encode_logp_backward", "hcf_op_input_grad",
+    "hcf_data_prepare_batch",
 ]
 
 
@@ -183,6 +185,7 @@ def load() -> C.CDLL:
     lib.hcf_op_conv_epilogue_backward.argtypes = [fp, fp, fp, i32, i32, f32, fp, i32, f32, fp, fp, fp, fp, f32, fp, fp, fp,
                                                   i32, i32, i32, i32, i32, i32, vp]
     lib.hcf_op_lu_chain.argtypes = [fp] * 7 + [i32, vp]
+    lib.hcf_data_prepare_batch.argtypes = [vp, C.c_size_t, vp, i32, vp, i32, i32, i32, i32, i32, fp, fp, vp]
     for name in SYMBOLS:
         fn = getattr(lib, name)
         if name not in ("hcf_destroy", "hcf_last_error", "hcf_workspace_bytes", "hcf_weight_bytes",

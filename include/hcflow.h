@@ -594,6 +594,30 @@ int hcf_op_set_precision(int32_t mode);
 int hcf_bench_conv(int32_t B, int32_t H, int32_t W, const int32_t* src_c, int32_t n_src, int32_t cout, int32_t k,
                    int32_t iters, double* ms_per_launch, double* flops_per_launch, hcf_stream_t stream);
 
+/* ---- device-side training batches (hcf_data.hip): crop + flip + transpose + bicubic LR of a batch in one launch ----
+ * The reference's GT_dataset.__getitem__ (train phase) on images that already live in device memory as packed HWC uint8:
+ *   gt[b] = crop of uint8 / 255.f (true division) at (top_lr * scale, left_lr * scale), size (lr_h * scale) x (lr_w * scale);
+ *   lq[b] = the window (top_lr, left_lr, lr_h, lr_w) of imresize_np(WHOLE image, 1 / scale) (data/util.py:407-474: antialiased
+ *           cubic, H pass then W pass on the H result, symmetric padding of the whole image), computed for the window only;
+ *   both then augment's hflip ([:, ::-1]), vflip ([::-1]), rot90 (transpose) in that order, BGR -> RGB when `bgr`, HWC -> CHW.
+ * Outputs are float32 NCHW in device memory: gt [B,3,lr_h*scale,lr_w*scale], lq [B,3,lr_h,lr_w] (a rot90 sample is the
+ * transpose, accepted for square crops only); either may be NULL (not wanted), not both.
+ *   bank:   device, bank_bytes bytes; image i = 3 * H * W bytes at its byte offset
+ *   images: HOST [n_images][3] = {byte offset, H, W}
+ *   crops:  HOST [B][6] = {image, top_lr, left_lr, hflip, vflip, rot90}
+ * scale is an integer in 2 .. 8. For an integer factor the normalised cubic weights are one vector of 4 * scale + 2 taps for
+ * every output pixel: tap k of output o reads source index o * scale + k + c0, c0 = scale - 1 + floor(0.5 - 2.5 * scale),
+ * reflected once at each border (i < 0: -i - 1, i >= n: 2n - 1 - i). The weights are computed on the host in double and rounded
+ * to float; they and the per-sample records travel as kernel arguments: no allocation, no copy, no synchronisation, and up to
+ * HCF_DATA_LAUNCH_BATCH samples per launch (larger batches: several launches of the same kernel).
+ * Every record is validated BEFORE any HIP call: HCF_ERR_ARG for null pointers, scale outside 2 .. 8, an image index, offset or crop
+ * outside its table / bank / image, flags other than 0 / 1, rot90 on a non-square crop; HCF_ERR_SHAPE for an image smaller than
+ * 4 * scale in either dimension (one reflection would not reach). The kernel clamps every source index into its image besides. */
+#define HCF_DATA_LAUNCH_BATCH 64
+int hcf_data_prepare_batch(const uint8_t* bank, size_t bank_bytes, const int64_t* images, int32_t n_images,
+                           const int32_t* crops, int32_t B, int32_t lr_h, int32_t lr_w, int32_t scale, int32_t bgr,
+                           float* gt, float* lq, hcf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
