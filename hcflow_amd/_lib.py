@@ -8,6 +8,8 @@ import ctypes as C
 import os
 from typing import List, Optional, Sequence, Tuple
 
+import torch
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("HCFLOW_LIB", os.path.join(_HERE, "libhcflow_hip.so"))   # override: kernel experiments
 
@@ -207,6 +209,34 @@ def check(rc: int, engine=None, what: str = ""):
     raise HcfError("%s failed: %s (%d) %s" % (what or "hcflow call", ERR_NAMES.get(rc, "?"), rc, msg))
 
 
+def current_stream(device) -> int:
+    """The raw handle of the stream that is current on `device`."""
+    return torch.cuda.current_stream(device).cuda_stream
+
+
+def launch(name: str, device, *args, engine=None, tape: Optional[int] = None):
+    """The one way to call a launching entry point (include/hcflow.h: status returned, stream last) outside _EngineModule:
+    `name(*args, stream)` under torch.cuda.device(device), on the stream current there. A tensor argument travels as its address
+    and must be contiguous and, if it is a CUDA tensor, live on `device` (HcfError naming the entry and the position otherwise;
+    host tensors pass, some entries take host pointers); None is NULL; anything else is ctypes' business. `engine`: the handle
+    whose last error joins a failure's text; with `tape`, hcf_train_select_tape(engine, tape) goes first under the same guard."""
+    fn = getattr(load(), name)
+    if isinstance(device, int):
+        device = torch.device("cuda", device)
+    argv = list(args)
+    for i, a in enumerate(argv):
+        if isinstance(a, torch.Tensor):
+            if not a.is_contiguous():
+                raise HcfError("%s: argument %d is not contiguous" % (name, i))
+            if a.is_cuda and a.device != device:
+                raise HcfError("%s: argument %d is on %s, the launch goes to %s" % (name, i, a.device, device))
+            argv[i] = a.data_ptr()
+    with torch.cuda.device(device):
+        if tape is not None:
+            check(load().hcf_train_select_tape(engine, tape), engine, "hcf_train_select_tape")
+        check(fn(*argv, C.c_void_p(current_stream(device))), engine, name)
+
+
 def make_config(cfg) -> hcf_config:
     """hcflow_amd.config.NetConfig -> C struct."""
     c = hcf_config()
@@ -253,6 +283,10 @@ class Engine:
     def handle(self):
         return self._h
 
+    def launch(self, name: str, idx: int, *args, tape: Optional[int] = None):
+        """launch() of an engine method on device `idx`: the handle leads the arguments; `tape` selects the training tape first."""
+        launch(name, idx, self._h, *args, engine=self._h, tape=tape)
+
     def param_spec(self) -> List[Tuple[str, Tuple[int, ...]]]:
         n = self.lib.hcf_param_count(self._h)
         out = []
@@ -279,7 +313,6 @@ class Engine:
 
     def get_param(self, key: str, numel: int):
         """The engine's host copy of a parameter as a flat fp32 CPU tensor."""
-        import torch
         out = torch.empty(int(numel), dtype=torch.float32)
         check(self.lib.hcf_get_param(self._h, key.encode(), C.c_void_p(out.data_ptr()), int(numel)), self._h,
               "hcf_get_param(%s)" % key)

@@ -248,6 +248,19 @@ class FlowNet(nn.Module):
 
 
 # ------------------------------------------------------------------ NLL training step (autograd bridge)
+def _taped_nll_forward(module, hr, lr, noise):
+    """hcf_train_forward_sr on tape 0, for the one-node and the two-node step: (engine, device index, (out_lr, nll, logdet))."""
+    dev = hr.device
+    eng, idx = module._engine_for(dev)
+    B, _, H, W = hr.shape
+    s = module.cfg.scale
+    out_lr = torch.empty(B, 3, H // s, W // s, device=dev)
+    nll = torch.empty(1, device=dev)
+    logdet = torch.empty(B, device=dev)
+    eng.launch("hcf_train_forward_sr", idx, hr, lr, noise, out_lr, nll, logdet, B, H, W, tape=0)
+    return eng, idx, (out_lr, nll.view(()), logdet)
+
+
 class _SRNLLStep(torch.autograd.Function):
     """``_, nll = netG(hr=, lr=, reverse=False)`` with gradients (HCFlow_SR_model.py:195-199): the engine keeps the
     intermediate tensors of the forward pass in HBM (hcf_train_forward_sr) and produces d nll / d parameters for the
@@ -257,25 +270,12 @@ class _SRNLLStep(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, module, hr, lr, noise, *params):
-        dev = hr.device
-        eng, idx = module._engine_for(dev)
-        B, _, H, W = hr.shape
-        s = module.cfg.scale
-        out_lr = torch.empty(B, 3, H // s, W // s, device=dev)
-        nll = torch.empty(1, device=dev)
-        logdet = torch.empty(B, device=dev)
-        with torch.cuda.device(idx):
-            _lib.check(eng.lib.hcf_train_select_tape(eng.handle, 0), eng.handle, "hcf_train_select_tape")
-            rc = eng.lib.hcf_train_forward_sr(eng.handle, hr.data_ptr(), lr.data_ptr(), noise.data_ptr(),
-                                              out_lr.data_ptr(), nll.data_ptr(), logdet.data_ptr(), B, H, W,
-                                              module._stream(idx))
-        _lib.check(rc, eng.handle, "hcf_train_forward_sr")
-        ctx.eng, ctx.idx = eng, idx
+        ctx.eng, ctx.idx, outs = _taped_nll_forward(module, hr, lr, noise)
         ctx.keep = (hr, lr, noise)                       # the engine's tape holds raw pointers to these
         ctx.image_needs_grad = (bool(hr.requires_grad), bool(lr.requires_grad))
         ctx.meta = [(tuple(p.shape), p.numel(), bool(p.requires_grad)) for p in params]
-        ctx.mark_non_differentiable(out_lr, logdet)
-        return out_lr, nll.view(()), logdet
+        ctx.mark_non_differentiable(outs[0], outs[2])
+        return outs
 
     @staticmethod
     def backward(ctx, g_lr, g_nll, g_logdet):
@@ -284,12 +284,7 @@ class _SRNLLStep(torch.autograd.Function):
         flat, total = _flat_grad_buffer(ctx.meta, hr.device)
         g_hr = torch.empty_like(hr) if ctx.image_needs_grad[0] else None
         g_lq = torch.empty_like(lr) if ctx.image_needs_grad[1] else None
-        with torch.cuda.device(idx):
-            _lib.check(eng.lib.hcf_train_select_tape(eng.handle, 0), eng.handle, "hcf_train_select_tape")
-            rc = eng.lib.hcf_train_backward_ex(eng.handle, float(g_nll), None if flat is None else flat.data_ptr(), total,
-                                               None if g_hr is None else g_hr.data_ptr(), None if g_lq is None else g_lq.data_ptr(),
-                                               C.c_void_p(torch.cuda.current_stream(idx).cuda_stream))
-        _lib.check(rc, eng.handle, "hcf_train_backward_ex")
+        eng.launch("hcf_train_backward_ex", idx, float(g_nll), flat, total, g_hr, g_lq, tape=0)
         return (None, g_hr, g_lq, None) + _split_flat(flat, ctx.meta)
 
 
@@ -325,11 +320,7 @@ class _SREncodeStep(torch.autograd.Function):
         eps = [torch.empty(sh, device=dev) for sh in eps_shapes(cfg, B, h, w)]
         logp = torch.empty(B, device=dev)
         arr = (C.c_void_p * len(eps))(*[e.data_ptr() for e in eps])
-        with torch.cuda.device(idx):
-            _lib.check(eng.lib.hcf_train_select_tape(eng.handle, 0), eng.handle, "hcf_train_select_tape")
-            rc = eng.lib.hcf_train_encode_sr(eng.handle, hr.data_ptr(), None if noise is None else noise.data_ptr(), z.data_ptr(),
-                                             arr, len(eps), logp.data_ptr(), B, H, W, 0, module._stream(idx))
-        _lib.check(rc, eng.handle, "hcf_train_encode_sr")
+        eng.launch("hcf_train_encode_sr", idx, hr, noise, z, arr, len(eps), logp, B, H, W, 0, tape=0)
         ctx.eng, ctx.idx = eng, idx
         ctx.keep = (hr, noise)                           # the engine's tape holds raw pointers to these
         ctx.n_levels = len(eps)
@@ -342,12 +333,7 @@ class _SREncodeStep(torch.autograd.Function):
         gs = [None if g is None else g.to(torch.float32).contiguous() for g in (g_z, g_logp) + tuple(g_eps)]
         arr = (C.c_void_p * ctx.n_levels)(*[None if g is None else g.data_ptr() for g in gs[2:]])
         g_hr = torch.empty_like(hr)
-        with torch.cuda.device(idx):
-            _lib.check(eng.lib.hcf_train_select_tape(eng.handle, 0), eng.handle, "hcf_train_select_tape")
-            rc = eng.lib.hcf_train_backward_encode(eng.handle, None if gs[0] is None else gs[0].data_ptr(), arr, ctx.n_levels,
-                                                   None if gs[1] is None else gs[1].data_ptr(), None, 0, g_hr.data_ptr(),
-                                                   C.c_void_p(torch.cuda.current_stream(idx).cuda_stream))
-        _lib.check(rc, eng.handle, "hcf_train_backward_encode")
+        eng.launch("hcf_train_backward_encode", idx, gs[0], arr, ctx.n_levels, gs[1], None, 0, g_hr, tape=0)
         return None, g_hr, None
 
 
@@ -403,39 +389,16 @@ class _SRNLLTwoPhase:
         self.flat = None
 
     def forward(self):
-        m, hr = self.module, self.hr
-        dev = hr.device
-        self.eng, self.idx = m._engine_for(dev)
-        B, _, H, W = hr.shape
-        s = m.cfg.scale
-        out_lr = torch.empty(B, 3, H // s, W // s, device=dev)
-        nll = torch.empty(1, device=dev)
-        logdet = torch.empty(B, device=dev)
-        eng = self.eng
-        with torch.cuda.device(self.idx):
-            _lib.check(eng.lib.hcf_train_select_tape(eng.handle, 0), eng.handle, "hcf_train_select_tape")
-            rc = eng.lib.hcf_train_forward_sr(eng.handle, hr.data_ptr(), self.lr.data_ptr(), self.noise.data_ptr(),
-                                              out_lr.data_ptr(), nll.data_ptr(), logdet.data_ptr(), B, H, W, m._stream(self.idx))
-        _lib.check(rc, eng.handle, "hcf_train_forward_sr")
-        return out_lr, nll.view(()), logdet
+        self.eng, self.idx, outs = _taped_nll_forward(self.module, self.hr, self.lr, self.noise)
+        return outs
 
     def backward(self, phase, g_outs):
-        eng, idx = self.eng, self.idx
         total = sum(n for _, n, _ in self.meta)
         if phase == 0:
             self.flat = torch.empty(total, device=self.hr.device, dtype=torch.float32)
             self.g_nll = float(g_outs[1])
-        with torch.cuda.device(idx):
-            _lib.check(eng.lib.hcf_train_select_tape(eng.handle, 0), eng.handle, "hcf_train_select_tape")
-            rc = eng.lib.hcf_train_backward_phase(eng.handle, phase, self.g_nll, self.flat.data_ptr(), total,
-                                                  C.c_void_p(torch.cuda.current_stream(idx).cuda_stream))
-        _lib.check(rc, eng.handle, "hcf_train_backward_phase")
-        grads, off = [], 0
-        for i, (shape, n, need) in enumerate(self.meta):
-            if (i in self.early_idx) == (phase == 0):
-                grads.append(self.flat[off:off + n].view(shape) if need else None)
-            off += n
-        return grads
+        self.eng.launch("hcf_train_backward_phase", self.idx, phase, self.g_nll, self.flat, total, tape=0)
+        return [g for i, g in enumerate(_split_flat(self.flat, self.meta)) if (i in self.early_idx) == (phase == 0)]
 
 
 def _grad_nodes() -> int:
@@ -479,12 +442,8 @@ class _SRReverseStep(torch.autograd.Function):
                 keep.append(e)
                 slots.append(i)
                 arr[i] = e.data_ptr()
-        with torch.cuda.device(idx):
-            _lib.check(eng.lib.hcf_train_select_tape(eng.handle, 1), eng.handle, "hcf_train_select_tape")
-            rc = eng.lib.hcf_train_inverse(eng.handle, lr.data_ptr(), arr, len(shapes), float(tau), int(seed),
-                                           out.data_ptr(), B, h, w, 0 if clamp else _lib.FLAG_NO_CLAMP,
-                                           module._stream(idx))
-        _lib.check(rc, eng.handle, "hcf_train_inverse")
+        eng.launch("hcf_train_inverse", idx, lr, arr, len(shapes), float(tau), int(seed), out, B, h, w,
+                   0 if clamp else _lib.FLAG_NO_CLAMP, tape=1)
         ctx.eng, ctx.idx = eng, idx
         ctx.keep = (lr, keep)
         ctx.lr_needs_grad = bool(lr.requires_grad)
@@ -503,12 +462,7 @@ class _SRReverseStep(torch.autograd.Function):
         arr = (C.c_void_p * ctx.n_levels)()
         for slot, g in zip(ctx.eps_slots, g_eps):
             arr[slot] = None if g is None else g.data_ptr()
-        with torch.cuda.device(idx):
-            _lib.check(eng.lib.hcf_train_select_tape(eng.handle, 1), eng.handle, "hcf_train_select_tape")
-            rc = eng.lib.hcf_train_backward_inverse_ex(eng.handle, g_out.data_ptr(), None if flat is None else flat.data_ptr(),
-                                                       total, None if g_lr is None else g_lr.data_ptr(), arr, ctx.n_levels,
-                                                       C.c_void_p(torch.cuda.current_stream(idx).cuda_stream))
-        _lib.check(rc, eng.handle, "hcf_train_backward_inverse_ex")
+        eng.launch("hcf_train_backward_inverse_ex", idx, g_out, flat, total, g_lr, arr, ctx.n_levels, tape=1)
         return (None, g_lr, None, None, None, None) + tuple(g_eps) + _split_flat(flat, ctx.meta)
 
 
@@ -525,11 +479,7 @@ class _RescaleForwardStep(torch.autograd.Function):
         out_lr = torch.empty(B, 3, H // 4, W // 4, device=dev)
         z1 = torch.empty(B, cfg.level_channels(0) - cfg.split_channels(0), H // 2, W // 2, device=dev)
         z2 = torch.empty(B, cfg.level_channels(1) - cfg.split_channels(1), H // 4, W // 4, device=dev)
-        with torch.cuda.device(idx):
-            _lib.check(eng.lib.hcf_train_select_tape(eng.handle, 0), eng.handle, "hcf_train_select_tape")
-            rc = eng.lib.hcf_train_forward_rescale(eng.handle, hr.data_ptr(), out_lr.data_ptr(), z1.data_ptr(), z2.data_ptr(),
-                                                   B, H, W, 0 if clamp else _lib.FLAG_NO_CLAMP, module._stream(idx))
-        _lib.check(rc, eng.handle, "hcf_train_forward_rescale")
+        eng.launch("hcf_train_forward_rescale", idx, hr, out_lr, z1, z2, B, H, W, 0 if clamp else _lib.FLAG_NO_CLAMP, tape=0)
         ctx.eng, ctx.idx, ctx.keep = eng, idx, hr
         ctx.hr_needs_grad = bool(hr.requires_grad)
         ctx.meta = [(tuple(p.shape), p.numel(), bool(p.requires_grad)) for p in params]
@@ -541,13 +491,7 @@ class _RescaleForwardStep(torch.autograd.Function):
         gs = [None if g is None else g.to(torch.float32).contiguous() for g in (g_lr, g_z1, g_z2)]
         flat, total = _flat_grad_buffer(ctx.meta, ctx.keep.device)
         g_hr = torch.empty_like(ctx.keep) if ctx.hr_needs_grad else None
-        with torch.cuda.device(idx):
-            _lib.check(eng.lib.hcf_train_select_tape(eng.handle, 0), eng.handle, "hcf_train_select_tape")
-            rc = eng.lib.hcf_train_backward_rescale_ex(eng.handle, *[None if g is None else g.data_ptr() for g in gs],
-                                                       None if flat is None else flat.data_ptr(), total,
-                                                       None if g_hr is None else g_hr.data_ptr(),
-                                                       C.c_void_p(torch.cuda.current_stream(idx).cuda_stream))
-        _lib.check(rc, eng.handle, "hcf_train_backward_rescale_ex")
+        eng.launch("hcf_train_backward_rescale_ex", idx, *gs, flat, total, g_hr, tape=0)
         return (None, g_hr, None) + _split_flat(flat, ctx.meta)
 
 

@@ -10,7 +10,6 @@ There is no CPU fallback: prepare_batch on a bank that is not on a GPU raises.
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import Dict, Optional, Sequence
 
 import numpy as np
@@ -99,13 +98,8 @@ def _launch(bank: ImageBank, crops: torch.Tensor, lr_h: int, lr_w: int, scale: i
     dev = bank.data.device
     if dev.type != "cuda":
         raise _lib.HcfError("hcflow_amd.data has no CPU path: the bank lives on %s" % dev)
-    lib = _lib.load()
-    with torch.cuda.device(dev):
-        rc = lib.hcf_data_prepare_batch(C.c_void_p(bank.data.data_ptr()), bank.nbytes, C.c_void_p(bank.table.data_ptr()), len(bank),
-                                        C.c_void_p(crops.data_ptr()), int(crops.shape[0]), lr_h, lr_w, int(scale), int(bank.bgr),
-                                        C.c_void_p(gt.data_ptr()), C.c_void_p(lq.data_ptr()),
-                                        C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    _lib.check(rc, None, "hcf_data_prepare_batch")
+    _lib.launch("hcf_data_prepare_batch", dev, bank.data, bank.nbytes, bank.table, len(bank), crops, int(crops.shape[0]), lr_h, lr_w,
+                int(scale), int(bank.bgr), gt, lq)
 
 
 def _outputs(bank, out, B, gh, gw, lh, lw) -> Dict[str, torch.Tensor]:

@@ -32,7 +32,6 @@ strictly; without one the weights are random. No CPU fallback: ``forward`` raise
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import Optional
 
 import torch
@@ -76,14 +75,6 @@ def _w4s2_as_3x3(w: torch.Tensor) -> torch.Tensor:
     return w3.reshape(O, 4 * Cc, 3, 3)
 
 
-def _ptr(t):
-    return None if t is None else t.data_ptr()
-
-
-def _stream(device):
-    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-
-
 def _workspace(work, key, need, device, zeroed):
     """The scratch buffer work[key] of at least `need` bytes on `device` (re)allocated when missing or too small. Every key names
     its DEVICE and STREAM: nn.DataParallel replicas share the dict (replicate() shallow-copies __dict__), one replica thread per
@@ -105,14 +96,11 @@ def _conv_forward(x, w, bias, act, prec, work, flags):
     y = torch.empty(B, H, W, (cout + 3) & ~3, device=x.device, dtype=torch.float32)
     if y.shape[3] != cout:
         y.zero_()
-    st = torch.cuda.current_stream(x.device).cuda_stream
-    wk = _workspace(work, (x.device.index, st, cin, cout, k, B, H, W), lib.hcf_aux_conv2d_workspace(cin, cout, k, B, H, W),
-                    x.device, zeroed=True)                                  # [0, 256): range flag + zero page
+    wk = _workspace(work, (x.device.index, _lib.current_stream(x.device), cin, cout, k, B, H, W),
+                    lib.hcf_aux_conv2d_workspace(cin, cout, k, B, H, W), x.device, zeroed=True)   # [0, 256): range flag + zero page
     flags.append(wk)
     b = None if bias is None else bias.contiguous()
-    rc = lib.hcf_aux_conv2d(x.data_ptr(), cs, cin, B, H, W, w.data_ptr(), _ptr(b), cout, k, act, y.data_ptr(), y.shape[3],
-                            wk.data_ptr(), wk.numel(), prec, C.c_void_p(st))
-    _lib.check(rc, None, "hcf_aux_conv2d")
+    _lib.launch("hcf_aux_conv2d", x.device, x, cs, cin, B, H, W, w, b, cout, k, act, y, y.shape[3], wk, wk.numel(), prec)
     return y, wk
 
 
@@ -120,9 +108,7 @@ def _conv_backward(x, w, g, dx, dw, wk, prec):
     """Gradients of conv_k(x, w) given g = dL/d(pre-activation) into the caller's dx (channels [0, cin)) and dw; None: skipped."""
     B, H, W, cs = x.shape
     cout, cin, k, _ = w.shape
-    rc = _lib.load().hcf_aux_conv2d_backward(x.data_ptr(), cs, cin, B, H, W, w.data_ptr(), cout, k, g.data_ptr(), g.shape[3],
-                                             _ptr(dx), cs, _ptr(dw), wk.data_ptr(), wk.numel(), prec, _stream(x.device))
-    _lib.check(rc, None, "hcf_aux_conv2d_backward")
+    _lib.launch("hcf_aux_conv2d_backward", x.device, x, cs, cin, B, H, W, w, cout, k, g, g.shape[3], dx, cs, dw, wk, wk.numel(), prec)
 
 
 def _range_redo(run, prec, restore=None):
@@ -151,8 +137,7 @@ class _ConvNHWC(torch.autograd.Function):
             raise _lib.HcfError("hcflow_amd.gan runs on MI355X only (no CPU fallback): move the module and its inputs to a GPU")
         assert x.shape[3] % 4 == 0 and x.shape[3] >= w.shape[1] and x.is_contiguous() and x.dtype == torch.float32
         w = w.contiguous()
-        with torch.cuda.device(x.device):
-            y, wk = _conv_forward(x, w, bias, act, prec, work, flag_owner)
+        y, wk = _conv_forward(x, w, bias, act, prec, work, flag_owner)
         ctx.save_for_backward(x, w, y if act else None)
         ctx.meta = (act, prec, bias is not None, wk)
         return y
@@ -168,8 +153,7 @@ class _ConvNHWC(torch.autograd.Function):
             g = g * torch.where(y > 0, torch.ones_like(y), torch.full_like(y, 0.2))
         dx = torch.zeros_like(x) if ctx.needs_input_grad[0] else None
         dw = torch.empty_like(w) if ctx.needs_input_grad[1] else None       # frozen weights (VGG; netD during the G step): skipped
-        with torch.cuda.device(x.device):
-            _conv_backward(x, w, g, dx, dw, wk, prec)
+        _conv_backward(x, w, g, dx, dw, wk, prec)
         db = g[..., :w.shape[0]].sum(dim=(0, 1, 2)) if (has_bias and ctx.needs_input_grad[2]) else None
         return dx, dw, db, None, None, None, None
 
@@ -184,8 +168,7 @@ def _interior(y: torch.Tensor):
 
 def _bn_workspace(work, x, need):
     # not inlined: the forward and the backward pass must name the same key
-    return _workspace(work, ("bn", x.device.index, torch.cuda.current_stream(x.device).cuda_stream), max(need, 256), x.device,
-                      zeroed=False)
+    return _workspace(work, ("bn", x.device.index, _lib.current_stream(x.device)), max(need, 256), x.device, zeroed=False)
 
 
 class _BnActNHWC(torch.autograd.Function):
@@ -230,11 +213,8 @@ class _BnActNHWC(torch.autograd.Function):
             smean = torch.empty(Cc, device=x.device, dtype=torch.float32)
             sinv = torch.empty(Cc, device=x.device, dtype=torch.float32)
             gamma, beta = gamma.contiguous(), beta.contiguous()
-        with torch.cuda.device(x.device):
-            rc = lib.hcf_aux_bn_act(x.data_ptr(), cs, Cc, B, H, W, y0, x0, Ho, Wo, _ptr(gamma), _ptr(beta), _ptr(rmean), _ptr(rvar),
-                                    mode, momentum, eps, act, y.data_ptr(), y.shape[3], _ptr(smean), _ptr(sinv),
-                                    _ptr(wk), 0 if wk is None else wk.numel(), _stream(x.device))
-        _lib.check(rc, None, "hcf_aux_bn_act")
+        _lib.launch("hcf_aux_bn_act", x.device, x, cs, Cc, B, H, W, y0, x0, Ho, Wo, gamma, beta, rmean, rvar, mode, momentum, eps, act,
+                    y, y.shape[3], smean, sinv, wk, 0 if wk is None else wk.numel())
         ctx.save_for_backward(x, gamma, beta, smean, sinv)
         ctx.meta = (Cc, window, act, mode, work)
         return y
@@ -253,11 +233,8 @@ class _BnActNHWC(torch.autograd.Function):
         wk = None
         if mode == _BN_TRAIN or need_p:
             wk = _bn_workspace(work, x, lib.hcf_aux_bn_act_workspace(Cc, B, Ho, Wo))
-        with torch.cuda.device(x.device):
-            rc = lib.hcf_aux_bn_act_backward(x.data_ptr(), cs, Cc, B, H, W, y0, x0, Ho, Wo, _ptr(gamma), _ptr(beta), _ptr(smean),
-                                             _ptr(sinv), mode, act, g.data_ptr(), g.shape[3], dx.data_ptr(), cs, _ptr(dgamma),
-                                             _ptr(dbeta), _ptr(wk), 0 if wk is None else wk.numel(), _stream(x.device))
-        _lib.check(rc, None, "hcf_aux_bn_act_backward")
+        _lib.launch("hcf_aux_bn_act_backward", x.device, x, cs, Cc, B, H, W, y0, x0, Ho, Wo, gamma, beta, smean, sinv, mode, act,
+                    g, g.shape[3], dx, cs, dgamma, dbeta, wk, 0 if wk is None else wk.numel())
         return (dx, dgamma if ctx.needs_input_grad[1] else None, dbeta if ctx.needs_input_grad[2] else None,
                 None, None, None, None, None)
 
@@ -511,12 +488,9 @@ class _PerceptualLossFn(torch.autograd.Function):
     def _pass(lib, netF, plan, x, prec, flags, keep):
         B, _, H, W = x.shape
         dev = x.device
-        stream = _stream(dev)
         y = torch.empty(B, H, W, 4, device=dev, dtype=torch.float32)
         norm = netF.use_input_norm
-        rc = lib.hcf_aux_input_norm(x.data_ptr(), netF.mean.data_ptr() if norm else None, netF.std.data_ptr() if norm else None,
-                                    B, H, W, y.data_ptr(), stream)
-        _lib.check(rc, None, "hcf_aux_input_norm")
+        _lib.launch("hcf_aux_input_norm", dev, x, netF.mean if norm else None, netF.std if norm else None, B, H, W, y)
         tape = []
         for conv, _, relu, pooled in plan:
             cout, w = conv.out_channels, conv.weight.contiguous()
@@ -529,8 +503,7 @@ class _PerceptualLossFn(torch.autograd.Function):
                     raise ValueError("PerceptualLoss: the input is too small for the %d max-pools of this feature_layer"
                                      % sum(p for _, _, _, p in plan))
                 p = torch.empty(B, H // 2, W // 2, cout, device=dev, dtype=torch.float32)
-                rc = lib.hcf_aux_maxpool2(y.data_ptr(), cout, cout, B, H, W, p.data_ptr(), cout, stream)
-                _lib.check(rc, None, "hcf_aux_maxpool2")
+                _lib.launch("hcf_aux_maxpool2", dev, y, cout, cout, B, H, W, p, cout)
                 y, H, W = p, H // 2, W // 2
         return y, tape
 
@@ -544,49 +517,38 @@ class _PerceptualLossFn(torch.autograd.Function):
             fr, _ = _PerceptualLossFn._pass(lib, netF, plan, xr, prec, flags, False)
             return (fr,) + _PerceptualLossFn._pass(lib, netF, plan, xf, prec, flags, need_grad)
 
-        with torch.cuda.device(fake.device):
-            stream = _stream(fake.device)
-            fr, ff, tape = _range_redo(both, _PREC[netF._prec[0]])
-            n = ff.numel()
-            wk = _workspace(netF._work, ("fea", fake.device.index, stream.value), lib.hcf_aux_feature_loss_workspace(n),
-                            fake.device, zeroed=False)
-            loss = torch.empty((), device=fake.device, dtype=torch.float32)
-            gfea = torch.empty_like(ff) if need_grad else None
-            rc = lib.hcf_aux_feature_loss(ff.data_ptr(), fr.data_ptr(), n, kind, loss.data_ptr(),
-                                          _ptr(gfea), wk.data_ptr(), wk.numel(), stream)
-            _lib.check(rc, None, "hcf_aux_feature_loss")
+        dev = fake.device
+        fr, ff, tape = _range_redo(both, _PREC[netF._prec[0]])
+        n = ff.numel()
+        wk = _workspace(netF._work, ("fea", dev.index, _lib.current_stream(dev)), lib.hcf_aux_feature_loss_workspace(n), dev,
+                        zeroed=False)
+        loss = torch.empty((), device=dev, dtype=torch.float32)
+        gfea = torch.empty_like(ff) if need_grad else None
+        _lib.launch("hcf_aux_feature_loss", dev, ff, fr, n, kind, loss, gfea, wk, wk.numel())
         ctx.tape, ctx.gfea, ctx.plan, ctx.netF = tape, gfea, plan, netF
         ctx.in_meta = (tuple(fake.shape), fake.dtype)
         return loss
 
     @staticmethod
     def backward(ctx, gout):
-        lib = _lib.load()
         plan, netF = ctx.plan, ctx.netF
         (B, _, H0, W0), dtype = ctx.in_meta
         g = ctx.gfea * gout                                    # a fresh tensor: the in-place activation backward below owns it
         dev = g.device
-        with torch.cuda.device(dev):
-            stream = _stream(dev)
-            for (conv, _, relu, pooled), (x, y, w, wk) in zip(reversed(plan), reversed(ctx.tape)):
-                _, H, W, _ = x.shape
-                cout, act = conv.out_channels, int(relu)
-                if pooled:
-                    gpre = torch.empty(B, H, W, cout, device=dev, dtype=torch.float32)
-                    rc = lib.hcf_aux_maxpool2_act_backward(g.data_ptr(), cout, y.data_ptr(), cout, cout, B, H, W, act, gpre.data_ptr(),
-                                                           cout, stream)
-                    _lib.check(rc, None, "hcf_aux_maxpool2_act_backward")
-                    g = gpre
-                elif act:
-                    rc = lib.hcf_aux_act_backward(g.data_ptr(), y.data_ptr(), act, g.numel(), g.data_ptr(), stream)
-                    _lib.check(rc, None, "hcf_aux_act_backward")
-                dx = torch.empty_like(x)                       # channels [0, cin) written; the 4th channel of the image layer is never read
-                _conv_backward(x, w, g, dx, None, wk, 0)
-                g = dx
-            gx = torch.empty(B, 3, H0, W0, device=dev, dtype=torch.float32)
-            rc = lib.hcf_aux_input_norm_backward(g.data_ptr(), netF.std.data_ptr() if netF.use_input_norm else None, B, H0, W0,
-                                                 gx.data_ptr(), stream)
-            _lib.check(rc, None, "hcf_aux_input_norm_backward")
+        for (conv, _, relu, pooled), (x, y, w, wk) in zip(reversed(plan), reversed(ctx.tape)):
+            _, H, W, _ = x.shape
+            cout, act = conv.out_channels, int(relu)
+            if pooled:
+                gpre = torch.empty(B, H, W, cout, device=dev, dtype=torch.float32)
+                _lib.launch("hcf_aux_maxpool2_act_backward", dev, g, cout, y, cout, cout, B, H, W, act, gpre, cout)
+                g = gpre
+            elif act:
+                _lib.launch("hcf_aux_act_backward", dev, g, y, act, g.numel(), g)
+            dx = torch.empty_like(x)                           # channels [0, cin) written; the 4th channel of the image layer is never read
+            _conv_backward(x, w, g, dx, None, wk, 0)
+            g = dx
+        gx = torch.empty(B, 3, H0, W0, device=dev, dtype=torch.float32)
+        _lib.launch("hcf_aux_input_norm_backward", dev, g, netF.std if netF.use_input_norm else None, B, H0, W0, gx)
         return gx.to(dtype), None, None, None, None
 
 

@@ -108,6 +108,49 @@ class AlexNetSlices(nn.Module):
         return [getattr(getattr(self, "slice%d" % (s + 1)), str(i)) for s, i in enumerate(ALEX_CONV_INDEX)]
 
 
+def _checked_params(metric, in0, in1, loss: bool):
+    """The input checks of ``LPIPS.forward`` (``loss`` off: inputs that require grad are refused) and ``LPIPSLoss.forward`` (on: the
+    metric's parameters must be frozen); returns ``metric._params()``, which live on the inputs' device."""
+    if loss and any(p.requires_grad for p in metric.parameters()):
+        raise ValueError("LPIPSLoss: the parameters of the metric must be frozen (requires_grad=False), no parameter "
+                         "gradient is computed")
+    if not (in0.is_cuda and in1.is_cuda):
+        raise _lib.HcfError("hcflow_amd.lpips runs on MI355X only (no CPU fallback): move the module and its inputs to a GPU")
+    if not loss and (in0.requires_grad or in1.requires_grad):
+        raise _lib.HcfError("hcflow_amd.lpips.LPIPS has no backward pass: call it on detached inputs (e.g. under torch.no_grad())")
+    if in0.dim() != 4 or in0.shape[1] != 3 or in0.shape != in1.shape:
+        raise _lib.HcfError("%s expects two [B,3,H,W] tensors of the same shape, got %s and %s"
+                            % ("LPIPSLoss" if loss else "LPIPS", tuple(in0.shape), tuple(in1.shape)))
+    H, W = in0.shape[2:]
+    if H < MIN_SIDE or W < MIN_SIDE:
+        raise _lib.HcfError("LPIPS (AlexNet) needs H, W >= %d, got %dx%d" % (MIN_SIDE, H, W))
+    dev = in0.device
+    if in1.device != dev:
+        raise _lib.HcfError("in0 and in1 are on different devices")
+    params = metric._params()
+    if any(t.device != dev for t in params):
+        raise _lib.HcfError("the LPIPS module's parameters are not on %s: call .to(%s) first" % (dev, dev))
+    return params
+
+
+def _param_ptrs(params):
+    return (C.c_void_p * len(params))(*[t.data_ptr() for t in params])
+
+
+def _alex_forward(params, in0, in1, normalize, per_layer: bool):
+    """The one ``hcf_lpips_alex`` call of the metric and of the loss: (out [B], layers [B, 5] or None, the call's workspace)."""
+    B, _, H, W = in0.shape
+    dev = in0.device
+    x0 = in0.detach().to(torch.float32).contiguous()
+    x1 = in1.detach().to(torch.float32).contiguous()
+    need = _lib.load().hcf_lpips_workspace(B, H, W)
+    work = torch.empty(need, dtype=torch.uint8, device=dev)       # stream-ordered reuse by the caching allocator
+    out = torch.empty(B, dtype=torch.float32, device=dev)
+    layers = torch.empty(B, 5, dtype=torch.float32, device=dev) if per_layer else None
+    _lib.launch("hcf_lpips_alex", dev, x0, x1, B, H, W, int(bool(normalize)), _param_ptrs(params), out, layers, work, need)
+    return out, layers, work
+
+
 class LPIPS(nn.Module):
     """Drop-in for ``lpips.LPIPS(net='alex')`` (v0.1) on the MI355X kernels. ``pnet_path`` / ``model_path``: local files of
     torchvision's AlexNet state dict and lpips' ``alex.pth`` (either may be omitted: those parameters stay seeded random).
@@ -186,35 +229,9 @@ class LPIPS(nn.Module):
         return [t.detach().float().contiguous() for t in ts]
 
     def forward(self, in0: torch.Tensor, in1: torch.Tensor, retPerLayer: bool = False, normalize: bool = False):
-        if not (in0.is_cuda and in1.is_cuda):
-            raise _lib.HcfError("hcflow_amd.lpips runs on MI355X only (no CPU fallback): move the module and its inputs to a GPU")
-        if in0.requires_grad or in1.requires_grad:
-            raise _lib.HcfError("hcflow_amd.lpips.LPIPS has no backward pass: call it on detached inputs (e.g. under torch.no_grad())")
-        if in0.dim() != 4 or in0.shape[1] != 3 or in0.shape != in1.shape:
-            raise _lib.HcfError("LPIPS expects two [B,3,H,W] tensors of the same shape, got %s and %s"
-                                % (tuple(in0.shape), tuple(in1.shape)))
-        B, _, H, W = in0.shape
-        if H < MIN_SIDE or W < MIN_SIDE:
-            raise _lib.HcfError("LPIPS (AlexNet) needs H, W >= %d, got %dx%d" % (MIN_SIDE, H, W))
-        dev = in0.device
-        if in1.device != dev:
-            raise _lib.HcfError("in0 and in1 are on different devices")
-        params = self._params()
-        if any(t.device != dev for t in params):
-            raise _lib.HcfError("the LPIPS module's parameters are not on %s: call .to(%s) first" % (dev, dev))
-        x0 = in0.to(torch.float32).contiguous()
-        x1 = in1.to(torch.float32).contiguous()
-        lib = _lib.load()
-        need = lib.hcf_lpips_workspace(B, H, W)
-        work = torch.empty(need, dtype=torch.uint8, device=dev)       # stream-ordered reuse by the caching allocator
-        out = torch.empty(B, dtype=torch.float32, device=dev)
-        layers = torch.empty(B, 5, dtype=torch.float32, device=dev) if retPerLayer else None
-        ptrs = (C.c_void_p * len(params))(*[t.data_ptr() for t in params])
-        with torch.cuda.device(dev):
-            rc = lib.hcf_lpips_alex(x0.data_ptr(), x1.data_ptr(), B, H, W, int(bool(normalize)), ptrs, out.data_ptr(),
-                                    None if layers is None else layers.data_ptr(), C.c_void_p(work.data_ptr()), need,
-                                    C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-        _lib.check(rc, None, "hcf_lpips_alex")
+        params = _checked_params(self, in0, in1, loss=False)
+        B = in0.shape[0]
+        out, layers, _ = _alex_forward(params, in0, in1, normalize, retPerLayer)
         val = out.view(B, 1, 1, 1)
         if retPerLayer:
             return val, [layers[:, l].reshape(B, 1, 1, 1) for l in range(5)]
@@ -222,25 +239,14 @@ class LPIPS(nn.Module):
 
 
 class _LPIPSLossFn(torch.autograd.Function):
-    """``metric(in0, in1)`` as ONE node. forward: the launch sequence of ``LPIPS.forward`` (``hcf_lpips_alex``); when an input
+    """``metric(in0, in1)`` as ONE node. forward: the call of ``LPIPS.forward`` (``_alex_forward``); when an input
     wants a gradient the workspace of that call -- the tape -- and the parameter tensors stay alive in ``ctx``. backward: one
     ``hcf_lpips_alex_backward`` call over the halves of the stacked batch that want a gradient."""
 
     @staticmethod
     def forward(ctx, in0, in1, params, normalize):
         B, _, H, W = in0.shape
-        dev = in0.device
-        x0 = in0.detach().to(torch.float32).contiguous()
-        x1 = in1.detach().to(torch.float32).contiguous()
-        lib = _lib.load()
-        need = lib.hcf_lpips_workspace(B, H, W)
-        work = torch.empty(need, dtype=torch.uint8, device=dev)
-        out = torch.empty(B, dtype=torch.float32, device=dev)
-        ptrs = (C.c_void_p * len(params))(*[t.data_ptr() for t in params])
-        with torch.cuda.device(dev):
-            rc = lib.hcf_lpips_alex(x0.data_ptr(), x1.data_ptr(), B, H, W, int(bool(normalize)), ptrs, out.data_ptr(), None,
-                                    C.c_void_p(work.data_ptr()), need, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-        _lib.check(rc, None, "hcf_lpips_alex")
+        out, _, work = _alex_forward(params, in0, in1, normalize, False)
         which = int(ctx.needs_input_grad[0]) | (int(ctx.needs_input_grad[1]) << 1)
         if which:                                                       # (under no_grad / detached inputs: no tape)
             ctx.tape = (work, params)
@@ -253,19 +259,13 @@ class _LPIPSLossFn(torch.autograd.Function):
         work, params = ctx.tape
         which, B, H, W, normalize, dt0, dt1 = ctx.meta
         dev = work.device
-        lib = _lib.load()
         g = gout.reshape(B).to(torch.float32).contiguous()
-        need = lib.hcf_lpips_backward_workspace(B, H, W, which)
+        need = _lib.load().hcf_lpips_backward_workspace(B, H, W, which)
         bwork = torch.empty(need, dtype=torch.uint8, device=dev)
         g0 = torch.empty(B, 3, H, W, dtype=torch.float32, device=dev) if which & 1 else None
         g1 = torch.empty(B, 3, H, W, dtype=torch.float32, device=dev) if which & 2 else None
-        ptrs = (C.c_void_p * len(params))(*[t.data_ptr() for t in params])
-        with torch.cuda.device(dev):
-            rc = lib.hcf_lpips_alex_backward(B, H, W, normalize, ptrs, g.data_ptr(), which,
-                                             None if g0 is None else g0.data_ptr(), None if g1 is None else g1.data_ptr(),
-                                             C.c_void_p(work.data_ptr()), work.numel(), C.c_void_p(bwork.data_ptr()), need,
-                                             C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-        _lib.check(rc, None, "hcf_lpips_alex_backward")
+        _lib.launch("hcf_lpips_alex_backward", dev, B, H, W, normalize, _param_ptrs(params), g, which, g0, g1, work, work.numel(),
+                    bwork, need)
         return (None if g0 is None else g0.to(dt0), None if g1 is None else g1.to(dt1), None, None)
 
 
@@ -295,24 +295,7 @@ class LPIPSLoss(nn.Module):
         self.reduction = reduction
 
     def forward(self, in0: torch.Tensor, in1: torch.Tensor, normalize: bool = False):
-        if any(p.requires_grad for p in self.metric.parameters()):
-            raise ValueError("LPIPSLoss: the parameters of the metric must be frozen (requires_grad=False), no parameter "
-                             "gradient is computed")
-        if not (in0.is_cuda and in1.is_cuda):
-            raise _lib.HcfError("hcflow_amd.lpips runs on MI355X only (no CPU fallback): move the module and its inputs to a GPU")
-        if in0.dim() != 4 or in0.shape[1] != 3 or in0.shape != in1.shape:
-            raise _lib.HcfError("LPIPSLoss expects two [B,3,H,W] tensors of the same shape, got %s and %s"
-                                % (tuple(in0.shape), tuple(in1.shape)))
-        H, W = in0.shape[2:]
-        if H < MIN_SIDE or W < MIN_SIDE:
-            raise _lib.HcfError("LPIPS (AlexNet) needs H, W >= %d, got %dx%d" % (MIN_SIDE, H, W))
-        dev = in0.device
-        if in1.device != dev:
-            raise _lib.HcfError("in0 and in1 are on different devices")
-        params = self.metric._params()
-        if any(t.device != dev for t in params):
-            raise _lib.HcfError("the LPIPS module's parameters are not on %s: call .to(%s) first" % (dev, dev))
-        d = _LPIPSLossFn.apply(in0, in1, params, normalize)
+        d = _LPIPSLossFn.apply(in0, in1, _checked_params(self.metric, in0, in1, loss=True), normalize)
         if self.reduction == "mean":
             return d.mean()
         if self.reduction == "sum":

@@ -1,7 +1,8 @@
 """Thin torch wrappers over the per-op C-ABI entry points (include/hcflow.h, ``hcf_op_*``).
 
 Used by the unit parity tests; every function takes CUDA fp32 NCHW tensors and returns a new CUDA
-tensor computed by the HIP kernels. No fallback paths.
+tensor computed by the HIP kernels. No fallback paths. Every call goes through ``_lib.launch``: on the device of its
+tensors, on the stream current there.
 """
 from __future__ import annotations
 
@@ -19,15 +20,8 @@ def _dev(t: torch.Tensor) -> torch.Tensor:
     return t.detach().to(torch.float32).contiguous()
 
 
-def _host(t: Optional[torch.Tensor]):
-    if t is None:
-        return None, None
-    h = t.detach().to("cpu", torch.float32).contiguous()
-    return h, C.c_void_p(h.data_ptr())
-
-
-def _stream(t):
-    return C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
+def _host(t: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+    return None if t is None else t.detach().to("cpu", torch.float32).contiguous()
 
 
 ACT = {None: 0, "none": 0, "relu": 1, "lrelu": 2}
@@ -41,7 +35,6 @@ def set_precision(mode: str):
 def conv2d(srcs: Sequence[torch.Tensor], weight: torch.Tensor, bias=None, scale=None, act=None,
            ups: Optional[Sequence[int]] = None, res1=None, rs1=0.0, res2=None, rs2=0.0) -> torch.Tensor:
     """act((conv(cat(upsampled srcs), weight) + bias) * scale) [* rs1 + res1] [* rs2 + res2]."""
-    lib = _lib.load()
     srcs = [_dev(s) for s in srcs]
     n = len(srcs)
     ups = list(ups) if ups is not None else [0] * n
@@ -52,16 +45,11 @@ def conv2d(srcs: Sequence[torch.Tensor], weight: torch.Tensor, bias=None, scale=
     ptrs = (C.c_void_p * n)(*[s.data_ptr() for s in srcs])
     cs = (C.c_int32 * n)(*[s.shape[1] for s in srcs])
     us = (C.c_int32 * n)(*ups)
-    wh, wp = _host(weight)
-    bh, bp = _host(bias)
-    sh, sp = _host(scale)
     out = torch.empty(B, cout, H, W, device=srcs[0].device)
     r1 = _dev(res1) if res1 is not None else None
     r2 = _dev(res2) if res2 is not None else None
-    rc = lib.hcf_op_conv2d(ptrs, cs, us, n, B, H, W, wp, bp, sp, cout, k, ACT[act],
-                           None if r1 is None else r1.data_ptr(), float(rs1),
-                           None if r2 is None else r2.data_ptr(), float(rs2), out.data_ptr(), _stream(out))
-    _lib.check(rc, None, "hcf_op_conv2d")
+    _lib.launch("hcf_op_conv2d", out.device, ptrs, cs, us, n, B, H, W, _host(weight), _host(bias), _host(scale), cout, k, ACT[act],
+                r1, float(rs1), r2, float(rs2), out)
     return out
 
 
@@ -69,7 +57,6 @@ def conv2d_backward(srcs: Sequence[torch.Tensor], weight: torch.Tensor, grad_out
                     ups: Optional[Sequence[int]] = None, need_input_grads: bool = True):
     """torch.autograd of ``F.conv2d(cat(upsampled srcs), weight, bias, 1, k // 2)``: returns
     ([d srcs] or None, d weight (CPU), d bias (CPU))."""
-    lib = _lib.load()
     srcs = [_dev(s) for s in srcs]
     g = _dev(grad_out)
     n = len(srcs)
@@ -80,133 +67,97 @@ def conv2d_backward(srcs: Sequence[torch.Tensor], weight: torch.Tensor, grad_out
     ptrs = (C.c_void_p * n)(*[s.data_ptr() for s in srcs])
     cs = (C.c_int32 * n)(*[s.shape[1] for s in srcs])
     us = (C.c_int32 * n)(*ups)
-    wh, wp = _host(weight)
     dsrcs = [torch.empty_like(s) for s in srcs] if need_input_grads else None
     dptrs = (C.c_void_p * n)(*([d.data_ptr() for d in dsrcs] if dsrcs else [None] * n))
     dw = torch.empty(cout, cin, k, k, dtype=torch.float32)
     db = torch.empty(cout, dtype=torch.float32)
-    rc = lib.hcf_op_conv2d_backward(ptrs, cs, us, n, B, H, W, wp, cout, k, g.data_ptr(), dptrs,
-                                    C.c_void_p(dw.data_ptr()), C.c_void_p(db.data_ptr()), _stream(g))
-    _lib.check(rc, None, "hcf_op_conv2d_backward")
+    _lib.launch("hcf_op_conv2d_backward", g.device, ptrs, cs, us, n, B, H, W, _host(weight), cout, k, g, dptrs, dw, db)
     return dsrcs, dw, db
 
 
 def squeeze2d(x: torch.Tensor, haar: bool = False) -> torch.Tensor:
-    lib = _lib.load()
     x = _dev(x)
     B, Cc, H, W = x.shape
     out = torch.empty(B, 4 * Cc, H // 2, W // 2, device=x.device)
-    _lib.check(lib.hcf_op_squeeze2d(x.data_ptr(), out.data_ptr(), B, Cc, H, W, int(haar), _stream(x)), None,
-               "hcf_op_squeeze2d")
+    _lib.launch("hcf_op_squeeze2d", x.device, x, out, B, Cc, H, W, int(haar))
     return out
 
 
 def unsqueeze2d(x: torch.Tensor, haar: bool = False) -> torch.Tensor:
-    lib = _lib.load()
     x = _dev(x)
     B, C4, H, W = x.shape
     out = torch.empty(B, C4 // 4, H * 2, W * 2, device=x.device)
-    _lib.check(lib.hcf_op_unsqueeze2d(x.data_ptr(), out.data_ptr(), B, C4, H, W, int(haar), _stream(x)), None,
-               "hcf_op_unsqueeze2d")
+    _lib.launch("hcf_op_unsqueeze2d", x.device, x, out, B, C4, H, W, int(haar))
     return out
 
 
 def step_inverse(z, h, mode: int, ns: int, mat, an_bias, an_logs) -> torch.Tensor:
-    lib = _lib.load()
     z, h = _dev(z), _dev(h)
     B, Cc, H, W = z.shape
     out = torch.empty_like(z)
-    mh, mp = _host(mat)
-    bh, bp = _host(an_bias.flatten())
-    lh, lp = _host(an_logs.flatten())
-    _lib.check(lib.hcf_op_step_inverse(z.data_ptr(), h.data_ptr(), out.data_ptr(), B, Cc, H, W, h.shape[1], mode, ns,
-                                       mp, bp, lp, _stream(z)), None, "hcf_op_step_inverse")
+    _lib.launch("hcf_op_step_inverse", z.device, z, h, out, B, Cc, H, W, h.shape[1], mode, ns,
+                _host(mat), _host(an_bias.flatten()), _host(an_logs.flatten()))
     return out
 
 
 def step_forward_head(z, mat, an_bias, an_logs) -> torch.Tensor:
-    lib = _lib.load()
     z = _dev(z)
     B, Cc, H, W = z.shape
     out = torch.empty_like(z)
-    mh, mp = _host(mat)
-    bh, bp = _host(an_bias.flatten())
-    lh, lp = _host(an_logs.flatten())
-    _lib.check(lib.hcf_op_step_forward_head(z.data_ptr(), out.data_ptr(), B, Cc, H, W, mp, bp, lp, _stream(z)), None,
-               "hcf_op_step_forward_head")
+    _lib.launch("hcf_op_step_forward_head", z.device, z, out, B, Cc, H, W,
+                _host(mat), _host(an_bias.flatten()), _host(an_logs.flatten()))
     return out
 
 
 def step_forward_couple(z, h, mode: int, ns: int):
-    lib = _lib.load()
     z, h = _dev(z), _dev(h)
     B, Cc, H, W = z.shape
     out = torch.empty_like(z)
     ld = torch.empty(B, device=z.device)
-    _lib.check(lib.hcf_op_step_forward_couple(z.data_ptr(), h.data_ptr(), out.data_ptr(), ld.data_ptr(), B, Cc, H, W,
-                                              h.shape[1], mode, ns, _stream(z)), None, "hcf_op_step_forward_couple")
+    _lib.launch("hcf_op_step_forward_couple", z.device, z, h, out, ld, B, Cc, H, W, h.shape[1], mode, ns)
     return out, ld
 
 
 def gauss_logp(h, x) -> torch.Tensor:
-    lib = _lib.load()
     h, x = _dev(h), _dev(x)
     B, Cc, H, W = x.shape
     out = torch.empty(B, device=x.device)
-    _lib.check(lib.hcf_op_gauss_logp(h.data_ptr(), x.data_ptr(), out.data_ptr(), B, Cc, H, W, _stream(x)), None,
-               "hcf_op_gauss_logp")
+    _lib.launch("hcf_op_gauss_logp", x.device, h, x, out, B, Cc, H, W)
     return out
 
 
 def gauss_sample(h, eps=None, tau: float = 1.0, seed: int = 0, rescale: bool = False) -> torch.Tensor:
-    lib = _lib.load()
     h = _dev(h)
     B, C2, H, W = h.shape
     out = torch.empty(B, C2 // 2, H, W, device=h.device)
     e = _dev(eps) if eps is not None else None
-    _lib.check(lib.hcf_op_gauss_sample(h.data_ptr(), None if e is None else e.data_ptr(), float(tau), int(seed),
-                                       out.data_ptr(), B, C2 // 2, H, W, int(rescale), _stream(h)), None,
-               "hcf_op_gauss_sample")
+    _lib.launch("hcf_op_gauss_sample", h.device, h, e, float(tau), int(seed), out, B, C2 // 2, H, W, int(rescale))
     return out
 
 
 # ---- backward kernels of the training path (hcf_train.hip), one entry per launcher ---------------------------------
-def _ptr(t):
-    return None if t is None else t.data_ptr()
-
-
 def step_forward_backward(gzout, zout, h, za, mode: int, ns: int, mat, an_logs, gobj: float, g_bias=None, g_logs=None):
     """Coupling backward, then head backward, of one forward flow step: (gzin, gh, g_bias, g_logs); the two per-channel
     sums are added to ``g_bias`` / ``g_logs`` when given (zeros otherwise)."""
-    lib = _lib.load()
     gzout, zout, h, za = _dev(gzout), _dev(zout), _dev(h), _dev(za)
     B, Cc, H, W = zout.shape
     gzin, gh = torch.empty_like(zout), torch.empty_like(h)
     gb = torch.zeros(Cc, device=zout.device) if g_bias is None else _dev(g_bias).flatten().clone()
     gl = torch.zeros(Cc, device=zout.device) if g_logs is None else _dev(g_logs).flatten().clone()
-    mh, mp = _host(mat)
-    lh, lp = _host(an_logs.flatten())
-    _lib.check(lib.hcf_op_step_forward_backward(gzout.data_ptr(), zout.data_ptr(), h.data_ptr(), za.data_ptr(), gzin.data_ptr(),
-                                                gh.data_ptr(), gb.data_ptr(), gl.data_ptr(), B, Cc, H, W, h.shape[1], mode, ns,
-                                                mp, lp, float(gobj), _stream(zout)), None, "hcf_op_step_forward_backward")
+    _lib.launch("hcf_op_step_forward_backward", zout.device, gzout, zout, h, za, gzin, gh, gb, gl, B, Cc, H, W, h.shape[1], mode, ns,
+                _host(mat), _host(an_logs.flatten()), float(gobj))
     return gzin, gh, gb, gl
 
 
 def step_inverse_backward(gx, x, zc, h, mode: int, ns: int, mat, an_bias, an_logs, g_bias=None, g_logs=None):
     """Backward of one inverse flow step: (gz, gh, gzc, y, g_bias, g_logs)."""
-    lib = _lib.load()
     gx, x, zc, h = _dev(gx), _dev(x), _dev(zc), _dev(h)
     B, Cc, H, W = x.shape
     gz, gh, gzc, y = torch.empty_like(x), torch.empty_like(h), torch.empty_like(x), torch.empty_like(x)
     gb = torch.zeros(Cc, device=x.device) if g_bias is None else _dev(g_bias).flatten().clone()
     gl = torch.zeros(Cc, device=x.device) if g_logs is None else _dev(g_logs).flatten().clone()
-    mh, mp = _host(mat)
-    bh, bp = _host(an_bias.flatten())
-    lh, lp = _host(an_logs.flatten())
-    _lib.check(lib.hcf_op_step_inverse_backward(gx.data_ptr(), x.data_ptr(), zc.data_ptr(), h.data_ptr(), gz.data_ptr(),
-                                                gh.data_ptr(), gzc.data_ptr(), y.data_ptr(), gb.data_ptr(), gl.data_ptr(), B, Cc,
-                                                H, W, h.shape[1], mode, ns, mp, bp, lp, _stream(x)), None,
-               "hcf_op_step_inverse_backward")
+    _lib.launch("hcf_op_step_inverse_backward", x.device, gx, x, zc, h, gz, gh, gzc, y, gb, gl, B, Cc, H, W, h.shape[1], mode, ns,
+                _host(mat), _host(an_bias.flatten()), _host(an_logs.flatten()))
     return gz, gh, gzc, y, gb, gl
 
 
@@ -215,78 +166,65 @@ PRIOR_KIND = {"logp": 0, "sample": 1, "encode": 2}
 
 def prior_backward(kind: str, a, h, ga=None, gz=None, rescale: bool = False, gobj: float = 1.0):
     """Gaussian prior backward: (ga, gh). ``ga`` is the input of kind "sample", ``gz`` (or None) that of "encode"."""
-    lib = _lib.load()
     a, h = _dev(a), _dev(h)
     B, Cc, H, W = a.shape
     ga = _dev(ga).clone() if kind == "sample" else torch.empty_like(a)
     gh = torch.empty_like(h)
     gzd = _dev(gz) if gz is not None else None
-    _lib.check(lib.hcf_op_prior_backward(PRIOR_KIND[kind], a.data_ptr(), h.data_ptr(), ga.data_ptr(), gh.data_ptr(), _ptr(gzd),
-                                         B, Cc, H, W, int(rescale), float(gobj), _stream(a)), None, "hcf_op_prior_backward")
+    _lib.launch("hcf_op_prior_backward", a.device, PRIOR_KIND[kind], a, h, ga, gh, gzd, B, Cc, H, W, int(rescale), float(gobj))
     return ga, gh
 
 
 def prior_sample_backward(a, h, ga, rescale: bool = False, want_geps: bool = True):
     """Backward of the prior sample a = mean + e^logs eps given ``ga`` = dL/da: (gh, geps) with geps = dL/d eps (None when
     ``want_geps`` is off: the entry then runs the kernel of ``prior_backward("sample", ...)``)."""
-    lib = _lib.load()
     a, h, ga = _dev(a), _dev(h), _dev(ga)
     B, Cc, H, W = a.shape
     gh = torch.empty_like(h)
     geps = torch.empty_like(a) if want_geps else None
-    _lib.check(lib.hcf_op_prior_sample_backward(a.data_ptr(), h.data_ptr(), ga.data_ptr(), gh.data_ptr(), _ptr(geps), B, Cc, H, W,
-                                                int(rescale), _stream(a)), None, "hcf_op_prior_sample_backward")
+    _lib.launch("hcf_op_prior_sample_backward", a.device, a, h, ga, gh, geps, B, Cc, H, W, int(rescale))
     return gh, geps
 
 
 def quant_logp_backward(z, lr, gobj: float, gz=None) -> torch.Tensor:
     """gz (zeros when None) + gobj * d logp(lr; Quant(z), logs = -6) / dz with the straight-through Quant."""
-    lib = _lib.load()
     z, lr = _dev(z), _dev(lr)
     B, _, H, W = z.shape
     out = torch.zeros_like(z) if gz is None else _dev(gz).clone()
-    _lib.check(lib.hcf_op_quant_logp_backward(z.data_ptr(), lr.data_ptr(), out.data_ptr(), B, H, W, float(gobj), _stream(z)),
-               None, "hcf_op_quant_logp_backward")
+    _lib.launch("hcf_op_quant_logp_backward", z.device, z, lr, out, B, H, W, float(gobj))
     return out
 
 
 def quant_logp_backward_lr(z, lr, gobj: float, gz=None):
     """``quant_logp_backward`` that also returns d / d lr = gobj * (Quant(z) - lr) * e^12: (gz, glr)."""
-    lib = _lib.load()
     z, lr = _dev(z), _dev(lr)
     B, _, H, W = z.shape
     out = torch.zeros_like(z) if gz is None else _dev(gz).clone()
     glr = torch.empty_like(lr)
-    _lib.check(lib.hcf_op_quant_logp_backward_lr(z.data_ptr(), lr.data_ptr(), out.data_ptr(), glr.data_ptr(), B, H, W, float(gobj),
-                                                 _stream(z)), None, "hcf_op_quant_logp_backward_lr")
+    _lib.launch("hcf_op_quant_logp_backward_lr", z.device, z, lr, out, glr, B, H, W, float(gobj))
     return out, glr
 
 
 def prior_encode_logp_backward(a, h, geps=None, glogp=None, rescale: bool = False, gobj: float = 0.0):
     """Prior backward of the SR encode (eps = (a - mean) e^-logs is an output and logp joins the log-density): (ga, gh) from the
     seeds ``geps`` = dL/d eps (None: zero) and ``glogp`` = dL/d logp per sample, a [B] tensor (None: the scalar ``gobj``)."""
-    lib = _lib.load()
     a, h = _dev(a), _dev(h)
     B, Cc, H, W = a.shape
     ga, gh = torch.empty_like(a), torch.empty_like(h)
     ge = _dev(geps) if geps is not None else None
     gl = _dev(glogp) if glogp is not None else None
     assert gl is None or gl.numel() == B
-    _lib.check(lib.hcf_op_prior_encode_logp_backward(a.data_ptr(), h.data_ptr(), ga.data_ptr(), gh.data_ptr(), _ptr(ge), _ptr(gl),
-                                                     B, Cc, H, W, int(rescale), float(gobj), _stream(a)), None,
-               "hcf_op_prior_encode_logp_backward")
+    _lib.launch("hcf_op_prior_encode_logp_backward", a.device, a, h, ga, gh, ge, gl, B, Cc, H, W, int(rescale), float(gobj))
     return ga, gh
 
 
 def input_grad(gz, haar: bool = False) -> torch.Tensor:
     """dL/d hr [B,C,2H,2W] from gz = dL/d z [B,4C,H,W] of z = squeeze2d(hr) (or Haar(hr)): unsqueeze2d(gz), or Haar inv(gz) / 4."""
-    lib = _lib.load()
     gz = _dev(gz)
     B, C4, H, W = gz.shape
     assert C4 % 4 == 0
     out = torch.empty(B, C4 // 4, 2 * H, 2 * W, device=gz.device, dtype=torch.float32)
-    _lib.check(lib.hcf_op_input_grad(gz.data_ptr(), out.data_ptr(), B, C4 // 4, H, W, int(haar), _stream(gz)), None,
-               "hcf_op_input_grad")
+    _lib.launch("hcf_op_input_grad", gz.device, gz, out, B, C4 // 4, H, W, int(haar))
     return out
 
 
@@ -295,13 +233,11 @@ GRAD_KIND = {"add": 0, "add_clamp01": 1, "mask_unit_range": 2, "mask_flat": 3}
 
 def output_grad_backward(kind: str, g, z, gz=None) -> torch.Tensor:
     """The gradient kernels of an NCHW (clamped) output on a copy of ``gz`` (include/hcflow.h: hcf_op_output_grad_backward)."""
-    lib = _lib.load()
     z = _dev(z)
     B, Cc, H, W = z.shape
     gd = _dev(g) if g is not None else None
     out = torch.zeros_like(z) if gz is None else _dev(gz).clone()
-    _lib.check(lib.hcf_op_output_grad_backward(GRAD_KIND[kind], _ptr(gd), z.data_ptr(), out.data_ptr(), B, Cc, H, W, _stream(z)),
-               None, "hcf_op_output_grad_backward")
+    _lib.launch("hcf_op_output_grad_backward", z.device, GRAD_KIND[kind], gd, z, out, B, Cc, H, W)
     return out
 
 
@@ -311,12 +247,10 @@ def conv_epilogue_backward(gy, y=None, scale=None, act=None, rs1=None, g1=None, 
     of g1 / g2 when given). want_max: 1 absmax, 2 absmax and absmax2 (``carry2``: a float folded into absmax2). The tensors sit
     at channels [c0, c0 + n) of an NHWC buffer of ``cs`` floats per pixel (default: n rounded up to 4).
     Returns a dict: gpre, g1, g2, sum_pre, sum_zy, absmax, absmax2 (None where not asked for)."""
-    lib = _lib.load()
     gy = _dev(gy)
     B, n, H, W = gy.shape
     dev = gy.device
     yd = _dev(y) if y is not None else None
-    sh, sp = _host(scale)
     g1d = _dev(g1).clone() if g1 is not None else None
     g2d = _dev(g2).clone() if g2 is not None else None
     gpre = torch.empty_like(gy)
@@ -326,19 +260,15 @@ def conv_epilogue_backward(gy, y=None, scale=None, act=None, rs1=None, g1=None, 
     m2 = torch.zeros(1, device=dev) if want_max >= 2 else None
     cr = torch.tensor([float(carry2)], device=dev, dtype=torch.float32) if carry2 is not None else None
     cs = ((n + 3) // 4) * 4 if cs is None else cs
-    rc = lib.hcf_op_conv_epilogue_backward(gy.data_ptr(), _ptr(yd), sp, ACT[act], int(rs1 is not None), float(rs1 or 0.0), _ptr(g1d),
-                                           int(rs2 is not None), float(rs2 or 0.0), _ptr(g2d), gpre.data_ptr(), _ptr(sp_), _ptr(sz_),
-                                           float(zy_mult), _ptr(m1), _ptr(m2), _ptr(cr), B, n, H, W, int(cs), int(c0), _stream(gy))
-    _lib.check(rc, None, "hcf_op_conv_epilogue_backward")
+    _lib.launch("hcf_op_conv_epilogue_backward", dev, gy, yd, _host(scale), ACT[act], int(rs1 is not None), float(rs1 or 0.0), g1d,
+                int(rs2 is not None), float(rs2 or 0.0), g2d, gpre, sp_, sz_, float(zy_mult), m1, m2, cr, B, n, H, W, int(cs), int(c0))
     return {"gpre": gpre, "g1": g1d, "g2": g2d, "sum_pre": sp_, "sum_zy": sz_, "absmax": m1, "absmax2": m2}
 
 
 def lu_chain(dW, P, L, U, dl, du, dlog_s):
     """(dl, du, dlog_s) + the chain rule of dL/dW into the factors of W = P L U' (copies of the given accumulators)."""
-    lib = _lib.load()
     dW, P, L, U = _dev(dW), _dev(P), _dev(L), _dev(U)
     Cc = dW.shape[0]
     dl, du, ds = _dev(dl).clone(), _dev(du).clone(), _dev(dlog_s).clone()
-    _lib.check(lib.hcf_op_lu_chain(dW.data_ptr(), P.data_ptr(), L.data_ptr(), U.data_ptr(), dl.data_ptr(), du.data_ptr(),
-                                   ds.data_ptr(), Cc, _stream(dW)), None, "hcf_op_lu_chain")
+    _lib.launch("hcf_op_lu_chain", dW.device, dW, P, L, U, dl, du, ds, Cc)
     return dl, du, ds

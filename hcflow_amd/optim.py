@@ -20,7 +20,6 @@ aligned slots) when the optimiser is built, so ``nn.Parameter`` identities, shap
 optimiser after ``.to(device)``, as the reference does): there is no CPU path.
 """
 import collections
-import ctypes as C
 
 import numpy as np
 import torch
@@ -103,7 +102,7 @@ class Adam(torch.optim.Optimizer):
         """The flat buffers (built with the optimiser; rebuilt from the parameters' current values in a copy that lost them:
         ``torch.optim.Optimizer.__getstate__`` keeps defaults, state and param_groups only)."""
         if "_flat" not in self.__dict__:
-            self._lib = _lib.load()
+            _lib.load()                                           # no library, no optimiser: fail when it is built
             self._flat = [_Flat(g["params"]) for g in self.param_groups]
             for g, fl in zip(self.param_groups, self._flat):      # moments that came along (unpickled state): into the flat buffers
                 for i, p in enumerate(g["params"]):
@@ -252,14 +251,9 @@ class Adam(torch.optim.Optimizer):
                         fl.recent.popitem(last=False)
                 fl.tables, fl.key = hit[1], key
             beta1, beta2 = group["betas"]
-            stream = torch.cuda.current_stream(fl.device).cuda_stream
-            with torch.cuda.device(fl.device):
-                for (first, dev, n, _keep) in fl.tables:          # one table per step count (`first`: a member tensor of it)
-                    rc = self._lib.hcf_adam_step(fl.P.data_ptr(), fl.M.data_ptr(), fl.V.data_ptr(), dev.data_ptr(), n,
-                                                 float(group["lr"]), float(beta1), float(beta2), float(group["eps"]),
-                                                 float(group["weight_decay"]), int(fl.t[first]) + 1, C.c_void_p(stream))
-                    if rc != 0:
-                        raise _lib.HcfError("hcf_adam_step failed (%d)" % rc)
+            for (first, dev, n, _keep) in fl.tables:              # one table per step count (`first`: a member tensor of it)
+                _lib.launch("hcf_adam_step", fl.device, fl.P, fl.M, fl.V, dev, n, float(group["lr"]), float(beta1), float(beta2),
+                            float(group["eps"]), float(group["weight_decay"]), int(fl.t[first]) + 1)
             fl.t[active] += 1
             # the kernel wrote through raw pointers: tell autograd (and the nets' engines, which watch _version) the tensors changed
             torch.autograd.graph.increment_version([params[i] for i in active])

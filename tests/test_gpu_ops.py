@@ -149,6 +149,22 @@ def test_squeeze_unsqueeze_bit_exact(dev):
     assert torch.equal(ops.squeeze2d(x.to(dev)).cpu(), O.squeeze2d(x))
 
 
+def test_ops_launch_on_the_callers_current_stream(dev):
+    """squeeze2d and conv2d under torch.cuda.stream(side): only `side` is synchronised before the results are read, and they
+    equal the default-stream results bit for bit."""
+    from hcflow_amd import ops
+    g = _gen(3)
+    x = torch.randn(1, 4, 4, 4, generator=g).to(dev)
+    w = torch.randn(4, 4, 3, 3, generator=g) / 6.0
+    ref_sq, ref_conv = ops.squeeze2d(x), ops.conv2d([x], w)
+    torch.cuda.synchronize()
+    side = torch.cuda.Stream(device=dev)
+    with torch.cuda.stream(side):
+        sq, conv = ops.squeeze2d(x), ops.conv2d([x], w)
+    side.synchronize()
+    assert torch.equal(sq, ref_sq) and torch.equal(conv, ref_conv)
+
+
 def test_haar(dev):
     from hcflow_amd import ops
     g = load_golden("ops_index")
