@@ -48,6 +48,7 @@ SYMBOLS = [
     "hcf_train_backward_ex", "hcf_train_backward_rescale_ex", "hcf_train_encode_sr", "hcf_train_backward_encode",
     "hcf_op_quant_logp_backward_lr", "hcf_op_prior_encode_logp_backward", "hcf_op_input_grad",
     "hcf_data_prepare_batch",
+    "hcf_op_fcn12", "hcf_op_conv2d_step_inverse",
 ]
 
 
@@ -171,6 +172,10 @@ def load() -> C.CDLL:
                                   i32, i32, i32, fp, f32, fp, f32, fp, vp]
     lib.hcf_op_conv2d_backward.argtypes = [C.POINTER(fp), C.POINTER(i32), C.POINTER(i32), i32, i32, i32, i32, fp, i32, i32,
                                            fp, C.POINTER(fp), fp, fp, vp]
+    lib.hcf_op_fcn12.argtypes = [C.POINTER(fp), C.POINTER(i32), C.POINTER(i32), i32, i32, i32, i32, fp, fp, fp, fp, fp, fp, fp, fp, i32,
+                                 C.POINTER(i32), vp]
+    lib.hcf_op_conv2d_step_inverse.argtypes = [fp, i32, fp, fp, fp, i32, fp, i32, i32, i32, fp, fp, fp, fp, fp, i32, i32, i32, i32,
+                                               C.POINTER(i32), vp]
     lib.hcf_op_squeeze2d.argtypes = [fp, fp, i32, i32, i32, i32, i32, vp]
     lib.hcf_op_unsqueeze2d.argtypes = [fp, fp, i32, i32, i32, i32, i32, vp]
     lib.hcf_op_step_inverse.argtypes = [fp, fp, fp, i32, i32, i32, i32, i32, i32, i32, fp, fp, fp, vp]

@@ -340,7 +340,8 @@ __global__ __launch_bounds__(256, 2) void fcn12_kernel(const ConvArgs a, const i
 }  // namespace fcn12
 
 // HCF_ERR_UNSUPPORTED: this call does not fit the small-K persistent form (the generic FUSE2 kernel takes it)
-int launch_fcn12(const ConvArgs& a, hipStream_t st) {
+// grid_out / ntiles_out (optional): the launch made, for the per-op entry that reports it (hcf_op_fcn12)
+int launch_fcn12(const ConvArgs& a, hipStream_t st, unsigned* grid_out, int* ntiles_out) {
   static const bool off = getenv("HCF_NO_FCN12") != nullptr;         // A/B knob, read once
   if (off) return HCF_ERR_UNSUPPORTED;
   auto v16 = [](const View& v) { return v.p && view_vec16(v); };      // (differs from view_vec16_or_null: both views are required)
@@ -370,6 +371,8 @@ int launch_fcn12(const ConvArgs& a, hipStream_t st) {
       attr_dev[dev][pre] = true;
     }
     hipLaunchKernelGGL(fn, dim3(grid), dim3(256), fcn12::LDS_BYTES, st, a, (int)ntiles);
+    if (grid_out) *grid_out = grid;
+    if (ntiles_out) *ntiles_out = (int)ntiles;
     return hipGetLastError() == hipSuccess ? HCF_OK : HCF_ERR_HIP;
   };
   return pre ? go(fcn12::fcn12_kernel<true>) : go(fcn12::fcn12_kernel<false>);

@@ -22,10 +22,13 @@
   int B_ = 0;   // batch of the running pass
 
   // f16x3 mode can run FCN conv1 (3x3 -> 64) and conv2 (1x1 64 -> 64) as ONE launch
-  bool can_fuse_fcn(const Conv& c1, const Conv& c2) const {
+  // z1 (optional): the window conv1 reads first. Both fused forms need it 16-byte addressable (launch_fcn12 declines it otherwise and
+  // plan_conv_f16x3 refuses the FUSE2 row with !vec): an Affine3shift step's shift half reads z[3:], which then takes two launches
+  bool can_fuse_fcn(const Conv& c1, const Conv& c2, const View* z1 = nullptr) const {
     static const bool off = getenv("HCF_NO_FUSE_FCN") != nullptr;      // debugging aid, read once
     if (off) return false;
     if (taping) return false;                         // the backward pass needs the intermediate tensor
+    if (z1 && ((z1->cs | z1->c0) & 3) != 0) return false;
     return use_f16 && c1.wpack16 && c2.wpack16 && c1.taps == 9 && c2.taps == 1 && c1.cout == 64 && c2.cout == 64 &&
            c2.nsrc == 1 && c2.src_n[0] == 64;
   }
@@ -284,7 +287,7 @@
         const FatExtra fx = {View(), ACT_NONE, false, s.w4f_frag};
         ConvOpt o; o.fuse2 = &s.c[1]; o.fat = &fx;
         run_conv(s.c1w, {sc.zpad.v(0, 16), *u}, H, W, sc.h2.v(0, s.hid), o);
-      } else if (can_fuse_fcn(s.c[0], s.c[1])) {
+      } else if (can_fuse_fcn(s.c[0], s.c[1], &z1)) {
         ConvOpt o; o.fuse2 = &s.c[1];
         run_conv(s.c[0], in, H, W, sc.h2.v(0, s.hid), o);
       } else {

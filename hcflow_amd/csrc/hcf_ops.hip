@@ -827,6 +827,177 @@ int hcf_op_lu_chain(const float* dW, const float* P, const float* L, const float
 
 }  // extern "C"
 
+// ---- the fused f16x3 conv launches of the inference path, one launch per call (tests/test_gpu_fused_convs.py) ----------
+namespace hcf {
+
+// the range flag + the zero page every f16x3 launch needs (as pack_and_launch)
+static int fused_flag(Tmp& t, ConvArgs& a, hipStream_t st) {
+  a.ovf = (int*)t.dev(64);
+  if (!a.ovf) return HCF_ERR_NOMEM;
+  if (hipMemsetAsync(a.ovf, 0, 256, st) != hipSuccess) return HCF_ERR_HIP;
+  a.zeros = reinterpret_cast<const float*>(a.ovf) + 16;
+  return HCF_OK;
+}
+
+// an f16x3 host pack in device memory; HCF_ERR_UNSUPPORTED: a weight beyond the pack's range
+static int fused_pack(Tmp& t, const float* w, int cin, int cout, int taps, const int* srcs, int n_src, const float*& dev, int& nchunk) {
+  std::vector<float> pk;
+  int npad = 0;
+  if (!pack_conv_weights_f16x3(w, cin, cout, taps, srcs, n_src, pk, nchunk, npad)) return HCF_ERR_UNSUPPORTED;
+  dev = t.up(pk);
+  return t.ok ? HCF_OK : HCF_ERR_NOMEM;
+}
+
+static float* fused_table(Tmp& t, const float* v, int n, int npad, float fill) {
+  std::vector<float> h(npad, fill);
+  for (int c = 0; c < n && v; ++c) h[c] = v[c];
+  return t.up(h);
+}
+
+// launch_conv_f16x3 with the plan it dispatches from written to info[1 .. 12] (include/hcflow.h: hcf_op_fcn12)
+static int fused_launch_f16x3(const ConvArgs& a, int32_t* info, hipStream_t st) {
+  const F16x3Plan p = plan_conv_f16x3(a, 9);
+  const int32_t v[12] = {p.status, p.v.ntb, p.v.vec, p.v.up, p.v.fuse2, p.v.tailc, p.v.th, p.v.scaled, p.v.k1, p.v.n16, (int32_t)p.grid, (int32_t)p.block};
+  info[0] = 1;
+  for (int i = 0; i < 12; ++i) info[1 + i] = v[i];
+  if (p.status != HCF_OK) return p.status;
+  return launch_conv_f16x3(a, 9, st);
+}
+
+// stream done, then the range flag: HCF_ERR_UNSUPPORTED when an input left the f16 range (info[15] = the flag word)
+static int fused_finish(const ConvArgs& a, int32_t* info, hipStream_t st) {
+  if (hipStreamSynchronize(st) != hipSuccess) return HCF_ERR_HIP;
+  int h = 0;
+  if (hipMemcpy(&h, a.ovf, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return HCF_ERR_HIP;
+  info[15] = h;
+  return h ? HCF_ERR_UNSUPPORTED : HCF_OK;
+}
+
+}  // namespace hcf
+
+extern "C" {
+
+int hcf_op_fcn12(const float* const* src, const int32_t* src_c, const int32_t* src_up, int32_t n_src, int32_t B, int32_t H,
+                 int32_t W, const float* w1, const float* bias1, const float* scale1, const float* w2, const float* bias2,
+                 const float* scale2, const float* pre, float* out, int32_t form, int32_t* info, hcf_stream_t stream) {
+  if (!src || !src_c || !w1 || !w2 || !out || !info || n_src < 1 || n_src > kMaxSrc || B < 1 || H < 1 || W < 1 || (form != 0 && form != 1))
+    return HCF_ERR_ARG;
+  for (int i = 0; i < n_src; ++i) {
+    const int up = src_up ? src_up[i] : 0;
+    if (!src[i] || src_c[i] < 1 || up < 0 || up > 8 || !up_divides(H, W, up)) return HCF_ERR_ARG;
+  }
+  for (int i = 0; i < 16; ++i) info[i] = 0;
+  hipStream_t st = (hipStream_t)stream;
+  Tmp t;
+  int rc = HCF_OK;
+  ConvArgs a;
+  memset(&a, 0, sizeof(a));
+  int cin = 0, srcs[kMaxSrc];
+  for (int i = 0; i < n_src; ++i) {
+    const int up = src_up ? src_up[i] : 0;
+    a.src[i] = nhwc_from_nchw(t, src[i], B, src_c[i], H >> up, W >> up, st, rc);
+    a.src[i].up = up;
+    srcs[i] = src_c[i];
+    cin += src_c[i];
+  }
+  for (int i = n_src; i < kMaxSrc; ++i) a.src[i] = a.src[0];
+  a.nsrc = n_src;
+  a.B = B; a.H = H; a.W = W;
+  a.bias = fused_table(t, bias1, 64, 64, 0.f);
+  a.scale = fused_table(t, scale1, 64, 64, 1.f);
+  a.bias2 = fused_table(t, bias2, 64, 64, 0.f);
+  a.scale2 = fused_table(t, scale2, 64, 64, 1.f);
+  a.act = ACT_RELU; a.act2 = ACT_RELU;
+  const size_t nout = (size_t)B * H * W * 64;
+  float* o = t.dev(nout);
+  a.out = mkview(o, 64, 0, 64);
+  a.res1 = mkview(nullptr, 0, 0, 0);
+  a.res2 = mkview(nullptr, 0, 0, 0);
+  if (pre) a.res1 = nhwc_from_nchw(t, pre, B, 64, H, W, st, rc);        // the pre-activation term travels as res1, as in the engine
+  if (!t.ok) return HCF_ERR_NOMEM;
+  if (rc != HCF_OK) return rc;
+  if (hipMemsetAsync(o, 0xff, nout * sizeof(float), st) != hipSuccess) return HCF_ERR_HIP;      // a pixel the launch skips reads NaN
+  if ((rc = fused_flag(t, a, st)) != HCF_OK) return rc;
+  int one = 64, nchunk2 = 0;
+  if ((rc = fused_pack(t, w1, cin, 64, 9, srcs, n_src, a.wpack, a.nchunk)) != HCF_OK) return rc;
+  if ((rc = fused_pack(t, w2, 64, 64, 1, &one, 1, a.w2, nchunk2)) != HCF_OK) return rc;
+  rc = HCF_ERR_UNSUPPORTED;
+  if (form == 0) {
+    unsigned grid = 0;
+    int ntiles = 0;
+    rc = launch_fcn12(a, st, &grid, &ntiles);
+    if (rc != HCF_ERR_UNSUPPORTED) {
+      info[0] = 0; info[1] = rc; info[11] = (int32_t)grid; info[12] = 256; info[13] = ntiles; info[14] = pre ? 1 : 0;
+    }
+  }
+  if (rc == HCF_ERR_UNSUPPORTED) rc = fused_launch_f16x3(a, info, st);
+  if (rc != HCF_OK) { hipStreamSynchronize(st); return rc; }      // (the temporaries are freed behind the staging launches)
+  if ((rc = fused_finish(a, info, st)) != HCF_OK) return rc;
+  rc = launch_nhwc_to_nchw(a.out, out, B, 64, H, W, 0, st);
+  if (hipStreamSynchronize(st) != hipSuccess) return HCF_ERR_HIP;
+  return rc;
+}
+
+int hcf_op_conv2d_step_inverse(const float* h2, int32_t hid, const float* w3, const float* bias3, const float* scale3,
+                               int32_t f_out, const float* z, int32_t C, int32_t mode, int32_t ns, const float* mat,
+                               const float* an_bias, const float* an_logs, float* out_z, float* out_zpad, int32_t zpad_n,
+                               int32_t B, int32_t H, int32_t W, int32_t* info, hcf_stream_t stream) {
+  if (!h2 || !w3 || !z || !an_bias || !an_logs || !out_z || !info || hid < 1 || f_out < 1 || f_out > 96) return HCF_ERR_ARG;
+  if (!step_shape_ok(B, C, H, W, f_out, mode, ns) || (out_zpad && (zpad_n < 0 || zpad_n > 16 || zpad_n > C))) return HCF_ERR_ARG;
+  for (int i = 0; i < 16; ++i) info[i] = 0;
+  const int M = step_cmax(C);
+  if (M < 0) return HCF_ERR_UNSUPPORTED;
+  hipStream_t st = (hipStream_t)stream;
+  Tmp t;
+  int rc = HCF_OK;
+  ConvArgs a;
+  memset(&a, 0, sizeof(a));
+  a.src[0] = nhwc_from_nchw(t, h2, B, hid, H, W, st, rc);
+  a.src[1] = a.src[0]; a.src[2] = a.src[0];
+  a.nsrc = 1;
+  a.B = B; a.H = H; a.W = W;
+  const int npad = ((f_out + 31) / 32) * 32;
+  a.bias = fused_table(t, bias3, f_out, npad, 0.f);
+  a.scale = fused_table(t, scale3, f_out, npad, 1.f);
+  a.act = ACT_NONE;
+  a.out = mkview(t.dev((size_t)B * H * W * ru4(f_out)), ru4(f_out), 0, f_out);      // (sc.hout of the engine: the fused launch leaves it alone)
+  a.res1 = mkview(nullptr, 0, 0, 0);
+  a.res2 = mkview(nullptr, 0, 0, 0);
+  // the tail fields, as run_conv fills them from the step's StepArgs (in place on z)
+  a.tz = nhwc_from_nchw(t, z, B, C, H, W, st, rc);
+  a.tzo = a.tz;
+  std::vector<float> hb(M, 0.f), hm(M, 0.f);
+  for (int c = 0; c < C; ++c) { hb[c] = an_bias[c]; hm[c] = expf(-an_logs[c]); }
+  a.tbias = t.up(hb);
+  a.tmul = t.up(hm);
+  if (mat) {
+    std::vector<float> wi;
+    if (!invert64(mat, C, wi, M)) return HCF_ERR_ARG;
+    a.tmat = t.up(wi);
+  }
+  a.tC = C; a.tns = ns; a.tmode = mode;
+  const size_t npadz = (size_t)B * H * W * 16;
+  if (out_zpad) {
+    a.tzpad = t.dev(npadz);
+    a.tzpad_n = zpad_n;
+  }
+  if (!t.ok) return HCF_ERR_NOMEM;
+  if (rc != HCF_OK) return rc;
+  if (a.tzpad && hipMemsetAsync(a.tzpad, 0xff, npadz * sizeof(float), st) != hipSuccess) return HCF_ERR_HIP;
+  if ((rc = fused_flag(t, a, st)) != HCF_OK) return rc;
+  int one = hid;
+  if ((rc = fused_pack(t, w3, hid, f_out, 9, &one, 1, a.wpack, a.nchunk)) != HCF_OK) return rc;
+  rc = fused_launch_f16x3(a, info, st);
+  if (rc != HCF_OK) { hipStreamSynchronize(st); return rc; }
+  if ((rc = fused_finish(a, info, st)) != HCF_OK) return rc;
+  rc = launch_nhwc_to_nchw(a.tzo, out_z, B, C, H, W, 0, st);
+  if (rc == HCF_OK && out_zpad) rc = launch_nhwc_to_nchw(mkview(a.tzpad, 16, 0, 16), out_zpad, B, 16, H, W, 0, st);
+  if (hipStreamSynchronize(st) != hipSuccess) return HCF_ERR_HIP;
+  return rc;
+}
+
+}  // extern "C"
+
 // ---- micro-benchmark of the conv kernel (tools/conv_bench.py) ---------------------------------
 // Allocates NHWC slabs once, launches the conv `iters` times back to back and times them with HIP
 // events on the given stream. Inputs are uniform random in [-1, 1) (never zeros: DVFS, cdna guide

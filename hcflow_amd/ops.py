@@ -100,6 +100,62 @@ def step_inverse(z, h, mode: int, ns: int, mat, an_bias, an_logs) -> torch.Tenso
     return out
 
 
+INFO_FIELDS = ("launcher", "status", "ntb", "vec", "up", "fuse2", "tailc", "th", "scaled", "k1", "n16", "grid", "block", "tiles",
+               "pre", "range_flag")
+
+
+def _fused_launch(name, device, info, *args):
+    """_lib.launch of a fused-conv entry; a failure carries the launch record gathered so far (``HcfError.info``) and the
+    entry's status (``HcfError.status``)."""
+    try:
+        _lib.launch(name, device, *args)
+    except _lib.HcfError as e:
+        e.info = dict(zip(INFO_FIELDS, (int(v) for v in info)))
+        e.status = next((k for k, v in _lib.ERR_NAMES.items() if "%s (%d)" % (v, k) in str(e)), None)
+        raise
+    return dict(zip(INFO_FIELDS, (int(v) for v in info)))
+
+
+def fcn12(srcs: Sequence[torch.Tensor], w1, bias1, scale1, w2, bias2, scale2, pre=None, ups: Optional[Sequence[int]] = None,
+          form: int = 0, out: Optional[torch.Tensor] = None):
+    """FCN layers 1 + 2 as ONE fused f16x3 launch (include/hcflow.h: hcf_op_fcn12): (out, info). ``form`` 0: the engine's routing
+    (persistent kernel first), 1: the direct FUSE2 kernel. ``out``: a [B,64,H,W] tensor to write into (a refused launch leaves it
+    untouched)."""
+    srcs = [_dev(s) for s in srcs]
+    n = len(srcs)
+    ups = list(ups) if ups is not None else [0] * n
+    B = srcs[0].shape[0]
+    H, W = srcs[0].shape[2] << ups[0], srcs[0].shape[3] << ups[0]
+    assert tuple(w1.shape) == (64, sum(s.shape[1] for s in srcs), 3, 3) and tuple(w2.shape) == (64, 64, 1, 1)
+    ptrs = (C.c_void_p * n)(*[s.data_ptr() for s in srcs])
+    cs = (C.c_int32 * n)(*[s.shape[1] for s in srcs])
+    us = (C.c_int32 * n)(*ups)
+    if out is None:
+        out = torch.empty(B, 64, H, W, device=srcs[0].device)
+    assert tuple(out.shape) == (B, 64, H, W) and out.dtype == torch.float32
+    info = (C.c_int32 * 16)()
+    p = _dev(pre) if pre is not None else None
+    rec = _fused_launch("hcf_op_fcn12", out.device, info, ptrs, cs, us, n, B, H, W, _host(w1), _host(bias1), _host(scale1), _host(w2),
+                        _host(bias2), _host(scale2), p, out, int(form), info)
+    return out, rec
+
+
+def conv2d_step_inverse(h2, w3, bias3, scale3, z, mode: int, ns: int, mat, an_bias, an_logs, zpad_n: Optional[int] = None):
+    """Conv2dZeros with the inverse flow step in its epilogue as ONE fused f16x3 launch (include/hcflow.h:
+    hcf_op_conv2d_step_inverse): (out_z, out_zpad or None, info)."""
+    h2, z = _dev(h2), _dev(z)
+    B, Cc, H, W = z.shape
+    f_out, hid = int(w3.shape[0]), int(w3.shape[1])
+    assert h2.shape == (B, hid, H, W) and tuple(w3.shape[2:]) == (3, 3)
+    out = torch.empty_like(z)
+    zpad = torch.empty(B, 16, H, W, device=z.device) if zpad_n is not None else None
+    info = (C.c_int32 * 16)()
+    rec = _fused_launch("hcf_op_conv2d_step_inverse", z.device, info, h2, hid, _host(w3), _host(bias3), _host(scale3), f_out, z, Cc,
+                        int(mode), int(ns), _host(mat), _host(an_bias.flatten()), _host(an_logs.flatten()), out, zpad,
+                        int(zpad_n or 0), B, H, W, info)
+    return out, zpad, rec
+
+
 def step_forward_head(z, mat, an_bias, an_logs) -> torch.Tensor:
     z = _dev(z)
     B, Cc, H, W = z.shape

@@ -369,6 +369,31 @@ int hcf_op_step_forward_head(const float* z, float* out, int32_t B, int32_t C, i
                              const float* an_bias, const float* an_logs, hcf_stream_t stream);
 int hcf_op_step_forward_couple(const float* z, const float* h, float* out, float* logdet, int32_t B, int32_t C,
                                int32_t H, int32_t W, int32_t hC, int32_t mode, int32_t ns, hcf_stream_t stream);
+/* The fused f16x3 conv launches of the default inference path, ONE launch per call (tests/test_gpu_fused_convs.py). Both entries
+ * always run the f16x3 kernels (never the Winograd form, which the engine excludes for these launches), build their packs with the
+ * engine's host packer, return a launcher's refusal as their status without substituting anything, and return HCF_ERR_UNSUPPORTED
+ * without writing their outputs when the launch raised the f16 range flag.
+ *   info[16] (HOST, filled from the launch made): 0 launcher (0 the persistent fcn12 kernel, 1 the f16x3 kernel), 1 the plan's /
+ *   launcher's status, 2 .. 10 the f16x3 kernel's template arguments NTB, VEC, UP, FUSE2, TAILC, TH, SCALED, K1, N16 (launcher 1),
+ *   11 grid, 12 block, 13 tiles walked and 14 the `pre` instantiation (launcher 0), 15 the range flag word.
+ *
+ * FCN layers 1 + 2 (Basic.py:441-444):
+ *   out = relu(((W2 . relu(((conv3x3(cat(up(src_i)), w1) + pre) + bias1) * scale1)) + bias2) * scale2)
+ * sources as hcf_op_conv2d; w1 HOST [64,cin,3,3], w2 HOST [64,64,1,1], bias / scale HOST [64] or NULL; pre device [B,64,H,W] or NULL
+ * (it travels as res1, as in the engine); out device [B,64,H,W]. form 0: what the engine's run_conv does -- the persistent form
+ * first, the direct FUSE2 form when that returns HCF_ERR_UNSUPPORTED; form 1: the direct FUSE2 form (which refuses `pre`:
+ * HCF_ERR_ARG). */
+int hcf_op_fcn12(const float* const* src, const int32_t* src_c, const int32_t* src_up, int32_t n_src, int32_t B, int32_t H,
+                 int32_t W, const float* w1, const float* bias1, const float* scale1, const float* w2, const float* bias2,
+                 const float* scale2, const float* pre, float* out, int32_t form, int32_t* info, hcf_stream_t stream);
+/* Conv2dZeros with the inverse flow step in its epilogue (FlowStep.py:53-64): h = (conv3x3(h2, w3) + bias3) * scale3, then
+ * out_z = actnorm^-1(Winv @ coupling^-1(z, h)) as hcf_op_step_inverse (same tables, same fp64 inverse of mat). h2 device
+ * [B,hid,H,W]; w3 HOST [f_out,hid,3,3]; bias3 / scale3 HOST [f_out] or NULL; z, out_z device [B,C,H,W]; out_zpad device
+ * [B,16,H,W] or NULL: out_z[:, :zpad_n] zero-padded to 16 channels, as the kernel stores it for the next step. */
+int hcf_op_conv2d_step_inverse(const float* h2, int32_t hid, const float* w3, const float* bias3, const float* scale3,
+                               int32_t f_out, const float* z, int32_t C, int32_t mode, int32_t ns, const float* mat,
+                               const float* an_bias, const float* an_logs, float* out_z, float* out_zpad, int32_t zpad_n,
+                               int32_t B, int32_t H, int32_t W, int32_t* info, hcf_stream_t stream);
 /* GaussianDiag.logp / sample (Basic.py:78-101) with (mean, logs) = h[:,0::2], h[:,1::2] */
 int hcf_op_gauss_logp(const float* h, const float* x, float* out_logp, int32_t B, int32_t C, int32_t H, int32_t W,
                       hcf_stream_t stream);
