@@ -86,7 +86,10 @@ struct Args {
   const char* zeros;       // >= 64 bytes of zeros
   int rev;                 // walk the units in reverse order (the engine alternates per launch: the consumer starts on what the producer touched last, which the 256 MB MALL still holds)
   int top_wait;            // A/B knob (HCF_WINO_TOP_WAIT=1): the 64-channel kernel waits at the top of every unit's first chunk as before round 5
-  unsigned long long* dbg; // WINO_PROF builds: [0] vmcnt wait [1] barrier wait [2] life [3] epilogue [4] samples [5] setup+issue [6] loads+transform
+  unsigned long long* dbg; // WINO_PROF builds: [0] vmcnt wait [1] barrier wait [2] life [3] epilogue [4] samples [5] setup+issue [6] loads+transform;
+                           // 64-channel kernel, one unit boundary (wino64_epilogue): [8] entry barrier, round 0: [9] R + write [10] barrier [11] read
+                           // [14] barrier "buffer read" [13] math [12] vmcnt(0), [15] round 0's stores among round 1's R + write, round 1: [16] barrier
+                           // [17] read [19] math + stores, [20] fused 1x1 layer, top of the next unit's first chunk: [21] wait [22] barrier [23] count
   unsigned long long* clk; // in-kernel clock probe of the 64-channel kernel (hcf_debug_clock_probe): block 0 adds its life in shader
                            // cycles (s_memtime) to clk[0] and in 100 MHz ticks (s_memrealtime) to clk[1] ([2], [3]: its start stamps); null: off
 };
@@ -699,8 +702,20 @@ constexpr int NPIECE4 = 22 + 48;                  // DMA instructions per chunk
 template <int RES>
 __device__ __forceinline__ void wino64_epilogue(const Args& a, char* const lds, const int tab_off, char* const xbase, f32x16 (&acc)[4][2],
                                                 const int eb, const int ey0, const int ex0, const int H, const int W, const float slope,
-                                                const float slope2, const float slope_f, const int wave, const int lane) {
+                                                const float slope2, const float slope_f, const int wave, const int lane
+#if defined(WINO_PROF)
+                                                , unsigned long long* const pw
+#endif
+                                                ) {
   constexpr bool F1 = (RES == 3);
+  // WINO_PROF builds: the phases of one unit boundary, pw[8 + ...] (Args::dbg). A stamp drains the LDS queue (s_memtime shares
+  // lgkmcnt with it), so "write" and "read" end when the data has moved, not when the instructions have issued.
+#if defined(WINO_PROF)
+  unsigned long long tl_ = __builtin_readcyclecounter();
+#define W64_STAMP(I) { asm volatile("" ::: "memory"); const unsigned long long t_ = __builtin_readcyclecounter(); pw[I] += t_ - tl_; tl_ = t_; asm volatile("" ::: "memory"); }
+#else
+#define W64_STAMP(I)
+#endif
   const int half = lane >> 5, li = lane & 31, xi = wave & 3, tg = wave >> 2;
   (void)li;
   // ---- epilogue: R[b] = sum_nu M[nu] A[nu][b] per wave (its transform row). The four rows of a tile group meet in LDS
@@ -715,74 +730,141 @@ __device__ __forceinline__ void wino64_epilogue(const Args& a, char* const lds, 
   const int wpos = (half * 32 + ((li + 4 * half) & 31)) * 16;                 // writer slot for even q; odd q: + 8 patches (mod 32)
   const int wpos1 = (half * 32 + ((li + 4 * half + 8) & 31)) * 16;
   const int rpos = (hd * 32 + ((patch + 4 * hd + 8 * (qd & 1)) & 31)) * 16 + qd * 1024;
-  f32x4 hv[2][2][2];                              // F1: the first layer's values of this lane (2 rounds x 2 x 2 pixels x 4 channels)
-  __builtin_amdgcn_s_barrier();                   // every wave is done reading the last chunk's weights
+  f32x4 hv[2][2][2];                              // the lane's values (2 rounds x 2 x 2 pixels x 4 channels): stored per round, or (F1) the first layer's
+  // The lane's 2 x 2 output pixels: ONE pixel index per unit (B H W < 2^24, launch()), one 64-bit product per tensor, and the
+  // other three pixels by adding the tensor's column / row stride (0 where the neighbour is outside the image: the clamped
+  // address of the form before, whose value is not used). The residuals of BOTH rounds are requested here, ahead of the entry
+  // barrier and of every store of the unit (a load queued behind round 0's stores would wait for their acknowledgements).
+  const int yy0 = ey0 + 4 * tg + 2 * prow, xx0 = ex0 + 2 * pcol;
+  const bool okx1 = xx0 + 1 < W, oky1 = yy0 + 1 < H;
+  const bool oks[2][2] = {{yy0 < H && xx0 < W, yy0 < H && okx1}, {oky1 && xx0 < W, oky1 && okx1}};
+  const int pix00 = (eb * H + (yy0 < H ? yy0 : H - 1)) * W + (xx0 < W ? xx0 : W - 1);
+  const int cb0 = 8 * qd + 4 * hd;
+#define W64_PTR(T, BASE, CS, C0, OA, OB) \
+  ((T)((BASE) + (ptrdiff_t)pix00 * (CS) + (C0) + cb0) + (((OA) && oky1) ? W * (CS) : 0) + (((OB) && okx1) ? (CS) : 0))
+  f32x4 rv1[2][2][2], rv2[2][2][2];
+  if (RES == 1 || RES == 2) {
 #pragma unroll
-  for (int nt = 0; nt < 2; ++nt) {
-    const int cb = nt * 32 + 8 * qd + 4 * hd;
-    f32x4 rv1[2][2], rv2[2][2];                   // this round's residuals: issued now, used after the exchange
-    size_t pixs[2][2];
-    bool oks[2][2];
+    for (int nt = 0; nt < 2; ++nt)
 #pragma unroll
-    for (int oa = 0; oa < 2; ++oa)
+      for (int oa = 0; oa < 2; ++oa)
 #pragma unroll
-      for (int ob = 0; ob < 2; ++ob) {
-        const int yy = ey0 + 4 * tg + 2 * prow + oa, xx = ex0 + 2 * pcol + ob;
-        oks[oa][ob] = yy < H && xx < W;
-        pixs[oa][ob] = (size_t)((size_t)eb * H + (yy < H ? yy : H - 1)) * W + (xx < W ? xx : W - 1);
-        if (RES == 1 || RES == 2) rv1[oa][ob] = *reinterpret_cast<const f32x4*>(a.res1 + pixs[oa][ob] * a.res1_cs + a.res1_c0 + cb);
-        if (RES == 2) rv2[oa][ob] = *reinterpret_cast<const f32x4*>(a.res2 + pixs[oa][ob] * a.res2_cs + a.res2_c0 + cb);
-      }
-    if (nt == 1) __builtin_amdgcn_s_barrier();    // round 0's buffer has been read
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      f32x4 Rq[2];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const int r = 4 * q + e;
-        Rq[0][e] = acc[0][nt][r] + acc[1][nt][r] + acc[2][nt][r];
-        Rq[1][e] = acc[1][nt][r] - acc[2][nt][r] - acc[3][nt][r];
-      }
-      char* const wbq = xbuf + ((xi * 2) * 4 + q) * 1024 + ((q & 1) ? wpos1 : wpos);
-      *reinterpret_cast<f32x4*>(wbq) = Rq[0];
-      *reinterpret_cast<f32x4*>(wbq + 4096) = Rq[1];
-    }
-    __builtin_amdgcn_s_barrier();
-    f32x4 R[4][2];
-#pragma unroll
-    for (int x = 0; x < 4; ++x)
-#pragma unroll
-      for (int bb = 0; bb < 2; ++bb) R[x][bb] = *reinterpret_cast<const f32x4*>(xbuf + ((x * 2 + bb) * 4) * 1024 + rpos);
-    const f32x4 bs = *reinterpret_cast<const f32x4*>(lds + tab_off + cb * 4);
-    const f32x4 ms = *reinterpret_cast<const f32x4*>(lds + tab_off + 256 + cb * 4);
-    const bool split_t = (nt == 1) && a.out2 != nullptr;         // second tile routed to its own tensor / activation
-    const float slope_t = split_t ? slope2 : slope;
-#pragma unroll
-    for (int oa = 0; oa < 2; ++oa)
-#pragma unroll
-      for (int ob = 0; ob < 2; ++ob) {
-        f32x4 v;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const float yv = oa ? (R[1][ob][e] - R[2][ob][e]) - R[3][ob][e] : (R[0][ob][e] + R[1][ob][e]) + R[2][ob][e];
-          chk = fmaf(yv, 0.f, chk);
-          const float z = fmaf(yv, ms[e], bs[e]);
-          v[e] = fmaxf(z, slope_t * z);
-          if (RES == 1 || RES == 2) v[e] = fmaf(v[e], a.rs1, rv1[oa][ob][e]);
-          if (RES == 2) v[e] = fmaf(v[e], a.rs2, rv2[oa][ob][e]);
+        for (int ob = 0; ob < 2; ++ob) {
+          rv1[nt][oa][ob] = *reinterpret_cast<const f32x4*>(W64_PTR(const float*, a.res1, a.res1_cs, a.res1_c0, oa, ob) + 32 * nt);
+          if (RES == 2) rv2[nt][oa][ob] = *reinterpret_cast<const f32x4*>(W64_PTR(const float*, a.res2, a.res2_cs, a.res2_c0, oa, ob) + 32 * nt);
         }
-        if (F1) hv[nt][oa][ob] = v;
-        else {
-          if (nt == 0 && oa == 0 && ob == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // every load of this wave (the next
-                                                    // unit's first chunk included) has landed BEFORE the unit's first store is issued:
-                                                    // the next chunk's top does not wait again (conv_wino4_kernel)
-        }
-        if (!F1 && oks[oa][ob] && cb < a.cout) {
-          if (split_t) *reinterpret_cast<f32x4*>(a.out2 + pixs[oa][ob] * a.out2_cs + a.out2_c0 + (cb - 32)) = v;
-          else *reinterpret_cast<f32x4*>(a.out + pixs[oa][ob] * a.out_cs + a.out_c0 + cb) = v;
-        }
-      }
   }
+  __builtin_amdgcn_s_barrier();                   // every wave is done reading the last chunk's weights
+  W64_STAMP(8)
+  // One round per channel tile: every wave writes its row R of the tile, barrier, every wave reads the four rows of its
+  // patches. The two rounds share the buffer, so round 1's writes wait for a barrier after round 0's READS -- not after round
+  // 0's stores: the global stores of round 0 (vector memory path) are issued BETWEEN the exchange writes of round 1 (LDS store
+  // path, 13 cycles per 16-byte write and the bound of that phase), one store per two writes. The two paths overlap in part:
+  // 1 420 cycles for both against 845 + 830 one after the other (profiles/r09_notes.md).
+#define W64_WRITE(NT, Q)                                                                           \
+  {                                                                                                \
+    f32x4 Rq[2];                                                                                   \
+    _Pragma("unroll") for (int e = 0; e < 4; ++e) {                                                \
+      const int r = 4 * (Q) + e;                                                                   \
+      Rq[0][e] = acc[0][NT][r] + acc[1][NT][r] + acc[2][NT][r];                                    \
+      Rq[1][e] = acc[1][NT][r] - acc[2][NT][r] - acc[3][NT][r];                                    \
+    }                                                                                              \
+    char* const wbq = xbuf + ((xi * 2) * 4 + (Q)) * 1024 + (((Q) & 1) ? wpos1 : wpos);             \
+    *reinterpret_cast<f32x4*>(wbq) = Rq[0];                                                        \
+    *reinterpret_cast<f32x4*>(wbq + 4096) = Rq[1];                                                 \
+  }
+#define W64_READ()                                                                                 \
+  _Pragma("unroll") for (int x = 0; x < 4; ++x)                                                    \
+    _Pragma("unroll") for (int bb = 0; bb < 2; ++bb) R[x][bb] = *reinterpret_cast<const f32x4*>(xbuf + ((x * 2 + bb) * 4) * 1024 + rpos);
+  // y (output transform), bias / scale / activation / residuals of the lane's four pixels of tile NT
+#define W64_MATH(NT, V)                                                                            \
+  _Pragma("unroll") for (int oa = 0; oa < 2; ++oa)                                                 \
+    _Pragma("unroll") for (int ob = 0; ob < 2; ++ob)                                               \
+      _Pragma("unroll") for (int e = 0; e < 4; ++e) {                                              \
+        const float yv = oa ? (R[1][ob][e] - R[2][ob][e]) - R[3][ob][e] : (R[0][ob][e] + R[1][ob][e]) + R[2][ob][e]; \
+        chk = fmaf(yv, 0.f, chk);                                                                  \
+        const float z = fmaf(yv, ms[e], bs[e]);                                                    \
+        float v_ = fmaxf(z, slope_t * z);                                                          \
+        if (RES == 1 || RES == 2) v_ = fmaf(v_, a.rs1, rv1[NT][oa][ob][e]);                        \
+        if (RES == 2) v_ = fmaf(v_, a.rs2, rv2[NT][oa][ob][e]);                                    \
+        V[oa][ob][e] = v_;                                                                         \
+      }
+#define W64_STORE(NT, OA, OB, V) \
+  if (oks[OA][OB] && (NT) * 32 + cb0 < a.cout) *reinterpret_cast<f32x4*>(W64_PTR(float*, o_base, o_cs, o_c0, OA, OB)) = V[OA][OB];
+  f32x4 R[4][2];
+  {                                               // ---- round 0
+#pragma unroll
+    for (int q = 0; q < 4; ++q) W64_WRITE(0, q)
+    W64_STAMP(9)
+    __builtin_amdgcn_s_barrier();
+    W64_STAMP(10)
+    W64_READ()
+    const f32x4 bs = *reinterpret_cast<const f32x4*>(lds + tab_off + cb0 * 4);
+    const f32x4 ms = *reinterpret_cast<const f32x4*>(lds + tab_off + 256 + cb0 * 4);
+    const float slope_t = slope;
+    float* const o_base = a.out;
+    const int o_cs = a.out_cs, o_c0 = a.out_c0;
+    (void)o_base; (void)o_cs; (void)o_c0;
+    if (!F1) {
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");          // this wave's reads of round 0 have left the buffer
+      W64_STAMP(11)
+      __builtin_amdgcn_s_barrier();               // ... and so have every wave's: round 1 may overwrite it
+      W64_STAMP(14)
+    }
+    W64_MATH(0, hv[0])
+    if (F1) {
+      W64_STAMP(11)
+      __builtin_amdgcn_s_barrier();               // round 0's buffer has been read (the reads fed the values above)
+      W64_STAMP(14)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) W64_WRITE(1, q)
+    } else {
+      W64_STAMP(13)
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");           // every load of this wave (the next unit's first chunk included) has
+                                                  // landed BEFORE the unit's first store is issued: the next chunk's top does not
+                                                  // wait again (conv_wino4_kernel)
+      if (RES == 1 || RES == 2) {                 // (the residuals are here too, and the compiler is told so: its own counted
+                                                  //  waits would otherwise sit out store acknowledgements before every later use)
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+          asm volatile("" : "+v"(rv1[i >> 2][(i >> 1) & 1][i & 1]));
+          if (RES == 2) asm volatile("" : "+v"(rv2[i >> 2][(i >> 1) & 1][i & 1]));
+        }
+      }
+      W64_STAMP(12)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        W64_STORE(0, q >> 1, q & 1, hv[0])
+        asm volatile("" ::: "memory");            // (keeps the order: store, two writes, store, ...)
+        W64_WRITE(1, q)
+        asm volatile("" ::: "memory");
+      }
+    }
+    W64_STAMP(15)
+  }
+  {                                               // ---- round 1
+    __builtin_amdgcn_s_barrier();
+    W64_STAMP(16)
+    W64_READ()
+    const f32x4 bs = *reinterpret_cast<const f32x4*>(lds + tab_off + (32 + cb0) * 4);
+    const f32x4 ms = *reinterpret_cast<const f32x4*>(lds + tab_off + 256 + (32 + cb0) * 4);
+    const bool split_t = a.out2 != nullptr;       // second tile routed to its own tensor / activation
+    const float slope_t = split_t ? slope2 : slope;
+    float* const o_base = split_t ? a.out2 : a.out;              // (uniform selects: one address form for both routes)
+    const int o_cs = split_t ? a.out2_cs : a.out_cs, o_c0 = split_t ? a.out2_c0 : a.out_c0 + 32;
+    (void)o_base; (void)o_cs; (void)o_c0;
+    W64_STAMP(17)
+    W64_MATH(1, hv[1])
+    if (!F1) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) W64_STORE(1, q >> 1, q & 1, hv[1])
+    }
+    W64_STAMP(19)
+  }
+#undef W64_WRITE
+#undef W64_READ
+#undef W64_MATH
+#undef W64_STORE
   if (F1) {
     // ---- second layer: h2 = act_f((W_f h1 + bias_f) * scale_f) on the tile's 256 pixels. The exchange buffer becomes 256 pixel
     // records of 256 bytes: 16 slots of 8 halves, slot (plane * 8 + channel / 8) ^ (pixel & 15) (a 128-bit LDS read is served in
@@ -836,7 +918,7 @@ __device__ __forceinline__ void wino64_epilogue(const Args& a, char* const lds, 
     for (int rr = 0; rr < 2; ++rr) {
       const int yy = ey0 + r0 + rr;
       const bool ok2 = yy < H && xx < W;
-      float* const op = a.out + ((size_t)((size_t)eb * H + (yy < H ? yy : H - 1)) * W + (size_t)(xx < W ? xx : W - 1)) * a.out_cs + a.out_c0;
+      float* const op = a.out + (ptrdiff_t)((eb * H + (yy < H ? yy : H - 1)) * W + (xx < W ? xx : W - 1)) * a.out_cs + a.out_c0;
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         const int cb2 = mt * 32 + 8 * q + 4 * half;
@@ -853,10 +935,13 @@ __device__ __forceinline__ void wino64_epilogue(const Args& a, char* const lds, 
         if (ok2) *reinterpret_cast<f32x4*>(op + cb2) = v;
       }
     }
+    W64_STAMP(20)
   }
   if (__any(chk != chk)) {
     if (lane == 0) atomicOr(a.ovf, 1 | (2 << (eb % 30)));       // bit 0 + the unit's sample slot (see hcf_conv_f16x3.hip)
   }
+#undef W64_PTR
+#undef W64_STAMP
 }
 
 template <int RES, bool SC = false>
@@ -988,7 +1073,7 @@ __global__ __launch_bounds__(512, 1) void conv_wino4_kernel(const Args a, const 
   int u = blockIdx.x;
   if (u >= nunits) return;
 #if defined(WINO_PROF)
-  unsigned long long pw[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  unsigned long long pw[24] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   const unsigned long long pw_t0 = __builtin_readcyclecounter();
 #endif
   if (a.clk != nullptr && blockIdx.x == 0 && tid == 0) {      // (start stamps parked in memory: nothing of the probe lives through the loop)
@@ -1036,6 +1121,7 @@ __global__ __launch_bounds__(512, 1) void conv_wino4_kernel(const Args a, const 
 #if defined(WINO_PROF)
       const unsigned long long q2 = __builtin_readcyclecounter();
       pw[0] += q1 - q0; pw[1] += q2 - q1;
+      if (c == 0 && g > 0) { pw[21] += q1 - q0; pw[22] += q2 - q1; pw[23] += 1; }     // the top of a later unit's first chunk
 #endif
 #pragma unroll
       for (int nu = 0; nu < 4; ++nu) asm volatile("" : "+v"(w11[nu]));      // (the fragments were written behind the compiler's back)
@@ -1108,7 +1194,11 @@ __global__ __launch_bounds__(512, 1) void conv_wino4_kernel(const Args a, const 
 #endif
     int lane_e = lane;                            // (opaque: the epilogue's lane-constant addresses are recomputed per unit, not kept
     asm volatile("" : "+v"(lane_e));              //  in registers through the chunk loop, where there are none to spare)
-    wino64_epilogue<RES>(a, lds, TAB4_OFF, lds + (((g - 1) & 1) ? W4_OFF0 + W4L_BYTES : W4_OFF0), acc, eb, ey0, ex0, H, W, slope, slope2, slope_f, wave, lane_e);
+    wino64_epilogue<RES>(a, lds, TAB4_OFF, lds + (((g - 1) & 1) ? W4_OFF0 + W4L_BYTES : W4_OFF0), acc, eb, ey0, ex0, H, W, slope, slope2, slope_f, wave, lane_e
+#if defined(WINO_PROF)
+                         , pw
+#endif
+                         );
 #if defined(WINO_PROF)
     pw[3] += __builtin_readcyclecounter() - qe0;
 #endif
@@ -1124,6 +1214,7 @@ __global__ __launch_bounds__(512, 1) void conv_wino4_kernel(const Args a, const 
     atomicAdd(a.dbg + 0, pw[0]); atomicAdd(a.dbg + 1, pw[1]); atomicAdd(a.dbg + 2, __builtin_readcyclecounter() - pw_t0);
     atomicAdd(a.dbg + 3, pw[3]); atomicAdd(a.dbg + 4, 1ull); atomicAdd(a.dbg + 5, pw[5]); atomicAdd(a.dbg + 6, pw[6]);
     atomicAdd(a.dbg + 7, pw[7]);
+    for (int i = 8; i < 24; ++i) atomicAdd(a.dbg + i, pw[i]);
   }
 #endif
 #undef W4_SETUP_UNIT
@@ -1152,6 +1243,11 @@ static inline int launch(const Args& a, int ncu, hipStream_t st, int version = 2
   if (a.res2 && !a.res1) return -1;
   if ((long long)a.B * a.H * a.W >= (1LL << 24)) return -6;                            // 24-bit pixel index (mul24)
   if (version == 4 && (a.ntile_n != 2 || a.cout > 64)) return -6;
+  if (version == 4) {                                                                  // 32-bit row strides (wino64_epilogue)
+    const int cs_[4] = {a.out_cs, a.out2 ? a.out2_cs : 0, a.res1 ? a.res1_cs : 0, a.res2 ? a.res2_cs : 0};
+    for (int i = 0; i < 4; ++i)
+      if (cs_[i] < 0 || (long long)(a.W + 1) * cs_[i] >= 0x7fffffffLL) return -6;
+  }
   const int th = (version == 2) ? v2::TH2 : (version == 4) ? v4::TH4 : TH;
   const int tiles_x = (a.W + TW - 1) / TW, tiles_y = (a.H + th - 1) / th;
   const long long nunits = (long long)a.B * tiles_x * tiles_y * (version == 4 ? 1 : a.ntile_n);

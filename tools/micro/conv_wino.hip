@@ -224,7 +224,13 @@ int main(int argc, char** argv) {
                  100 * h[5] / life, 100 * h[6] / life, 100 * h[7] / life, 100 * h[8] / life, 100 * h[9] / life, 100 * h[10] / life, 100 * h[11] / life); } }
 #endif
 #if defined(WINO_PROF)
-      { unsigned long long h[8]; CK(hipMemcpy(h, dbg, 64, hipMemcpyDeviceToHost));
+      { unsigned long long h[24]; CK(hipMemcpy(h, dbg, 192, hipMemcpyDeviceToHost));
+        // one unit boundary of the 64-channel kernel, shader cycles per unit (hcf_conv_wino.h: wino64_epilogue's stamps)
+        if (h[4] && h[23]) { const double ne = (double)(h[23] + h[4]), nb = (double)h[23];
+          printf("    boundary, cycles per unit (%.0f units per wave, %.0f kcyc per unit): entry barrier %.0f | round 0: R + write %.0f  barrier %.0f  read %.0f  barrier (buffer read) %.0f  math %.0f  vmcnt(0) %.0f |"
+                 " round 0 stores among round 1 R + write %.0f | round 1: barrier %.0f  read %.0f  math + stores %.0f | 1x1 layer %.0f | next top: wait %.0f  barrier %.0f | epilogue total %.0f\n",
+                 ne / h[4], h[2] / 1e3 / ne, h[8] / ne, h[9] / ne, h[10] / ne, h[11] / ne, h[14] / ne, h[13] / ne, h[12] / ne, h[15] / ne, h[16] / ne, h[17] / ne, h[19] / ne,
+                 h[20] / ne, h[21] / nb, h[22] / nb, h[3] / ne); }
         if (h[4]) printf("    per wave: life %.0f kcyc (%.2f GHz)  vmcnt %.1f %%  barrier %.1f %%  setup+issue %.1f %%  loads+transform %.1f %%  epilogue %.1f %%\n",
                          h[2] / 1e3 / h[4], h[2] / (double)h[4] / (us * 1e3), 100.0 * h[0] / h[2], 100.0 * h[1] / h[2], 100.0 * h[5] / h[2], 100.0 * h[6] / h[2], 100.0 * h[3] / h[2]);
         if (h[4] && h[7]) printf("    of the epilogue: %.1f %% of the life waiting at its first barrier\n", 100.0 * h[7] / h[2]); }
