@@ -47,7 +47,7 @@ SYMBOLS = [
     "hcf_aux_act_backward", "hcf_aux_feature_loss_workspace", "hcf_aux_feature_loss",
     "hcf_train_backward_ex", "hcf_train_backward_rescale_ex", "hcf_train_encode_sr", "hcf_train_backward_encode",
     "hcf_op_quant_logp_backward_lr", "hcf_op_prior_encode_logp_backward", "hcf_op_input_grad",
-    "hcf_data_prepare_batch",
+    "hcf_data_prepare_batch", "hcf_data_prepare_paired",
     "hcf_op_fcn12", "hcf_op_conv2d_step_inverse",
 ]
 
@@ -193,6 +193,7 @@ def load() -> C.CDLL:
                                                   i32, i32, i32, i32, i32, i32, vp]
     lib.hcf_op_lu_chain.argtypes = [fp] * 7 + [i32, vp]
     lib.hcf_data_prepare_batch.argtypes = [vp, C.c_size_t, vp, i32, vp, i32, i32, i32, i32, i32, fp, fp, vp]
+    lib.hcf_data_prepare_paired.argtypes = [vp, C.c_size_t, vp, vp, C.c_size_t, vp, i32, vp, i32, i32, i32, i32, i32, fp, fp, vp]
     for name in SYMBOLS:
         fn = getattr(lib, name)
         if name not in ("hcf_destroy", "hcf_last_error", "hcf_workspace_bytes", "hcf_weight_bytes",

@@ -11,6 +11,9 @@
 //   GT      the (8 S) x (32 S) source pixels of the tile, uint8 / 255.f, stored through the same index map.
 // Every output value is one fixed chain of fmaf over the taps in tap order, whatever tile or sample it lands in: a crop is
 // bit-identical to the same window of the whole image.
+//
+// Paired banks (hcf_data_prepare_paired: LRHR_PKL_dataset.py:96-135, GTLQnpy_dataset.py:42-78, GTLQx_dataset.py:82-122) keep the LQ
+// images as data beside the HR images: prepare_paired_kernel is the GT copy above for both halves, LQ at scale 1, no taps, no LDS.
 #include <math.h>
 #include "../../include/hcflow.h"
 #include "hcf_common.h"
@@ -152,6 +155,75 @@ static void tap_weights(int S, float* w) {
   for (int k = 0; k < kMaxTaps; ++k) w[k] = k < P ? (float)(v[k] / sum) : 0.f;
 }
 
+// ---- paired banks (LRHR_PKL, GTLQ / GTLQnpy / GTLQx): the LQ image is data of its own, not a function of the HR image ----
+struct PairSample { long long gt_off, lq_off; int gt_h, gt_w, lq_h, lq_w, top, left, flags, pad; };
+
+struct PairArgs {
+  const uint8_t* gt_bank;
+  const uint8_t* lq_bank;
+  float* gt;               // first sample of this launch, or nullptr
+  float* lq;
+  int lr_h, lr_w, scale, bgr, tiles_x, pad;
+  PairSample s[HCF_DATA_LAUNCH_BATCH];
+};
+static_assert(sizeof(PairArgs) <= 4096, "the records travel in the kernel argument block");
+
+// The rows x cols window of an H x W HWC image at (top + cy0, left + cx0) -> the (cy0, cx0) corner of a crop of ch x cw pixels in
+// `out` (3 planes of ch * cw), uint8 / 255.f, through the augment's index map. Consecutive lanes read consecutive bytes of a
+// source row; U rows are in flight per lane before the first store. Every source index is clamped into the image.
+template <int U>
+__device__ __forceinline__ void copy_window(const uint8_t* img, int H, int W, int top, int left, int cy0, int cx0, int rows,
+                                            int cols, int ch, int cw, int flags, int bgr, float* out) {
+  const size_t pitch = (size_t)W * 3, plane = (size_t)ch * cw;
+  const int hf = flags & 1, vf = (flags >> 1) & 1, rot = (flags >> 2) & 1;
+  const int w3 = cols * 3;
+  for (int r0 = 0; r0 < rows; r0 += U) {
+    for (int j = threadIdx.x; j < w3; j += 256) {
+      const int col = j / 3, c = j - col * 3;
+      const int cx = cx0 + col;                                // column in the crop
+      const uint8_t* p = img + (size_t)min(max(left + cx, 0), W - 1) * 3 + c;
+      uint8_t b[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u)                              // rows past the tile are clamped into the image and dropped below
+        b[u] = p[(size_t)min(max(top + cy0 + r0 + u, 0), H - 1) * pitch];
+      const int x = hf ? cw - 1 - cx : cx;
+      float* q = out + (size_t)(bgr ? 2 - c : c) * plane;
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int cy = cy0 + r0 + u;                           // row in the crop
+        const int y = vf ? ch - 1 - cy : cy;
+        if (r0 + u < rows) q[rot ? (size_t)x * ch + y : (size_t)y * cw + x] = (float)b[u] / 255.f;
+      }
+    }
+  }
+}
+
+// One block owns an 8 x 32 tile of a sample's LQ crop and the (8 scale) x (32 scale) HR pixels above it. No taps: scale is a
+// runtime argument. Rows in flight: the LQ tile has 8; for GT 16 measured 2 % under 8 and 32 no better.
+__global__ __launch_bounds__(256) void prepare_paired_kernel(const PairArgs a) {
+  const PairSample sm = a.s[blockIdx.y];
+  const int ty = blockIdx.x / a.tiles_x, tx = blockIdx.x - ty * a.tiles_x;
+  const int y0 = ty * kTH, x0 = tx * kTW;                     // tile origin in the crop's LQ grid
+  const int th = min(kTH, a.lr_h - y0), tw = min(kTW, a.lr_w - x0);
+  const int S = a.scale;
+  if (a.lq)
+    copy_window<8>(a.lq_bank + sm.lq_off, sm.lq_h, sm.lq_w, sm.top, sm.left, y0, x0, th, tw, a.lr_h, a.lr_w, sm.flags, a.bgr,
+                a.lq + (size_t)blockIdx.y * 3 * a.lr_h * a.lr_w);
+  if (a.gt)
+    copy_window<16>(a.gt_bank + sm.gt_off, sm.gt_h, sm.gt_w, sm.top * S, sm.left * S, y0 * S, x0 * S, th * S, tw * S, a.lr_h * S,
+                a.lr_w * S, sm.flags, a.bgr, a.gt + (size_t)blockIdx.y * 3 * a.lr_h * S * a.lr_w * S);
+}
+
+// {byte offset, H, W} rows of one bank's host table
+static int check_table(const int64_t* images, int n_images, size_t bank_bytes) {
+  for (int i = 0; i < n_images; ++i) {
+    const int64_t off = images[3 * i], H = images[3 * i + 1], W = images[3 * i + 2];
+    if (H < 1 || W < 1 || H > (1 << 24) || W > (1 << 24) || off < 0) return HCF_ERR_ARG;
+    if ((uint64_t)off > bank_bytes || (uint64_t)(3 * H * W) > bank_bytes - (uint64_t)off) return HCF_ERR_ARG;
+  }
+  return HCF_OK;
+}
+
 typedef void (*Kernel)(const Args);
 static Kernel kernel_of(int S) {
   switch (S) {
@@ -216,6 +288,56 @@ int hcf_data_prepare_batch(const uint8_t* bank, size_t bank_bytes, const int64_t
     a.gt = gt ? gt + (size_t)b0 * gt_n : nullptr;
     a.lq = lq ? lq + (size_t)b0 * lq_n : nullptr;
     hipLaunchKernelGGL(k, dim3((unsigned)tiles, (unsigned)nb), dim3(256), 0, (hipStream_t)stream, a);
+    if (hipGetLastError() != hipSuccess) return HCF_ERR_HIP;
+  }
+  return HCF_OK;
+}
+
+int hcf_data_prepare_paired(const uint8_t* gt_bank, size_t gt_bytes, const int64_t* gt_images, const uint8_t* lq_bank,
+                            size_t lq_bytes, const int64_t* lq_images, int32_t n_images, const int32_t* crops, int32_t B,
+                            int32_t lr_h, int32_t lr_w, int32_t scale, int32_t bgr, float* gt, float* lq, hcf_stream_t stream) {
+  using namespace hcf::data;
+  // ---- every record is checked here, before any HIP call: the kernel reads what these tables say ----
+  if (!gt_bank || !gt_images || !lq_bank || !lq_images || !crops || (!gt && !lq)) return HCF_ERR_ARG;
+  if (scale < 2 || scale > 8 || n_images < 1 || B < 0 || lr_h < 1 || lr_w < 1) return HCF_ERR_ARG;
+  if (lr_h > (1 << 20) || lr_w > (1 << 20)) return HCF_ERR_ARG;
+  if (check_table(gt_images, n_images, gt_bytes) != HCF_OK || check_table(lq_images, n_images, lq_bytes) != HCF_OK)
+    return HCF_ERR_ARG;
+  for (int i = 0; i < n_images; ++i)       // a larger HR image is the mod-crop case: its extra rows and columns are never read
+    if (gt_images[3 * i + 1] < scale * lq_images[3 * i + 1] || gt_images[3 * i + 2] < scale * lq_images[3 * i + 2])
+      return HCF_ERR_SHAPE;
+  for (int b = 0; b < B; ++b) {
+    const int32_t* c = crops + 6 * b;
+    if (c[0] < 0 || c[0] >= n_images || c[1] < 0 || c[2] < 0) return HCF_ERR_ARG;
+    for (int f = 3; f < 6; ++f)
+      if (c[f] != 0 && c[f] != 1) return HCF_ERR_ARG;
+    if (c[5] && lr_h != lr_w) return HCF_ERR_ARG;
+    const int64_t H = lq_images[3 * c[0] + 1], W = lq_images[3 * c[0] + 2];
+    if ((int64_t)c[1] + lr_h > H || (int64_t)c[2] + lr_w > W) return HCF_ERR_ARG;
+  }
+  if (B == 0) return HCF_OK;
+
+  PairArgs a;
+  a.gt_bank = gt_bank; a.lq_bank = lq_bank;
+  a.lr_h = lr_h; a.lr_w = lr_w; a.scale = scale; a.bgr = bgr ? 1 : 0; a.pad = 0;
+  a.tiles_x = (lr_w + kTW - 1) / kTW;
+  const long long tiles = (long long)a.tiles_x * ((lr_h + kTH - 1) / kTH);
+  if (tiles > 0x7fffffffLL) return HCF_ERR_ARG;
+  const size_t lq_n = (size_t)3 * lr_h * lr_w, gt_n = lq_n * scale * scale;
+  for (int b0 = 0; b0 < B; b0 += HCF_DATA_LAUNCH_BATCH) {
+    const int nb = B - b0 < HCF_DATA_LAUNCH_BATCH ? B - b0 : HCF_DATA_LAUNCH_BATCH;
+    for (int i = 0; i < HCF_DATA_LAUNCH_BATCH; ++i) {
+      const int32_t* c = crops + 6 * (size_t)(b0 + (i < nb ? i : 0));      // unused slots repeat a valid record
+      const int64_t* g = gt_images + 3 * c[0];
+      const int64_t* l = lq_images + 3 * c[0];
+      PairSample& s = a.s[i];
+      s.gt_off = g[0]; s.gt_h = (int)g[1]; s.gt_w = (int)g[2];
+      s.lq_off = l[0]; s.lq_h = (int)l[1]; s.lq_w = (int)l[2];
+      s.top = c[1]; s.left = c[2]; s.flags = c[3] | (c[4] << 1) | (c[5] << 2); s.pad = 0;
+    }
+    a.gt = gt ? gt + (size_t)b0 * gt_n : nullptr;
+    a.lq = lq ? lq + (size_t)b0 * lq_n : nullptr;
+    hipLaunchKernelGGL(prepare_paired_kernel, dim3((unsigned)tiles, (unsigned)nb), dim3(256), 0, (hipStream_t)stream, a);
     if (hipGetLastError() != hipSuccess) return HCF_ERR_HIP;
   }
   return HCF_OK;

@@ -643,6 +643,31 @@ int hcf_data_prepare_batch(const uint8_t* bank, size_t bank_bytes, const int64_t
                            const int32_t* crops, int32_t B, int32_t lr_h, int32_t lr_w, int32_t scale, int32_t bgr,
                            float* gt, float* lq, hcf_stream_t stream);
 
+/* ---- paired image banks (hcf_data.hip): the LRHR_PKL and GTLQ / GTLQnpy / GTLQx samples of a batch in one launch ----
+ * The reference's paired datasets (LRHR_PKL_dataset.py:96-135, GTLQnpy_dataset.py:42-78, GTLQx_dataset.py:82-122) on pairs that
+ * already live in device memory as two packed HWC uint8 banks. The LQ image is data, never computed from the HR image:
+ *   lq[b] = the window (top_lr, left_lr, lr_h, lr_w) of LQ image i, uint8 / 255.f (true division);
+ *   gt[b] = the window (top_lr * scale, left_lr * scale, lr_h * scale, lr_w * scale) of HR image i, uint8 / 255.f;
+ *   both then hflip ([:, ::-1]), vflip ([::-1]), rot90 (transpose) in that order, the channel reversal when `bgr`, HWC -> CHW.
+ * np.rot90(k, axes=(1, 2)) after np.flip(axis=2) of the PKL mode is a flag triple of this map (hcflow_amd/data.py: PKL_FLAGS).
+ * Outputs are float32 NCHW in device memory: gt [B,3,lr_h*scale,lr_w*scale], lq [B,3,lr_h,lr_w] (a rot90 sample is the
+ * transpose, accepted for square crops only); either may be NULL (not wanted), not both.
+ *   gt_bank, lq_bank:     device, gt_bytes / lq_bytes bytes; image i = 3 * H * W bytes at its byte offset
+ *   gt_images, lq_images: HOST [n_images][3] = {byte offset, H, W}, row i of both = pair i
+ *   crops:                HOST [B][6] = {image, top_lr, left_lr, hflip, vflip, rot90}, on the LQ grid
+ * scale is an integer in 2 .. 8 and a runtime argument of the one kernel (there are no taps). The per-sample records travel as
+ * kernel arguments: no allocation, no copy, no synchronisation, up to HCF_DATA_LAUNCH_BATCH samples per launch (larger batches:
+ * several launches of the same kernel).
+ * Every record is validated BEFORE any HIP call: HCF_ERR_ARG for null pointers, scale outside 2 .. 8, n_images < 1, an offset or
+ * image outside its bank, an image index or crop outside its (LQ) image, flags other than 0 / 1, rot90 on a non-square crop;
+ * HCF_ERR_SHAPE for a pair with H_gt < scale * H_lq or W_gt < scale * W_lq. A larger HR image is legal (the reference's
+ * mod-crop, GTLQx_dataset.py:118-120): its extra rows and columns are never read. The kernel clamps every source index into its
+ * image besides. */
+int hcf_data_prepare_paired(const uint8_t* gt_bank, size_t gt_bytes, const int64_t* gt_images,
+                            const uint8_t* lq_bank, size_t lq_bytes, const int64_t* lq_images, int32_t n_images,
+                            const int32_t* crops, int32_t B, int32_t lr_h, int32_t lr_w, int32_t scale, int32_t bgr,
+                            float* gt, float* lq, hcf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
