@@ -14,6 +14,7 @@
 //
 // Paired banks (hcf_data_prepare_paired: LRHR_PKL_dataset.py:96-135, GTLQnpy_dataset.py:42-78, GTLQx_dataset.py:82-122) keep the LQ
 // images as data beside the HR images: prepare_paired_kernel is the GT copy above for both halves, LQ at scale 1, no taps, no LDS.
+// Both entries share the host side: check_geometry, check_table, check_crops and launch_chunks.
 #include <math.h>
 #include "../../include/hcflow.h"
 #include "hcf_common.h"
@@ -214,16 +215,6 @@ __global__ __launch_bounds__(256) void prepare_paired_kernel(const PairArgs a) {
                 a.lr_w * S, sm.flags, a.bgr, a.gt + (size_t)blockIdx.y * 3 * a.lr_h * S * a.lr_w * S);
 }
 
-// {byte offset, H, W} rows of one bank's host table
-static int check_table(const int64_t* images, int n_images, size_t bank_bytes) {
-  for (int i = 0; i < n_images; ++i) {
-    const int64_t off = images[3 * i], H = images[3 * i + 1], W = images[3 * i + 2];
-    if (H < 1 || W < 1 || H > (1 << 24) || W > (1 << 24) || off < 0) return HCF_ERR_ARG;
-    if ((uint64_t)off > bank_bytes || (uint64_t)(3 * H * W) > bank_bytes - (uint64_t)off) return HCF_ERR_ARG;
-  }
-  return HCF_OK;
-}
-
 typedef void (*Kernel)(const Args);
 static Kernel kernel_of(int S) {
   switch (S) {
@@ -238,6 +229,65 @@ static Kernel kernel_of(int S) {
   return nullptr;
 }
 
+// ---- the host side of both entries. Every record is checked before any HIP call: the kernels read what these tables say ----
+static int check_geometry(int scale, int n_images, int B, int lr_h, int lr_w) {
+  if (scale < 2 || scale > 8 || n_images < 1 || B < 0 || lr_h < 1 || lr_w < 1) return HCF_ERR_ARG;
+  if (lr_h > (1 << 20) || lr_w > (1 << 20)) return HCF_ERR_ARG;
+  return HCF_OK;
+}
+
+// {byte offset, H, W} rows of one bank's host table; an image with a side below min_side is HCF_ERR_SHAPE
+static int check_table(const int64_t* images, int n_images, size_t bank_bytes, int min_side) {
+  for (int i = 0; i < n_images; ++i) {
+    const int64_t off = images[3 * i], H = images[3 * i + 1], W = images[3 * i + 2];
+    if (H < 1 || W < 1 || H > (1 << 24) || W > (1 << 24) || off < 0) return HCF_ERR_ARG;
+    if (H < min_side || W < min_side) return HCF_ERR_SHAPE;
+    if ((uint64_t)off > bank_bytes || (uint64_t)(3 * H * W) > bank_bytes - (uint64_t)off) return HCF_ERR_ARG;
+  }
+  return HCF_OK;
+}
+
+// {image, top, left, hflip, vflip, rot90} rows; a window of lr_h x lr_w crop pixels is (lr_h unit) x (lr_w unit) pixels of the
+// table that bounds it: unit = scale on the HR table of the single bank, 1 on the LQ table of the paired banks
+static int check_crops(const int32_t* crops, int B, const int64_t* images, int n_images, int lr_h, int lr_w, int unit) {
+  for (int b = 0; b < B; ++b) {
+    const int32_t* c = crops + 6 * b;
+    if (c[0] < 0 || c[0] >= n_images || c[1] < 0 || c[2] < 0) return HCF_ERR_ARG;
+    for (int f = 3; f < 6; ++f)
+      if (c[f] != 0 && c[f] != 1) return HCF_ERR_ARG;
+    if (c[5] && lr_h != lr_w) return HCF_ERR_ARG;
+    const int64_t H = images[3 * c[0] + 1], W = images[3 * c[0] + 2];
+    if (((int64_t)c[1] + lr_h) * unit > H || ((int64_t)c[2] + lr_w) * unit > W) return HCF_ERR_ARG;
+  }
+  return HCF_OK;
+}
+
+// The launches of one batch, at most HCF_DATA_LAUNCH_BATCH records each: `a` arrives with its banks (and taps) set, image(s, c)
+// fills record s with the table rows of crop row c.
+template <class A, class Image>
+static int launch_chunks(void (*kernel)(const A), A& a, const int32_t* crops, int B, int lr_h, int lr_w, int scale, int bgr,
+                         float* gt, float* lq, hcf_stream_t stream, Image image) {
+  if (B == 0) return HCF_OK;
+  a.lr_h = lr_h; a.lr_w = lr_w; a.bgr = bgr ? 1 : 0;
+  a.tiles_x = (lr_w + kTW - 1) / kTW;
+  const long long tiles = (long long)a.tiles_x * ((lr_h + kTH - 1) / kTH);
+  if (tiles > 0x7fffffffLL) return HCF_ERR_ARG;
+  const size_t lq_n = (size_t)3 * lr_h * lr_w, gt_n = lq_n * scale * scale;
+  for (int b0 = 0; b0 < B; b0 += HCF_DATA_LAUNCH_BATCH) {
+    const int nb = B - b0 < HCF_DATA_LAUNCH_BATCH ? B - b0 : HCF_DATA_LAUNCH_BATCH;
+    for (int i = 0; i < HCF_DATA_LAUNCH_BATCH; ++i) {
+      const int32_t* c = crops + 6 * (size_t)(b0 + (i < nb ? i : 0));      // unused slots repeat a valid record
+      image(a.s[i], c);
+      a.s[i].top = c[1]; a.s[i].left = c[2]; a.s[i].flags = c[3] | (c[4] << 1) | (c[5] << 2); a.s[i].pad = 0;
+    }
+    a.gt = gt ? gt + (size_t)b0 * gt_n : nullptr;
+    a.lq = lq ? lq + (size_t)b0 * lq_n : nullptr;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)tiles, (unsigned)nb), dim3(256), 0, (hipStream_t)stream, a);
+    if (hipGetLastError() != hipSuccess) return HCF_ERR_HIP;
+  }
+  return HCF_OK;
+}
+
 }  // namespace data
 }  // namespace hcf
 
@@ -247,100 +297,44 @@ int hcf_data_prepare_batch(const uint8_t* bank, size_t bank_bytes, const int64_t
                            int32_t B, int32_t lr_h, int32_t lr_w, int32_t scale, int32_t bgr, float* gt, float* lq,
                            hcf_stream_t stream) {
   using namespace hcf::data;
-  // ---- every record is checked here, before any HIP call: the kernel reads what these tables say ----
   if (!bank || !images || !crops || (!gt && !lq)) return HCF_ERR_ARG;
-  if (scale < 2 || scale > 8 || n_images < 1 || B < 0 || lr_h < 1 || lr_w < 1) return HCF_ERR_ARG;
-  if (lr_h > (1 << 20) || lr_w > (1 << 20)) return HCF_ERR_ARG;
-  for (int i = 0; i < n_images; ++i) {
-    const int64_t off = images[3 * i], H = images[3 * i + 1], W = images[3 * i + 2];
-    if (H < 1 || W < 1 || H > (1 << 24) || W > (1 << 24) || off < 0) return HCF_ERR_ARG;
-    if (H < 4 * scale || W < 4 * scale) return HCF_ERR_SHAPE;
-    if ((uint64_t)off > bank_bytes || (uint64_t)(3 * H * W) > bank_bytes - (uint64_t)off) return HCF_ERR_ARG;
-  }
-  for (int b = 0; b < B; ++b) {
-    const int32_t* c = crops + 6 * b;
-    if (c[0] < 0 || c[0] >= n_images || c[1] < 0 || c[2] < 0) return HCF_ERR_ARG;
-    for (int f = 3; f < 6; ++f)
-      if (c[f] != 0 && c[f] != 1) return HCF_ERR_ARG;
-    if (c[5] && lr_h != lr_w) return HCF_ERR_ARG;
-    const int64_t H = images[3 * c[0] + 1], W = images[3 * c[0] + 2];
-    if (((int64_t)c[1] + lr_h) * scale > H || ((int64_t)c[2] + lr_w) * scale > W) return HCF_ERR_ARG;
-  }
-  if (B == 0) return HCF_OK;
+  int rc = check_geometry(scale, n_images, B, lr_h, lr_w);
+  if (rc == HCF_OK) rc = check_table(images, n_images, bank_bytes, 4 * scale);      // below 4 * scale one reflection does not reach
+  if (rc == HCF_OK) rc = check_crops(crops, B, images, n_images, lr_h, lr_w, scale);
+  if (rc != HCF_OK) return rc;
 
   Args a;
   a.bank = bank;
-  a.lr_h = lr_h; a.lr_w = lr_w; a.bgr = bgr ? 1 : 0;
-  a.tiles_x = (lr_w + kTW - 1) / kTW;
-  const long long tiles = (long long)a.tiles_x * ((lr_h + kTH - 1) / kTH);
-  if (tiles > 0x7fffffffLL) return HCF_ERR_ARG;
   tap_weights(scale, a.w);
-  const Kernel k = kernel_of(scale);
-  const size_t lq_n = (size_t)3 * lr_h * lr_w, gt_n = lq_n * scale * scale;
-  for (int b0 = 0; b0 < B; b0 += HCF_DATA_LAUNCH_BATCH) {
-    const int nb = B - b0 < HCF_DATA_LAUNCH_BATCH ? B - b0 : HCF_DATA_LAUNCH_BATCH;
-    for (int i = 0; i < HCF_DATA_LAUNCH_BATCH; ++i) {
-      const int32_t* c = crops + 6 * (size_t)(b0 + (i < nb ? i : 0));      // unused slots repeat a valid record
-      Sample& s = a.s[i];
-      s.off = images[3 * c[0]]; s.H = (int)images[3 * c[0] + 1]; s.W = (int)images[3 * c[0] + 2];
-      s.top = c[1]; s.left = c[2]; s.flags = c[3] | (c[4] << 1) | (c[5] << 2); s.pad = 0;
-    }
-    a.gt = gt ? gt + (size_t)b0 * gt_n : nullptr;
-    a.lq = lq ? lq + (size_t)b0 * lq_n : nullptr;
-    hipLaunchKernelGGL(k, dim3((unsigned)tiles, (unsigned)nb), dim3(256), 0, (hipStream_t)stream, a);
-    if (hipGetLastError() != hipSuccess) return HCF_ERR_HIP;
-  }
-  return HCF_OK;
+  return launch_chunks(kernel_of(scale), a, crops, B, lr_h, lr_w, scale, bgr, gt, lq, stream, [&](Sample& s, const int32_t* c) {
+    s.off = images[3 * c[0]]; s.H = (int)images[3 * c[0] + 1]; s.W = (int)images[3 * c[0] + 2];
+  });
 }
 
 int hcf_data_prepare_paired(const uint8_t* gt_bank, size_t gt_bytes, const int64_t* gt_images, const uint8_t* lq_bank,
                             size_t lq_bytes, const int64_t* lq_images, int32_t n_images, const int32_t* crops, int32_t B,
                             int32_t lr_h, int32_t lr_w, int32_t scale, int32_t bgr, float* gt, float* lq, hcf_stream_t stream) {
   using namespace hcf::data;
-  // ---- every record is checked here, before any HIP call: the kernel reads what these tables say ----
   if (!gt_bank || !gt_images || !lq_bank || !lq_images || !crops || (!gt && !lq)) return HCF_ERR_ARG;
-  if (scale < 2 || scale > 8 || n_images < 1 || B < 0 || lr_h < 1 || lr_w < 1) return HCF_ERR_ARG;
-  if (lr_h > (1 << 20) || lr_w > (1 << 20)) return HCF_ERR_ARG;
-  if (check_table(gt_images, n_images, gt_bytes) != HCF_OK || check_table(lq_images, n_images, lq_bytes) != HCF_OK)
-    return HCF_ERR_ARG;
+  int rc = check_geometry(scale, n_images, B, lr_h, lr_w);
+  if (rc == HCF_OK) rc = check_table(gt_images, n_images, gt_bytes, 1);
+  if (rc == HCF_OK) rc = check_table(lq_images, n_images, lq_bytes, 1);
+  if (rc != HCF_OK) return rc;
   for (int i = 0; i < n_images; ++i)       // a larger HR image is the mod-crop case: its extra rows and columns are never read
     if (gt_images[3 * i + 1] < scale * lq_images[3 * i + 1] || gt_images[3 * i + 2] < scale * lq_images[3 * i + 2])
       return HCF_ERR_SHAPE;
-  for (int b = 0; b < B; ++b) {
-    const int32_t* c = crops + 6 * b;
-    if (c[0] < 0 || c[0] >= n_images || c[1] < 0 || c[2] < 0) return HCF_ERR_ARG;
-    for (int f = 3; f < 6; ++f)
-      if (c[f] != 0 && c[f] != 1) return HCF_ERR_ARG;
-    if (c[5] && lr_h != lr_w) return HCF_ERR_ARG;
-    const int64_t H = lq_images[3 * c[0] + 1], W = lq_images[3 * c[0] + 2];
-    if ((int64_t)c[1] + lr_h > H || (int64_t)c[2] + lr_w > W) return HCF_ERR_ARG;
-  }
-  if (B == 0) return HCF_OK;
+  rc = check_crops(crops, B, lq_images, n_images, lr_h, lr_w, 1);
+  if (rc != HCF_OK) return rc;
 
   PairArgs a;
-  a.gt_bank = gt_bank; a.lq_bank = lq_bank;
-  a.lr_h = lr_h; a.lr_w = lr_w; a.scale = scale; a.bgr = bgr ? 1 : 0; a.pad = 0;
-  a.tiles_x = (lr_w + kTW - 1) / kTW;
-  const long long tiles = (long long)a.tiles_x * ((lr_h + kTH - 1) / kTH);
-  if (tiles > 0x7fffffffLL) return HCF_ERR_ARG;
-  const size_t lq_n = (size_t)3 * lr_h * lr_w, gt_n = lq_n * scale * scale;
-  for (int b0 = 0; b0 < B; b0 += HCF_DATA_LAUNCH_BATCH) {
-    const int nb = B - b0 < HCF_DATA_LAUNCH_BATCH ? B - b0 : HCF_DATA_LAUNCH_BATCH;
-    for (int i = 0; i < HCF_DATA_LAUNCH_BATCH; ++i) {
-      const int32_t* c = crops + 6 * (size_t)(b0 + (i < nb ? i : 0));      // unused slots repeat a valid record
-      const int64_t* g = gt_images + 3 * c[0];
-      const int64_t* l = lq_images + 3 * c[0];
-      PairSample& s = a.s[i];
-      s.gt_off = g[0]; s.gt_h = (int)g[1]; s.gt_w = (int)g[2];
-      s.lq_off = l[0]; s.lq_h = (int)l[1]; s.lq_w = (int)l[2];
-      s.top = c[1]; s.left = c[2]; s.flags = c[3] | (c[4] << 1) | (c[5] << 2); s.pad = 0;
-    }
-    a.gt = gt ? gt + (size_t)b0 * gt_n : nullptr;
-    a.lq = lq ? lq + (size_t)b0 * lq_n : nullptr;
-    hipLaunchKernelGGL(prepare_paired_kernel, dim3((unsigned)tiles, (unsigned)nb), dim3(256), 0, (hipStream_t)stream, a);
-    if (hipGetLastError() != hipSuccess) return HCF_ERR_HIP;
-  }
-  return HCF_OK;
+  a.gt_bank = gt_bank; a.lq_bank = lq_bank; a.scale = scale; a.pad = 0;
+  return launch_chunks(prepare_paired_kernel, a, crops, B, lr_h, lr_w, scale, bgr, gt, lq, stream,
+                       [&](PairSample& s, const int32_t* c) {
+    const int64_t* g = gt_images + 3 * c[0];
+    const int64_t* l = lq_images + 3 * c[0];
+    s.gt_off = g[0]; s.gt_h = (int)g[1]; s.gt_w = (int)g[2];
+    s.lq_off = l[0]; s.lq_h = (int)l[1]; s.lq_w = (int)l[2];
+  });
 }
 
 }  // extern "C"

@@ -85,39 +85,68 @@ def _lr_size(gt_size: int, scale: int) -> int:
     return gt_size // scale
 
 
+def _bank_indices(bank, indices) -> torch.Tensor:
+    idx = torch.as_tensor(indices, dtype=torch.int64).reshape(-1)
+    if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= len(bank)):
+        raise ValueError("image index outside the bank")
+    return idx
+
+
+def _draw(idx: torch.Tensor, hw: torch.Tensor, n: int, rule: str, use_flip, use_rot, generator) -> torch.Tensor:
+    """The crop table of both banks: idx = validated image indices [B], hw = their (H, W) in LR pixels (each >= n, the caller's
+    check). One torch.rand(B, 5) per call: columns 0-1 the positions, 2-4 the three coins of "augment", or 2 = f and 3 = k of "pkl"
+    (draw_paired_crops states both rules)."""
+    room = hw - n                                                   # largest top / left
+    r = torch.rand(idx.numel(), 5, generator=generator, dtype=torch.float64)
+    pos = torch.minimum((r[:, :2] * (room + 1)).floor().to(torch.int64), room)
+    if rule == "augment":
+        flags = ((r[:, 2:] < 0.5) & torch.tensor([bool(use_flip), bool(use_rot), bool(use_rot)])).to(torch.int64)
+    else:
+        f = ((r[:, 2] < 0.5) & bool(use_flip)).to(torch.int64)
+        k = (r[:, 3] * 3).floor().to(torch.int64).clamp_(max=2) * int(bool(use_rot))      # 0, 1, 2 stand for k = 0, 1, 3
+        table = torch.tensor([PKL_FLAGS[(fi, ki)] for ki in (0, 1, 3) for fi in (0, 1)], dtype=torch.int64)
+        flags = table[k * 2 + f]
+    return torch.cat([idx[:, None], pos, flags], dim=1).to(torch.int32).contiguous()
+
+
 def draw_crops(bank: ImageBank, indices, gt_size: int, scale: int, use_flip: bool = True, use_rot: bool = True,
                generator: Optional[torch.Generator] = None) -> torch.Tensor:
     """CPU int32 [B, 6] = (image, top_lr, left_lr, hflip, vflip, rot90) as GT_dataset.__getitem__ and augment draw them:
     top_lr uniform in [0, H // scale - lr_size], left_lr likewise, hflip = use_flip and p < 1/2, vflip and rot90 = use_rot and
     p < 1/2 each. Deterministic under `generator`."""
     n = _lr_size(gt_size, scale)
-    idx = torch.as_tensor(indices, dtype=torch.int64).reshape(-1)
-    if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= len(bank)):
-        raise ValueError("image index outside the bank")
-    hw = bank.table[idx, 1:3] // scale - n                       # largest top / left
-    if idx.numel() and int(hw.min()) < 0:
+    idx = _bank_indices(bank, indices)
+    hw = bank.table[idx, 1:3] // scale
+    if idx.numel() and int(hw.min()) < n:
         raise ValueError("an image is smaller than the %d x %d crop" % (gt_size, gt_size))
-    r = torch.rand(idx.numel(), 5, generator=generator, dtype=torch.float64)
-    pos = torch.minimum((r[:, :2] * (hw + 1)).floor().to(torch.int64), hw)
-    gate = torch.tensor([bool(use_flip), bool(use_rot), bool(use_rot)])
-    flags = (r[:, 2:] < 0.5) & gate
-    return torch.cat([idx[:, None], pos, flags.to(torch.int64)], dim=1).to(torch.int32).contiguous()
+    return _draw(idx, hw, n, "augment", use_flip, use_rot, generator)
+
+
+def _device(bank):
+    """The bank's GPU; the one place that refuses a bank that is not on one."""
+    dev = bank.device
+    if dev.type != "cuda":
+        raise _lib.HcfError("hcflow_amd.data has no CPU path: the bank lives on %s" % dev)
+    return dev
 
 
 def _launch(bank: ImageBank, crops: torch.Tensor, lr_h: int, lr_w: int, scale: int, gt: torch.Tensor, lq: torch.Tensor):
-    dev = bank.data.device
-    if dev.type != "cuda":
-        raise _lib.HcfError("hcflow_amd.data has no CPU path: the bank lives on %s" % dev)
-    _lib.launch("hcf_data_prepare_batch", dev, bank.data, bank.nbytes, bank.table, len(bank), crops, int(crops.shape[0]), lr_h, lr_w,
-                int(scale), int(bank.bgr), gt, lq)
+    _lib.launch("hcf_data_prepare_batch", _device(bank), bank.data, bank.nbytes, bank.table, len(bank), crops, int(crops.shape[0]),
+                lr_h, lr_w, int(scale), int(bank.bgr), gt, lq)
 
 
-def _outputs(bank, out, B, gh, gw, lh, lw) -> Dict[str, torch.Tensor]:
-    shapes = {"GT": (B, 3, gh, gw), "LQ": (B, 3, lh, lw)}
+def _outputs(bank, out, B, lh, lw, scale, partial=False) -> Dict[str, Optional[torch.Tensor]]:
+    """out=None: both tensors, new. Otherwise the caller's dict, checked; with `partial` (the paired calls) one of its two entries
+    may be None (that half is not made)."""
+    shapes = {"GT": (B, 3, lh * scale, lw * scale), "LQ": (B, 3, lh, lw)}
     if out is None:
         return {k: torch.empty(s, dtype=torch.float32, device=bank.device) for k, s in shapes.items()}
+    if partial and out.get("GT") is None and out.get("LQ") is None:
+        raise ValueError("out: need at least one of 'GT' and 'LQ'")
     for k, s in shapes.items():
-        t = out[k]
+        t = out.get(k) if partial else out[k]
+        if partial and t is None:
+            continue
         if tuple(t.shape) != s or t.dtype != torch.float32 or t.device != bank.device or not t.is_contiguous():
             raise ValueError("out[%r]: need a contiguous float32 %s on %s" % (k, s, bank.device))
     return out
@@ -134,7 +163,7 @@ def prepare_crops(bank: ImageBank, crops, lr_h: int, lr_w: int, scale: int, out:
     """prepare_batch for rectangular crops of lr_h x lr_w LR pixels (rot90 rows need lr_h == lr_w)."""
     _lr_size(scale, scale)
     c = _crop_table(crops)
-    o = _outputs(bank, out, int(c.shape[0]), lr_h * scale, lr_w * scale, lr_h, lr_w)
+    o = _outputs(bank, out, int(c.shape[0]), lr_h, lr_w, scale)
     _launch(bank, c, int(lr_h), int(lr_w), scale, o["GT"], o["LQ"])
     return o
 
@@ -156,9 +185,19 @@ def whole_image(bank: ImageBank, index: int, scale: int, out: Optional[Dict[str,
     if H % scale or W % scale:
         raise ValueError("image %d is %d x %d: not a multiple of scale %d" % (index, H, W, scale))
     c = torch.tensor([[int(index), 0, 0, 0, 0, 0]], dtype=torch.int32)
-    o = _outputs(bank, out, 1, H, W, H // scale, W // scale)
+    o = _outputs(bank, out, 1, H // scale, W // scale, scale)
     _launch(bank, c, H // scale, W // scale, scale, o["GT"], o["LQ"])
     return o
+
+
+def _epoch(loader, order, lq_paths, batch):
+    """The batch loop of both loaders: slices of the epoch's index order, the last partial batch dropped; batch(idx) draws the
+    crops of one slice and prepares them."""
+    for i in range(len(loader)):
+        idx = order[i * loader.batch_size:(i + 1) * loader.batch_size]
+        o = batch(idx)
+        yield {"LQ": o["LQ"], "GT": o["GT"], "LQ_path": [lq_paths[int(j)] for j in idx],
+               "GT_path": [loader.bank.paths[int(j)] for j in idx]}
 
 
 class BankLoader:
@@ -173,19 +212,16 @@ class BankLoader:
             raise ValueError("batch_size %d for a bank of %d images" % (batch_size, len(bank)))
         self.bank, self.batch_size, self.gt_size, self.scale = bank, int(batch_size), int(gt_size), int(scale)
         self.use_flip, self.use_rot, self.generator = use_flip, use_rot, generator
-        self._out = _outputs(bank, None, self.batch_size, gt_size, gt_size, gt_size // scale, gt_size // scale) if reuse_out else None
+        self._out = _outputs(bank, None, self.batch_size, gt_size // scale, gt_size // scale, scale) if reuse_out else None
 
     def __len__(self) -> int:
         return len(self.bank) // self.batch_size
 
     def __iter__(self):
-        perm = torch.randperm(len(self.bank), generator=self.generator)
-        for i in range(len(self)):
-            idx = perm[i * self.batch_size:(i + 1) * self.batch_size]
-            crops = draw_crops(self.bank, idx, self.gt_size, self.scale, self.use_flip, self.use_rot, self.generator)
-            o = prepare_batch(self.bank, crops, self.gt_size, self.scale, out=self._out)
-            paths = [self.bank.paths[int(j)] for j in idx]
-            yield {"LQ": o["LQ"], "GT": o["GT"], "LQ_path": paths, "GT_path": paths}
+        perm = torch.randperm(len(self.bank), generator=self.generator)         # from the same generator, before the crops
+        yield from _epoch(self, perm, self.bank.paths, lambda idx: prepare_batch(
+            self.bank, draw_crops(self.bank, idx, self.gt_size, self.scale, self.use_flip, self.use_rot, self.generator),
+            self.gt_size, self.scale, out=self._out))
 
 
 # ---- paired banks: LRHR_PKL and GTLQ / GTLQnpy / GTLQx, the LQ image is data ----
@@ -252,13 +288,6 @@ class PairedBank:
         return self.lq.shape(index)
 
 
-def _bank_indices(bank, indices) -> torch.Tensor:
-    idx = torch.as_tensor(indices, dtype=torch.int64).reshape(-1)
-    if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= len(bank)):
-        raise ValueError("image index outside the bank")
-    return idx
-
-
 def draw_paired_crops(bank: PairedBank, indices, gt_size: int, rule: str, use_flip: bool = True, use_rot: bool = True,
                       generator: Optional[torch.Generator] = None) -> torch.Tensor:
     """CPU int32 [B, 6] = (image, top_lr, left_lr, hflip, vflip, rot90): top_lr uniform in [0, H_lq - n], left_lr likewise,
@@ -271,19 +300,10 @@ def draw_paired_crops(bank: PairedBank, indices, gt_size: int, rule: str, use_fl
         raise ValueError("rule must be 'augment' or 'pkl', got %r" % (rule,))
     n = _lr_size(gt_size, bank.scale)
     idx = _bank_indices(bank, indices)
-    hw = bank.lq.table[idx, 1:3] - n                                # largest top / left
-    if idx.numel() and int(hw.min()) < 0:
+    hw = bank.lq.table[idx, 1:3]
+    if idx.numel() and int(hw.min()) < n:
         raise ValueError("an LQ image is smaller than the %d x %d crop" % (n, n))
-    r = torch.rand(idx.numel(), 5, generator=generator, dtype=torch.float64)
-    pos = torch.minimum((r[:, :2] * (hw + 1)).floor().to(torch.int64), hw)
-    if rule == "augment":
-        flags = ((r[:, 2:] < 0.5) & torch.tensor([bool(use_flip), bool(use_rot), bool(use_rot)])).to(torch.int64)
-    else:
-        f = ((r[:, 2] < 0.5) & bool(use_flip)).to(torch.int64)
-        k = (r[:, 3] * 3).floor().to(torch.int64).clamp_(max=2) * int(bool(use_rot))      # 0, 1, 2 stand for k = 0, 1, 3
-        table = torch.tensor([PKL_FLAGS[(fi, ki)] for ki in (0, 1, 3) for fi in (0, 1)], dtype=torch.int64)
-        flags = table[k * 2 + f]
-    return torch.cat([idx[:, None], pos, flags], dim=1).to(torch.int32).contiguous()
+    return _draw(idx, hw, n, rule, use_flip, use_rot, generator)
 
 
 def center_crops(bank: PairedBank, indices, hr_size: int) -> torch.Tensor:
@@ -307,29 +327,11 @@ def center_crops(bank: PairedBank, indices, hr_size: int) -> torch.Tensor:
     return torch.tensor(rows, dtype=torch.int32).reshape(-1, 6)
 
 
-def _paired_outputs(bank: PairedBank, out, B, lh, lw) -> Dict[str, Optional[torch.Tensor]]:
-    """out=None: both tensors, new. Otherwise the caller's dict; one of its two entries may be None (that half is not made)."""
-    s = bank.scale
-    shapes = {"GT": (B, 3, lh * s, lw * s), "LQ": (B, 3, lh, lw)}
-    if out is None:
-        return {k: torch.empty(v, dtype=torch.float32, device=bank.device) for k, v in shapes.items()}
-    if out.get("GT") is None and out.get("LQ") is None:
-        raise ValueError("out: need at least one of 'GT' and 'LQ'")
-    for k, v in shapes.items():
-        t = out.get(k)
-        if t is not None and (tuple(t.shape) != v or t.dtype != torch.float32 or t.device != bank.device or not t.is_contiguous()):
-            raise ValueError("out[%r]: need a contiguous float32 %s on %s" % (k, v, bank.device))
-    return out
-
-
 def prepare_paired_crops(bank: PairedBank, crops, lr_h: int, lr_w: int, out: Optional[Dict[str, torch.Tensor]] = None):
     """prepare_paired_batch for rectangular crops of lr_h x lr_w LQ pixels (rot90 rows need lr_h == lr_w)."""
     c = _crop_table(crops)
-    o = _paired_outputs(bank, out, int(c.shape[0]), int(lr_h), int(lr_w))
-    dev = bank.device
-    if dev.type != "cuda":
-        raise _lib.HcfError("hcflow_amd.data has no CPU path: the bank lives on %s" % dev)
-    _lib.launch("hcf_data_prepare_paired", dev, bank.gt.data, bank.gt.nbytes, bank.gt.table, bank.lq.data, bank.lq.nbytes,
+    o = _outputs(bank, out, int(c.shape[0]), int(lr_h), int(lr_w), bank.scale, partial=True)
+    _lib.launch("hcf_data_prepare_paired", _device(bank), bank.gt.data, bank.gt.nbytes, bank.gt.table, bank.lq.data, bank.lq.nbytes,
                 bank.lq.table, len(bank), c, int(c.shape[0]), int(lr_h), int(lr_w), bank.scale, int(bank.bgr), o.get("GT"),
                 o.get("LQ"))
     return o
@@ -372,7 +374,7 @@ class PairedBankLoader:
         self.bank, self.batch_size, self.gt_size, self.rule = bank, int(batch_size), int(gt_size), rule
         self.use_flip, self.use_rot, self.generator = use_flip, use_rot, generator
         self.rank, self.world, self.seed, self.epoch = int(rank), int(world), int(seed), 0
-        self._out = _paired_outputs(bank, None, self.batch_size, n, n) if reuse_out else None
+        self._out = _outputs(bank, None, self.batch_size, n, n, bank.scale) if reuse_out else None
 
     def set_epoch(self, epoch: int):
         self.epoch = int(epoch)
@@ -386,10 +388,6 @@ class PairedBankLoader:
         return len(self.bank) // self.world // self.batch_size
 
     def __iter__(self):
-        mine = self.shard()
-        for i in range(len(self)):
-            idx = mine[i * self.batch_size:(i + 1) * self.batch_size]
-            crops = draw_paired_crops(self.bank, idx, self.gt_size, self.rule, self.use_flip, self.use_rot, self.generator)
-            o = prepare_paired_batch(self.bank, crops, self.gt_size, out=self._out)
-            yield {"LQ": o["LQ"], "GT": o["GT"], "LQ_path": [self.bank.lq_paths[int(j)] for j in idx],
-                   "GT_path": [self.bank.paths[int(j)] for j in idx]}
+        yield from _epoch(self, self.shard(), self.bank.lq_paths, lambda idx: prepare_paired_batch(
+            self.bank, draw_paired_crops(self.bank, idx, self.gt_size, self.rule, self.use_flip, self.use_rot, self.generator),
+            self.gt_size, out=self._out))

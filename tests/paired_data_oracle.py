@@ -8,6 +8,8 @@ exact in every mode -- float32(double(u) / 255.0) (PKL: float64 divide, then tor
 """
 import numpy as np
 
+from tests.data_oracle import augment, to_chw      # the kernel's index map (data/util.py:122-129) and HWC -> CHW RGB, on HWC
+
 # (f, k) of the PKL mode -- np.flip(axis=2) when f, then np.rot90(k, axes=(1, 2)) on CHW -- as (hflip, vflip, rot90)
 PKL_FLAGS = {(0, 0): (0, 0, 0), (1, 0): (1, 0, 0), (0, 1): (1, 0, 1), (1, 1): (0, 0, 1), (0, 3): (0, 1, 1), (1, 3): (1, 1, 1)}
 
@@ -17,17 +19,6 @@ MODE_PKL_TRAIN, MODE_PKL_CENTER, MODE_GTLQ_TRAIN, MODE_GTLQ_WHOLE = 0, 1, 2, 3
 def conversions_agree():
     u = np.arange(256, dtype=np.uint8)
     return np.array_equal((u / 255.0).astype(np.float32), u.astype(np.float32) / np.float32(255.))
-
-
-def augment(img, hflip, vflip, rot90):
-    """HWC; the kernel's index map, data/util.py:122-129."""
-    if hflip:
-        img = img[:, ::-1, :]
-    if vflip:
-        img = img[::-1, :, :]
-    if rot90:
-        img = img.transpose(1, 0, 2)
-    return img
 
 
 def pkl_augment(img_chw, f, k):
@@ -41,10 +32,7 @@ def window(img_u8, top, left, h, w, hflip=0, vflip=0, rot90=0, bgr=True):
     """float32 CHW RGB of one window of an HWC uint8 image."""
     crop = img_u8[top:top + h, left:left + w, :]
     assert crop.shape[:2] == (h, w), "crop outside the image"
-    crop = augment(crop, hflip, vflip, rot90)
-    if bgr:
-        crop = crop[:, :, ::-1]
-    return np.ascontiguousarray(np.transpose(crop, (2, 0, 1))).astype(np.float32) / np.float32(255.)
+    return to_chw(augment(crop, hflip, vflip, rot90), bgr).astype(np.float32) / np.float32(255.)
 
 
 def sample(gt_u8, lq_u8, scale, top_lr, left_lr, lr_h, lr_w, hflip=0, vflip=0, rot90=0, bgr=True):

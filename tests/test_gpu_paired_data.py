@@ -85,6 +85,35 @@ def test_tile_crossing_crops_against_the_oracle(scale):
             assert np.array_equal(lq[j], want_lq), ("LQ", h, w, r)
 
 
+@pytest.mark.parametrize("scale", [2, 3, 4, 8])
+def test_both_entries_copy_the_same_window(scale):
+    """The GT of hcf_data_prepare_batch and of hcf_data_prepare_paired is the same copy, stated in prepare_batch_kernel with 8 rows
+    in flight and as copy_window with 16: on the same HR images and crop rows both are the same bytes / 255.f through the same
+    index map, so torch.equal.
+    Two pairs, LQ 10 x 35 and HR exactly scale times that, the HR images as an ImageBank too; every origin of a 9 x 33 crop (over
+    the 8-row and the 32-column tile edge) with both flips on and off, the same rows as one batch of 65 (the second launch of the
+    chunk loop), every origin of a 6 x 6 crop under each of the eight flag triples. The paired LQ is the oracle's window."""
+    rs = np.random.RandomState(50 + scale)
+    H, W = 10, 35
+    order = "bgr" if scale in (2, 4) else "rgb"
+    lqs = [rs.randint(0, 256, size=(H, W, 3)).astype(np.uint8) for _ in range(2)]
+    gts = [rs.randint(0, 256, size=(H * scale, W * scale, 3)).astype(np.uint8) for _ in range(2)]
+    pairs, single = D.PairedBank(gts, lqs, DEV, order=order), D.ImageBank(gts, DEV, order=order)
+    wide = [[(t + l) % 2, t, l, hf, vf, 0] for t in range(H - 9 + 1) for l in range(W - 33 + 1) for vf in (0, 1) for hf in (0, 1)]
+    batches = [(9, 33, wide), (9, 33, (wide * 3)[:_lib.DATA_LAUNCH_BATCH + 1])]
+    batches += [(6, 6, [[(t + l) % 2, t, l, hf, vf, rot] for t in range(H - 6 + 1) for l in range(W - 6 + 1)])
+                for rot in (0, 1) for vf in (0, 1) for hf in (0, 1)]
+    assert len(wide) == 24 and len(batches[1][2]) == 65 and len(batches) == 10 and len(batches[2][2]) == 150
+    for h, w, rows in batches:
+        one = D.prepare_crops(single, rows, h, w, scale)
+        two = D.prepare_paired_crops(pairs, rows, h, w)
+        assert tuple(two["GT"].shape) == (len(rows), 3, h * scale, w * scale)
+        assert torch.equal(one["GT"], two["GT"]), (h, w, rows[0][3:])
+        lq = two["LQ"].cpu().numpy()
+        for j, r in enumerate(rows):
+            assert np.array_equal(lq[j], O.window(lqs[r[0]], r[1], r[2], h, w, r[3], r[4], r[5], bgr=order == "bgr")), (h, w, r)
+
+
 @pytest.fixture(scope="module")
 def small_bank():
     rs = np.random.RandomState(41)
