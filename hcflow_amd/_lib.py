@@ -39,6 +39,7 @@ SYMBOLS = [
     "hcf_debug_range_probe", "hcf_debug_range_probe_read", "hcf_debug_conv_plan",
     "hcf_aux_conv2d_workspace", "hcf_aux_conv2d", "hcf_aux_conv2d_backward", "hcf_adam_step",
     "hcf_lpips_workspace", "hcf_lpips_alex", "hcf_lpips_backward_workspace", "hcf_lpips_alex_backward",
+    "hcf_lpips_embed_bytes", "hcf_lpips_alex_embed", "hcf_lpips_map_workspace", "hcf_lpips_alex_map",
     "hcf_aux_bn_act_workspace", "hcf_aux_bn_act", "hcf_aux_bn_act_backward",
     "hcf_op_step_forward_backward", "hcf_op_step_inverse_backward", "hcf_op_prior_backward", "hcf_op_quant_logp_backward",
     "hcf_op_output_grad_backward", "hcf_op_conv_epilogue_backward", "hcf_op_lu_chain",
@@ -151,6 +152,13 @@ def load() -> C.CDLL:
     lib.hcf_lpips_backward_workspace.argtypes = [i32, i32, i32, i32]
     lib.hcf_lpips_backward_workspace.restype = C.c_size_t
     lib.hcf_lpips_alex_backward.argtypes = [i32, i32, i32, i32, C.POINTER(fp), fp, i32, fp, fp, vp, C.c_size_t, vp, C.c_size_t, vp]
+    lib.hcf_lpips_embed_bytes.argtypes = [i32, i32, i32]
+    lib.hcf_lpips_embed_bytes.restype = C.c_size_t
+    lib.hcf_lpips_alex_embed.argtypes = [fp, i32, i32, i32, i32, C.POINTER(fp), vp, C.c_size_t, vp]
+    lib.hcf_lpips_map_workspace.argtypes = [i32, i32, i32]
+    lib.hcf_lpips_map_workspace.restype = C.c_size_t
+    lib.hcf_lpips_alex_map.argtypes = [vp, C.c_size_t, fp, i32, i32, i32, i32, C.POINTER(fp), fp, fp, fp, fp, fp, fp, i32, vp,
+                                       C.c_size_t, vp]
     lib.hcf_debug_range_probe.argtypes = [vp, i32]
     lib.hcf_debug_range_probe_read.argtypes = [vp, i32, C.c_char_p, i32, C.POINTER(f32), C.POINTER(i32)]
     lib.hcf_debug_conv_plan.argtypes = [C.POINTER(i32), i32, C.POINTER(i64), i32]
@@ -198,7 +206,7 @@ def load() -> C.CDLL:
         fn = getattr(lib, name)
         if name not in ("hcf_destroy", "hcf_last_error", "hcf_workspace_bytes", "hcf_weight_bytes",
                         "hcf_fallback_count", "hcf_debug_last_clock_mhz", "hcf_aux_conv2d_workspace", "hcf_lpips_workspace",
-                        "hcf_lpips_backward_workspace",
+                        "hcf_lpips_backward_workspace", "hcf_lpips_embed_bytes", "hcf_lpips_map_workspace",
                         "hcf_aux_bn_act_workspace", "hcf_aux_feature_loss_workspace"):
             fn.restype = C.c_int
     _lib = lib

@@ -14,6 +14,9 @@
 // Every reduction has a fixed order that depends only on (H, W): results are bit-reproducible and per image independent of B.
 // The call leaves the s2d input and every feature map in its workspace; hcf_lpips_alex_backward (below) walks back down from
 // there to the image gradients (hcflow_amd/lpips.py: LPIPSLoss).
+// hcf_lpips_alex_embed / hcf_lpips_alex_map (hcflow_amd/lpips.py: LPIPSMap) run the same walk over ONE input of B images, the head
+// against a stored reference (the same per-pixel function: bit-equal values), and one fused kernel for the per-pixel map
+// D = sum_l bilinear_up(d_l), the per-pixel best over a sample set and their means.
 #include <algorithm>
 #include <cstring>
 
@@ -36,9 +39,10 @@ struct LpipsPlan {
   size_t o_s2d, o_f1, o_p1, o_f2, o_p2, o_f3, o_f4, o_f5, o_pk, o_bias, o_scale, o_part, o_aux, aux_bytes, total;
 };
 
-static bool lpips_plan(int B, int H, int W, LpipsPlan& p) {
+// The slabs hold Nimg images: 2B for the metric (in0 and in1 stacked), B for one embedded input (hcf_lpips_alex_embed / _map).
+static bool lpips_plan_n(int B, int Nimg, int H, int W, LpipsPlan& p) {
   memset(&p, 0, sizeof(p));
-  if (B < 1 || H < 31 || W < 31 || H >= 32768 || W >= 32768) return false;
+  if (B < 1 || Nimg < B || H < 31 || W < 31 || H >= 32768 || W >= 32768) return false;
   p.Hs = (H + 3) / 4; p.Ws = (W + 3) / 4;
   p.H1 = (H - 7) / 4 + 1; p.W1 = (W - 7) / 4 + 1;            // conv1: floor((H + 4 - 11) / 4) + 1
   p.H2 = (p.H1 - 3) / 2 + 1; p.W2 = (p.W1 - 3) / 2 + 1;
@@ -51,7 +55,7 @@ static bool lpips_plan(int B, int H, int W, LpipsPlan& p) {
     c0 += p.nchunk[l];
   }
   p.nchunk_total = c0;
-  const size_t N = 2 * (size_t)B, f = sizeof(float);
+  const size_t N = (size_t)Nimg, f = sizeof(float);
   const size_t gs = N * p.Hs * p.Ws, g2 = N * p.H2 * p.W2, g3 = N * p.H3 * p.W3;
   size_t o = 256;                                              // [0, 256): unused header
   auto take = [&](size_t bytes) { const size_t r = o; o += lp_al256(bytes); return r; };
@@ -77,13 +81,15 @@ static bool lpips_plan(int B, int H, int W, LpipsPlan& p) {
   return aux > 0;
 }
 
-// ---- prep: one thread per (image n of 2B, s2d pixel, 4-channel unit q = c * 4 + a) -> 4 input columns 4X .. 4X+3 of row 4Y+a
+static bool lpips_plan(int B, int H, int W, LpipsPlan& p) { return lpips_plan_n(B, 2 * B, H, W, p); }
+
+// ---- prep: one thread per (image n of N = 2B, or of N = B with in0 alone, s2d pixel, 4-channel unit q = c * 4 + a) -> 4 input columns 4X .. 4X+3 of row 4Y+a
 __global__ __launch_bounds__(256) void lpips_prep_kernel(const float* __restrict__ in0, const float* __restrict__ in1, int B,
-                                                         int H, int W, int Hs, int Ws, int normalize,
+                                                         int N, int H, int W, int Hs, int Ws, int normalize,
                                                          const float* __restrict__ shift, const float* __restrict__ scale,
                                                          float* __restrict__ out) {
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  const long long total = 2LL * B * Hs * Ws * 12;
+  const long long total = (long long)N * Hs * Ws * 12;
   if (i >= total) return;
   const int q = (int)(i % 12);
   const long long pix = i / 12;
@@ -152,6 +158,50 @@ __device__ __forceinline__ float group16_sum(float v) {      // butterfly over t
   return v;
 }
 
+// One pixel's layer value d = sum_c w_c (f0_c / (sqrt n0 + 1e-10) - f1_c / (sqrt n1 + 1e-10))^2 by the 16 lanes of a group (lane j
+// over the float4 channel units j + 16 i, i < ni = C / 64); f0, f1: the pixel's C channels in the two feature maps. Every lane of
+// the group returns the sum. The two head kernels share it: their values agree bit for bit.
+__device__ __forceinline__ float lpips_pixel_term(const float* __restrict__ f0, const float* __restrict__ f1,
+                                                  const float* __restrict__ lin, int ni, int j) {
+  const float eps = 1e-10f;
+  f32x4 v0[6], v1[6];
+  float n0 = 0.f, n1 = 0.f;
+#pragma unroll
+  for (int i = 0; i < 6; ++i) {
+    if (i < ni) {
+      v0[i] = *reinterpret_cast<const f32x4*>(f0 + 4 * (j + 16 * i));
+      v1[i] = *reinterpret_cast<const f32x4*>(f1 + 4 * (j + 16 * i));
+      n0 += v0[i].x * v0[i].x + v0[i].y * v0[i].y + v0[i].z * v0[i].z + v0[i].w * v0[i].w;
+      n1 += v1[i].x * v1[i].x + v1[i].y * v1[i].y + v1[i].z * v1[i].z + v1[i].w * v1[i].w;
+    }
+  }
+  n0 = __shfl(group16_sum(n0), 0, 16);
+  n1 = __shfl(group16_sum(n1), 0, 16);
+  const float d0 = sqrtf(n0) + eps, d1 = sqrtf(n1) + eps;
+  float t = 0.f;
+#pragma unroll
+  for (int i = 0; i < 6; ++i) {
+    if (i < ni) {
+      const float* w = lin + 4 * (j + 16 * i);                  // (any alignment: four scalar loads)
+      const float ex = v0[i].x / d0 - v1[i].x / d1, ey = v0[i].y / d0 - v1[i].y / d1;
+      const float ez = v0[i].z / d0 - v1[i].z / d1, ew = v0[i].w / d0 - v1[i].w / d1;
+      t += w[0] * ex * ex + w[1] * ey * ey + w[2] * ez * ez + w[3] * ew * ew;
+    }
+  }
+  return group16_sum(t);
+}
+
+// the 16 group sums of a head block, added in group order by thread 0
+__device__ __forceinline__ void lpips_head_block_sum(float s, int g, int j, float* gsum, float* dst) {
+  if (j == 0) gsum[g] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float t = 0.f;
+    for (int k = 0; k < 16; ++k) t += gsum[k];
+    *dst = t;
+  }
+}
+
 // grid (nchunk_total, B), 256 threads: 16 groups x 16 lanes, one pixel per group at a time, lanes over float4 channel units
 __global__ __launch_bounds__(256) void lpips_head_kernel(const LpipsHeadArgs a) {
   __shared__ float gsum[16];
@@ -162,7 +212,6 @@ __global__ __launch_bounds__(256) void lpips_head_kernel(const LpipsHeadArgs a) 
   const LpipsLayer L = a.L[l];
   const int g = threadIdx.x >> 4, j = threadIdx.x & 15;
   const int hw = L.h * L.w, C = L.C, ni = C >> 6;              // C / 4 float4 units over 16 lanes: 1 .. 6 each
-  const float eps = 1e-10f;
   float s = 0.f;
   for (int k = 0; k < kHeadPix / 16; ++k) {
     const int p = (blk - L.chunk0) * kHeadPix + k * 16 + g;
@@ -170,38 +219,194 @@ __global__ __launch_bounds__(256) void lpips_head_kernel(const LpipsHeadArgs a) 
     const int y = p / L.w, x = p - y * L.w;
     const float* f0 = L.f + (((size_t)b * L.Hst + y) * L.Wst + x) * C;
     const float* f1 = L.f + (((size_t)(a.B + b) * L.Hst + y) * L.Wst + x) * C;
-    f32x4 v0[6], v1[6];
-    float n0 = 0.f, n1 = 0.f;
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-      if (i < ni) {
-        v0[i] = *reinterpret_cast<const f32x4*>(f0 + 4 * (j + 16 * i));
-        v1[i] = *reinterpret_cast<const f32x4*>(f1 + 4 * (j + 16 * i));
-        n0 += v0[i].x * v0[i].x + v0[i].y * v0[i].y + v0[i].z * v0[i].z + v0[i].w * v0[i].w;
-        n1 += v1[i].x * v1[i].x + v1[i].y * v1[i].y + v1[i].z * v1[i].z + v1[i].w * v1[i].w;
-      }
-    }
-    n0 = __shfl(group16_sum(n0), 0, 16);
-    n1 = __shfl(group16_sum(n1), 0, 16);
-    const float d0 = sqrtf(n0) + eps, d1 = sqrtf(n1) + eps;
-    float t = 0.f;
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-      if (i < ni) {
-        const float* w = L.lin + 4 * (j + 16 * i);                // (any alignment: four scalar loads)
-        const float ex = v0[i].x / d0 - v1[i].x / d1, ey = v0[i].y / d0 - v1[i].y / d1;
-        const float ez = v0[i].z / d0 - v1[i].z / d1, ew = v0[i].w / d0 - v1[i].w / d1;
-        t += w[0] * ex * ex + w[1] * ey * ey + w[2] * ez * ez + w[3] * ew * ew;
-      }
-    }
-    s += group16_sum(t);                                        // lane 0's value is the one kept
+    s += lpips_pixel_term(f0, f1, L.lin, ni, j);                // lane 0's value is the one kept
   }
-  if (j == 0) gsum[g] = s;
+  lpips_head_block_sum(s, g, j, gsum, a.part + (size_t)b * a.nchunk_total + blk);
+}
+
+// ---- head over two feature bases (hcf_lpips_alex_map): image b of the reference store against image b of the sample's maps, both
+// slabs of B images. The grid, the lane layout and the partials of lpips_head_kernel; each pixel's d_l also goes to the layer-map
+// buffer dl [B][dl_total] (layer l's h_l x w_l grid, row-major, from dl0[l] on), which the map kernel upsamples.
+struct LpipsHead2Args {
+  LpipsLayer L[kLpipsLayers];          // f: the sample's maps
+  const float* fr[kLpipsLayers];       // the reference's maps, the same layout
+  int dl0[kLpipsLayers], dl_total, nchunk_total;
+  float* dl;
+  float* part;                         // [B][nchunk_total]
+};
+
+__global__ __launch_bounds__(256) void lpips_head2_kernel(const LpipsHead2Args a) {
+  __shared__ float gsum[16];
+  const int b = blockIdx.y, blk = blockIdx.x;
+  int l = 0;
+#pragma unroll
+  for (int k = 1; k < kLpipsLayers; ++k) l = (blk >= a.L[k].chunk0) ? k : l;
+  const LpipsLayer L = a.L[l];
+  const float* const fr = a.fr[l];
+  float* const dl = a.dl + (size_t)b * a.dl_total + a.dl0[l];
+  const int g = threadIdx.x >> 4, j = threadIdx.x & 15;
+  const int hw = L.h * L.w, C = L.C, ni = C >> 6;
+  float s = 0.f;
+  for (int k = 0; k < kHeadPix / 16; ++k) {
+    const int p = (blk - L.chunk0) * kHeadPix + k * 16 + g;
+    if (p >= hw) break;                                         // (uniform over the group)
+    const int y = p / L.w, x = p - y * L.w;
+    const size_t o = (((size_t)b * L.Hst + y) * L.Wst + x) * C;
+    const float d = lpips_pixel_term(fr + o, L.f + o, L.lin, ni, j);
+    if (j == 0) dl[p] = d;
+    s += d;
+  }
+  lpips_head_block_sum(s, g, j, gsum, a.part + (size_t)b * a.nchunk_total + blk);
+}
+
+// ---- the spatial map: D[b, y, x] = sum over l = 0..4, in that order, of the bilinear upsampling (align_corners = False) of d_l to
+// H x W. Source row of output row y on an h-row grid: sy = max(0, (y + 0.5) h / H - 0.5) = max(0, ((2y + 1) h - H) / (2H)),
+// i0 = floor(sy), i1 = min(i0 + 1, h - 1), weight sy - i0 -- taken from the integer quotient and remainder, so the weight carries
+// one rounding. Columns alike. A thread owns 4 consecutive columns of one row: w_l <= W / 4, so they read at most 3 source columns.
+// The divisors 2H, 2W and W4 are the launch's: quotients come from a float estimate with the host's reciprocal and one correction
+// step (lpips_divmod), weights from a multiplication by that reciprocal.
+struct LpipsMapArgs {
+  const float* dl;                     // [B][dl_total]
+  int dl0[kLpipsLayers], dl_total;
+  int h[3], w[3];                      // the grids of layer 0, layer 1 and layers 2..4
+  int H, W, W4, nblk, first, vec;      // W4 = ceil(W / 4) units per row; nblk blocks of 256 units per image; vec: 16-byte accesses
+  float inv2H, inv2W, invW4;           // 1 / (2H), 1 / (2W), 1 / W4
+  float* out_map;                      // [B][H][W] or null
+  float* best_map;                     // [B][H][W] or null: best = first ? D : fminf(best, D)
+  double* part;                        // [B][nblk][2]: the block's sums of D and of the updated best_map
+};
+
+struct LpipsAxis { int i0, i1, rem; float t; };
+
+// q = floor(num / d) and *rem = num - q d for 0 <= num < 2^31, d >= 1 and q < 2^15, inv = 1.f / d: the float product is within
+// q 2^-22 < 1 of the quotient, so its truncation is off by at most one, which the remainder shows
+__device__ __forceinline__ int lpips_divmod(int num, int d, float inv, int* rem) {
+  int q = (int)((float)num * inv);
+  int r = num - q * d;
+  if (r < 0) { --q; r += d; }
+  else if (r >= d) { ++q; r -= d; }
+  *rem = r;
+  return q;
+}
+
+// output index y of an H-long axis on an h-long source axis; twoH = 2H, inv = 1.f / twoH. rem: the numerator's remainder (the
+// numerator itself where it is <= 0 and the source coordinate clamps to 0)
+__device__ __forceinline__ LpipsAxis lpips_axis(int y, int h, int twoH, float inv) {
+  const int num = (2 * y + 1) * h - (twoH >> 1);
+  LpipsAxis a;
+  if (num <= 0) { a.i0 = 0; a.rem = num; a.t = 0.f; }
+  else { a.i0 = lpips_divmod(num, twoH, inv, &a.rem); a.t = (float)a.rem * inv; }
+  a.i1 = min(a.i0 + 1, h - 1);
+  return a;
+}
+
+__device__ __forceinline__ double wave_sum_f64(double v) {     // butterfly: every lane gets the sum, in a fixed order
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// grid (nblk, B), 256 threads, one unit (row y, columns 4u .. 4u + 3) each
+__global__ __launch_bounds__(256) void lpips_map_kernel(const LpipsMapArgs a) {
+  __shared__ double wsum[4][2];
+  const int b = blockIdx.y;
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  const bool live = i < a.H * a.W4;
+  double sd = 0.0, sb = 0.0;
+  if (live) {
+    int u;
+    const int y = lpips_divmod(i, a.W4, a.invW4, &u), x0 = u * 4;
+    float D[4] = {0.f, 0.f, 0.f, 0.f};
+    const float* const dimg = a.dl + (size_t)b * a.dl_total;
+    // layers 2, 3, 4 share one grid: three sets of indices and weights serve the five layers
+    LpipsAxis r[3];
+    int ci[3][3], up[3][4];
+    float tx[3][4];
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+      const int h = a.h[q], w = a.w[q];
+      r[q] = lpips_axis(y, h, 2 * a.H, a.inv2H);
+      const LpipsAxis c = lpips_axis(x0, w, 2 * a.W, a.inv2W);
+      ci[q][0] = c.i0; ci[q][1] = min(c.i0 + 1, w - 1); ci[q][2] = min(c.i0 + 2, w - 1);
+      // column k: numerator (2 (x0 + k) + 1) w - W = that of column 0 + 2 k w; 6 w < 2 W, so the quotient grows by at most 1
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        int rem = max(c.rem + 2 * k * w, 0);
+        up[q][k] = rem >= 2 * a.W;
+        rem = up[q][k] ? rem - 2 * a.W : rem;
+        tx[q][k] = (float)rem * a.inv2W;
+      }
+    }
+#pragma unroll
+    for (int l = 0; l < kLpipsLayers; ++l) {
+      const int q = l < 2 ? l : 2, w = a.w[q];
+      const float* const r0 = dimg + a.dl0[l] + r[q].i0 * w;
+      const float* const r1 = dimg + a.dl0[l] + r[q].i1 * w;
+      // the three source columns, interpolated along y
+      const float v0 = r0[ci[q][0]] + r[q].t * (r1[ci[q][0]] - r0[ci[q][0]]);
+      const float v1 = r0[ci[q][1]] + r[q].t * (r1[ci[q][1]] - r0[ci[q][1]]);
+      const float v2 = r0[ci[q][2]] + r[q].t * (r1[ci[q][2]] - r0[ci[q][2]]);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const float lo = up[q][k] ? v1 : v0, hi = up[q][k] ? v2 : v1;
+        D[k] += lo + tx[q][k] * (hi - lo);
+      }
+    }
+    const size_t o = ((size_t)b * a.H + y) * a.W + x0;
+    const int nv = min(4, a.W - x0);
+    float Bv[4] = {0.f, 0.f, 0.f, 0.f};
+    if (a.vec) {                                               // (W % 4 == 0 and 16-byte aligned bases: nv == 4)
+      const f32x4 d4 = {D[0], D[1], D[2], D[3]};
+      if (a.out_map) *reinterpret_cast<f32x4*>(a.out_map + o) = d4;
+      if (a.best_map) {
+        f32x4 b4 = d4;
+        if (!a.first) {
+          const f32x4 old = *reinterpret_cast<const f32x4*>(a.best_map + o);
+          b4.x = fminf(old.x, d4.x); b4.y = fminf(old.y, d4.y); b4.z = fminf(old.z, d4.z); b4.w = fminf(old.w, d4.w);
+        }
+        *reinterpret_cast<f32x4*>(a.best_map + o) = b4;
+        Bv[0] = b4.x; Bv[1] = b4.y; Bv[2] = b4.z; Bv[3] = b4.w;
+      }
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        if (k < nv) {
+          if (a.out_map) a.out_map[o + k] = D[k];
+          if (a.best_map) {
+            Bv[k] = a.first ? D[k] : fminf(a.best_map[o + k], D[k]);
+            a.best_map[o + k] = Bv[k];
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      if (k < nv) { sd += (double)D[k]; sb += (double)Bv[k]; }
+    }
+  }
+  sd = wave_sum_f64(sd);
+  sb = wave_sum_f64(sb);
+  const int wv = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) { wsum[wv][0] = sd; wsum[wv][1] = sb; }
   __syncthreads();
-  if (threadIdx.x == 0) {
-    float t = 0.f;
-    for (int k = 0; k < 16; ++k) t += gsum[k];
-    a.part[(size_t)b * a.nchunk_total + blk] = t;
+  if (threadIdx.x < 2) {
+    const double t = ((wsum[0][threadIdx.x] + wsum[1][threadIdx.x]) + wsum[2][threadIdx.x]) + wsum[3][threadIdx.x];
+    a.part[((size_t)b * a.nblk + blockIdx.x) * 2 + threadIdx.x] = t;
+  }
+}
+
+// one block of 64 threads per image: lane t adds the blocks t, t + 64, .. in order, a butterfly adds the lanes; / (H W)
+__global__ __launch_bounds__(64) void lpips_map_final_kernel(const double* __restrict__ part, int nblk, double hw,
+                                                             float* __restrict__ out_map_mean, float* __restrict__ out_best_mean) {
+  const int b = blockIdx.x, t = threadIdx.x;
+  const double* p = part + (size_t)b * nblk * 2;
+  double sd = 0.0, sb = 0.0;
+  for (int k = t; k < nblk; k += 64) { sd += p[2 * k]; sb += p[2 * k + 1]; }
+  sd = wave_sum_f64(sd);
+  sb = wave_sum_f64(sb);
+  if (t == 0) {
+    if (out_map_mean) out_map_mean[b] = (float)(sd / hw);
+    if (out_best_mean) out_best_mean[b] = (float)(sb / hw);
   }
 }
 
@@ -478,18 +683,10 @@ size_t hcf_lpips_workspace(int32_t B, int32_t H, int32_t W) {
   return lpips_plan(B, H, W, p) ? p.total : 0;
 }
 
-int hcf_lpips_alex(const float* in0, const float* in1, int32_t B, int32_t H, int32_t W, int32_t normalize,
-                   const float* const* params, float* out, float* out_layers, void* work, size_t work_bytes,
-                   hcf_stream_t stream) {
-  if (!in0 || !in1 || !params || !out || !work) return HCF_ERR_ARG;
-  for (int i = 0; i < HCF_LPIPS_NPARAMS; ++i)
-    if (!params[i]) return HCF_ERR_ARG;
-  LpipsPlan p;
-  if (!lpips_plan(B, H, W, p)) return HCF_ERR_SHAPE;
-  if (work_bytes < p.total) return HCF_ERR_NOMEM;
+// prep, conv1, pool1, conv2, pool2, conv3..5 over the N images of plan p (N = 2B: in0 and in1 stacked; N = B: in0 alone) into `wk`
+static int lpips_features(const float* in0, const float* in1, int B, int N, int H, int W, int normalize, const float* const* params,
+                          char* wk, const LpipsPlan& p, hcf_stream_t stream) {
   hipStream_t st = (hipStream_t)stream;
-  char* wk = (char*)work;
-  const int N = 2 * B;
   float *s2d = (float*)(wk + p.o_s2d), *f1 = (float*)(wk + p.o_f1), *p1 = (float*)(wk + p.o_p1), *f2 = (float*)(wk + p.o_f2);
   float *p2 = (float*)(wk + p.o_p2), *f3 = (float*)(wk + p.o_f3), *f4 = (float*)(wk + p.o_f4), *f5 = (float*)(wk + p.o_f5);
   const float *shift = params[0], *scale = params[1];
@@ -498,7 +695,7 @@ int hcf_lpips_alex(const float* in0, const float* in1, int32_t B, int32_t H, int
 
   unsigned g;
   if (lpips_grid((long long)N * p.Hs * p.Ws * 12, &g) != HCF_OK) return HCF_ERR_ARG;
-  hipLaunchKernelGGL(lpips_prep_kernel, dim3(g), dim3(256), 0, st, in0, in1, B, H, W, p.Hs, p.Ws, normalize, shift, scale, s2d);
+  hipLaunchKernelGGL(lpips_prep_kernel, dim3(g), dim3(256), 0, st, in0, in1, B, N, H, W, p.Hs, p.Ws, normalize, shift, scale, s2d);
   if (hipGetLastError() != hipSuccess) return HCF_ERR_HIP;
   int rc = lpips_conv5(s2d, 48, N, p.Hs, p.Ws, cw[0], cb[0], f1, 64, 0, wk, p, st);
   if (rc == HCF_OK) rc = lpips_pool(f1, N, p.Hs, p.Ws, 64, p.H2, p.W2, p1, st);
@@ -512,26 +709,146 @@ int hcf_lpips_alex(const float* in0, const float* in1, int32_t B, int32_t H, int
   for (int l = 2; l < kLpipsLayers && rc == HCF_OK; ++l)
     rc = hcf_aux_conv2d(xin[l - 2], kAlexC[l - 1], kAlexC[l - 1], N, p.H3, p.W3, cw[l], cb[l], kAlexC[l], 3, ACT_RELU,
                         yout[l - 2], kAlexC[l], aux, p.aux_bytes, HCF_PRECISION_EXACT, stream);
+  return rc;
+}
+
+// the head's view of the five feature maps in `wk` (plan p), and the final kernel's chunk table
+static void lpips_head_layers(const char* wk, const LpipsPlan& p, const float* const* params, LpipsLayer* L, LpipsFinalArgs* fa) {
+  const size_t feat[kLpipsLayers] = {p.o_f1, p.o_f2, p.o_f3, p.o_f4, p.o_f5};
+  const int hst[kLpipsLayers] = {p.Hs, p.H2, p.H3, p.H3, p.H3}, wst[kLpipsLayers] = {p.Ws, p.W2, p.W3, p.W3, p.W3};
+  const int hh[kLpipsLayers] = {p.H1, p.H2, p.H3, p.H3, p.H3}, ww[kLpipsLayers] = {p.W1, p.W2, p.W3, p.W3, p.W3};
+  for (int l = 0; l < kLpipsLayers; ++l) {
+    L[l].f = (const float*)(wk + feat[l]); L[l].C = kAlexC[l]; L[l].Hst = hst[l]; L[l].Wst = wst[l]; L[l].h = hh[l]; L[l].w = ww[l];
+    L[l].chunk0 = p.chunk0[l];
+    L[l].lin = params[12 + l];
+    fa->chunk0[l] = p.chunk0[l]; fa->nchunk[l] = p.nchunk[l]; fa->hw[l] = hh[l] * ww[l];
+  }
+  fa->nchunk_total = p.nchunk_total;
+}
+
+int hcf_lpips_alex(const float* in0, const float* in1, int32_t B, int32_t H, int32_t W, int32_t normalize,
+                   const float* const* params, float* out, float* out_layers, void* work, size_t work_bytes,
+                   hcf_stream_t stream) {
+  if (!in0 || !in1 || !params || !out || !work) return HCF_ERR_ARG;
+  for (int i = 0; i < HCF_LPIPS_NPARAMS; ++i)
+    if (!params[i]) return HCF_ERR_ARG;
+  LpipsPlan p;
+  if (!lpips_plan(B, H, W, p)) return HCF_ERR_SHAPE;
+  if (work_bytes < p.total) return HCF_ERR_NOMEM;
+  hipStream_t st = (hipStream_t)stream;
+  char* wk = (char*)work;
+  const int rc = lpips_features(in0, in1, B, 2 * B, H, W, normalize, params, wk, p, stream);
   if (rc != HCF_OK) return rc;
 
   LpipsHeadArgs h;
   memset(&h, 0, sizeof(h));
-  const float* feat[kLpipsLayers] = {f1, f2, f3, f4, f5};
-  const int hst[kLpipsLayers] = {p.Hs, p.H2, p.H3, p.H3, p.H3}, wst[kLpipsLayers] = {p.Ws, p.W2, p.W3, p.W3, p.W3};
-  const int hh[kLpipsLayers] = {p.H1, p.H2, p.H3, p.H3, p.H3}, ww[kLpipsLayers] = {p.W1, p.W2, p.W3, p.W3, p.W3};
   LpipsFinalArgs fa;
   memset(&fa, 0, sizeof(fa));
-  for (int l = 0; l < kLpipsLayers; ++l) {
-    h.L[l].f = feat[l]; h.L[l].C = kAlexC[l]; h.L[l].Hst = hst[l]; h.L[l].Wst = wst[l]; h.L[l].h = hh[l]; h.L[l].w = ww[l];
-    h.L[l].chunk0 = p.chunk0[l];
-    h.L[l].lin = params[12 + l];
-    fa.chunk0[l] = p.chunk0[l]; fa.nchunk[l] = p.nchunk[l]; fa.hw[l] = hh[l] * ww[l];
-  }
+  lpips_head_layers(wk, p, params, h.L, &fa);
   h.B = B; h.nchunk_total = p.nchunk_total; h.part = (float*)(wk + p.o_part);
   hipLaunchKernelGGL(lpips_head_kernel, dim3((unsigned)p.nchunk_total, (unsigned)B), dim3(256), 0, st, h);
   if (hipGetLastError() != hipSuccess) return HCF_ERR_HIP;
-  fa.nchunk_total = p.nchunk_total; fa.part = h.part; fa.out = out; fa.out_layers = out_layers;
+  fa.part = h.part; fa.out = out; fa.out_layers = out_layers;
   hipLaunchKernelGGL(lpips_final_kernel, dim3((unsigned)B), dim3(64), 0, st, fa);
+  return hipGetLastError() == hipSuccess ? HCF_OK : HCF_ERR_HIP;
+}
+
+// ---- one embedded input and the map against it (hcflow_amd/lpips.py: LPIPSMap). The store of hcf_lpips_alex_embed and the
+// front of hcf_lpips_alex_map's work are one B-image plan; behind it the map call keeps the layer maps d_l, the map kernel's
+// fp64 partials and a [B] vector for the final kernel when `out` is not asked for.
+struct LpipsMapPlan {
+  int dl0[kLpipsLayers], dl_total, W4, nblk;
+  size_t o_dl, o_mpart, o_out, total;
+};
+
+static bool lpips_map_plan(int B, int H, int W, LpipsPlan& p, LpipsMapPlan& q) {
+  memset(&q, 0, sizeof(q));
+  if (!lpips_plan_n(B, B, H, W, p)) return false;
+  const int hw[kLpipsLayers] = {p.H1 * p.W1, p.H2 * p.W2, p.H3 * p.W3, p.H3 * p.W3, p.H3 * p.W3};
+  for (int l = 0; l < kLpipsLayers; ++l) { q.dl0[l] = q.dl_total; q.dl_total += hw[l]; }
+  q.W4 = (W + 3) / 4;
+  q.nblk = (int)(((long long)H * q.W4 + 255) / 256);
+  size_t o = p.total;
+  auto take = [&](size_t bytes) { const size_t r = o; o += lp_al256(bytes); return r; };
+  q.o_dl = take((size_t)B * q.dl_total * sizeof(float));
+  q.o_mpart = take((size_t)B * q.nblk * 2 * sizeof(double));
+  q.o_out = take((size_t)B * sizeof(float));
+  q.total = o;
+  return true;
+}
+
+size_t hcf_lpips_embed_bytes(int32_t B, int32_t H, int32_t W) {
+  LpipsPlan p;
+  return lpips_plan_n(B, B, H, W, p) ? p.total : 0;
+}
+
+int hcf_lpips_alex_embed(const float* x, int32_t B, int32_t H, int32_t W, int32_t normalize, const float* const* params,
+                         void* store, size_t store_bytes, hcf_stream_t stream) {
+  if (!x || !params || !store) return HCF_ERR_ARG;
+  for (int i = 0; i < HCF_LPIPS_NPARAMS; ++i)
+    if (!params[i]) return HCF_ERR_ARG;
+  LpipsPlan p;
+  if (!lpips_plan_n(B, B, H, W, p)) return HCF_ERR_SHAPE;
+  if (store_bytes < p.total) return HCF_ERR_NOMEM;
+  return lpips_features(x, x, B, B, H, W, normalize, params, (char*)store, p, stream);
+}
+
+size_t hcf_lpips_map_workspace(int32_t B, int32_t H, int32_t W) {
+  LpipsPlan p;
+  LpipsMapPlan q;
+  return lpips_map_plan(B, H, W, p, q) ? q.total : 0;
+}
+
+int hcf_lpips_alex_map(const void* ref_store, size_t ref_bytes, const float* x, int32_t B, int32_t H, int32_t W,
+                       int32_t normalize, const float* const* params, float* out, float* out_layers, float* out_map,
+                       float* out_map_mean, float* best_map, float* out_best_mean, int32_t first, void* work, size_t work_bytes,
+                       hcf_stream_t stream) {
+  if (!ref_store || !x || !params || !work || (out_best_mean && !best_map)) return HCF_ERR_ARG;
+  for (int i = 0; i < HCF_LPIPS_NPARAMS; ++i)
+    if (!params[i]) return HCF_ERR_ARG;
+  LpipsPlan p;
+  LpipsMapPlan q;
+  if (!lpips_map_plan(B, H, W, p, q)) return HCF_ERR_SHAPE;
+  if (ref_bytes < p.total || work_bytes < q.total) return HCF_ERR_NOMEM;
+  hipStream_t st = (hipStream_t)stream;
+  char* wk = (char*)work;
+  const int rc = lpips_features(x, x, B, B, H, W, normalize, params, wk, p, stream);
+  if (rc != HCF_OK) return rc;
+
+  LpipsHead2Args h;
+  memset(&h, 0, sizeof(h));
+  LpipsLayer ref[kLpipsLayers];
+  LpipsFinalArgs fa, fa_ref;
+  memset(&fa, 0, sizeof(fa));
+  lpips_head_layers(wk, p, params, h.L, &fa);
+  lpips_head_layers((const char*)ref_store, p, params, ref, &fa_ref);
+  for (int l = 0; l < kLpipsLayers; ++l) { h.fr[l] = ref[l].f; h.dl0[l] = q.dl0[l]; }
+  h.dl_total = q.dl_total; h.nchunk_total = p.nchunk_total;
+  h.dl = (float*)(wk + q.o_dl); h.part = (float*)(wk + p.o_part);
+  hipLaunchKernelGGL(lpips_head2_kernel, dim3((unsigned)p.nchunk_total, (unsigned)B), dim3(256), 0, st, h);
+  if (hipGetLastError() != hipSuccess) return HCF_ERR_HIP;
+  if (out || out_layers) {
+    fa.part = h.part; fa.out = out ? out : (float*)(wk + q.o_out); fa.out_layers = out_layers;
+    hipLaunchKernelGGL(lpips_final_kernel, dim3((unsigned)B), dim3(64), 0, st, fa);
+    if (hipGetLastError() != hipSuccess) return HCF_ERR_HIP;
+  }
+  if (!out_map && !out_map_mean && !best_map) return HCF_OK;
+
+  LpipsMapArgs m;
+  memset(&m, 0, sizeof(m));
+  m.dl = h.dl; m.dl_total = q.dl_total;
+  for (int l = 0; l < kLpipsLayers; ++l) m.dl0[l] = q.dl0[l];
+  const int gh[3] = {p.H1, p.H2, p.H3}, gw[3] = {p.W1, p.W2, p.W3};
+  for (int g = 0; g < 3; ++g) { m.h[g] = gh[g]; m.w[g] = gw[g]; }
+  m.H = H; m.W = W; m.W4 = q.W4; m.nblk = q.nblk; m.first = first != 0;
+  m.inv2H = 1.f / (float)(2 * H); m.inv2W = 1.f / (float)(2 * W); m.invW4 = 1.f / (float)q.W4;
+  m.vec = (W % 4 == 0) && (((uintptr_t)out_map | (uintptr_t)best_map) & 15) == 0;
+  m.out_map = out_map; m.best_map = best_map; m.part = (double*)(wk + q.o_mpart);
+  hipLaunchKernelGGL(lpips_map_kernel, dim3((unsigned)q.nblk, (unsigned)B), dim3(256), 0, st, m);
+  if (hipGetLastError() != hipSuccess) return HCF_ERR_HIP;
+  if (!out_map_mean && !out_best_mean) return HCF_OK;
+  hipLaunchKernelGGL(lpips_map_final_kernel, dim3((unsigned)B), dim3(64), 0, st, m.part, q.nblk, (double)H * (double)W,
+                     out_map_mean, out_best_mean);
   return hipGetLastError() == hipSuccess ? HCF_OK : HCF_ERR_HIP;
 }
 

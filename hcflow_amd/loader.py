@@ -13,7 +13,10 @@ image, B = 16: 8.6 ms per image). This module is the drop-in for those two piece
   (``HCFlow_SR_model.py:281-301``: NLL pass + one sampling pass per heat and sample) on the whole batch and computes the log
   line's numbers per image on the device (hcflow_amd/metrics.py: PSNR / SSIM / PSNR_Y / SSIM_Y of SR vs GT with the border
   crop, the same on the bicubic down-scaled pair, LR consistency, sample diversity). LPIPS is computed when an ``lpips_fn`` is
-  passed, e.g. ``hcflow_amd.lpips.LPIPS(...).cuda()`` (AlexNet v0.1 on the HIP kernels, weights from local files).
+  passed, e.g. ``hcflow_amd.lpips.LPIPS(...).cuda()`` (AlexNet v0.1 on the HIP kernels, weights from local files);
+* ``evaluate_sample_set(net, batch, heats, n_sample, lpips_map)`` judges the same samples as a SET with an
+  ``hcflow_amd.lpips.LPIPSMap``: per image and heat the mean LPIPS, the best whole sample, the mean of the per-pixel best over the
+  samples and their relative gap (defined in ``hcflow_amd/lpips.py``), the GT going through AlexNet once per heat.
 
 The numbers per image are identical to feeding the images one at a time (every op of the path is per sample)."""
 from __future__ import annotations
@@ -100,4 +103,32 @@ def evaluate_batch(net, batch: Dict, heats: Iterable[float], n_sample: int, scal
                     ent["lpips"] = lp[b]
                 ent["diversity"] = M.diversity([s[b:b + 1] for s in samples]) if n_sample > 1 else 0.0
                 res[b][float(heat)] = ent
+    return res
+
+
+def evaluate_sample_set(net, batch: Dict, heats: Iterable[float], n_sample: int, lpips_map, seed: Optional[int] = None) -> List[Dict]:
+    """Per image of the batch and per heat: {"lpips": mean over the samples of the scalar LPIPS (``evaluate_batch``'s "lpips"),
+    "lpips_best": the best whole sample's map mean, "local_best": the mean of the per-pixel best over the samples, "score":
+    (lpips_best - local_best) / lpips_best} as floats -- ``global_best`` / ``local_best`` / ``score`` of
+    ``hcflow_amd.lpips.LPIPSMap.sample_set`` (defined there). ``lpips_map`` is an ``LPIPSMap`` on the net's device. Per heat the
+    samples are those of ``evaluate_batch`` (seeds ``seed + 1000 * hi + s``, ``cache_cond=True``); the GT goes through AlexNet once
+    per heat, the samples accumulate on the device, and each result vector is read back once per heat."""
+    dev = next(net.parameters()).device
+    lq, gt = batch["LQ"].to(dev), batch["GT"].to(dev)
+    B = lq.shape[0]
+    res: List[Dict] = [dict() for _ in range(B)]
+    with torch.no_grad():
+        for hi, heat in enumerate(heats):
+            acc = lpips_map.sample_set(gt, normalize=True, capacity=n_sample)
+            for s in range(n_sample):
+                kw = {} if seed is None else {"seed": seed + 1000 * hi + s}
+                acc.add(net(lr=lq, z=None, u=None, eps_std=heat, reverse=True, training=False, cache_cond=True, **kw))
+            r = acc.result()
+            lp = r["lpips"].double().cpu().tolist()                                # [M][B]
+            best, local, score = (r[k].double().cpu().tolist() for k in ("global_best", "local_best", "score"))
+            for b in range(B):
+                mean = 0.0
+                for s in range(n_sample):
+                    mean += lp[s][b] / n_sample
+                res[b][float(heat)] = {"lpips": mean, "lpips_best": best[b], "local_best": local[b], "score": score[b]}
     return res

@@ -41,6 +41,19 @@ and ``a_c = 2 w_c (f0_c / d0 - f1_c / d1) gout[b] / (h_l w_l)``:
 the term through the norm is DEFINED as 0 where ``n_i == 0`` (PyTorch autograd of the formula gives ``0 * inf = NaN`` there).
 The max-pool backward gives a window's gradient to its first maximum in row-major order, as PyTorch does. No atomics: the
 gradient is bit-reproducible, and sample b's gradient does not depend on the rest of the batch. No double backward.
+
+``LPIPSMap(metric)`` is the same measure for sample sets, where one GT meets M samples (``hcf_lpips_alex_embed`` /
+``hcf_lpips_alex_map``). ``embed(gt)`` runs AlexNet over the GT once and keeps its feature maps; ``compare(ref, sr)`` runs it over
+the sample alone and the head against the kept maps: its ``[B, 1, 1, 1]`` is ``metric(gt, sr)`` bit for bit, with the convolutions
+over B (M + 1) images where M metric calls take 2 B M. With ``spatial=True`` it also returns the per-pixel map
+``D = sum_l up_l(d_l)`` of ``lpips.LPIPS(spatial=True)``: ``d_l`` is layer l's per-pixel value before the spatial mean, ``up_l``
+PyTorch's bilinear upsampling to ``(H, W)`` with ``align_corners=False`` (source row ``sy = max(0, (y + 0.5) h_l / H - 0.5)``,
+rows ``floor(sy)`` and ``min(floor(sy) + 1, h_l - 1)``, weight ``sy - floor(sy)``; columns alike), summed in layer order.
+``sample_set(gt)`` accumulates, on the device, over the samples given to ``add``: ``map_mean[m, b] = mean_yx D_m[b]``,
+``best_map[b] = min_m D_m[b]`` per pixel, ``local_best[b] = mean_yx best_map[b]``, ``global_best[b] = min_m map_mean[m, b]`` and
+``score[b] = (global_best - local_best) / global_best`` (0 where ``global_best == 0``): the best whole sample against the
+per-pixel best over the set. ``mean(D)`` is not the scalar LPIPS (the upsampling moves the mean by about 1e-4 relative), so the
+scalar is returned next to it. The means are fixed-order fp64 sums: the same guarantees as the metric's.
 """
 from __future__ import annotations
 
@@ -301,3 +314,111 @@ class LPIPSLoss(nn.Module):
         if self.reduction == "sum":
             return d.sum()
         return d
+
+
+class LPIPSRef:
+    """What ``LPIPSMap.embed`` returns: the feature maps of one input in a device buffer (private layout), its shape and its
+    ``normalize`` flag, and the parameter tensors the maps were made with."""
+
+    def __init__(self, store, shape, normalize, params):
+        self.store, self.shape, self.normalize, self.params = store, tuple(shape), bool(normalize), params
+
+
+class LPIPSMap(nn.Module):
+    """Per-pixel LPIPS and sample-set scores on the kernels of ``metric`` (a ``LPIPS``; no parameters of its own):
+
+        m = LPIPSMap(metric)
+        d_map = m(in0, in1, normalize=False)            # [B,1,H,W] fp32: lpips.LPIPS(spatial=True)'s value
+        ref = m.embed(gt, normalize=True)               # GT through AlexNet once
+        d = m.compare(ref, sr)                          # [B,1,1,1], bit-equal to metric(gt, sr, normalize=True)
+        d, d_map = m.compare(ref, sr, spatial=True)
+        acc = m.sample_set(gt, normalize=True)
+        for sr in samples: acc.add(sr)                  # no host sync; no allocation after the first add
+        r = acc.result()                                # lpips, map_mean [M,B]; global_best(_index), local_best, score [B]; best_map
+
+    The input checks are ``LPIPS.forward``'s (``HcfError``). See the module docstring for the definitions."""
+
+    def __init__(self, metric: LPIPS):
+        super().__init__()
+        if not isinstance(metric, LPIPS):
+            raise TypeError("LPIPSMap: metric must be a hcflow_amd.lpips.LPIPS, got %s" % type(metric).__name__)
+        self.metric = metric
+
+    def embed(self, x: torch.Tensor, normalize: bool = False) -> LPIPSRef:
+        params = _checked_params(self.metric, x, x, loss=False)
+        B, _, H, W = x.shape
+        need = _lib.load().hcf_lpips_embed_bytes(B, H, W)
+        store = torch.empty(need, dtype=torch.uint8, device=x.device)
+        xf = x.detach().to(torch.float32).contiguous()
+        _lib.launch("hcf_lpips_alex_embed", x.device, xf, B, H, W, int(bool(normalize)), _param_ptrs(params), store, need)
+        return LPIPSRef(store, x.shape, normalize, params)
+
+    def _map_call(self, ref: LPIPSRef, x, out, out_map, map_mean, best_map, best_mean, first, work):
+        """One ``hcf_lpips_alex_map`` call of ``x`` against ``ref`` (``work``: the call's scratch, or None for a fresh one)."""
+        if not isinstance(ref, LPIPSRef):
+            raise TypeError("LPIPSMap: ref must come from LPIPSMap.embed, got %s" % type(ref).__name__)
+        _checked_params(self.metric, x, x, loss=False)
+        if tuple(x.shape) != ref.shape or x.device != ref.store.device:
+            raise _lib.HcfError("LPIPSMap: the reference was embedded for %s on %s, got %s on %s"
+                                % (ref.shape, ref.store.device, tuple(x.shape), x.device))
+        B, _, H, W = x.shape
+        need = _lib.load().hcf_lpips_map_workspace(B, H, W)
+        if work is None:
+            work = torch.empty(need, dtype=torch.uint8, device=x.device)
+        xf = x.detach().to(torch.float32).contiguous()
+        _lib.launch("hcf_lpips_alex_map", x.device, ref.store, ref.store.numel(), xf, B, H, W, int(ref.normalize),
+                    _param_ptrs(ref.params), out, None, out_map, map_mean, best_map, best_mean, int(bool(first)), work, need)
+        return work
+
+    def compare(self, ref: LPIPSRef, x: torch.Tensor, spatial: bool = False, normalize: Optional[bool] = None):
+        """``metric(gt, x)`` for the embedded ``gt`` as ``[B,1,1,1]``; ``spatial=True``: ``(that, the map [B,1,H,W])``.
+        ``normalize`` is the reference's; passing another value is refused."""
+        if normalize is not None and isinstance(ref, LPIPSRef) and bool(normalize) != ref.normalize:
+            raise _lib.HcfError("LPIPSMap.compare: the reference was embedded with normalize=%s" % ref.normalize)
+        B, _, H, W = x.shape if x.dim() == 4 else (0, 0, 0, 0)
+        out = torch.empty(B, dtype=torch.float32, device=x.device)
+        d_map = torch.empty(B, 1, H, W, dtype=torch.float32, device=x.device) if spatial else None
+        self._map_call(ref, x, out, d_map, None, None, None, True, None)
+        return (out.view(B, 1, 1, 1), d_map) if spatial else out.view(B, 1, 1, 1)
+
+    def forward(self, in0: torch.Tensor, in1: torch.Tensor, normalize: bool = False):
+        _checked_params(self.metric, in0, in1, loss=False)
+        return self.compare(self.embed(in0, normalize), in1, spatial=True)[1]
+
+    def sample_set(self, gt: torch.Tensor, normalize: bool = False, capacity: int = 64) -> "LPIPSSampleSet":
+        return LPIPSSampleSet(self, self.embed(gt, normalize), capacity)
+
+
+class LPIPSSampleSet:
+    """The accumulator of ``LPIPSMap.sample_set``. Its buffers (the call's scratch, ``best_map``, ``capacity`` rows of per-sample
+    values) are allocated with the set; ``add`` launches one ``hcf_lpips_alex_map`` call into them and does not synchronise. Beyond
+    ``capacity`` samples the row buffers double (the one allocation after the first add)."""
+
+    def __init__(self, owner: LPIPSMap, ref: LPIPSRef, capacity: int = 64):
+        B, _, H, W = ref.shape
+        dev = ref.store.device
+        self.owner, self.ref, self.M = owner, ref, 0
+        self._rows = torch.empty(2, max(1, int(capacity)), B, dtype=torch.float32, device=dev)      # lpips, map_mean
+        self._best_mean = torch.empty(B, dtype=torch.float32, device=dev)
+        self._best_map = torch.empty(B, 1, H, W, dtype=torch.float32, device=dev)
+        self._work = torch.empty(_lib.load().hcf_lpips_map_workspace(B, H, W), dtype=torch.uint8, device=dev)
+
+    def add(self, x: torch.Tensor):
+        if self.M == self._rows.shape[1]:
+            self._rows = torch.cat([self._rows, torch.empty_like(self._rows)], 1)
+        m = self.M
+        self.owner._map_call(self.ref, x, self._rows[0, m], None, self._rows[1, m], self._best_map, self._best_mean, m == 0,
+                             self._work)
+        self.M = m + 1
+        return self
+
+    def result(self):
+        if self.M == 0:
+            raise _lib.HcfError("LPIPSSampleSet.result: no sample was added")
+        lp, mm = self._rows[0, :self.M].clone(), self._rows[1, :self.M].clone()
+        gb, gi = mm.min(dim=0)
+        lb = self._best_mean.clone()
+        g64, l64 = gb.double(), lb.double()
+        score = torch.where(g64 == 0, torch.zeros_like(g64), (g64 - l64) / g64)
+        return {"lpips": lp, "map_mean": mm, "global_best": gb, "global_best_index": gi, "local_best": lb,
+                "best_map": self._best_map.clone(), "score": score}

@@ -580,6 +580,33 @@ int hcf_lpips_alex_backward(int32_t B, int32_t H, int32_t W, int32_t normalize, 
                             const float* gout, int32_t which, float* gin0, float* gin1, const void* fwd_work,
                             size_t fwd_work_bytes, void* work, size_t work_bytes, hcf_stream_t stream);
 
+/* ---- LPIPS against a stored reference, with the per-pixel map (hcflow_amd/lpips.py: LPIPSMap): the measure above for sample
+ * sets, where one GT meets many samples. hcf_lpips_alex_embed runs the AlexNet part over ONE input of B images (not a stacked
+ * 2B) and leaves its five feature maps in `store` (hcf_lpips_embed_bytes(B, H, W) bytes; 0: bad shape; the layout is private
+ * and stays valid while the caller leaves the buffer alone). hcf_lpips_alex_map embeds x the same way into `work` and runs the
+ * head against the stored reference of the SAME (B, H, W, normalize, params):
+ *   out [B], out_layers [B][5]: as hcf_lpips_alex(ref, x): bit-equal to it (one per-pixel function, the same partial sums)
+ *   out_map [B][H][W]:   D = sum over the layers l = 0..4, in that order, of the bilinear upsampling (align_corners = False,
+ *                        PyTorch's F.interpolate / lpips' upsample()) of the layer's per-pixel value
+ *                        d_l = sum_c w_lc (f0_c / (sqrt n0 + 1e-10) - f1_c / (sqrt n1 + 1e-10))^2 to H x W: the value of
+ *                        lpips.LPIPS(spatial=True). Source row of output row y on an h-row grid: sy = max(0, (y + .5) h / H - .5),
+ *                        i0 = floor(sy), i1 = min(i0 + 1, h - 1), weight sy - i0; columns alike
+ *   out_map_mean [B]:    the mean of D over the image (NOT `out`: the upsampling moves the mean by about 1e-4 relative)
+ *   best_map [B][H][W]:  read and written: best = first != 0 ? D : fminf(best, D), the per-pixel best over the calls so far
+ *   out_best_mean [B]:   the mean of the updated best_map (needs best_map)
+ * Every output may be NULL; with neither out_map, out_map_mean nor best_map no map kernel is launched. The means are fp64 sums
+ * of per-block partials over a grid fixed by (H, W), added in a fixed order. out_map / best_map take 16-byte accesses when
+ * W % 4 == 0 and they are 16-byte aligned, scalar ones otherwise (the same arithmetic). work: hcf_lpips_map_workspace(B, H, W)
+ * bytes. On `stream`, no host synchronisation, no atomics: bit-reproducible, and image b's results depend on image b only. */
+size_t hcf_lpips_embed_bytes(int32_t B, int32_t H, int32_t W);
+int hcf_lpips_alex_embed(const float* x, int32_t B, int32_t H, int32_t W, int32_t normalize, const float* const* params,
+                         void* store, size_t store_bytes, hcf_stream_t stream);
+size_t hcf_lpips_map_workspace(int32_t B, int32_t H, int32_t W);
+int hcf_lpips_alex_map(const void* ref_store, size_t ref_bytes, const float* x, int32_t B, int32_t H, int32_t W,
+                       int32_t normalize, const float* const* params, float* out, float* out_layers, float* out_map,
+                       float* out_map_mean, float* best_map, float* out_best_mean, int32_t first, void* work, size_t work_bytes,
+                       hcf_stream_t stream);
+
 /* Range-headroom probe of the f16x3 path (tools/range_headroom.py): while enabled, every conv launch of the following passes
  * also records max |x| over its input windows and -- for layers that own a Winograd pack -- max |B^T d B| over the F(2x2,3x3)
  * input patches, i.e. the values the split has to represent (f16 limit 65504). hcf_debug_range_probe_read returns record
