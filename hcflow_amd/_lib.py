@@ -50,6 +50,7 @@ SYMBOLS = [
     "hcf_op_quant_logp_backward_lr", "hcf_op_prior_encode_logp_backward", "hcf_op_input_grad",
     "hcf_data_prepare_batch", "hcf_data_prepare_paired",
     "hcf_op_fcn12", "hcf_op_conv2d_step_inverse",
+    "hcf_inverse_taus", "hcf_metric_stats_bytes", "hcf_metric_stats_add", "hcf_metric_stats_finish",
 ]
 
 
@@ -94,6 +95,7 @@ def load() -> C.CDLL:
     lib.hcf_finalize.argtypes = [vp, C.c_int]
     lib.hcf_inverse.argtypes = [vp, fp, C.POINTER(fp), i32, f32, u64, fp, i32, i32, i32, u32, vp]
     lib.hcf_inverse_ex.argtypes = [vp, fp, C.POINTER(fp), i32, f32, u64, i64, fp, i32, i32, i32, u32, vp]
+    lib.hcf_inverse_taus.argtypes = [vp, fp, C.POINTER(fp), i32, fp, u64, i64, fp, i32, i32, i32, u32, vp]
     lib.hcf_check_range.argtypes = [vp, C.POINTER(i32)]
     lib.hcf_check_range_samples.argtypes = [vp, C.POINTER(i32), C.POINTER(u32)]
     lib.hcf_aux_stream.argtypes = [i32, i32, C.POINTER(vp)]
@@ -120,6 +122,10 @@ def load() -> C.CDLL:
                                      C.POINTER(C.c_double)]
     lib.hcf_metric_psnr_ssim.argtypes = [fp, fp, i32, i32, i32, i32, i32, fp, vp]
     lib.hcf_metric_imresize_down.argtypes = [fp, i32, i32, i32, i32, fp, vp]
+    lib.hcf_metric_stats_bytes.argtypes = [i32, i32, i32]
+    lib.hcf_metric_stats_bytes.restype = C.c_size_t
+    lib.hcf_metric_stats_add.argtypes = [vp, C.c_size_t, fp, i32, i32, i32, i64, vp]
+    lib.hcf_metric_stats_finish.argtypes = [vp, C.c_size_t, i32, i32, i32, i64, fp, fp, fp, vp]
     lib.hcf_train_inverse.argtypes = [vp, fp, C.POINTER(fp), i32, f32, u64, fp, i32, i32, i32, C.c_uint32, vp]
     lib.hcf_train_backward_inverse.argtypes = [vp, fp, fp, i64, fp, vp]
     lib.hcf_train_backward_inverse_ex.argtypes = [vp, fp, fp, i64, fp, C.POINTER(fp), i32, vp]
@@ -207,7 +213,7 @@ def load() -> C.CDLL:
         if name not in ("hcf_destroy", "hcf_last_error", "hcf_workspace_bytes", "hcf_weight_bytes",
                         "hcf_fallback_count", "hcf_debug_last_clock_mhz", "hcf_aux_conv2d_workspace", "hcf_lpips_workspace",
                         "hcf_lpips_backward_workspace", "hcf_lpips_embed_bytes", "hcf_lpips_map_workspace",
-                        "hcf_aux_bn_act_workspace", "hcf_aux_feature_loss_workspace"):
+                        "hcf_aux_bn_act_workspace", "hcf_aux_feature_loss_workspace", "hcf_metric_stats_bytes"):
             fn.restype = C.c_int
     _lib = lib
     return lib

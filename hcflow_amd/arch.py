@@ -519,6 +519,38 @@ class _StaleParameters(Exception):
     the enqueued pass has been drained and the call is redone on the checked path."""
 
 
+def is_tau_vector(eps_std) -> bool:
+    """``eps_std`` as one temperature PER SAMPLE: a sequence, an array or a tensor of one or more dimensions. None, a Python
+    number and a 0-dim tensor are the reference's scalar ``eps_std``."""
+    if eps_std is None or isinstance(eps_std, (int, float)):
+        return False
+    if torch.is_tensor(eps_std) or isinstance(eps_std, np.ndarray):
+        return eps_std.ndim >= 1
+    return isinstance(eps_std, (list, tuple))
+
+
+def tau_vector(eps_std, B: Optional[int]) -> Optional[torch.Tensor]:
+    """None for a scalar ``eps_std`` (today's path, untouched); for a per-sample vector the validated 1-D fp32 tensor, on the
+    device it came from. ValueError for anything but ``B`` finite, non-negative values -- decided on the host, before any
+    engine or device is touched (a vector that lives on a GPU is read back for it: one small synchronising copy)."""
+    if not is_tau_vector(eps_std):
+        return None
+    try:
+        t = eps_std.detach() if torch.is_tensor(eps_std) else torch.as_tensor(np.asarray(eps_std, dtype=np.float64))
+    except (TypeError, ValueError) as e:
+        raise ValueError("eps_std: a per-sample vector must hold numbers (%s)" % e)
+    if t.dim() != 1:
+        raise ValueError("eps_std: a per-sample vector must be 1-D with one temperature per sample, got shape %s" % (tuple(t.shape),))
+    if not (t.is_floating_point() or t.dtype in (torch.int32, torch.int64)):
+        raise ValueError("eps_std: a per-sample vector must be a float tensor, got %s" % t.dtype)
+    if B is not None and t.numel() != B:
+        raise ValueError("eps_std: %d temperatures for a batch of %d samples" % (t.numel(), B))
+    host = t.double().cpu()
+    if t.numel() and not bool((torch.isfinite(host) & (host >= 0)).all()):
+        raise ValueError("eps_std: every per-sample temperature must be finite and >= 0, got %s" % host.tolist())
+    return t.to(torch.float32).contiguous()
+
+
 def _split_threaded() -> bool:
     """Second half of a split call enqueued by the helper thread? Default: yes (Face x8 at LR 20 x 20: 1 542 against 1 403 img/s with
     one thread enqueueing both halves, 1 416 unsplit; the -25 % once measured for this case was a garbage-collection pause inside
@@ -977,9 +1009,19 @@ class _EngineModule(nn.Module):
     def _inverse(self, lr, eps_std, eps=None, clamp=True, seed=None, sample_offset=0, cache_cond=False):
         """``sample_offset``: this call is samples [offset, offset + B) of a larger (sharded) batch: the device draws are
         those of the global samples (hcf_inverse_ex). ``cache_cond``: keep / reuse the deepest level's conditional features
-        while ``lr`` (same tensor, unchanged) and the parameters stay the same (tau sweeps, repeated sampling)."""
+        while ``lr`` (same tensor, unchanged) and the parameters stay the same (tau sweeps, repeated sampling).
+        ``eps_std``: the reference's scalar, or one temperature per sample (1-D float tensor / sequence of length B,
+        hcf_inverse_taus): row b then holds the bits of the scalar call with ``eps_std[b]``, the same seed and the same global
+        sample index. Inference only; a wrong length or a negative / non-finite entry is a ValueError."""
+        taus = tau_vector(eps_std, int(lr.shape[0]) if torch.is_tensor(lr) and lr.dim() == 4 else None)
+        if taus is not None:
+            eps_std = taus                                         # validated: 1-D fp32, one temperature per sample
         eps_grad = eps is not None and any(torch.is_tensor(e) and e.requires_grad for e in eps)
         if self._wants_grad() or (torch.is_grad_enabled() and ((torch.is_tensor(lr) and lr.requires_grad) or eps_grad)):
+            if taus is not None:
+                raise _lib.HcfError(
+                    "a per-sample eps_std vector has no differentiable (taped) inverse pass in hcflow_amd: call under "
+                    "torch.no_grad() with frozen inputs, or pass one scalar temperature per call.")
             if self.training and self._pending_actnorms():
                 raise NotImplementedError(
                     "un-initialised ActNorm layers in train() mode on the REVERSE path: run one forward (hr -> z) pass "
@@ -1036,7 +1078,11 @@ class _EngineModule(nn.Module):
                 keep.append(e)
                 keep_at[i] = e
                 arr[i] = e.data_ptr()
-        tau = 0.0 if eps_std is None else float(eps_std)
+        # a 1-D tensor is the per-sample vector _inverse validated (hcf_inverse_taus): it lives on the device while the pass runs
+        taus = self._prep(eps_std, dev) if torch.is_tensor(eps_std) and eps_std.dim() == 1 else None
+        if taus is not None and taus.numel() != B:
+            raise ValueError("eps_std: %d temperatures for a batch of %d samples" % (taus.numel(), B))
+        tau = 0.0 if eps_std is None or taus is not None else float(eps_std)
         flags = 0 if clamp else _lib.FLAG_NO_CLAMP
         if self._range_check[0] == "off":
             flags |= _lib.FLAG_NO_RANGE_CHECK
@@ -1065,7 +1111,11 @@ class _EngineModule(nn.Module):
 
         def run(eng_, lo, hi, stream_, fl=flags):
             # samples [lo, hi): their LR rows, their rows of the injected draws (or the same seed with their global sample index:
-            # the device draws are indexed by sample, hcf_inverse_ex), their output rows
+            # the device draws are indexed by sample, hcf_inverse_ex), their output rows, their slice of a temperature vector
+            if taus is not None:
+                return eng_.lib.hcf_inverse_taus(eng_.handle, lr[lo:hi].data_ptr(), arr_for(lo, hi), len(shapes),
+                                                 taus[lo:hi].data_ptr(), seed, int(sample_offset) + lo, out[lo:hi].data_ptr(),
+                                                 hi - lo, h, w, fl, stream_)
             return eng_.lib.hcf_inverse_ex(eng_.handle, lr[lo:hi].data_ptr(), arr_for(lo, hi), len(shapes), tau, seed,
                                            int(sample_offset) + lo, out[lo:hi].data_ptr(), hi - lo, h, w, fl, stream_)
 

@@ -344,6 +344,7 @@ struct GaussArgs {
   // sample
   const float* eps;      // NCHW [B,C,H,W] already N(0,tau) (injected), or nullptr -> device Philox
   float tau; uint64_t seed; uint64_t offset;
+  const float* tau_b;    // device [B] or nullptr: one temperature per sample of THIS launch (row b, not b0 + b) in place of tau
   int64_t b0;            // device draws: sample b of this call is sample b0 + b of the (sharded) batch, so shards reproduce the full batch
   View out;              // sample: latent out.  logp/encode: latent in
   float* aux;            // encode (rescale fwd): NCHW output z = (a-mean) exp(-logs)

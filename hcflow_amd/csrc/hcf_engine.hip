@@ -541,6 +541,14 @@ int hcf_inverse_ex(hcf_engine* e, const float* lr, const float* const* eps, int3
                      (hipStream_t)stream, flags, {1, B, h, w});
 }
 
+int hcf_inverse_taus(hcf_engine* e, const float* lr, const float* const* eps, int32_t n_eps, const float* taus_dev, uint64_t seed,
+                     int64_t first_sample, float* out_hr, int32_t B, int32_t h, int32_t w, uint32_t flags, hcf_stream_t stream) {
+  if (!e || !lr || !taus_dev || !out_hr || B < 1 || h < 1 || w < 1 || first_sample < 0) return HCF_ERR_ARG;
+  // (the plan key is hcf_inverse_ex's: the vector changes no buffer and no kernel choice)
+  return e->run_pass([&]() { e->pass_inverse(lr, eps, n_eps, 0.f, seed, first_sample, out_hr, B, h, w, flags, taus_dev); },
+                     (hipStream_t)stream, flags, {1, B, h, w});
+}
+
 int hcf_inverse(hcf_engine* e, const float* lr, const float* const* eps, int32_t n_eps, float tau, uint64_t seed,
                 float* out_hr, int32_t B, int32_t h, int32_t w, uint32_t flags, hcf_stream_t stream) {
   return hcf_inverse_ex(e, lr, eps, n_eps, tau, seed, 0, out_hr, B, h, w, flags, stream);

@@ -579,8 +579,9 @@
 
   // ---------------------------------------------------------------- inverse pass
   // FlowNet.reverse_flow (FlowNet_SR_x4.py:106-123, FlowNet_SR_x8.py:121-144, FlowNet_Rescaling_x4.py:111-128)
+  // taus_dev (hcf_inverse_taus): device [B], one temperature per sample of this call, read by the prior kernels; nullptr -> tau
   void pass_inverse(const float* lr, const float* const* eps, int n_eps, float tau, uint64_t seed, int64_t sample0, float* out,
-                    int B, int h, int w, uint32_t flags) {
+                    int B, int h, int w, uint32_t flags, const float* taus_dev = nullptr) {
     B_ = B;
     arena.top = 0;
     const int L = cfg.L;
@@ -624,7 +625,7 @@
         GaussArgs g = gauss_args(kept ? hkeep.all() : sc.hout.v(0, cf.Ca * 2), a.all(), cf.Ca, H, W);
         const int draw = L - 1 - level;
         g.eps = (eps && draw < n_eps) ? eps[draw] : nullptr;
-        g.tau = tau; g.seed = seed; g.offset = (uint64_t)draw; g.b0 = sample0;
+        g.tau = tau; g.seed = seed; g.offset = (uint64_t)draw; g.b0 = sample0; g.tau_b = taus_dev;
         HCF_LAUNCH(launch_gauss_sample(g, st));
       }
       zpad_valid = false;

@@ -1256,7 +1256,7 @@
         GaussArgs g = gauss_args(ho.v.v(0, cf.Ca * 2), a.v.all(), cf.Ca, H, W);
         const int draw = L - 1 - level;
         g.eps = (eps && draw < n_eps) ? eps[draw] : nullptr;
-        g.tau = tau; g.seed = seed; g.offset = (uint64_t)draw;
+        g.tau = tau; g.seed = seed; g.offset = (uint64_t)draw; g.tau_b = nullptr;      // (one temperature per taped call)
         HCF_LAUNCH(launch_gauss_sample(g, st));
         const TB a0 = a;
         const int Ca = cf.Ca;

@@ -505,7 +505,7 @@ int hcf_op_gauss_sample(const float* h, const float* eps, float tau, uint64_t se
   g.B = B; g.H = H; g.W = W; g.C = C;
   g.h = nhwc_from_nchw(t, h, B, 2 * C, H, W, st, rc);
   g.rescale = rescale;
-  g.eps = eps; g.tau = tau; g.seed = seed; g.offset = 0;
+  g.eps = eps; g.tau = tau; g.seed = seed; g.offset = 0; g.tau_b = nullptr;
   float* o = t.dev((size_t)B * H * W * ru4(C));
   g.out = mkview(o, ru4(C), 0, C);
   if (!t.ok) return HCF_ERR_NOMEM;

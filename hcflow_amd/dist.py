@@ -77,7 +77,12 @@ def sharded_inverse(net, lr: torch.Tensor, eps_std: float, eps: Optional[Sequenc
     Without ``eps`` the draws happen on the device: every rank uses the SAME seed and the offset of its shard in the batch, so
     sample k of the gathered batch gets the eps sample k would get on one GPU (hcf_inverse_ex) -- the reference seeds all ranks
     identically (train_HCFlow.py:43-46), which with shard-local indexing would repeat the same eps in every shard.
+    ``eps_std`` is one scalar for the whole batch: a per-sample vector (hcflow_amd/arch.py) is not sharded and is refused.
     """
+    from .arch import is_tau_vector
+    if is_tau_vector(eps_std):
+        raise ValueError("sharded_inverse: a per-sample eps_std vector is not sharded across ranks; pass one scalar temperature "
+                         "(or call the net on this rank's rows with their slice of the vector)")
     if eps is None:
         sd = common_seed(lr.device, group, seed)
         return sharded_apply(lambda s, offset: net(lr=s, z=None, u=None, eps_std=eps_std, reverse=True, seed=sd,

@@ -16,12 +16,15 @@ image, B = 16: 8.6 ms per image). This module is the drop-in for those two piece
   passed, e.g. ``hcflow_amd.lpips.LPIPS(...).cuda()`` (AlexNet v0.1 on the HIP kernels, weights from local files);
 * ``evaluate_sample_set(net, batch, heats, n_sample, lpips_map)`` judges the same samples as a SET with an
   ``hcflow_amd.lpips.LPIPSMap``: per image and heat the mean LPIPS, the best whole sample, the mean of the per-pixel best over the
-  samples and their relative gap (defined in ``hcflow_amd/lpips.py``), the GT going through AlexNet once per heat.
+  samples and their relative gap (defined in ``hcflow_amd/lpips.py``), the GT going through AlexNet once per heat;
+* ``evaluate_sweep(net, batch, heats, n_sample, scale)`` returns ``evaluate_batch``'s dict with the heats sharing calls: the rows
+  of one call are (image, heat) pairs, each with its own temperature, and the diversity comes from a streaming
+  ``metrics.SampleStats`` instead of the held samples.
 
 The numbers per image are identical to feeding the images one at a time (every op of the path is per sample)."""
 from __future__ import annotations
 
-from typing import Dict, Iterable, Iterator, List, Optional, Sequence
+from typing import Dict, Iterable, Iterator, List, Optional, Sequence, Tuple
 
 import torch
 
@@ -103,6 +106,81 @@ def evaluate_batch(net, batch: Dict, heats: Iterable[float], n_sample: int, scal
                     ent["lpips"] = lp[b]
                 ent["diversity"] = M.diversity([s[b:b + 1] for s in samples]) if n_sample > 1 else 0.0
                 res[b][float(heat)] = ent
+    return res
+
+
+def sweep_chunks(B: int, n_heats: int, max_batch: int = 16) -> List[Tuple[int, int]]:
+    """The call plan of ``evaluate_sweep``: the R = B * n_heats rows (image b, heat hi) -> r = b * n_heats + hi, cut in order into
+    contiguous chunks [(row0, rows)] of at most ``max_batch`` rows, one inverse call each."""
+    if B < 0 or n_heats < 0 or max_batch < 1:
+        raise ValueError("sweep_chunks: B >= 0, n_heats >= 0 and max_batch >= 1 expected, got %r, %r, %r" % (B, n_heats, max_batch))
+    R = B * n_heats
+    return [(r0, min(max_batch, R - r0)) for r0 in range(0, R, max_batch)]
+
+
+def evaluate_sweep(net, batch: Dict, heats: Iterable[float], n_sample: int, scale: int, crop_border: Optional[int] = None,
+                   seed: Optional[int] = None, lpips_fn=None, max_batch: int = 16) -> List[Dict]:
+    """``evaluate_batch``'s per-image dict ("nll", "lr", and per heat the eight metric keys, the optional "lpips", "diversity")
+    with the heats SHARING calls: the reference's validation loop draws every (heat, sample) pair of an image in a call of its
+    own (test_HCFlow.py:116-131, HCFlow_SR_model.py:296-316); here the rows of a call each carry their temperature
+    (``eps_std`` as a vector, hcflow_amd/arch.py).
+
+    Rows are the (image b, heat hi) pairs, r = b * len(heats) + hi. Sample s is ONE pass over all rows with ``seed + s``, cut by
+    ``sweep_chunks`` into calls of at most ``max_batch`` rows: ``lr`` = the rows' images, ``eps_std`` = the rows' heats,
+    ``sample_offset`` = the chunk's first row, ``cache_cond=True`` (which pays when a pass is a single chunk: the kept features
+    are those of the last call). Row r of sample s therefore IS
+    ``net(lr=lq[b:b+1], eps_std=heats[hi], seed=seed + s, sample_offset=r, reverse=True, training=False)`` whatever ``max_batch``
+    is -- other draws than ``evaluate_batch``'s (seed + 1000 hi + s over the image batch), the same distribution. ``seed=None``
+    draws a fresh seed per sample pass. The samples are not kept: one ``metrics.SampleStats`` over the R rows accumulates the
+    diversity; PSNR / SSIM / LPIPS are evaluated per chunk against the matching GT rows and averaged as in ``evaluate_batch``."""
+    heats = [float(t) for t in heats]
+    dev = next(net.parameters()).device
+    lq = batch["LQ"].to(dev)
+    gt = batch["GT"].to(dev) if "GT" in batch else None
+    B, nH = lq.shape[0], len(heats)
+    crop = scale if crop_border is None else crop_border          # test_HCFlow.py:48
+    res = evaluate_batch(net, batch, (), 0, scale, crop_border)   # "nll" and "lr" (no heats: the NLL pass alone)
+    chunks = sweep_chunks(B, nH, max_batch)
+    if not chunks or n_sample < 1:
+        return res
+    R = B * nH
+    image_of = torch.arange(R, device=dev) // nH
+    taus = torch.tensor(heats, dtype=torch.float32).repeat(B)                        # host: validated there, per call
+    # one tensor per chunk, held for the whole sweep: the kept conditional features are keyed by the tensor they came from
+    lq_rows = lq[image_of]
+    lq_c = [lq_rows[r0:r0 + n] for r0, n in chunks]
+    gt_c = None if gt is None else [gt[image_of[r0:r0 + n]] for r0, n in chunks]
+    acc = [dict.fromkeys(M.KEYS, 0.0) for _ in range(R)]
+    lp = [0.0] * R
+    stats = None
+    with torch.no_grad():
+        for s in range(n_sample):
+            sd = int(torch.randint(0, 2 ** 62, (1,)).item()) if seed is None else seed + s
+            outs = []
+            for ci, (r0, n) in enumerate(chunks):
+                sr = net(lr=lq_c[ci], z=None, u=None, eps_std=taus[r0:r0 + n], reverse=True, training=False, seed=sd,
+                         sample_offset=r0, cache_cond=True)
+                outs.append(sr)
+                if gt is None:
+                    continue
+                for i, m in enumerate(M.psnr_ssim(gt_c[ci], sr, crop, scale)):
+                    for k in M.KEYS:
+                        acc[r0 + i][k] += m[k] / n_sample
+                if lpips_fn is not None:
+                    d = lpips_fn(2 * gt_c[ci] - 1, 2 * sr - 1).reshape(n, -1).mean(dim=1)
+                    for i, v in enumerate(d.double().cpu().tolist()):
+                        lp[r0 + i] += v / n_sample
+            if n_sample > 1:
+                rows = outs[0] if len(outs) == 1 else torch.cat(outs, 0)
+                stats = M.SampleStats.like(rows) if stats is None else stats
+                stats.add(rows)
+        div = stats.result()["diversity"].cpu().tolist() if stats is not None else [0.0] * R
+    for r in range(R):
+        ent = dict(acc[r]) if gt is not None else {}
+        if gt is not None and lpips_fn is not None:
+            ent["lpips"] = lp[r]
+        ent["diversity"] = div[r]
+        res[r // nH][heats[r % nH]] = ent
     return res
 
 

@@ -125,6 +125,16 @@ int hcf_inverse(hcf_engine* e, const float* lr, const float* const* eps, int32_t
 int hcf_inverse_ex(hcf_engine* e, const float* lr, const float* const* eps, int32_t n_eps, float tau, uint64_t seed,
                    int64_t first_sample, float* out_hr, int32_t B, int32_t h, int32_t w, uint32_t flags, hcf_stream_t stream);
 
+/* The same with ONE TEMPERATURE PER SAMPLE: the reference's validation loop draws every (heat, sample) pair of an image in a
+ * call of its own (test_HCFlow.py:116-131, HCFlow_SR_model.py:296-316); here the rows of one call may each have their heat.
+ *   taus_dev  [B] fp32 DEVICE memory, finite and >= 0 (the caller checks), read by the prior kernels when the pass runs: it
+ *             must stay valid and unchanged until then. taus_dev[b] belongs to sample b of THIS call (not first_sample + b).
+ * Row b holds the bits of hcf_inverse_ex(tau = taus[b]) with the same seed and global sample index first_sample + b (same
+ * kernel schedule, see above). Levels with an injected eps ignore the vector, as they ignore tau. Enqueue-only like its
+ * neighbours: no host copy, no synchronisation, no allocation in the steady state. */
+int hcf_inverse_taus(hcf_engine* e, const float* lr, const float* const* eps, int32_t n_eps, const float* taus_dev, uint64_t seed,
+                     int64_t first_sample, float* out_hr, int32_t B, int32_t h, int32_t w, uint32_t flags, hcf_stream_t stream);
+
 /* netG(hr=hr, lr=lr, reverse=False) for HCFlowNet_SR: normal_flow_diracLR (HCFlowNet_SR_arch.py:47-67).
  *   hr [B,3,H,W], lr [B,3,H/scale,W/scale] (NULL -> no Dirac term), noise [B,3,H,W] U[0,1) or NULL
  *   (NULL -> no dequantisation noise is added)
@@ -332,6 +342,24 @@ int hcf_metric_psnr_ssim(const float* gt, const float* sr, int32_t B, int32_t H,
                          int32_t scale, double* out, hcf_stream_t stream);
 int hcf_metric_imresize_down(const float* x, int32_t B, int32_t H, int32_t W, int32_t scale, double* out,
                              hcf_stream_t stream);
+
+/* Streaming per-pixel statistics of a SET of samples: what the reference gets from torch.cat(sr_img_list).std([0]) with every
+ * sample of an image held at once (test_HCFlow.py:127-131, :165-167), here with a state that does not grow with the number of
+ * samples: one (mean, M2) pair of doubles per element, updated by Welford's recurrence (hcf_metrics.hip).
+ *   hcf_metric_stats_bytes   size of the caller-allocated device state for [B,3,H,W] samples (16 bytes per element plus one
+ *                            double per 1024 elements for the finishing pass); 0 for an invalid shape. Needs no clearing.
+ *   hcf_metric_stats_add     folds one sample batch x (device [B,3,H,W] fp32) into the state. n = the number of samples the
+ *                            state holds AFTER this call (a host count, by value): n = 1 starts a new set. One launch.
+ *   hcf_metric_stats_finish  from a state of n >= 1 samples: mean [B,3,H,W] fp32, std [B,3,H,W] fp32 (unbiased, n - 1, in the
+ *                            samples' units; 0 for n = 1) and diversity [B] DEVICE double = mean over (c, y, x) of 255 * std,
+ *                            summed in float64 in a fixed order (no atomics: two runs agree bit for bit, and an image's values
+ *                            do not depend on the rest of the batch). The state is left as it was: adding may go on.
+ * All three only enqueue on `stream`: no synchronisation, no allocation. */
+size_t hcf_metric_stats_bytes(int32_t B, int32_t H, int32_t W);
+int hcf_metric_stats_add(void* state, size_t state_bytes, const float* x, int32_t B, int32_t H, int32_t W, int64_t n,
+                         hcf_stream_t stream);
+int hcf_metric_stats_finish(void* state, size_t state_bytes, int32_t B, int32_t H, int32_t W, int64_t n, float* mean, float* std,
+                            double* diversity, hcf_stream_t stream);
 
 /* ---- per-op entry points (unit parity tests; tensors are device NCHW fp32) ------------------- */
 /* F.conv2d(x, w, stride 1, padding k/2) with the fused epilogue
