@@ -51,6 +51,7 @@ SYMBOLS = [
     "hcf_data_prepare_batch", "hcf_data_prepare_paired",
     "hcf_op_fcn12", "hcf_op_conv2d_step_inverse",
     "hcf_inverse_taus", "hcf_metric_stats_bytes", "hcf_metric_stats_add", "hcf_metric_stats_finish",
+    "hcf_metric_pair_ref_bytes", "hcf_metric_pair_workspace", "hcf_metric_pair_embed", "hcf_metric_pair_compare",
 ]
 
 
@@ -126,6 +127,12 @@ def load() -> C.CDLL:
     lib.hcf_metric_stats_bytes.restype = C.c_size_t
     lib.hcf_metric_stats_add.argtypes = [vp, C.c_size_t, fp, i32, i32, i32, i64, vp]
     lib.hcf_metric_stats_finish.argtypes = [vp, C.c_size_t, i32, i32, i32, i64, fp, fp, fp, vp]
+    lib.hcf_metric_pair_ref_bytes.argtypes = [i32, i32, i32, i32]
+    lib.hcf_metric_pair_ref_bytes.restype = C.c_size_t
+    lib.hcf_metric_pair_workspace.argtypes = [i32, i32, i32, i32]
+    lib.hcf_metric_pair_workspace.restype = C.c_size_t
+    lib.hcf_metric_pair_embed.argtypes = [fp, i32, i32, i32, i32, i32, vp, C.c_size_t, vp]
+    lib.hcf_metric_pair_compare.argtypes = [vp, C.c_size_t, fp, i32, i32, i32, i32, i32, fp, vp, vp, C.c_size_t, vp]
     lib.hcf_train_inverse.argtypes = [vp, fp, C.POINTER(fp), i32, f32, u64, fp, i32, i32, i32, C.c_uint32, vp]
     lib.hcf_train_backward_inverse.argtypes = [vp, fp, fp, i64, fp, vp]
     lib.hcf_train_backward_inverse_ex.argtypes = [vp, fp, fp, i64, fp, C.POINTER(fp), i32, vp]
@@ -213,7 +220,8 @@ def load() -> C.CDLL:
         if name not in ("hcf_destroy", "hcf_last_error", "hcf_workspace_bytes", "hcf_weight_bytes",
                         "hcf_fallback_count", "hcf_debug_last_clock_mhz", "hcf_aux_conv2d_workspace", "hcf_lpips_workspace",
                         "hcf_lpips_backward_workspace", "hcf_lpips_embed_bytes", "hcf_lpips_map_workspace",
-                        "hcf_aux_bn_act_workspace", "hcf_aux_feature_loss_workspace", "hcf_metric_stats_bytes"):
+                        "hcf_aux_bn_act_workspace", "hcf_aux_feature_loss_workspace", "hcf_metric_stats_bytes",
+                        "hcf_metric_pair_ref_bytes", "hcf_metric_pair_workspace"):
             fn.restype = C.c_int
     _lib = lib
     return lib

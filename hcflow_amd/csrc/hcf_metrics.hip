@@ -111,8 +111,8 @@ static double cubic(double x) {                                   // utils/imres
   return 0.0;
 }
 
-// utils/imresize.py:60-82 (all columns kept: the dropped ones have zero weight)
-static void contributions(int in_len, int out_len, double scale, std::vector<double>& w, std::vector<int>& idx, int& P) {
+// utils/imresize.py:60-82 (all columns kept: the dropped ones have zero weight); shared with hcf_pair_metrics.hip
+void contributions(int in_len, int out_len, double scale, std::vector<double>& w, std::vector<int>& idx, int& P) {
   const double kw = (scale < 1) ? 4.0 / scale : 4.0;
   P = (int)ceil(kw) + 2;
   w.assign((size_t)out_len * P, 0.0);

@@ -57,7 +57,8 @@ def batched_test_loader(dataset, batch_size: int = 16, keys: Sequence[str] = ("L
 
 
 def evaluate_batch(net, batch: Dict, heats: Iterable[float], n_sample: int, scale: int, crop_border: Optional[int] = None,
-                   seed: Optional[int] = None, noise: Optional[torch.Tensor] = None, lpips_fn=None) -> List[Dict]:
+                   seed: Optional[int] = None, noise: Optional[torch.Tensor] = None, lpips_fn=None,
+                   pair_metrics: Optional[M.PairMetrics] = None) -> List[Dict]:
     """Per image of the batch: {"nll": float, "lr": {psnr, ssim, psnr_y, ssim_y} of LR^ vs LQ (SR nets), and per heat:
     {"psnr", "ssim", "psnr_y", "ssim_y", "bic_psnr", ... (means over the samples), "diversity"}} -- the numbers of the
     reference's per-image log line (test_HCFlow.py:166-175). LPIPS needs the ``lpips`` package's pretrained AlexNet: pass the
@@ -65,7 +66,10 @@ def evaluate_batch(net, batch: Dict, heats: Iterable[float], n_sample: int, scal
     "lpips" = the mean over the samples of ``lpips_fn(2 gt - 1, 2 sr - 1)`` per image (:132-133, :168), evaluated on the whole
     batch at once; without it the key is absent. ``net`` is an eval()-mode HCFlowNet_SR on a GPU.
     ``seed`` fixes the device draws of the samples, ``noise`` ([B,3,H,W] in [0,1)) replaces the dequantisation noise of the
-    NLL pass (HCFlowNet_SR_arch.py:52); both default to fresh draws, as in the reference."""
+    NLL pass (HCFlowNet_SR_arch.py:52); both default to fresh draws, as in the reference.
+    ``pair_metrics`` (a ``metrics.PairMetrics``): the same dicts with the PSNR / SSIM block kept on the device -- the GT is
+    prepared once per call, every sample is one ``compare`` into a device row, the per-sample LPIPS values stay on the device
+    too, the means over the samples are taken there in float64 and each heat's numbers are read back once."""
     dev = next(net.parameters()).device
     lq = batch["LQ"].to(dev)
     gt = batch["GT"].to(dev) if "GT" in batch else None
@@ -80,19 +84,28 @@ def evaluate_batch(net, batch: Dict, heats: Iterable[float], n_sample: int, scal
             pix = float(gt.shape[2] * gt.shape[3])
             for b, o in enumerate(obj.double().cpu().tolist()):
                 res[b]["nll"] = -o / (0.6931471805599453 * pix)
-            for b, m in enumerate(M.psnr_ssim(lq, lr_hat, 0, 0)):
+            lr_rows = (M.psnr_ssim(lq, lr_hat, 0, 0) if pair_metrics is None
+                       else M.rows_to_dicts(pair_metrics.compare(pair_metrics.embed(lq, 0, 0), lr_hat)))
+            for b, m in enumerate(lr_rows):
                 res[b]["lr"] = {k: m[k] for k in ("psnr", "ssim", "psnr_y", "ssim_y")}
+        on_dev = gt is not None and pair_metrics is not None
+        ref = pair_metrics.embed(gt, crop, scale) if on_dev and n_sample > 0 else None      # the GT is prepared once per call
         for hi, heat in enumerate(heats):
             samples = []
             acc = [dict.fromkeys(M.KEYS, 0.0) for _ in range(B)]
             lp = [0.0] * B
+            pset, lps = (M.PairSampleSet(pair_metrics, ref, n_sample), []) if ref is not None else (None, [])
             for s in range(n_sample):
                 kw = {} if seed is None else {"seed": seed + 1000 * hi + s}
                 # every heat / sample of the sweep conditions on the SAME lq: the deepest level's conditional features (the RRDB
                 # trunk: most of a Face x8 call) are computed once and reused, bit-identical outputs (arch.py: cache_cond)
                 sr = net(lr=lq, z=None, u=None, eps_std=heat, reverse=True, training=False, cache_cond=True, **kw)
                 samples.append(sr)
-                if gt is not None:
+                if pset is not None:                                   # one compare into a device row; LPIPS stays there too
+                    pset.add(sr)
+                    if lpips_fn is not None:
+                        lps.append(lpips_fn(2 * gt - 1, 2 * sr - 1).reshape(B, -1).mean(dim=1))
+                elif gt is not None:
                     for b, m in enumerate(M.psnr_ssim(gt, sr, crop, scale)):
                         for k in M.KEYS:
                             acc[b][k] += m[k] / n_sample
@@ -100,6 +113,9 @@ def evaluate_batch(net, batch: Dict, heats: Iterable[float], n_sample: int, scal
                         d = lpips_fn(2 * gt - 1, 2 * sr - 1).reshape(B, -1).mean(dim=1)      # [B, 1, 1, 1] -> one value per image
                         for b, v in enumerate(d.double().cpu().tolist()):
                             lp[b] += v / n_sample
+            if pset is not None:
+                for b, row in enumerate(_heat_rows(pset, lps)):
+                    acc[b], lp[b] = dict(zip(M.KEYS, row[:8])), row[-1]
             for b in range(B):
                 ent = dict(acc[b]) if gt is not None else {}
                 if gt is not None and lpips_fn is not None:
@@ -107,6 +123,15 @@ def evaluate_batch(net, batch: Dict, heats: Iterable[float], n_sample: int, scal
                 ent["diversity"] = M.diversity([s[b:b + 1] for s in samples]) if n_sample > 1 else 0.0
                 res[b][float(heat)] = ent
     return res
+
+
+def _heat_rows(pset: "M.PairSampleSet", lps: List[torch.Tensor]) -> List[List[float]]:
+    """One readback of a sample set's numbers: per image the eight float64 means over the samples and, when ``lps`` (the samples'
+    per-image LPIPS vectors) is not empty, their float64 mean as a ninth column."""
+    cols = [pset.result()["mean"]]
+    if lps:
+        cols.append(torch.stack(lps, 0).double().mean(dim=0).unsqueeze(1))
+    return torch.cat(cols, 1).cpu().tolist()
 
 
 def sweep_chunks(B: int, n_heats: int, max_batch: int = 16) -> List[Tuple[int, int]]:
@@ -119,7 +144,8 @@ def sweep_chunks(B: int, n_heats: int, max_batch: int = 16) -> List[Tuple[int, i
 
 
 def evaluate_sweep(net, batch: Dict, heats: Iterable[float], n_sample: int, scale: int, crop_border: Optional[int] = None,
-                   seed: Optional[int] = None, lpips_fn=None, max_batch: int = 16) -> List[Dict]:
+                   seed: Optional[int] = None, lpips_fn=None, max_batch: int = 16,
+                   pair_metrics: Optional[M.PairMetrics] = None) -> List[Dict]:
     """``evaluate_batch``'s per-image dict ("nll", "lr", and per heat the eight metric keys, the optional "lpips", "diversity")
     with the heats SHARING calls: the reference's validation loop draws every (heat, sample) pair of an image in a call of its
     own (test_HCFlow.py:116-131, HCFlow_SR_model.py:296-316); here the rows of a call each carry their temperature
@@ -132,14 +158,16 @@ def evaluate_sweep(net, batch: Dict, heats: Iterable[float], n_sample: int, scal
     ``net(lr=lq[b:b+1], eps_std=heats[hi], seed=seed + s, sample_offset=r, reverse=True, training=False)`` whatever ``max_batch``
     is -- other draws than ``evaluate_batch``'s (seed + 1000 hi + s over the image batch), the same distribution. ``seed=None``
     draws a fresh seed per sample pass. The samples are not kept: one ``metrics.SampleStats`` over the R rows accumulates the
-    diversity; PSNR / SSIM / LPIPS are evaluated per chunk against the matching GT rows and averaged as in ``evaluate_batch``."""
+    diversity; PSNR / SSIM / LPIPS are evaluated per chunk against the matching GT rows and averaged as in ``evaluate_batch``.
+    With ``pair_metrics`` each chunk's GT rows are prepared once, every (sample, chunk) is one ``compare`` into a device row, and
+    a chunk's means are read back once at the end (see ``evaluate_batch``)."""
     heats = [float(t) for t in heats]
     dev = next(net.parameters()).device
     lq = batch["LQ"].to(dev)
     gt = batch["GT"].to(dev) if "GT" in batch else None
     B, nH = lq.shape[0], len(heats)
     crop = scale if crop_border is None else crop_border          # test_HCFlow.py:48
-    res = evaluate_batch(net, batch, (), 0, scale, crop_border)   # "nll" and "lr" (no heats: the NLL pass alone)
+    res = evaluate_batch(net, batch, (), 0, scale, crop_border, pair_metrics=pair_metrics)   # "nll" and "lr" (no heats: the NLL pass alone)
     chunks = sweep_chunks(B, nH, max_batch)
     if not chunks or n_sample < 1:
         return res
@@ -153,6 +181,10 @@ def evaluate_sweep(net, batch: Dict, heats: Iterable[float], n_sample: int, scal
     acc = [dict.fromkeys(M.KEYS, 0.0) for _ in range(R)]
     lp = [0.0] * R
     stats = None
+    on_dev = gt is not None and pair_metrics is not None
+    if on_dev:
+        psets = [M.PairSampleSet(pair_metrics, pair_metrics.embed(g, crop, scale), n_sample) for g in gt_c]
+        lps: List[List[torch.Tensor]] = [[] for _ in chunks]
     with torch.no_grad():
         for s in range(n_sample):
             sd = int(torch.randint(0, 2 ** 62, (1,)).item()) if seed is None else seed + s
@@ -162,6 +194,11 @@ def evaluate_sweep(net, batch: Dict, heats: Iterable[float], n_sample: int, scal
                          sample_offset=r0, cache_cond=True)
                 outs.append(sr)
                 if gt is None:
+                    continue
+                if on_dev:
+                    psets[ci].add(sr)
+                    if lpips_fn is not None:
+                        lps[ci].append(lpips_fn(2 * gt_c[ci] - 1, 2 * sr - 1).reshape(n, -1).mean(dim=1))
                     continue
                 for i, m in enumerate(M.psnr_ssim(gt_c[ci], sr, crop, scale)):
                     for k in M.KEYS:
@@ -175,6 +212,12 @@ def evaluate_sweep(net, batch: Dict, heats: Iterable[float], n_sample: int, scal
                 stats = M.SampleStats.like(rows) if stats is None else stats
                 stats.add(rows)
         div = stats.result()["diversity"].cpu().tolist() if stats is not None else [0.0] * R
+        if on_dev:
+            for ci, (r0, n) in enumerate(chunks):
+                for i, row in enumerate(_heat_rows(psets[ci], lps[ci])):
+                    acc[r0 + i] = dict(zip(M.KEYS, row[:8]))
+                    if lpips_fn is not None:
+                        lp[r0 + i] = row[8]
     for r in range(R):
         ent = dict(acc[r]) if gt is not None else {}
         if gt is not None and lpips_fn is not None:

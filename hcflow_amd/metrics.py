@@ -4,7 +4,7 @@ down-scaled copies (utils/imresize.py), and the sample diversity (``std`` over s
 computed by HIP kernels in float64 (include/hcflow.h: hcf_metric_*). No CPU fallback."""
 import ctypes as C
 import math
-from typing import Dict, List
+from typing import Dict, List, Optional
 
 import numpy as np
 import torch
@@ -101,3 +101,113 @@ class SampleStats:
         div = torch.empty(B, dtype=torch.float64, device=self.device)
         _lib.launch("hcf_metric_stats_finish", self.device, self._state, self._bytes, B, H, W, self.count, mean, std, div)
         return {"mean": mean, "std": std, "diversity": div}
+
+
+class MetricRef:
+    """What ``PairMetrics.embed`` returns: one GT batch prepared for comparison in a device buffer (private layout), the shape,
+    ``crop_border`` and ``scale`` it was prepared for, and the scratch its ``compare`` calls run in (they share it: issue the
+    compares of one reference on one stream)."""
+
+    def __init__(self, store, shape, crop_border, scale, work):
+        self.store, self.shape, self.crop_border, self.scale, self.work = store, tuple(shape), int(crop_border), int(scale), work
+
+
+class PairMetrics:
+    """``psnr_ssim``'s eight numbers for many samples against ONE GT, kept on the device (include/hcflow.h: hcf_metric_pair_*):
+
+        pm = PairMetrics()
+        ref = pm.embed(gt, crop_border=4, scale=4)      # GT quantised, down-scaled and its tables uploaded once
+        m = pm.compare(ref, sr)                         # [B,8] float64 CUDA tensor in KEYS order; no host sync
+        m, u8 = pm.compare(ref, sr, image=True)         # + [B,H,W,3] uint8 BGR = util.tensor2img(sr) per image
+        acc = pm.sample_set(gt, crop_border=4, scale=4)
+        for sr in samples: acc.add(sr)                  # one compare into row M of a [capacity,B,8] buffer
+        r = acc.result()                                # per_sample [M,B,8], mean [B,8], best_psnr / best_psnr_index [B]
+
+    ``out=`` / ``image_out=`` write into the caller's tensors; with them ``compare`` allocates nothing (the scratch belongs to the
+    reference). Two runs agree bit for bit and an image's row does not depend on the rest of the batch. ``rows_to_dicts`` turns a
+    result into ``psnr_ssim``'s list of dicts. No CPU fallback."""
+
+    def embed(self, gt: torch.Tensor, crop_border: int = 0, scale: int = 0) -> MetricRef:
+        if not torch.is_tensor(gt) or not gt.is_cuda:
+            raise _lib.HcfError("PairMetrics needs a GPU tensor (got %s); hcflow_amd has no CPU fallback"
+                                % (gt.device if torch.is_tensor(gt) else type(gt).__name__,))
+        if gt.dim() != 4 or gt.shape[1] != 3:
+            raise _lib.HcfError("PairMetrics.embed: expected [B,3,H,W], got %s" % (tuple(gt.shape),))
+        B, _, H, W = gt.shape
+        lib = _lib.load()
+        need = int(lib.hcf_metric_pair_ref_bytes(B, H, W, int(scale)))
+        wneed = int(lib.hcf_metric_pair_workspace(B, H, W, int(scale)))
+        if need == 0 or wneed == 0:
+            raise _lib.HcfError("PairMetrics.embed: invalid shape %s or scale %d" % (tuple(gt.shape), scale))
+        store = torch.empty(need, dtype=torch.uint8, device=gt.device)
+        work = torch.empty(wneed, dtype=torch.uint8, device=gt.device)
+        _lib.launch("hcf_metric_pair_embed", gt.device, _prep(gt), B, H, W, int(crop_border), int(scale), store, need)
+        return MetricRef(store, gt.shape, crop_border, scale, work)
+
+    def _check(self, ref: MetricRef, sr: torch.Tensor):
+        if not isinstance(ref, MetricRef):
+            raise TypeError("PairMetrics: ref must come from PairMetrics.embed, got %s" % type(ref).__name__)
+        if not torch.is_tensor(sr) or tuple(sr.shape) != ref.shape or sr.device != ref.store.device:
+            raise _lib.HcfError("PairMetrics: the reference was embedded for %s on %s, got %s on %s"
+                                % (ref.shape, ref.store.device, tuple(getattr(sr, "shape", ())), getattr(sr, "device", None)))
+
+    def _call(self, ref: MetricRef, sr: torch.Tensor, out: torch.Tensor, image_out: Optional[torch.Tensor]):
+        self._check(ref, sr)
+        B, _, H, W = ref.shape
+        if out.dtype != torch.float64 or tuple(out.shape) != (B, 8):
+            raise _lib.HcfError("PairMetrics.compare: out must be float64 [%d,8], got %s %s" % (B, out.dtype, tuple(out.shape)))
+        if image_out is not None and (image_out.dtype != torch.uint8 or tuple(image_out.shape) != (B, H, W, 3)):
+            raise _lib.HcfError("PairMetrics.compare: image_out must be uint8 [%d,%d,%d,3], got %s %s"
+                                % (B, H, W, image_out.dtype, tuple(image_out.shape)))
+        _lib.launch("hcf_metric_pair_compare", sr.device, ref.store, ref.store.numel(), _prep(sr), B, H, W, ref.crop_border, ref.scale,
+                    out, image_out, ref.work, ref.work.numel())
+
+    def compare(self, ref: MetricRef, sr: torch.Tensor, image: bool = False, out: Optional[torch.Tensor] = None,
+                image_out: Optional[torch.Tensor] = None):
+        """The ``[B,8]`` float64 rows of ``sr`` against the embedded GT; with ``image=True`` (or an ``image_out``) the pair
+        ``(rows, [B,H,W,3] uint8 BGR)``."""
+        self._check(ref, sr)
+        B, _, H, W = ref.shape
+        if out is None:
+            out = torch.empty(B, 8, dtype=torch.float64, device=sr.device)
+        if image_out is None and image:
+            image_out = torch.empty(B, H, W, 3, dtype=torch.uint8, device=sr.device)
+        self._call(ref, sr, out, image_out)
+        return (out, image_out) if image_out is not None else out
+
+    def sample_set(self, gt: torch.Tensor, crop_border: int = 0, scale: int = 0, capacity: int = 64) -> "PairSampleSet":
+        return PairSampleSet(self, self.embed(gt, crop_border, scale), capacity)
+
+
+class PairSampleSet:
+    """The accumulator of ``PairMetrics.sample_set``: ``add`` is one ``compare`` into row M of a ``[capacity,B,8]`` device buffer
+    allocated with the set (beyond ``capacity`` samples it doubles: the one allocation after the first add); nothing synchronises
+    until the caller reads ``result()``: {"per_sample": [M,B,8], "mean": [B,8] (float64 mean over the samples), "best_psnr" [B],
+    "best_psnr_index" [B]: the sample with the highest PSNR per image}."""
+
+    def __init__(self, owner: PairMetrics, ref: MetricRef, capacity: int = 64):
+        self.owner, self.ref, self.M = owner, ref, 0
+        self._rows = torch.empty(max(1, int(capacity)), ref.shape[0], 8, dtype=torch.float64, device=ref.store.device)
+
+    def __len__(self):
+        return self.M
+
+    def add(self, sr: torch.Tensor) -> "PairSampleSet":
+        self.owner._check(self.ref, sr)                              # a refused sample does not count (and grows nothing)
+        if self.M == self._rows.shape[0]:
+            self._rows = torch.cat([self._rows, torch.empty_like(self._rows)], 0)
+        self.owner._call(self.ref, sr, self._rows[self.M], None)
+        self.M += 1
+        return self
+
+    def result(self) -> Dict[str, torch.Tensor]:
+        if self.M == 0:
+            raise _lib.HcfError("PairSampleSet.result: no sample was added")
+        rows = self._rows[:self.M].clone()
+        best, idx = rows[:, :, 0].max(dim=0)
+        return {"per_sample": rows, "mean": rows.mean(dim=0), "best_psnr": best, "best_psnr_index": idx}
+
+
+def rows_to_dicts(m: torch.Tensor) -> List[Dict[str, float]]:
+    """A ``[B,8]`` result of ``PairMetrics.compare`` as ``psnr_ssim``'s list of dicts (one readback)."""
+    return [dict(zip(KEYS, row)) for row in m.detach().double().cpu().tolist()]

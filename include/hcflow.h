@@ -361,6 +361,34 @@ int hcf_metric_stats_add(void* state, size_t state_bytes, const float* x, int32_
 int hcf_metric_stats_finish(void* state, size_t state_bytes, int32_t B, int32_t H, int32_t W, int64_t n, float* mean, float* std,
                             double* diversity, hcf_stream_t stream);
 
+/* PSNR / SSIM of many samples against ONE prepared GT: the eight numbers of hcf_metric_psnr_ssim (util.tensor2img,
+ * utils/util.py:790-816; util.calculate_psnr_ssim, :898-982; utils/imresize.py) with the GT-side work done once per GT and
+ * nothing allocated, copied from the host or synchronised per sample (hcf_pair_metrics.hip).
+ *   hcf_metric_pair_ref_bytes  size of the caller-allocated device buffer that holds a prepared GT batch [B,3,H,W] (private
+ *                              layout: the tensor2img planes as uint8; for scale > 1 the bicubic down-scaled planes as fp64 and the
+ *                              tables of imresize.py's contributions()); 0 for an invalid shape (utils/util.py:790-816,
+ *                              utils/imresize.py).
+ *   hcf_metric_pair_workspace  size of the caller-allocated device scratch of one compare call; 0 for an invalid shape. Image
+ *                              b's part starts at b * (the size for B = 1) (utils/util.py:898-982, utils/imresize.py).
+ *   hcf_metric_pair_embed      prepares gt (device [B,3,H,W] RGB fp32) into ref. The one entry that copies host tables (kept alive
+ *                              by the library) to the device, stream-ordered; it allocates nothing (utils/util.py:790-816,
+ *                              utils/imresize.py).
+ *   hcf_metric_pair_compare    sr (device [B,3,H,W] RGB fp32) against ref -> out, DEVICE double [B][8] = psnr, ssim, psnr_y,
+ *                              ssim_y, then the four down-scaled values: inf where the mse is 0, nan where a side of the compared
+ *                              window is under 11 pixels, columns 4..7 = 0 for scale <= 1. image_out: NULL or device uint8
+ *                              [B][H][W][3] BGR = util.tensor2img(sr) of every image. SSIM by the separable 11 + 11 tap form of
+ *                              the reference's Gaussian window, float64; every sum is joined in a fixed order (no atomics: two
+ *                              runs agree bit for bit, an image's numbers do not depend on the rest of the batch). Only enqueues
+ *                              on `stream` (utils/util.py:790-816, 898-982, utils/imresize.py).
+ * compare takes the crop_border / scale that embed was given. Checked before anything touches a device: null pointers, B, H, W < 1,
+ * negative crop_border or scale -> HCF_ERR_ARG; short buffers, H - 2 crop_border < 1 or W - 2 crop_border < 1 -> HCF_ERR_SHAPE. */
+size_t hcf_metric_pair_ref_bytes(int32_t B, int32_t H, int32_t W, int32_t scale);
+size_t hcf_metric_pair_workspace(int32_t B, int32_t H, int32_t W, int32_t scale);
+int hcf_metric_pair_embed(const float* gt, int32_t B, int32_t H, int32_t W, int32_t crop_border, int32_t scale, void* ref,
+                          size_t ref_bytes, hcf_stream_t stream);
+int hcf_metric_pair_compare(const void* ref, size_t ref_bytes, const float* sr, int32_t B, int32_t H, int32_t W, int32_t crop_border,
+                            int32_t scale, double* out, uint8_t* image_out, void* work, size_t work_bytes, hcf_stream_t stream);
+
 /* ---- per-op entry points (unit parity tests; tensors are device NCHW fp32) ------------------- */
 /* F.conv2d(x, w, stride 1, padding k/2) with the fused epilogue
  *   y = res2 + rs2 * (res1 + rs1 * act((conv + bias) * scale))
