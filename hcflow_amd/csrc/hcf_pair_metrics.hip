@@ -1,6 +1,9 @@
-// PSNR / SSIM of sample batches against ONE prepared GT (hcf_metric_pair_*): the numbers of hcf_metric_psnr_ssim (hcf_metrics.hip;
-// utils/util.py:790-816, 898-982, utils/imresize.py) with the GT-side work done once, nothing allocated, copied from the host or
-// synchronised per sample, and every sum joined in a fixed order (no atomics).
+// Validation metrics on the device: what test_HCFlow.py computes per image on the CPU -- tensor2img
+// (utils/util.py:790-816), calculate_psnr_ssim (:898-982) with the Y channel of data/util.py:209-230, and the same on MATLAB-style
+// bicubic down-scaled copies (utils/imresize.py) -- in float64 like the reference, every sum joined in a fixed order (no atomics).
+// The project's one PSNR / SSIM / imresize implementation. hcf_metric_pair_* compare sample batches against ONE prepared GT: the
+// GT-side work is done once, nothing is allocated, copied from the host or synchronised per sample. hcf_metric_psnr_ssim and
+// hcf_metric_imresize_down are one-shot host wrappers over them (allocate, embed, compare, read back, free).
 //
 //   embed    gt -> reference buffer: the tensor2img planes as uint8 [B][3 (B,G,R)][H][W]; for scale > 1 the bicubic down-scaled
 //            planes as fp64 [B][3][Ho][Wo] (rows first, not re-quantised) and the weight / index tables of contributions().
@@ -24,9 +27,6 @@
 #include "hcf_common.h"
 
 namespace hcf {
-namespace metrics {
-void contributions(int in_len, int out_len, double scale, std::vector<double>& w, std::vector<int>& idx, int& P);   // hcf_metrics.hip
-}
 namespace pairm {
 
 #define PM_TH 16                       // tile: rows / columns of top-left positions (= owned pixels)
@@ -39,7 +39,7 @@ namespace pairm {
 
 struct Gauss11 { double g[11]; };
 
-// tensor2img of one value: clamp to [0, 1], * 255 in fp32, round half to even (img255_kernel of hcf_metrics.hip)
+// tensor2img of one value: clamp to [0, 1], * 255 in fp32, round half to even (numpy .round())
 __device__ __forceinline__ double quant255(float x) {
   const float v = fminf(fmaxf(x, 0.f), 1.f);
   return rint((double)(v * 255.0f));
@@ -368,6 +368,37 @@ static bool layout(int B, int H, int W, int scale, Layout& L) {
   return true;
 }
 
+static double cubic(double x) {                                   // utils/imresize.py:50-57
+  const double ax = fabs(x), ax2 = ax * ax, ax3 = ax2 * ax;
+  if (ax <= 1) return 1.5 * ax3 - 2.5 * ax2 + 1;
+  if (ax <= 2) return -0.5 * ax3 + 2.5 * ax2 - 4 * ax + 2;
+  return 0.0;
+}
+
+// utils/imresize.py:60-82 (all columns kept: the dropped ones have zero weight)
+static void contributions(int in_len, int out_len, double scale, std::vector<double>& w, std::vector<int>& idx, int& P) {
+  const double kw = (scale < 1) ? 4.0 / scale : 4.0;
+  P = (int)ceil(kw) + 2;
+  w.assign((size_t)out_len * P, 0.0);
+  idx.assign((size_t)out_len * P, 0);
+  for (int o = 0; o < out_len; ++o) {
+    const double u = (o + 1) / scale + 0.5 * (1 - 1 / scale);
+    const double left = floor(u - kw / 2);
+    double sum = 0;
+    for (int k = 0; k < P; ++k) {
+      const int ind = (int)(left + k - 1);
+      const double t = u - ind - 1;
+      const double v = (scale < 1) ? scale * cubic(scale * t) : cubic(t);
+      w[(size_t)o * P + k] = v;
+      sum += v;
+      const int m = 2 * in_len;
+      int r = ((ind % m) + m) % m;                                // mirror padding through aux = [0..n-1, n-1..0]
+      idx[(size_t)o * P + k] = r < in_len ? r : 2 * in_len - 1 - r;
+    }
+    for (int k = 0; k < P; ++k) w[(size_t)o * P + k] /= sum;
+  }
+}
+
 // host tables of contributions(), built once per (length, scale) and kept for the life of the process: embed's stream-ordered
 // uploads read them after the call has returned
 struct Table { std::vector<double> w; std::vector<int> idx; int P = 0; };
@@ -378,7 +409,7 @@ static const Table* table_for(int len, int scale) {
   Table*& t = cache[std::make_pair(len, scale)];
   if (!t) {
     t = new Table();
-    metrics::contributions(len, (len + scale - 1) / scale, 1.0 / scale, t->w, t->idx, t->P);
+    contributions(len, (len + scale - 1) / scale, 1.0 / scale, t->w, t->idx, t->P);
   }
   return t;
 }
@@ -390,6 +421,20 @@ static Gauss11 gauss11() {
   for (int i = 0; i < 11; ++i) gk.g[i] /= sum;
   return gk;
 }
+
+// the device buffers of a one-shot call, freed when it returns. The work queued on them is stream-ordered: the caller
+// synchronises the stream before returning, unless nothing was launched
+struct DevBuf {
+  std::vector<void*> ptrs;
+  bool ok = true;
+  template <class T> T* get(size_t n) {
+    void* p = nullptr;
+    if (hipMalloc(&p, n * sizeof(T)) != hipSuccess) { ok = false; return nullptr; }
+    ptrs.push_back(p);
+    return (T*)p;
+  }
+  ~DevBuf() { for (void* p : ptrs) hipFree(p); }
+};
 
 }  // namespace pairm
 }  // namespace hcf
@@ -466,6 +511,43 @@ int hcf_metric_pair_compare(const void* ref, size_t ref_bytes, const float* sr, 
   fa.H = H; fa.W = W; fa.crop = crop_border; fa.Ho = L.Ho; fa.Wo = L.Wo; fa.low = L.low;
   hipLaunchKernelGGL(pair_finish_kernel, dim3((unsigned)B), dim3(256), 0, st, (const double*)wk, fa, out);
   return hipGetLastError() == hipSuccess ? HCF_OK : HCF_ERR_HIP;
+}
+
+// one-shot: embed gt, compare sr, read the rows back. Everything is refused before the first device call; once work may have
+// been launched the stream is synchronised before the buffers go, on the error paths too
+int hcf_metric_psnr_ssim(const float* gt, const float* sr, int32_t B, int32_t H, int32_t W, int32_t crop_border,
+                         int32_t scale, double* out, hcf_stream_t stream) {
+  Layout L;
+  if (!gt || !sr || !out || crop_border < 0 || scale < 0 || !layout(B, H, W, scale, L)) return HCF_ERR_ARG;
+  if (H - 2 * crop_border < 1 || W - 2 * crop_border < 1) return HCF_ERR_SHAPE;
+  hipStream_t st = (hipStream_t)stream;
+  DevBuf d;
+  char* ref = d.get<char>(L.ref_bytes);
+  char* work = d.get<char>(L.work_bytes);
+  double* rows = d.get<double>((size_t)B * 8);
+  if (!d.ok) return HCF_ERR_NOMEM;
+  int rc = hcf_metric_pair_embed(gt, B, H, W, crop_border, scale, ref, L.ref_bytes, stream);
+  if (rc == HCF_OK)
+    rc = hcf_metric_pair_compare(ref, L.ref_bytes, sr, B, H, W, crop_border, scale, rows, nullptr, work, L.work_bytes, stream);
+  if (rc == HCF_OK && hipMemcpyAsync(out, rows, sizeof(double) * (size_t)B * 8, hipMemcpyDeviceToHost, st) != hipSuccess)
+    rc = HCF_ERR_HIP;
+  if (hipStreamSynchronize(st) != hipSuccess && rc == HCF_OK) rc = HCF_ERR_HIP;
+  return rc;
+}
+
+// one-shot: embed x and read back the reference's down-scaled planes [B][3][Ho][Wo] (rows first, not re-quantised)
+int hcf_metric_imresize_down(const float* x, int32_t B, int32_t H, int32_t W, int32_t scale, double* out, hcf_stream_t stream) {
+  Layout L;
+  if (!x || !out || scale < 2 || !layout(B, H, W, scale, L)) return HCF_ERR_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  DevBuf d;
+  char* ref = d.get<char>(L.ref_bytes);
+  if (!d.ok) return HCF_ERR_NOMEM;
+  int rc = hcf_metric_pair_embed(x, B, H, W, 0, scale, ref, L.ref_bytes, stream);
+  if (rc == HCF_OK && hipMemcpyAsync(out, ref + L.r_low, sizeof(double) * (size_t)B * 3 * L.Ho * L.Wo, hipMemcpyDeviceToHost, st) != hipSuccess)
+    rc = HCF_ERR_HIP;
+  if (hipStreamSynchronize(st) != hipSuccess && rc == HCF_OK) rc = HCF_ERR_HIP;
+  return rc;
 }
 
 }  // extern "C"

@@ -57,8 +57,7 @@ def batched_test_loader(dataset, batch_size: int = 16, keys: Sequence[str] = ("L
 
 
 def evaluate_batch(net, batch: Dict, heats: Iterable[float], n_sample: int, scale: int, crop_border: Optional[int] = None,
-                   seed: Optional[int] = None, noise: Optional[torch.Tensor] = None, lpips_fn=None,
-                   pair_metrics: Optional[M.PairMetrics] = None) -> List[Dict]:
+                   seed: Optional[int] = None, noise: Optional[torch.Tensor] = None, lpips_fn=None) -> List[Dict]:
     """Per image of the batch: {"nll": float, "lr": {psnr, ssim, psnr_y, ssim_y} of LR^ vs LQ (SR nets), and per heat:
     {"psnr", "ssim", "psnr_y", "ssim_y", "bic_psnr", ... (means over the samples), "diversity"}} -- the numbers of the
     reference's per-image log line (test_HCFlow.py:166-175). LPIPS needs the ``lpips`` package's pretrained AlexNet: pass the
@@ -67,9 +66,10 @@ def evaluate_batch(net, batch: Dict, heats: Iterable[float], n_sample: int, scal
     batch at once; without it the key is absent. ``net`` is an eval()-mode HCFlowNet_SR on a GPU.
     ``seed`` fixes the device draws of the samples, ``noise`` ([B,3,H,W] in [0,1)) replaces the dequantisation noise of the
     NLL pass (HCFlowNet_SR_arch.py:52); both default to fresh draws, as in the reference.
-    ``pair_metrics`` (a ``metrics.PairMetrics``): the same dicts with the PSNR / SSIM block kept on the device -- the GT is
-    prepared once per call, every sample is one ``compare`` into a device row, the per-sample LPIPS values stay on the device
-    too, the means over the samples are taken there in float64 and each heat's numbers are read back once."""
+    The PSNR / SSIM block stays on the device (``metrics.PairMetrics``): the GT is prepared once per call, every sample is one
+    ``compare`` into a device row, the per-sample LPIPS values stay on the device too, the means over the samples are taken
+    there in float64 and each heat's numbers are read back once."""
+    pm = M.PairMetrics()
     dev = next(net.parameters()).device
     lq = batch["LQ"].to(dev)
     gt = batch["GT"].to(dev) if "GT" in batch else None
@@ -84,17 +84,12 @@ def evaluate_batch(net, batch: Dict, heats: Iterable[float], n_sample: int, scal
             pix = float(gt.shape[2] * gt.shape[3])
             for b, o in enumerate(obj.double().cpu().tolist()):
                 res[b]["nll"] = -o / (0.6931471805599453 * pix)
-            lr_rows = (M.psnr_ssim(lq, lr_hat, 0, 0) if pair_metrics is None
-                       else M.rows_to_dicts(pair_metrics.compare(pair_metrics.embed(lq, 0, 0), lr_hat)))
-            for b, m in enumerate(lr_rows):
+            for b, m in enumerate(M.rows_to_dicts(pm.compare(pm.embed(lq, 0, 0), lr_hat))):
                 res[b]["lr"] = {k: m[k] for k in ("psnr", "ssim", "psnr_y", "ssim_y")}
-        on_dev = gt is not None and pair_metrics is not None
-        ref = pair_metrics.embed(gt, crop, scale) if on_dev and n_sample > 0 else None      # the GT is prepared once per call
+        ref = pm.embed(gt, crop, scale) if gt is not None and n_sample > 0 else None      # the GT is prepared once per call
         for hi, heat in enumerate(heats):
-            samples = []
-            acc = [dict.fromkeys(M.KEYS, 0.0) for _ in range(B)]
-            lp = [0.0] * B
-            pset, lps = (M.PairSampleSet(pair_metrics, ref, n_sample), []) if ref is not None else (None, [])
+            samples, lps = [], []
+            pset = M.PairSampleSet(pm, ref, n_sample) if ref is not None else None
             for s in range(n_sample):
                 kw = {} if seed is None else {"seed": seed + 1000 * hi + s}
                 # every heat / sample of the sweep conditions on the SAME lq: the deepest level's conditional features (the RRDB
@@ -104,22 +99,12 @@ def evaluate_batch(net, batch: Dict, heats: Iterable[float], n_sample: int, scal
                 if pset is not None:                                   # one compare into a device row; LPIPS stays there too
                     pset.add(sr)
                     if lpips_fn is not None:
-                        lps.append(lpips_fn(2 * gt - 1, 2 * sr - 1).reshape(B, -1).mean(dim=1))
-                elif gt is not None:
-                    for b, m in enumerate(M.psnr_ssim(gt, sr, crop, scale)):
-                        for k in M.KEYS:
-                            acc[b][k] += m[k] / n_sample
-                    if lpips_fn is not None:
-                        d = lpips_fn(2 * gt - 1, 2 * sr - 1).reshape(B, -1).mean(dim=1)      # [B, 1, 1, 1] -> one value per image
-                        for b, v in enumerate(d.double().cpu().tolist()):
-                            lp[b] += v / n_sample
-            if pset is not None:
-                for b, row in enumerate(_heat_rows(pset, lps)):
-                    acc[b], lp[b] = dict(zip(M.KEYS, row[:8])), row[-1]
+                        lps.append(lpips_fn(2 * gt - 1, 2 * sr - 1).reshape(B, -1).mean(dim=1))      # [B, 1, 1, 1] -> one value per image
+            rows = _heat_rows(pset, lps) if pset is not None else [[0.0] * 9] * B             # no samples: zeros, as a sum of none
             for b in range(B):
-                ent = dict(acc[b]) if gt is not None else {}
+                ent = dict(zip(M.KEYS, rows[b][:8])) if gt is not None else {}
                 if gt is not None and lpips_fn is not None:
-                    ent["lpips"] = lp[b]
+                    ent["lpips"] = rows[b][-1]
                 ent["diversity"] = M.diversity([s[b:b + 1] for s in samples]) if n_sample > 1 else 0.0
                 res[b][float(heat)] = ent
     return res
@@ -144,8 +129,7 @@ def sweep_chunks(B: int, n_heats: int, max_batch: int = 16) -> List[Tuple[int, i
 
 
 def evaluate_sweep(net, batch: Dict, heats: Iterable[float], n_sample: int, scale: int, crop_border: Optional[int] = None,
-                   seed: Optional[int] = None, lpips_fn=None, max_batch: int = 16,
-                   pair_metrics: Optional[M.PairMetrics] = None) -> List[Dict]:
+                   seed: Optional[int] = None, lpips_fn=None, max_batch: int = 16) -> List[Dict]:
     """``evaluate_batch``'s per-image dict ("nll", "lr", and per heat the eight metric keys, the optional "lpips", "diversity")
     with the heats SHARING calls: the reference's validation loop draws every (heat, sample) pair of an image in a call of its
     own (test_HCFlow.py:116-131, HCFlow_SR_model.py:296-316); here the rows of a call each carry their temperature
@@ -159,15 +143,15 @@ def evaluate_sweep(net, batch: Dict, heats: Iterable[float], n_sample: int, scal
     is -- other draws than ``evaluate_batch``'s (seed + 1000 hi + s over the image batch), the same distribution. ``seed=None``
     draws a fresh seed per sample pass. The samples are not kept: one ``metrics.SampleStats`` over the R rows accumulates the
     diversity; PSNR / SSIM / LPIPS are evaluated per chunk against the matching GT rows and averaged as in ``evaluate_batch``.
-    With ``pair_metrics`` each chunk's GT rows are prepared once, every (sample, chunk) is one ``compare`` into a device row, and
-    a chunk's means are read back once at the end (see ``evaluate_batch``)."""
+    Each chunk's GT rows are prepared once, every (sample, chunk) is one ``compare`` into a device row, and a chunk's means are
+    read back once at the end (see ``evaluate_batch``)."""
     heats = [float(t) for t in heats]
     dev = next(net.parameters()).device
     lq = batch["LQ"].to(dev)
     gt = batch["GT"].to(dev) if "GT" in batch else None
     B, nH = lq.shape[0], len(heats)
     crop = scale if crop_border is None else crop_border          # test_HCFlow.py:48
-    res = evaluate_batch(net, batch, (), 0, scale, crop_border, pair_metrics=pair_metrics)   # "nll" and "lr" (no heats: the NLL pass alone)
+    res = evaluate_batch(net, batch, (), 0, scale, crop_border)   # "nll" and "lr" (no heats: the NLL pass alone)
     chunks = sweep_chunks(B, nH, max_batch)
     if not chunks or n_sample < 1:
         return res
@@ -178,12 +162,10 @@ def evaluate_sweep(net, batch: Dict, heats: Iterable[float], n_sample: int, scal
     lq_rows = lq[image_of]
     lq_c = [lq_rows[r0:r0 + n] for r0, n in chunks]
     gt_c = None if gt is None else [gt[image_of[r0:r0 + n]] for r0, n in chunks]
-    acc = [dict.fromkeys(M.KEYS, 0.0) for _ in range(R)]
-    lp = [0.0] * R
     stats = None
-    on_dev = gt is not None and pair_metrics is not None
-    if on_dev:
-        psets = [M.PairSampleSet(pair_metrics, pair_metrics.embed(g, crop, scale), n_sample) for g in gt_c]
+    if gt is not None:
+        pm = M.PairMetrics()
+        psets = [M.PairSampleSet(pm, pm.embed(g, crop, scale), n_sample) for g in gt_c]
         lps: List[List[torch.Tensor]] = [[] for _ in chunks]
     with torch.no_grad():
         for s in range(n_sample):
@@ -193,35 +175,20 @@ def evaluate_sweep(net, batch: Dict, heats: Iterable[float], n_sample: int, scal
                 sr = net(lr=lq_c[ci], z=None, u=None, eps_std=taus[r0:r0 + n], reverse=True, training=False, seed=sd,
                          sample_offset=r0, cache_cond=True)
                 outs.append(sr)
-                if gt is None:
-                    continue
-                if on_dev:
+                if gt is not None:
                     psets[ci].add(sr)
                     if lpips_fn is not None:
                         lps[ci].append(lpips_fn(2 * gt_c[ci] - 1, 2 * sr - 1).reshape(n, -1).mean(dim=1))
-                    continue
-                for i, m in enumerate(M.psnr_ssim(gt_c[ci], sr, crop, scale)):
-                    for k in M.KEYS:
-                        acc[r0 + i][k] += m[k] / n_sample
-                if lpips_fn is not None:
-                    d = lpips_fn(2 * gt_c[ci] - 1, 2 * sr - 1).reshape(n, -1).mean(dim=1)
-                    for i, v in enumerate(d.double().cpu().tolist()):
-                        lp[r0 + i] += v / n_sample
             if n_sample > 1:
                 rows = outs[0] if len(outs) == 1 else torch.cat(outs, 0)
                 stats = M.SampleStats.like(rows) if stats is None else stats
                 stats.add(rows)
         div = stats.result()["diversity"].cpu().tolist() if stats is not None else [0.0] * R
-        if on_dev:
-            for ci, (r0, n) in enumerate(chunks):
-                for i, row in enumerate(_heat_rows(psets[ci], lps[ci])):
-                    acc[r0 + i] = dict(zip(M.KEYS, row[:8]))
-                    if lpips_fn is not None:
-                        lp[r0 + i] = row[8]
+        means = [] if gt is None else [row for ci in range(len(chunks)) for row in _heat_rows(psets[ci], lps[ci])]
     for r in range(R):
-        ent = dict(acc[r]) if gt is not None else {}
+        ent = dict(zip(M.KEYS, means[r][:8])) if gt is not None else {}
         if gt is not None and lpips_fn is not None:
-            ent["lpips"] = lp[r]
+            ent["lpips"] = means[r][-1]
         ent["diversity"] = div[r]
         res[r // nH][heats[r % nH]] = ent
     return res

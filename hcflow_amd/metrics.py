@@ -21,7 +21,11 @@ def _prep(t):
 
 def psnr_ssim(gt: torch.Tensor, sr: torch.Tensor, crop_border: int = 0, scale: int = 0) -> List[Dict[str, float]]:
     """Per image: PSNR / SSIM / PSNR_Y / SSIM_Y of tensor2img(gt) vs tensor2img(sr) (borders cropped), and for
-    ``scale > 1`` the same four on the bicubic down-scaled pair (the "bicHR" columns of the reference's log line)."""
+    ``scale > 1`` the same four on the bicubic down-scaled pair (the "bicHR" columns of the reference's log line).
+
+    A one-shot ``PairMetrics.embed`` + ``compare`` inside the library (it allocates, prepares the GT, compares, reads back and
+    synchronises per call): the numbers equal ``PairMetrics.compare``'s bit for bit, two calls agree bit for bit, and an
+    image's numbers do not depend on the rest of the batch. For many samples of one GT use ``PairMetrics``."""
     gt, sr = _prep(gt), _prep(sr)
     assert gt.shape == sr.shape
     B, _, H, W = gt.shape
@@ -31,7 +35,9 @@ def psnr_ssim(gt: torch.Tensor, sr: torch.Tensor, crop_border: int = 0, scale: i
 
 
 def imresize_down(x: torch.Tensor, scale: int) -> np.ndarray:
-    """imresize(tensor2img(x) / 255., 1 / scale) * 255 as a float64 array [B, h, w, 3] in BGR order (0..255 units)."""
+    """imresize(tensor2img(x) / 255., 1 / scale) * 255 as a float64 array [B, h, w, 3] in BGR order (0..255 units), ``scale >= 2``:
+    the down-scaled planes ``PairMetrics.embed`` keeps of a GT (rows first, not re-quantised), i.e. the ones ``psnr_ssim`` and
+    ``PairMetrics.compare`` measure against. Reproducible bit for bit; an image's planes do not depend on the rest of the batch."""
     x = _prep(x)
     B, _, H, W = x.shape
     h, w = math.ceil(H / scale), math.ceil(W / scale)

@@ -336,8 +336,14 @@ int hcf_adam_step(float* param, float* exp_avg, float* exp_avg_sq, const hcf_ada
  * crop_border) (:898-982; Y channel as data/util.py:209-230) and, for scale > 1, the same on
  * imresize(gt, 1/scale), imresize(sr, 1/scale) with crop 0 (utils/imresize.py, MATLAB bicubic with antialiasing).
  * gt, sr: device [B,3,H,W] RGB fp32; out: HOST double [B][8] = psnr, ssim, psnr_y, ssim_y, then the four
- * down-scaled ("bicHR") values (0 when scale <= 1). float64 arithmetic. hcf_metric_imresize_down returns the
- * down-scaled tensor2img image itself (HOST double [B][3 (B,G,R)][ceil(H/scale)][ceil(W/scale)], 0..255 units). */
+ * down-scaled ("bicHR") values (0 when scale <= 1). float64 arithmetic. hcf_metric_imresize_down (scale >= 2) returns the
+ * down-scaled tensor2img image itself (HOST double [B][3 (B,G,R)][ceil(H/scale)][ceil(W/scale)], 0..255 units).
+ * Both are one-shot wrappers over hcf_metric_pair_* below: they allocate their device buffers, run embed (+ compare), copy
+ * the result to the host, synchronise `stream` and free. So the eight numbers are bit for bit those of embed + compare: two
+ * calls agree exactly and an image's numbers do not depend on the rest of the batch; the planes of imresize_down are the
+ * ones embed keeps (rows first, not re-quantised). Checked before anything touches a device: null pointers, B, H, W < 1,
+ * negative crop_border or scale, a shape the pair entries refuse (B > 21845, scale > 1024, ...) -> HCF_ERR_ARG;
+ * H - 2 crop_border < 1 or W - 2 crop_border < 1 -> HCF_ERR_SHAPE. */
 int hcf_metric_psnr_ssim(const float* gt, const float* sr, int32_t B, int32_t H, int32_t W, int32_t crop_border,
                          int32_t scale, double* out, hcf_stream_t stream);
 int hcf_metric_imresize_down(const float* x, int32_t B, int32_t H, int32_t W, int32_t scale, double* out,
@@ -363,7 +369,7 @@ int hcf_metric_stats_finish(void* state, size_t state_bytes, int32_t B, int32_t 
 
 /* PSNR / SSIM of many samples against ONE prepared GT: the eight numbers of hcf_metric_psnr_ssim (util.tensor2img,
  * utils/util.py:790-816; util.calculate_psnr_ssim, :898-982; utils/imresize.py) with the GT-side work done once per GT and
- * nothing allocated, copied from the host or synchronised per sample (hcf_pair_metrics.hip).
+ * nothing allocated, copied from the host or synchronised per sample (hcf_pair_metrics.hip: the one implementation).
  *   hcf_metric_pair_ref_bytes  size of the caller-allocated device buffer that holds a prepared GT batch [B,3,H,W] (private
  *                              layout: the tensor2img planes as uint8; for scale > 1 the bicubic down-scaled planes as fp64 and the
  *                              tables of imresize.py's contributions()); 0 for an invalid shape (utils/util.py:790-816,

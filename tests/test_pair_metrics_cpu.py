@@ -1,5 +1,6 @@
-"""CPU checks of the PairMetrics boundary (include/hcflow.h: hcf_metric_pair_*): the symbols, the size queries, the argument checks
-that run before anything touches a device, and the Python surface. No compute calls."""
+"""CPU checks of the PairMetrics boundary (include/hcflow.h: hcf_metric_pair_* and the one-shot hcf_metric_psnr_ssim /
+hcf_metric_imresize_down over them): the symbols, the size queries, the argument checks that run before anything touches a device,
+and the Python surface. No compute calls."""
 import ctypes as C
 import inspect
 import os
@@ -59,9 +60,16 @@ def test_entries_check_their_arguments_before_any_device_call():
     for args in [(p, rb - 1, p, B, H, W, 4, s, p, n, p, wb), (p, rb, p, B, H, W, 4, s, p, n, p, wb - 1),
                  (p, rb, p, B, H, W, 12, s, p, n, p, wb), (p, rb, p, B, H, W, 16, s, p, n, p, wb)]:
         assert lib.hcf_metric_pair_compare(*args, n) == ERR_SHAPE, args
+    # the one-shots (gt, sr, B, H, W, crop, scale, out) / (x, B, H, W, scale, out): here any device call would fail differently
+    for args in [(n, p, B, H, W, 4, s, p), (p, n, B, H, W, 4, s, p), (p, p, B, H, W, 4, s, n), (p, p, 0, H, W, 4, s, p),
+                 (p, p, B, H, W, -1, s, p), (p, p, B, H, W, 4, -1, p)]:
+        assert lib.hcf_metric_psnr_ssim(*args, n) == ERR_ARG, args
+    assert lib.hcf_metric_psnr_ssim(p, p, B, H, W, 12, s, p, n) == ERR_SHAPE            # H - 2 crop = 0
+    for args in [(n, B, H, W, s, p), (p, B, H, W, s, n), (p, B, H, W, 1, p)]:
+        assert lib.hcf_metric_imresize_down(*args, n) == ERR_ARG, args
 
 
-def test_cpu_tensors_are_refused_and_the_loader_takes_the_object():
+def test_cpu_tensors_are_refused_and_the_loaders_have_no_path_option():
     from hcflow_amd import loader, metrics
     pm = metrics.PairMetrics()
     with pytest.raises(_lib.HcfError, match="no CPU fallback"):
@@ -69,5 +77,4 @@ def test_cpu_tensors_are_refused_and_the_loader_takes_the_object():
     with pytest.raises(TypeError):
         pm.compare(object(), torch.rand(1, 3, 16, 16))
     for fn in (loader.evaluate_batch, loader.evaluate_sweep):
-        par = inspect.signature(fn).parameters
-        assert "pair_metrics" in par and par["pair_metrics"].default is None
+        assert "pair_metrics" not in inspect.signature(fn).parameters         # removed, not defaulted: there is one path

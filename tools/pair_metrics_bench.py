@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Time metrics.PairMetrics (GT prepared once, device-resident rows) against metrics.psnr_ssim on one GPU.
+"""Time metrics.PairMetrics (GT prepared once, device-resident rows) against the one-shot metrics.psnr_ssim on one GPU.
 
     python tools/pair_metrics_bench.py [--parts pairs,sweep] [--shapes 16x640x640,16x160x160,1x1356x2040] [--samples 10]
                                        [--preset SR_DF2K_4X] [--lr-size 160] [--heats 11] [--n-sample 5]
@@ -8,17 +8,16 @@
     python tools/pair_metrics_bench.py --trace-run 16x640x640          # embed + M compares once, for a profiler to wrap
 
 (a) pairs: M samples against one GT (crop 4, scale 4), generated once and held by the tool, per shape BxHxW:
-  psnr_ssim:   M metrics.psnr_ssim calls (the yardstick: each allocates, uploads its tables, synchronises and reads back);
+  psnr_ssim:   M metrics.psnr_ssim calls, the one-shot wrapper per sample (each allocates, prepares the GT again, compares,
+               synchronises and reads back): what preparing the GT on every call costs;
   pair:        PairMetrics.embed + M compare calls into one [M,B,8] device buffer, one synchronise at the end;
   sample_set:  PairMetrics.sample_set + M add + result() + the one readback of "mean".
-  "peak_extra_mb": torch.cuda.max_memory_allocated over one iteration minus what was allocated before it; torch cannot see
-  psnr_ssim's own hipMalloc calls, so its line carries "hipmalloc_mb", the sum of their sizes computed from the shape
-  (hcf_metrics.hip: six image planes + two Y planes + accumulators at full resolution, and for scale > 1 the two resize
-  intermediates and results, two more Y planes and the tables, all float64).
+  "peak_extra_mb": torch.cuda.max_memory_allocated over one iteration minus what was allocated before it (torch cannot see
+  psnr_ssim's own hipMalloc calls: the reference buffer and workspace that `pair` gets from torch).
   "compares_ms": the M compare calls alone between device events (launch gaps included, not a kernel time).
-  "max_rel_dev_from_psnr_ssim": the largest relative difference of a finite entry of the last sample's rows between the paths.
+  "equals_psnr_ssim": the last sample's rows equal psnr_ssim's exactly (one computation; the tool stops if they do not).
 (b) sweep: loader.evaluate_sweep on ONE LR image WITH its GT, `heats` temperatures, `n_sample` samples each, seeded random
-  weights: evaluate_sweep (psnr_ssim per chunk) against evaluate_sweep_pair (pair_metrics=PairMetrics()).
+  weights.
 --kernel-stats: the kernel statistics (or kernel trace) CSV of ONE profiler run of --trace-run (kernel trace only, no counters);
 the total time of the kernels named pair_* joins the output per kernel, and summed over the compare kernels as
 "compare_kernels_ms".
@@ -80,17 +79,6 @@ def run_part(configs, a, extra):
     return out
 
 
-def old_path_hipmalloc_bytes(B, H, W, scale):
-    """The sum of the sizes hcf_metric_psnr_ssim hipMallocs in one call (hcf_metrics.hip), from the shape."""
-    def planes(h, w):                       # psnr_ssim_planes: two Y planes + 10 accumulators per image
-        return 2 * B * h * w * 8 + B * 10 * 8
-    total = 2 * B * 3 * H * W * 8 + planes(H, W)
-    if scale > 1:
-        ho, wo, P = math.ceil(H / scale), math.ceil(W / scale), 4 * scale + 2
-        total += 2 * ((ho + wo) * P * (8 + 4) + B * 3 * ho * W * 8 + B * 3 * ho * wo * 8) + planes(ho, wo)
-    return total
-
-
 def make_samples(B, H, W, M):
     g = torch.Generator(device="cuda").manual_seed(1)
     gt = torch.rand(B, 3, H, W, device="cuda", generator=g)
@@ -108,7 +96,7 @@ def part_pairs(a):
 
         def psnr_ssim():
             for s in samples:
-                res["old"] = metrics.psnr_ssim(gt, s, CROP, SCALE)
+                res["one_shot"] = metrics.psnr_ssim(gt, s, CROP, SCALE)
 
         def pair():
             ref = pm.embed(gt, CROP, SCALE)
@@ -131,14 +119,14 @@ def part_pairs(a):
             e1.synchronize()
             return e0.elapsed_time(e1)
 
-        part = run_part([("psnr_ssim", psnr_ssim), ("pair", pair), ("sample_set", sample_set)], a, lambda m: dict(
-            {"part": "pairs", "shape": [B, 3, H, W], "samples": a.samples, "crop_border": CROP, "scale": SCALE},
-            **({"hipmalloc_mb": round(old_path_hipmalloc_bytes(B, H, W, SCALE) / 2 ** 20, 1)} if m == "psnr_ssim" else {})))
+        part = run_part([("psnr_ssim", psnr_ssim), ("pair", pair), ("sample_set", sample_set)], a, lambda m: {
+            "part": "pairs", "shape": [B, 3, H, W], "samples": a.samples, "crop_border": CROP, "scale": SCALE})
         cmp_ms = [compares_ms() for _ in range(a.rounds)]
-        new = metrics.rows_to_dicts(rows[-1])
-        dev = max(abs(n[k] - o[k]) / abs(o[k]) for n, o in zip(new, res["old"]) for k in metrics.KEYS if math.isfinite(o[k]))
+        same = all(n[k] == o[k] or (math.isnan(n[k]) and math.isnan(o[k]))
+                   for n, o in zip(metrics.rows_to_dicts(rows[-1]), res["one_shot"]) for k in metrics.KEYS)
+        assert same, "psnr_ssim and PairMetrics.compare are one computation and must agree exactly"
         part[1].update({"compares_ms": round(statistics.median(cmp_ms), 3), "compares_min_ms": round(min(cmp_ms), 3),
-                        "compares_max_ms": round(max(cmp_ms), 3), "max_rel_dev_from_psnr_ssim": dev,
+                        "compares_max_ms": round(max(cmp_ms), 3), "equals_psnr_ssim": same,
                         "ratio_psnr_ssim_over_pair": round(part[0]["median_ms"] / part[1]["median_ms"], 2)})
         print(json.dumps(part[1]), flush=True)
         out += part
@@ -160,11 +148,8 @@ def part_sweep(a):
     gt = torch.rand(1, 3, a.lr_size * cfg.scale, a.lr_size * cfg.scale, generator=g)
     heats = [i / max(1, a.heats - 1) for i in range(a.heats)]
     batch = {"LQ": lq.cuda(), "GT": gt.cuda()}
-    pm = metrics.PairMetrics()
     mb = max(16, a.heats)
-    configs = [("evaluate_sweep", lambda: evaluate_sweep(net, batch, heats, a.n_sample, cfg.scale, seed=7, max_batch=mb)),
-               ("evaluate_sweep_pair", lambda: evaluate_sweep(net, batch, heats, a.n_sample, cfg.scale, seed=7, max_batch=mb,
-                                                              pair_metrics=pm))]
+    configs = [("evaluate_sweep", lambda: evaluate_sweep(net, batch, heats, a.n_sample, cfg.scale, seed=7, max_batch=mb))]
     return run_part(configs, a, lambda m: {"part": "sweep", "preset": a.preset, "lr": [1, 3, a.lr_size, a.lr_size],
                                            "heats": a.heats, "n_sample": a.n_sample, "with_gt": True})
 
