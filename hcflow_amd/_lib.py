@@ -52,6 +52,7 @@ SYMBOLS = [
     "hcf_op_fcn12", "hcf_op_conv2d_step_inverse",
     "hcf_inverse_taus", "hcf_metric_stats_bytes", "hcf_metric_stats_add", "hcf_metric_stats_finish",
     "hcf_metric_pair_ref_bytes", "hcf_metric_pair_workspace", "hcf_metric_pair_embed", "hcf_metric_pair_compare",
+    "hcf_op_conv2d_views", "hcf_op_conv2d_wgrad_views", "hcf_op_conv_epilogue_backward_views",
 ]
 
 
@@ -68,6 +69,11 @@ class hcf_config(C.Structure):
         ("rrdb_nb", C.c_int32 * 2), ("rrdb_nf", C.c_int32), ("rrdb_gc", C.c_int32),
         ("lu_decomposed", C.c_int32),
     ]
+
+
+class hcf_view(C.Structure):
+    """A channel window [c0, c0 + n) of a caller-owned NHWC buffer of ``cs`` floats per pixel (include/hcflow.h: hcf_view)."""
+    _fields_ = [("p", C.c_void_p), ("cs", C.c_int32), ("c0", C.c_int32), ("n", C.c_int32), ("up", C.c_int32)]
 
 
 _lib = None
@@ -197,6 +203,11 @@ def load() -> C.CDLL:
                                  C.POINTER(i32), vp]
     lib.hcf_op_conv2d_step_inverse.argtypes = [fp, i32, fp, fp, fp, i32, fp, i32, i32, i32, fp, fp, fp, fp, fp, i32, i32, i32, i32,
                                                C.POINTER(i32), vp]
+    pv = C.POINTER(hcf_view)
+    lib.hcf_op_conv2d_views.argtypes = [pv, i32, i32, i32, i32, fp, fp, fp, i32, i32, pv, f32, pv, f32, pv, i32, C.POINTER(i32), vp]
+    lib.hcf_op_conv2d_wgrad_views.argtypes = [pv, i32, i32, i32, i32, pv, i32, fp, C.POINTER(i32), vp]
+    lib.hcf_op_conv_epilogue_backward_views.argtypes = [pv, pv, fp, i32, i32, f32, pv, i32, f32, pv, pv, fp, fp, f32, fp, fp, fp,
+                                                        i32, i32, i32, C.POINTER(i32), vp]
     lib.hcf_op_squeeze2d.argtypes = [fp, fp, i32, i32, i32, i32, i32, vp]
     lib.hcf_op_unsqueeze2d.argtypes = [fp, fp, i32, i32, i32, i32, i32, vp]
     lib.hcf_op_step_inverse.argtypes = [fp, fp, fp, i32, i32, i32, i32, i32, i32, i32, fp, fp, fp, vp]

@@ -5,6 +5,15 @@
 // A `View` names a channel window [c0, c0+n) of such a tensor, optionally read through a nearest
 // upsample by 2^up (the reference's F.interpolate(mode='nearest'), FlowNet_SR_x4.py:98,117, is
 // folded into the consumer's addressing and never materialised).
+//
+// Window contract of the conv kernels (hcf_conv.hip, hcf_conv_f16x3.hip, hcf_conv_wino.hip, hcf_conv_wgrad.hip, the epilogue
+// backward of hcf_train.hip; pinned per op by tests/test_gpu_view_convs.py). The floats around a window belong to somebody else:
+// other channels of the same pixel records are live tensors (z2 beside z1, the growth channels a later conv fills), and scratch
+// may hold NaN or inf. A kernel stages a window in units of 4 channels, so it may READ up to 3 floats past the window's last
+// channel -- with 16-byte addressable views (view_vec16) these stay inside the pixel record, on the scalar staging path (c0 or cs
+// not a multiple of 4, or an unaligned base) the last pixel's unit reaches up to 3 floats (12 bytes) past the end of the buffer,
+// which is why every activation buffer is allocated with 64 bytes of slack. Whatever is read there is masked before it meets an
+// accumulator: no value outside the source windows reaches a result, NaN included. A kernel never WRITES outside `out`'s window.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <vector>

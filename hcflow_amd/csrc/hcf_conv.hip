@@ -300,41 +300,55 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(const ConvArgs a) {
   }
 }
 
-template <int TAPS, int NT>
-static int launch_t(const ConvArgs& a, hipStream_t st) {
+// What launch_conv decides, without a launch (hcf_launch.h): the kernel's NT, its VEC staging, the epilogue form and the grid.
+ExactPlan plan_conv_exact(const ConvArgs& a, int taps) {
+  ExactPlan p = {};
+  p.status = HCF_ERR_ARG;
+  if (a.nsrc < 1 || a.nsrc > kMaxSrc || a.H >= 32768 || a.W >= 32768 || a.H < 1 || a.W < 1) return p;
+  for (int i = 0; i < a.nsrc; ++i)
+    if (!up_divides(a.H, a.W, a.src[i].up)) return p;
+  p.nt = (a.out.n + 31) / 32;
+  const bool known = ((taps == 9 || taps == 1) && p.nt >= 1 && p.nt <= 3) || (taps == 25 && p.nt == 2);
+  if (!known) { p.status = HCF_ERR_UNSUPPORTED; return p; }
   const int tiles_x = (a.W + TW - 1) / TW, tiles_y = (a.H + TH - 1) / TH;
   const long long nblk = (long long)a.B * tiles_x * tiles_y;
-  if (nblk <= 0 || nblk > 0x7fffffffLL) return HCF_ERR_ARG;
-  bool vec = true;
-  for (int i = 0; i < a.nsrc; ++i) vec = vec && view_vec16(a.src[i]);
+  if (nblk <= 0 || nblk > 0x7fffffffLL) return p;
+  p.vec = true;
+  for (int i = 0; i < a.nsrc; ++i) p.vec = p.vec && view_vec16(a.src[i]);
+  p.vec_epi = a.out.p && (a.out.n & 3) == 0 && view_vec16_or_null(a.out) && view_vec16_or_null(a.res1) && view_vec16_or_null(a.res2);
+  p.grid = (unsigned)nblk;
+  p.status = HCF_OK;
+  return p;
+}
+
+template <int TAPS, int NT>
+static int launch_t(const ConvArgs& a, const ExactPlan& p, hipStream_t st) {
   ConvArgs b = a;
-  b.vec_epi = a.out.p && (a.out.n & 3) == 0 && view_vec16_or_null(a.out) && view_vec16_or_null(a.res1) && view_vec16_or_null(a.res2);
-  if (vec)
-    hipLaunchKernelGGL((conv_mfma_kernel<TAPS, NT, true>), dim3((unsigned)nblk), dim3(256), 0, st, b);
+  b.vec_epi = p.vec_epi;
+  if (p.vec)
+    hipLaunchKernelGGL((conv_mfma_kernel<TAPS, NT, true>), dim3(p.grid), dim3(256), 0, st, b);
   else
-    hipLaunchKernelGGL((conv_mfma_kernel<TAPS, NT, false>), dim3((unsigned)nblk), dim3(256), 0, st, b);
+    hipLaunchKernelGGL((conv_mfma_kernel<TAPS, NT, false>), dim3(p.grid), dim3(256), 0, st, b);
   return hipGetLastError() == hipSuccess ? HCF_OK : HCF_ERR_HIP;
 }
 
 int launch_conv(const ConvArgs& a, int taps, hipStream_t st) {
-  if (a.nsrc < 1 || a.nsrc > kMaxSrc || a.H >= 32768 || a.W >= 32768 || a.H < 1 || a.W < 1) return HCF_ERR_ARG;
-  for (int i = 0; i < a.nsrc; ++i)
-    if (!up_divides(a.H, a.W, a.src[i].up)) return HCF_ERR_ARG;
-  const int nt = (a.out.n + 31) / 32;
+  const ExactPlan p = plan_conv_exact(a, taps);
+  if (p.status != HCF_OK) return p.status;
   if (taps == 9) {
-    switch (nt) {
-      case 1: return launch_t<9, 1>(a, st);
-      case 2: return launch_t<9, 2>(a, st);
-      case 3: return launch_t<9, 3>(a, st);
+    switch (p.nt) {
+      case 1: return launch_t<9, 1>(a, p, st);
+      case 2: return launch_t<9, 2>(a, p, st);
+      case 3: return launch_t<9, 3>(a, p, st);
     }
   } else if (taps == 1) {
-    switch (nt) {
-      case 1: return launch_t<1, 1>(a, st);
-      case 2: return launch_t<1, 2>(a, st);
-      case 3: return launch_t<1, 3>(a, st);
+    switch (p.nt) {
+      case 1: return launch_t<1, 1>(a, p, st);
+      case 2: return launch_t<1, 2>(a, p, st);
+      case 3: return launch_t<1, 3>(a, p, st);
     }
-  } else if (taps == 25 && nt == 2) {            // 5x5 pad 2, 64-channel blocks: AlexNet conv1 (on the 4x4 space-to-depth grid) / conv2
-    return launch_t<25, 2>(a, st);
+  } else if (taps == 25 && p.nt == 2) {            // 5x5 pad 2, 64-channel blocks: AlexNet conv1 (on the 4x4 space-to-depth grid) / conv2
+    return launch_t<25, 2>(a, p, st);
   }
   return HCF_ERR_UNSUPPORTED;
 }

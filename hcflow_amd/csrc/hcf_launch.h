@@ -24,6 +24,16 @@ static inline bool lds_opt_in(const void* kernel, int bytes, bool (&done)[64]) {
   return done[dev] = true;
 }
 
+// ---- exact fp32 conv (hcf_conv.hip) ----
+struct ExactPlan {
+  int status;              // HCF_OK, or why launch_conv refuses the call
+  int nt; bool vec;        // conv_mfma_kernel<taps, nt, vec>
+  int vec_epi;             // the ConvArgs field "set by the launcher" (the 1x1 kernel of 64 / 96 channels has the scalar epilogue only)
+  unsigned grid;
+};
+ExactPlan plan_conv_exact(const ConvArgs& a, int taps);
+bool conv_epilogue_bwd_vec(const EpiBwdArgs& a);      // launch_conv_epilogue_bwd runs conv_epilogue_bwd_vec_kernel (hcf_train.hip)
+
 // ---- f16x3 conv (hcf_conv_f16x3.hip) ----
 struct F16x3Variant { int ntb, vec, up, fuse2, tailc, th, scaled, k1, n16; };      // conv_f16x3_kernel's template arguments (no padding: rows compare bytewise)
 struct F16x3Plan {

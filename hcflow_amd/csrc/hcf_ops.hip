@@ -998,6 +998,206 @@ int hcf_op_conv2d_step_inverse(const float* h2, int32_t hid, const float* w3, co
 
 }  // extern "C"
 
+// ---- the conv kernels on the caller's channel windows, one launch per call (tests/test_gpu_view_convs.py) --------------
+namespace hcf {
+
+// a well-formed descriptor (include/hcflow.h: hcf_view); max_up = 0 for every view that is not a conv source
+static bool view_ok(const hcf_view* v, int max_up) {
+  return v && v->p && v->cs >= 1 && v->c0 >= 0 && v->n >= 1 && (long long)v->c0 + v->n <= v->cs && v->up >= 0 && v->up <= max_up;
+}
+static View as_view(const hcf_view* v) { return v ? mkview(v->p, v->cs, v->c0, v->n, v->up) : mkview(nullptr, 0, 0, 0); }
+
+// 1 .. 3 source descriptors of a conv on [B, H, W] -> views (unused slots repeat source 0, as everywhere); false: HCF_ERR_ARG
+static bool views_of_sources(const hcf_view* src, int n_src, int H, int W, View* dst, int* srcs, int& cin) {
+  if (!src || n_src < 1 || n_src > kMaxSrc) return false;
+  cin = 0;
+  for (int i = 0; i < n_src; ++i) {
+    if (!view_ok(&src[i], 8) || !up_divides(H, W, src[i].up)) return false;
+    dst[i] = as_view(&src[i]);
+    srcs[i] = src[i].n;
+    cin += src[i].n;
+  }
+  for (int i = n_src; i < kMaxSrc; ++i) dst[i] = dst[0];
+  return true;
+}
+
+// *slot (zero-initialised by the caller) = max |x| over the source windows, as the running maximum of the engine's backward is
+static int sources_absmax(const View* src, int n_src, int B, int H, int W, float* slot, hipStream_t st) {
+  int rc = HCF_OK;
+  for (int i = 0; i < n_src && rc == HCF_OK; ++i) rc = launch_absmax(src[i], B, H >> src[i].up, W >> src[i].up, slot, st);
+  return rc;
+}
+
+}  // namespace hcf
+
+extern "C" {
+
+int hcf_op_conv2d_views(const hcf_view* src, int32_t n_src, int32_t B, int32_t H, int32_t W, const float* w, const float* bias,
+                        const float* scale, int32_t k, int32_t act, const hcf_view* res1, float rs1, const hcf_view* res2,
+                        float rs2, const hcf_view* out, int32_t scaled, int32_t* info, hcf_stream_t stream) {
+  if (!w || !info || (k != 1 && k != 3) || B < 1 || H < 1 || W < 1 || act < ACT_NONE || act > ACT_LRELU) return HCF_ERR_ARG;
+  if (!view_ok(out, 0) || out->n > 96) return HCF_ERR_ARG;
+  if ((res1 && (!view_ok(res1, 0) || res1->n != out->n)) || (res2 && (!view_ok(res2, 0) || res2->n != out->n))) return HCF_ERR_ARG;
+  ConvArgs a;
+  memset(&a, 0, sizeof(a));
+  int cin = 0, srcs[kMaxSrc];
+  if (!views_of_sources(src, n_src, H, W, a.src, srcs, cin)) return HCF_ERR_ARG;
+  for (int i = 0; i < 16; ++i) info[i] = 0;
+  hipStream_t st = (hipStream_t)stream;
+  Tmp t;
+  int rc = HCF_OK;
+  a.nsrc = n_src;
+  a.B = B; a.H = H; a.W = W;
+  const int cout = out->n, taps = k * k;
+  const int npad = ((cout + 31) / 32) * 32;
+  a.bias = fused_table(t, bias, cout, npad, 0.f);
+  a.scale = fused_table(t, scale, cout, npad, 1.f);
+  a.act = act;
+  a.out = as_view(out);
+  a.res1 = as_view(res1); a.rs1 = res1 ? rs1 : 0.f;
+  a.res2 = as_view(res2); a.rs2 = res2 ? rs2 : 0.f;
+  if (!t.ok) return HCF_ERR_NOMEM;
+  bool f16 = g_op_precision == PREC_F16X3 && cout <= 64;
+  if (f16) {
+    if ((rc = fused_flag(t, a, st)) != HCF_OK) return rc;
+    if (scaled) {
+      float* m = t.dev(1);
+      if (!m) return HCF_ERR_NOMEM;
+      if (hipMemsetAsync(m, 0, sizeof(float), st) != hipSuccess) return HCF_ERR_HIP;
+      if ((rc = sources_absmax(a.src, n_src, B, H, W, m, st)) != HCF_OK) { hipStreamSynchronize(st); return rc; }
+      a.in_max = m;
+    }
+    // a stand-alone 1x1 conv the f16x3 plan refuses runs on the exact kernel, as in the engine
+    if (k == 1 && plan_conv_f16x3(a, 1).status == HCF_ERR_UNSUPPORTED) {
+      f16 = false;
+      a.ovf = nullptr; a.zeros = nullptr; a.in_max = nullptr;
+    }
+  }
+  std::vector<float> pk;
+  int nchunk = 0, np = 0;
+  if (f16) {
+    if (!pack_conv_weights_f16x3(w, cin, cout, taps, srcs, n_src, pk, nchunk, np)) return HCF_ERR_UNSUPPORTED;
+  } else {
+    pack_conv_weights(w, cin, cout, taps, srcs, n_src, pk, nchunk, np);
+  }
+  a.wpack = t.up(pk);
+  a.nchunk = nchunk;
+  if (!t.ok) return HCF_ERR_NOMEM;
+  rc = HCF_ERR_UNSUPPORTED;
+  if (f16 && k == 3 && !(g_f16x3_ablation & 256)) {      // eligible layers take the Winograd form, as in the engine
+    std::vector<float> pkw;
+    const float* wino = pack_conv_weights_wino(w, cin, cout, srcs, n_src, pkw) ? t.up(pkw) : nullptr;
+    if (!t.ok) return HCF_ERR_NOMEM;
+    if (wino) rc = launch_conv_wino(a, wino, st);
+    if (rc != HCF_ERR_UNSUPPORTED) {
+      info[0] = cout == 64 ? 3 : 2; info[1] = rc; info[11] = conv_wino_grid(B, H, W, cout / 32);
+    }
+  }
+  if (rc == HCF_ERR_UNSUPPORTED && f16) {
+    const F16x3Plan p = plan_conv_f16x3(a, taps);
+    const int32_t v[14] = {p.status, p.v.ntb, p.v.vec, p.v.up, p.v.fuse2, p.v.tailc, p.v.th, p.v.scaled, p.v.k1, p.v.n16,
+                           (int32_t)p.grid, (int32_t)p.block, p.vec_epi, p.strip_w};
+    info[0] = 1;
+    for (int i = 0; i < 14; ++i) info[1 + i] = v[i];
+    rc = p.status != HCF_OK ? p.status : launch_conv_f16x3(a, taps, st);
+  } else if (rc == HCF_ERR_UNSUPPORTED) {
+    const ExactPlan p = plan_conv_exact(a, taps);
+    info[0] = 0; info[1] = p.status; info[2] = p.vec; info[3] = p.vec_epi; info[4] = p.nt;
+    info[11] = (int32_t)p.grid; info[12] = 256; info[13] = p.vec_epi;
+    rc = p.status != HCF_OK ? p.status : launch_conv(a, taps, st);
+  }
+  if (hipStreamSynchronize(st) != hipSuccess) return HCF_ERR_HIP;      // (also behind a refusal: the temporaries are freed behind the staging work)
+  if (rc != HCF_OK) return rc;
+  if (a.ovf) {
+    int h = 0;
+    if (hipMemcpy(&h, a.ovf, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return HCF_ERR_HIP;
+    info[15] = h;
+    if (h) return HCF_ERR_UNSUPPORTED;      // an input beyond the f16 range
+  }
+  return HCF_OK;
+}
+
+int hcf_op_conv2d_wgrad_views(const hcf_view* src, int32_t n_src, int32_t B, int32_t H, int32_t W, const hcf_view* g, int32_t taps,
+                              float* dw, int32_t* info, hcf_stream_t stream) {
+  if (!dw || !info || (taps != 1 && taps != 9) || B < 1 || H < 1 || W < 1 || !view_ok(g, 0) || g->n > 96) return HCF_ERR_ARG;
+  WgradArgs wa;
+  memset(&wa, 0, sizeof(wa));
+  int cin = 0, srcs[kMaxSrc];
+  if (!views_of_sources(src, n_src, H, W, wa.src, srcs, cin)) return HCF_ERR_ARG;
+  for (int i = 0; i < 16; ++i) info[i] = 0;
+  hipStream_t st = (hipStream_t)stream;
+  Tmp t;
+  int rc = HCF_OK;
+  wa.nsrc = n_src;
+  wa.g = as_view(g);
+  wa.B = B; wa.H = H; wa.W = W; wa.taps = taps;
+  const size_t nw = (size_t)g->n * cin * taps;
+  wa.dw = t.dev(nw);
+  if (!t.ok) return HCF_ERR_NOMEM;
+  if (hipMemsetAsync(wa.dw, 0, nw * sizeof(float), st) != hipSuccess) return HCF_ERR_HIP;
+  if (g_op_precision == PREC_F16X3) {          // as hcf_op_conv2d_backward: g scaled from max |g|, X must sit inside the f16 range
+    float* gm = t.dev(2);
+    if (!t.ok) return HCF_ERR_NOMEM;
+    if (hipMemsetAsync(gm, 0, 2 * sizeof(float), st) != hipSuccess) return HCF_ERR_HIP;
+    rc = launch_absmax(wa.g, B, H, W, gm, st);
+    if (rc == HCF_OK) rc = sources_absmax(wa.src, n_src, B, H, W, gm + 1, st);
+    float xmax = 0.f;
+    if (hipMemcpyAsync(&xmax, gm + 1, sizeof(float), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+      return HCF_ERR_HIP;
+    if (rc != HCF_OK) return rc;
+    if (xmax < 65504.f) wa.g_max = gm;           // NaN / inf compare false -> fp32 kernel
+  }
+  wa.part_cap = conv_wgrad_scratch_floats(wa);
+  wa.part = t.dev(wa.part_cap);
+  if (!t.ok) return HCF_ERR_NOMEM;
+  const WgradPlan p = plan_conv_wgrad(wa);
+  const int32_t v[8] = {p.status, p.f16, p.taps, p.vec, p.db, p.strip_w, p.tpb, p.nblk_x};
+  for (int i = 0; i < 8; ++i) info[i] = v[i];
+  rc = launch_conv_wgrad(wa, st);
+  if (rc == HCF_OK && hipMemcpyAsync(dw, wa.dw, nw * sizeof(float), hipMemcpyDeviceToHost, st) != hipSuccess) rc = HCF_ERR_HIP;
+  if (hipStreamSynchronize(st) != hipSuccess) return HCF_ERR_HIP;
+  return rc;
+}
+
+int hcf_op_conv_epilogue_backward_views(const hcf_view* gy, const hcf_view* y, const float* scale, int32_t act, int32_t has1,
+                                        float rs1, const hcf_view* g1, int32_t has2, float rs2, const hcf_view* g2,
+                                        const hcf_view* gpre, float* sum_pre, float* sum_zy, float zy_mult, float* absmax,
+                                        float* absmax2, const float* carry2, int32_t B, int32_t H, int32_t W, int32_t* info,
+                                        hcf_stream_t stream) {
+  if (!info || !view_ok(gy, 0) || !view_ok(gpre, 0) || gy->n > 256 || gpre->n != gy->n || B < 1 || H < 1 || W < 1) return HCF_ERR_ARG;
+  const int n = gy->n;
+  if ((y && (!view_ok(y, 0) || y->n != n)) || (g1 && (!view_ok(g1, 0) || g1->n != n)) || (g2 && (!view_ok(g2, 0) || g2->n != n)))
+    return HCF_ERR_ARG;
+  if (act < ACT_NONE || act > ACT_LRELU || (!y && (act != ACT_NONE || sum_zy)) || (absmax2 && !absmax)) return HCF_ERR_ARG;
+  for (int i = 0; i < 4; ++i) info[i] = 0;
+  hipStream_t st = (hipStream_t)stream;
+  Tmp t;
+  int rc = HCF_OK;
+  EpiBwdArgs e;
+  memset(&e, 0, sizeof(e));
+  e.B = B; e.H = H; e.W = W;
+  e.gy = as_view(gy);
+  e.gpre = as_view(gpre);
+  e.y = y ? as_view(y) : mkview(nullptr, gy->cs, gy->c0, n);
+  if (scale) e.scale = fused_table(t, scale, n, ((n + 31) / 32) * 32, 1.f);
+  e.act = act;
+  e.has1 = has1; e.rs1 = rs1; e.has2 = has2; e.rs2 = rs2;
+  e.g1 = (has1 && g1) ? as_view(g1) : mkview(nullptr, gy->cs, gy->c0, n);
+  e.g2 = (has2 && g2) ? as_view(g2) : mkview(nullptr, gy->cs, gy->c0, n);
+  e.sum_pre = sum_pre; e.sum_zy = sum_zy; e.zy_mult = zy_mult;
+  e.absmax = absmax; e.absmax2 = absmax2; e.carry2 = carry2;
+  const int nblk = conv_epilogue_bwd_blocks(B, H, W);
+  if (sum_pre || sum_zy) e.part = part_rows(t, (size_t)nblk * 2 * n, st, rc);
+  if (!t.ok) return HCF_ERR_NOMEM;
+  info[0] = conv_epilogue_bwd_vec(e); info[1] = nblk;
+  if (rc == HCF_OK) rc = launch_conv_epilogue_bwd(e, st);
+  if (rc == HCF_OK && e.part) rc = reduce_rows(t, e.part, nblk, n, n, sum_pre, sum_zy, zy_mult, st);
+  if (hipStreamSynchronize(st) != hipSuccess) return HCF_ERR_HIP;
+  return rc;
+}
+
+}  // extern "C"
+
 // ---- micro-benchmark of the conv kernel (tools/conv_bench.py) ---------------------------------
 // Allocates NHWC slabs once, launches the conv `iters` times back to back and times them with HIP
 // events on the given stream. Inputs are uniform random in [-1, 1) (never zeros: DVFS, cdna guide

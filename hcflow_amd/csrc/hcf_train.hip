@@ -196,12 +196,17 @@ int launch_sum_jobs(const SumJob* jobs_dev, int njobs, hipStream_t st) {
   HCF_RET_T();
 }
 
+// the vector kernel's condition (hcf_launch.h): whole channel quads, every view and the scale table 16-byte addressable
+bool conv_epilogue_bwd_vec(const EpiBwdArgs& a) {
+  return (a.gy.n & 3) == 0 && a.gy.n >= 4 && view_vec16_or_null(a.gy) && view_vec16_or_null(a.gpre) && view_vec16_or_null(a.y) &&
+         view_vec16_or_null(a.g1) && view_vec16_or_null(a.g2) && ptr16(a.scale);
+}
+
 int launch_conv_epilogue_bwd(const EpiBwdArgs& a, hipStream_t st) {
   if (a.gy.n < 1 || a.gy.n > 256 || a.gpre.n != a.gy.n) return HCF_ERR_ARG;
   const long long npix = (long long)a.B * a.H * a.W;
   const int ppb = epi_bwd_ppb();
-  const bool vec = (a.gy.n & 3) == 0 && a.gy.n >= 4 && view_vec16_or_null(a.gy) && view_vec16_or_null(a.gpre) && view_vec16_or_null(a.y) &&
-                   view_vec16_or_null(a.g1) && view_vec16_or_null(a.g2) && ptr16(a.scale);
+  const bool vec = conv_epilogue_bwd_vec(a);
   if (vec) hipLaunchKernelGGL(conv_epilogue_bwd_vec_kernel, dim3((unsigned)((npix + ppb - 1) / ppb)), dim3(256), 0, st, a, npix, ppb);
   else hipLaunchKernelGGL(conv_epilogue_bwd_kernel, dim3((unsigned)((npix + ppb - 1) / ppb)), dim3(256), 0, st, a, npix, ppb);
   HCF_RET_T();

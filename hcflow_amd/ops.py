@@ -7,7 +7,7 @@ tensors, on the stream current there.
 from __future__ import annotations
 
 import ctypes as C
-from typing import Optional, Sequence
+from typing import NamedTuple, Optional, Sequence
 
 import torch
 
@@ -104,16 +104,16 @@ INFO_FIELDS = ("launcher", "status", "ntb", "vec", "up", "fuse2", "tailc", "th",
                "pre", "range_flag")
 
 
-def _fused_launch(name, device, info, *args):
-    """_lib.launch of a fused-conv entry; a failure carries the launch record gathered so far (``HcfError.info``) and the
-    entry's status (``HcfError.status``)."""
+def _fused_launch(name, device, info, *args, fields=INFO_FIELDS):
+    """_lib.launch of an entry that reports its launch in ``info``; a failure carries the record gathered so far
+    (``HcfError.info``) and the entry's status (``HcfError.status``)."""
     try:
         _lib.launch(name, device, *args)
     except _lib.HcfError as e:
-        e.info = dict(zip(INFO_FIELDS, (int(v) for v in info)))
+        e.info = dict(zip(fields, (int(v) for v in info)))
         e.status = next((k for k, v in _lib.ERR_NAMES.items() if "%s (%d)" % (v, k) in str(e)), None)
         raise
-    return dict(zip(INFO_FIELDS, (int(v) for v in info)))
+    return dict(zip(fields, (int(v) for v in info)))
 
 
 def fcn12(srcs: Sequence[torch.Tensor], w1, bias1, scale1, w2, bias2, scale2, pre=None, ups: Optional[Sequence[int]] = None,
@@ -154,6 +154,72 @@ def conv2d_step_inverse(h2, w3, bias3, scale3, z, mode: int, ns: int, mat, an_bi
                         int(mode), int(ns), _host(mat), _host(an_bias.flatten()), _host(an_logs.flatten()), out, zpad,
                         int(zpad_n or 0), B, H, W, info)
     return out, zpad, rec
+
+
+class View(NamedTuple):
+    """Channels [c0, c0 + n) of an NHWC buffer of ``cs`` floats per pixel that starts ``off`` floats into the flat CUDA fp32 tensor
+    ``buf`` (include/hcflow.h: hcf_view). The *_views entries below use such windows as they are: nothing is copied or cleared."""
+    buf: torch.Tensor
+    off: int
+    cs: int
+    c0: int
+    n: int
+    up: int = 0
+
+
+def _views(vs, device):
+    """ctypes array of hcf_view for a sequence of View (None stays None: a NULL descriptor)."""
+    if vs is None:
+        return None
+    for v in vs:
+        if not (v.buf.is_cuda and v.buf.device == device and v.buf.dtype == torch.float32 and v.buf.is_contiguous()):
+            raise _lib.HcfError("a view's buffer must be a contiguous CUDA fp32 tensor on %s" % device)
+    return (_lib.hcf_view * len(vs))(*[_lib.hcf_view(v.buf.data_ptr() + 4 * int(v.off), int(v.cs), int(v.c0), int(v.n), int(v.up))
+                                      for v in vs])
+
+
+CONV_VIEWS_FIELDS = ("launcher", "status", "ntb", "vec", "up", "fuse2", "tailc", "th", "scaled", "k1", "n16", "grid", "block", "vec_epi",
+                     "strip_w", "range_flag")
+WGRAD_VIEWS_FIELDS = ("status", "f16", "taps", "vec", "db", "strip_w", "tpb", "nblk_x")
+EPI_VIEWS_FIELDS = ("vec", "blocks")
+
+
+def conv2d_views(srcs: Sequence[View], B: int, H: int, W: int, weight, bias, scale, act, out: View, res1: Optional[View] = None,
+                 rs1: float = 0.0, res2: Optional[View] = None, rs2: float = 0.0, scaled: bool = False):
+    """conv2d() on the caller's windows, written into ``out``'s window (include/hcflow.h: hcf_op_conv2d_views): the launch record.
+    launcher 0 (exact kernel): ``ntb`` / ``vec`` / ``up`` hold VEC, vec_epi and NT of conv_mfma_kernel."""
+    dev = out.buf.device
+    k = int(weight.shape[2])
+    assert int(weight.shape[0]) == out.n and int(weight.shape[1]) == sum(s.n for s in srcs)
+    info = (C.c_int32 * 16)()
+    return _fused_launch("hcf_op_conv2d_views", dev, info, _views(srcs, dev), len(srcs), B, H, W, _host(weight),
+                         _host(bias), _host(scale), k, ACT[act], _views(None if res1 is None else [res1], dev), float(rs1),
+                         _views(None if res2 is None else [res2], dev), float(rs2), _views([out], dev), int(bool(scaled)), info,
+                         fields=CONV_VIEWS_FIELDS)
+
+
+def conv2d_wgrad_views(srcs: Sequence[View], B: int, H: int, W: int, g: View, k: int):
+    """(dw on the CPU [g.n, cin, k, k], the plan record) of hcf_op_conv2d_wgrad_views."""
+    dev = g.buf.device
+    dw = torch.empty(g.n, sum(s.n for s in srcs), k, k, dtype=torch.float32)
+    info = (C.c_int32 * 16)()
+    rec = _fused_launch("hcf_op_conv2d_wgrad_views", dev, info, _views(srcs, dev), len(srcs), B, H, W,
+                        _views([g], dev), k * k, dw, info, fields=WGRAD_VIEWS_FIELDS)
+    return dw, rec
+
+
+def conv_epilogue_backward_views(gy: View, B: int, H: int, W: int, y: Optional[View] = None, scale=None, act=None, rs1=None,
+                                 g1: Optional[View] = None, rs2=None, g2: Optional[View] = None, gpre: Optional[View] = None,
+                                 sum_pre=None, sum_zy=None, zy_mult: float = 1.0, absmax=None, absmax2=None, carry2=None):
+    """hcf_op_conv_epilogue_backward_views: gpre (default: gy, in place) is written, g1 / g2 accumulated in the caller's buffers;
+    sum_pre / sum_zy / absmax / absmax2 / carry2 are CUDA tensors or None. Returns the record (vec, blocks)."""
+    dev = gy.buf.device
+    one = lambda v: _views(None if v is None else [v], dev)
+    info = (C.c_int32 * 4)()
+    return _fused_launch("hcf_op_conv_epilogue_backward_views", dev, info, one(gy), one(y), _host(scale), ACT[act],
+                         int(rs1 is not None), float(rs1 or 0.0), one(g1), int(rs2 is not None), float(rs2 or 0.0), one(g2),
+                         one(gy if gpre is None else gpre), sum_pre, sum_zy, float(zy_mult), absmax, absmax2, carry2, B, H, W, info,
+                         fields=EPI_VIEWS_FIELDS)
 
 
 def step_forward_head(z, mat, an_bias, an_logs) -> torch.Tensor:

@@ -456,6 +456,42 @@ int hcf_op_conv2d_step_inverse(const float* h2, int32_t hid, const float* w3, co
                                int32_t f_out, const float* z, int32_t C, int32_t mode, int32_t ns, const float* mat,
                                const float* an_bias, const float* an_logs, float* out_z, float* out_zpad, int32_t zpad_n,
                                int32_t B, int32_t H, int32_t W, int32_t* info, hcf_stream_t stream);
+/* The conv kernels on the CALLER's memory (tests/test_gpu_view_convs.py): every activation is a channel window of an NHWC buffer
+ * the caller owns, described as the engine's View is (hcf_common.h) and used AS IS -- the entries allocate nothing for
+ * activations, copy nothing and zero-fill nothing; only packs, flags, partial-sum scratch and the input maximum are theirs.
+ * Test path: the engine never calls them. */
+typedef struct hcf_view {
+  float* p;              /* device: base of the NHWC buffer [B][H >> up][W >> up][cs] */
+  int32_t cs, c0, n;     /* floats per pixel, first channel and channels of the window: 0 <= c0, 1 <= n, c0 + n <= cs */
+  int32_t up;            /* log2 nearest-upsample factor of a conv source (0 .. 8, must divide H and W); 0 for every other view */
+} hcf_view;
+/* hcf_op_conv2d's arithmetic, out = res2 + rs2 * (res1 + rs1 * act((conv(cat(up(src_i)), w) + bias) * scale)), with src (n_src
+ * = 1 .. 3 descriptors), res1 / res2 (NULL: none) and out (n = cout <= 96) as views; w HOST [cout,cin,k,k], bias / scale HOST
+ * [cout] or NULL. Routing as hcf_op_conv2d for the process-wide op precision (f16x3: Winograd where eligible and not ablated, else
+ * the f16x3 kernel, > 64 output channels exact), plus: k = 1 takes the f16x3 kernel's K1 rows where its plan accepts the call and
+ * the exact kernel where it answers HCF_ERR_UNSUPPORTED (as the engine does); scaled != 0 (f16x3 only) is the training
+ * data-gradient form: the entry takes max |x| over the source windows (launch_absmax) and passes it as ConvArgs::in_max.
+ *   info[16] (HOST): 0 launcher (0 exact, 1 f16x3, 2 Winograd 32 channels, 3 Winograd 64), 1 the plan's / launcher's status,
+ *   2 .. 10 the f16x3 kernel's template arguments NTB, VEC, UP, FUSE2, TAILC, TH, SCALED, K1, N16 (launcher 1) or 2 VEC, 3 vec_epi,
+ *   4 NT of conv_mfma_kernel (launcher 0), 11 grid, 12 block, 13 vec_epi, 14 strip_w, 15 the range flag word.
+ * HCF_ERR_UNSUPPORTED with info[15] != 0: an input left the f16 range (the out window then holds what the launch wrote). */
+int hcf_op_conv2d_views(const hcf_view* src, int32_t n_src, int32_t B, int32_t H, int32_t W, const float* w, const float* bias,
+                        const float* scale, int32_t k, int32_t act, const hcf_view* res1, float rs1, const hcf_view* res2,
+                        float rs2, const hcf_view* out, int32_t scaled, int32_t* info, hcf_stream_t stream);
+/* dw HOST [g.n, cin, k, k] = the weight gradient of that conv given g = dL/d(conv output) as a view (taps = 9 or 1). f16x3 op
+ * precision: the matrix-core kernel with max |g| taken over the window, the fp32 kernel when max |x| over the source windows is
+ * not below 65504 (as hcf_op_conv2d_backward).
+ *   info[16] (HOST), plan_conv_wgrad's: 0 status, 1 f16x3 kernel, 2 TAPS, 3 VEC, 4 DB, 5 strip_w, 6 tpb, 7 nblk_x. */
+int hcf_op_conv2d_wgrad_views(const hcf_view* src, int32_t n_src, int32_t B, int32_t H, int32_t W, const hcf_view* g, int32_t taps,
+                              float* dw, int32_t* info, hcf_stream_t stream);
+/* hcf_op_conv_epilogue_backward on views, each with its own cs / c0 and all of n channels: gy in, gpre out (gpre may BE gy: the
+ * engine runs it in place), y (NULL as there), g1 / g2 (NULL: not wanted) accumulated. scale HOST [n] or NULL; the sums, maxima and
+ * carry2 as there. info[4] (HOST): 0 the vector kernel ran, 1 blocks. */
+int hcf_op_conv_epilogue_backward_views(const hcf_view* gy, const hcf_view* y, const float* scale, int32_t act, int32_t has1,
+                                        float rs1, const hcf_view* g1, int32_t has2, float rs2, const hcf_view* g2,
+                                        const hcf_view* gpre, float* sum_pre, float* sum_zy, float zy_mult, float* absmax,
+                                        float* absmax2, const float* carry2, int32_t B, int32_t H, int32_t W, int32_t* info,
+                                        hcf_stream_t stream);
 /* GaussianDiag.logp / sample (Basic.py:78-101) with (mean, logs) = h[:,0::2], h[:,1::2] */
 int hcf_op_gauss_logp(const float* h, const float* x, float* out_logp, int32_t B, int32_t C, int32_t H, int32_t W,
                       hcf_stream_t stream);

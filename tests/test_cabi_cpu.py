@@ -38,6 +38,49 @@ def test_backward_op_entries_reject_null_tensors_without_a_device():
     assert lib.hcf_op_lu_chain(n, n, n, n, n, n, n, 3, n) == -1
 
 
+def test_view_entries_refuse_malformed_descriptors_before_the_device():
+    """hcf_op_*_views (include/hcflow.h: hcf_view): every malformed descriptor is HCF_ERR_ARG, nothing is dereferenced."""
+    import ctypes as C
+    lib = _lib.load()
+    n = None
+    info = (C.c_int32 * 16)()
+    w = torch.zeros(32 * 64 * 9)
+    buf = (C.c_float * 4)()                                            # never dereferenced: every call below is refused first
+    p = C.cast(buf, C.c_void_p).value
+
+    def V(cs, c0, nn, up=0, ptr=p):
+        return (_lib.hcf_view * 1)(_lib.hcf_view(ptr, cs, c0, nn, up))
+    good_s, good_o = V(64, 0, 64), V(32, 0, 32)
+    wp = C.c_void_p(w.data_ptr())
+
+    def conv(src=good_s, n_src=1, B=1, H=4, W=4, wt=wp, k=3, act=0, r1=None, r2=None, out=good_o, inf=info):
+        return lib.hcf_op_conv2d_views(src, n_src, B, H, W, wt, n, n, k, act, r1, 0.2, r2, 0.2, out, 0, inf, n)
+    assert conv(src=n) == -1 and conv(out=n) == -1 and conv(wt=n) == -1 and conv(inf=n) == -1
+    assert conv(n_src=0) == -1 and conv(n_src=4) == -1 and conv(k=2) == -1 and conv(act=3) == -1 and conv(B=0) == -1
+    assert conv(src=V(64, 0, 64, ptr=None)) == -1                      # null base
+    assert conv(src=V(64, 1, 64)) == -1                                # c0 + n > cs
+    assert conv(src=V(64, -1, 4)) == -1 and conv(src=V(64, 0, 0)) == -1
+    assert conv(src=V(64, 0, 64, up=1), H=5) == -1                     # the upsample does not divide H
+    assert conv(src=V(64, 0, 64, up=9)) == -1
+    assert conv(out=V(32, 0, 32, up=1)) == -1                          # only sources are upsampled
+    assert conv(out=V(128, 0, 97)) == -1                               # > 96 output channels
+    assert conv(r1=V(32, 0, 31)) == -1 and conv(r2=V(64, 8, 32, ptr=None)) == -1
+    dw = C.c_void_p(w.data_ptr())
+
+    def wgrad(src=good_s, n_src=1, g=good_o, taps=9, out=dw, inf=info, W=4):
+        return lib.hcf_op_conv2d_wgrad_views(src, n_src, 1, 4, W, g, taps, out, inf, n)
+    assert wgrad(src=n) == -1 and wgrad(g=n) == -1 and wgrad(out=n) == -1 and wgrad(inf=n) == -1 and wgrad(taps=4) == -1
+    assert wgrad(g=V(32, 4, 32)) == -1 and wgrad(src=V(64, 0, 64, up=1), W=3) == -1 and wgrad(n_src=0) == -1
+
+    def epi(gy=good_o, y=None, act=0, g1=None, g2=None, gpre=good_o, sum_zy=None, absmax2=None, inf=info):
+        return lib.hcf_op_conv_epilogue_backward_views(gy, y, n, act, 1, 0.2, g1, 1, 0.3, g2, gpre, n, sum_zy, 1.0, n, absmax2, n, 1, 4, 4, inf, n)
+    assert epi(gy=n) == -1 and epi(gpre=n) == -1 and epi(inf=n) == -1
+    assert epi(gpre=V(32, 0, 28)) == -1 and epi(y=V(32, 0, 28)) == -1 and epi(g1=V(32, 4, 32)) == -1 and epi(g2=V(32, 0, 32, up=1)) == -1
+    assert epi(act=1) == -1 and epi(act=5, y=good_o) == -1             # an activation needs y
+    assert epi(sum_zy=dw) == -1 and epi(absmax2=dw) == -1              # sum_zy needs y, absmax2 needs absmax
+    assert epi(gy=V(512, 0, 257), gpre=V(512, 0, 257)) == -1
+
+
 @pytest.mark.parametrize("name", PRESETS)
 def test_engine_param_table_matches_python(name):
     cfg = preset(name)
