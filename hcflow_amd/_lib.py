@@ -53,6 +53,7 @@ SYMBOLS = [
     "hcf_inverse_taus", "hcf_metric_stats_bytes", "hcf_metric_stats_add", "hcf_metric_stats_finish",
     "hcf_metric_pair_ref_bytes", "hcf_metric_pair_workspace", "hcf_metric_pair_embed", "hcf_metric_pair_compare",
     "hcf_op_conv2d_views", "hcf_op_conv2d_wgrad_views", "hcf_op_conv_epilogue_backward_views",
+    "hcf_op_seed_sum", "hcf_op_axpy_job", "hcf_train_backward_encode_ex",
 ]
 
 
@@ -224,6 +225,9 @@ def load() -> C.CDLL:
     lib.hcf_op_conv_epilogue_backward.argtypes = [fp, fp, fp, i32, i32, f32, fp, i32, f32, fp, fp, fp, fp, f32, fp, fp, fp,
                                                   i32, i32, i32, i32, i32, i32, vp]
     lib.hcf_op_lu_chain.argtypes = [fp] * 7 + [i32, vp]
+    lib.hcf_train_backward_encode_ex.argtypes = [vp, fp, C.POINTER(fp), i32, fp, fp, i64, fp, vp]
+    lib.hcf_op_seed_sum.argtypes = [fp, i32, fp, vp]
+    lib.hcf_op_axpy_job.argtypes = [fp, fp, i32, f32, fp, vp]
     lib.hcf_data_prepare_batch.argtypes = [vp, C.c_size_t, vp, i32, vp, i32, i32, i32, i32, i32, fp, fp, vp]
     lib.hcf_data_prepare_paired.argtypes = [vp, C.c_size_t, vp, vp, C.c_size_t, vp, i32, vp, i32, i32, i32, i32, i32, fp, fp, vp]
     for name in SYMBOLS:

@@ -306,11 +306,12 @@ def _split_flat(flat, meta):
 
 
 class _SREncodeStep(torch.autograd.Function):
-    """``z, eps, logp = net.encode(hr)`` with the gradient w.r.t. ``hr`` (weights frozen): hcf_train_encode_sr keeps the tape,
-    hcf_train_backward_encode turns dL/d z, dL/d eps_l and dL/d logp (per sample) into dL/d hr. Outputs: (z, logp, *eps)."""
+    """``z, eps, logp = net.encode(hr)`` with gradients: hcf_train_encode_sr keeps the tape, hcf_train_backward_encode_ex turns
+    dL/d z, dL/d eps_l and dL/d logp (per sample) into the flat parameter gradient and dL/d hr (each only where asked for: with no
+    parameter requiring grad the backward pass is the input-gradient-only one). Outputs: (z, logp, *eps)."""
 
     @staticmethod
-    def forward(ctx, module, hr, noise):
+    def forward(ctx, module, hr, noise, *params):
         dev = hr.device
         eng, idx = module._engine_for(dev)
         cfg = module.cfg
@@ -324,6 +325,11 @@ class _SREncodeStep(torch.autograd.Function):
         ctx.eng, ctx.idx = eng, idx
         ctx.keep = (hr, noise)                           # the engine's tape holds raw pointers to these
         ctx.n_levels = len(eps)
+        # an output the loss does not use sends None, not zeros: a null seed costs the engine nothing, and without a seed on logp
+        # the backward pass queues no log-det update
+        ctx.set_materialize_grads(False)
+        ctx.hr_needs_grad = bool(hr.requires_grad)
+        ctx.meta = [(tuple(p.shape), p.numel(), bool(p.requires_grad)) for p in params]
         return (z, logp) + tuple(eps)
 
     @staticmethod
@@ -332,9 +338,10 @@ class _SREncodeStep(torch.autograd.Function):
         hr = ctx.keep[0]
         gs = [None if g is None else g.to(torch.float32).contiguous() for g in (g_z, g_logp) + tuple(g_eps)]
         arr = (C.c_void_p * ctx.n_levels)(*[None if g is None else g.data_ptr() for g in gs[2:]])
-        g_hr = torch.empty_like(hr)
-        eng.launch("hcf_train_backward_encode", idx, gs[0], arr, ctx.n_levels, gs[1], None, 0, g_hr, tape=0)
-        return None, g_hr, None
+        flat, total = _flat_grad_buffer(ctx.meta, hr.device)
+        g_hr = torch.empty_like(hr) if ctx.hr_needs_grad else None
+        eng.launch("hcf_train_backward_encode_ex", idx, gs[0], arr, ctx.n_levels, gs[1], flat, total, g_hr, tape=0)
+        return (None, g_hr, None) + _split_flat(flat, ctx.meta)
 
 
 # ---- the same step as TWO autograd nodes (gradient all-reduce overlapped with the backward pass) -----------------------------
@@ -1215,7 +1222,7 @@ class HCFlowNet_SR(_EngineModule):
         return self._inverse(lr, eps_std, eps=eps, clamp=clamp, seed=seed, sample_offset=sample_offset, cache_cond=cache_cond)
 
     # -- latent encoding: hr -> (z_lr, eps per level, log-density) and its exact inverse
-    def encode(self, hr, noise=None, add_gt_noise=False):
+    def encode(self, hr, noise=None, add_gt_noise=False, param_grad=False):
         """hr -> (z_lr, eps, logp): the forward flow of normal_flow_diracLR (HCFlowNet_SR_arch.py:52-56) that RETURNS what each
         conditional prior standardises, eps_l = (a_l - mean_l) * exp(-logs_l) (ConditionalFlow.py:46-57), instead of folding it
         into the log-probability. ``z_lr`` [B,3,h,w] is the LR latent before quantisation, unclamped; ``eps`` is a list shaped
@@ -1226,17 +1233,30 @@ class HCFlowNet_SR(_EngineModule):
         ``noise``: an explicit U[0,1) tensor; ``add_gt_noise=True`` draws it with torch.rand as the reference does (:52); by
         default none is added, so that the decode target is ``hr`` itself. Un-initialised ActNorms are not fitted.
         With grad mode on, an ``hr`` that requires grad and every weight frozen the outputs are differentiable w.r.t. ``hr``
-        (one taped pass, the engine's input-gradient-only backward); with trainable weights beside such an ``hr`` the call raises
-        NotImplementedError (parameter gradients of the encode are not implemented: freeze the weights or detach ``hr``).
-        Otherwise the inference path (as ``return_internals=True`` is): no autograd graph, and a batch of >= 4 runs as two half
-        batches on the two side streams (set_streams)."""
+        (one taped pass, the engine's input-gradient-only backward).
+        ``param_grad=True`` makes the encode TRAINABLE: with grad mode on and a parameter or ``hr`` requiring grad the outputs
+        carry a graph to the parameters (and to such an ``hr``), so any loss over ``z_lr``, every ``eps_l`` and ``logp`` -- a
+        per-sample weighted NLL (latent.nll_per_sample), a latent regulariser, distillation on ``eps`` -- trains the net. In
+        train() mode with un-initialised ActNorms that route raises NotImplementedError, as the other taped paths without a
+        fitting pass do: run one NLL forward pass first, load a checkpoint / set ``.inited = True``, or call ``.eval()``.
+        Without it the call is what it was before parameter gradients existed, so that code which encodes with a trainable net in
+        grad mode (a monitor inside a training loop) keeps getting graph-free tensors from the two-stream inference path: a plain
+        ``hr`` is the inference path whatever the weights' flags, and trainable weights beside an ``hr`` that requires grad raise
+        NotImplementedError.
+        Otherwise (under no_grad, or nothing requires grad) the inference path (as ``return_internals=True`` is): no autograd
+        graph, and a batch of >= 4 runs as two half batches on the two side streams (set_streams)."""
         dev = self._device()
-        if self._image_wants_grad(hr):
-            if self._wants_grad():
+        if self._image_wants_grad(hr) or (param_grad and self._wants_grad()):
+            if self._wants_grad() and not param_grad:
                 raise NotImplementedError(
                     "encode(hr) with hr.requires_grad and trainable weights: the encode is differentiable w.r.t. hr with the "
-                    "weights frozen only (requires_grad_(False) on the parameters), or detach hr.")
-            hr_t = self._link(hr, dev)
+                    "weights frozen only (requires_grad_(False) on the parameters), or detach hr; encode(hr, param_grad=True) "
+                    "returns the gradients of the parameters beside that of hr.")
+            if param_grad and self.training and self._pending_actnorms():
+                raise NotImplementedError(
+                    "un-initialised ActNorm layers in train() mode on the taped ENCODE path: the encode does not fit them; run "
+                    "one NLL forward (hr, lr -> nll) pass first, load a checkpoint / set .inited = True, or call .eval().")
+            hr_t = self._link(hr, dev) if self._image_wants_grad(hr) else self._prep(hr, dev)
             assert hr_t.dim() == 4 and hr_t.shape[1] == 3 and hr_t.shape[2] % self.cfg.scale == 0 and \
                 hr_t.shape[3] % self.cfg.scale == 0, "{}".format(tuple(hr_t.shape))
             if noise is None and add_gt_noise:
@@ -1244,7 +1264,7 @@ class HCFlowNet_SR(_EngineModule):
             if noise is not None:
                 noise = self._prep(noise, dev)
                 assert noise.shape == hr_t.shape, (tuple(noise.shape), tuple(hr_t.shape))
-            outs = _SREncodeStep.apply(self, hr_t, noise)
+            outs = _SREncodeStep.apply(self, hr_t, noise, *(self._params() if param_grad else ()))
             return outs[0], list(outs[2:]), outs[1]
         B_ = int(hr.shape[0]) if torch.is_tensor(hr) and hr.dim() == 4 else 0
         eng, idx = self._engine_for(dev, twin_hint=self._nstreams[0] >= 2 and B_ >= 4)

@@ -337,8 +337,13 @@ int launch_add_view(View in, View out, int B, int H, int W, float alpha, hipStre
 int launch_add_const(float* p, size_t n, float v, hipStream_t st);                             // p[i] += v
 int launch_axpy(const float* x, float* y, size_t n, float alpha, hipStream_t st);              // y += alpha * x
 // many of the two above in one launch (the data-independent log-det terms of a training step: 2 small updates per flow step)
-struct AxpyJob { const float* x; float* y; int n; float alpha; };                              // y += alpha * (x ? x : 1)
+// k_dev (device, one float, nullable): the job's factor is alpha * *k_dev -- the log-det terms of an encode backward, whose seed on
+// logp is per sample: *k_dev = sum_b g_logp[b] (launch_seed_sum), alpha = H * W. Null: alpha alone, the arithmetic of a job
+// before the field existed.
+struct AxpyJob { const float* x; float* y; int n; float alpha; const float* k_dev; };           // y += alpha [* *k_dev] * (x ? x : 1)
 int launch_axpy_jobs(const AxpyJob* jobs_dev, int njobs, hipStream_t st);
+// out[0] = sum_b g[b], b < B: one block, fixed order, float64 accumulation, one fp32 store (bit-reproducible; no atomics)
+int launch_seed_sum(const float* g, int B, float* out, hipStream_t st);
 // LU-decomposed invertible 1x1 conv (Permutations.py:78-86: W = P L U', L = l o mask + I, U' = u o mask^T + diag(sign_s e^log_s)):
 // chain rule of dL/dW into the factors, A = P^T dW:  dl += strict_lower(A U'^T),  du += strict_upper(L^T A),
 // dlog_s[i] += (L^T A)[i][i] * U'[i][i].  All matrices [C][C] row-major, C <= 48; one block.

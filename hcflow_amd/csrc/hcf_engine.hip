@@ -452,7 +452,7 @@ void hcf_destroy(hcf_engine* e) {
   if (e->ovf_ev) hipEventDestroy(e->ovf_ev);
   if (e->stats_dev) hipFree(e->stats_dev);
   if (e->probe_dev) hipFree(e->probe_dev);
-  for (auto& t : e->slots) { if (t.a.base) hipFree(t.a.base); if (t.g.base) hipFree(t.g.base); }
+  for (auto& t : e->slots) { if (t.a.base) hipFree(t.a.base); if (t.g.base) hipFree(t.g.base); if (t.bwd.seed_sum) hipFree(t.bwd.seed_sum); }
   if (e->wg_scratch) hipFree(e->wg_scratch);
   e->wg_stream.close();
   e->dg_stream.close();
@@ -665,6 +665,16 @@ int hcf_train_backward_encode(hcf_engine* e, const float* g_z, const float* cons
   hcf_engine::BwdIn in = {4, 0.f, nullptr, nullptr, nullptr, nullptr, nullptr, 0};
   in.ghr = grad_hr;
   in.enc_z = g_z; in.enc_eps = g_eps; in.n_enc_eps = n_eps; in.enc_logp = g_logp;
+  return e->run_backward(in, dparams, (size_t)numel, (hipStream_t)stream);
+}
+
+int hcf_train_backward_encode_ex(hcf_engine* e, const float* g_z, const float* const* g_eps, int32_t n_eps, const float* g_logp,
+                                 float* dparams, int64_t numel, float* grad_hr, hcf_stream_t stream) {
+  if (!e || numel < 0 || n_eps < 0 || (n_eps > 0 && !g_eps)) return HCF_ERR_ARG;
+  hcf_engine::BwdIn in = {4, 0.f, nullptr, nullptr, nullptr, nullptr, nullptr, 0};
+  in.ghr = grad_hr;
+  in.enc_z = g_z; in.enc_eps = g_eps; in.n_enc_eps = n_eps; in.enc_logp = g_logp;
+  in.enc_params = true;
   return e->run_backward(in, dparams, (size_t)numel, (hipStream_t)stream);
 }
 

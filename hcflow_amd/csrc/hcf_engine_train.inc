@@ -77,6 +77,9 @@
       const float* const* g_enc_eps = nullptr;
       int n_enc_eps = 0;
       const float* g_enc_logp = nullptr;
+      // encode pass with a gradient buffer: sum_b g_enc_logp[b], one device float owned by this tape (allocated on first use, freed
+      // with the engine), written on the caller's stream at the start of the pass and read by the log-det jobs at its end
+      float* seed_sum = nullptr;
       float* const* geps = nullptr;                  // inverse pass, optional: geps[draw] receives dL / d eps of that draw (entries nullable)
       int n_geps = 0;
       // parameter-gradient work of the last backward pass on this tape (hcf_train_backward_counts): launch_conv_wgrad calls, convs
@@ -126,11 +129,21 @@
   }
   // data-independent log-det terms (logs += k, dW += k W^-T): queued, one launch at the end of the pass
   JobQueue<AxpyJob> axpy_jobs;
-  void add_axpy_job(const float* x, float* y, int n, float alpha) {
+  void add_axpy_job(const float* x, float* y, int n, float alpha, const float* k_dev = nullptr) {
     if (tape->bwd.inputs_only) return;
     ++tape->bwd.counts[3];
-    AxpyJob j; j.x = x; j.y = y; j.n = n; j.alpha = alpha;
+    AxpyJob j; j.x = x; j.y = y; j.n = n; j.alpha = alpha; j.k_dev = k_dev;
     axpy_jobs.host.push_back(j);
+  }
+  // d(sum_b g_b logdet_b) / d(logs, log_s, W) of a flow step at H x W: y += k * (x ? x : 1). NLL pass: every g_b is the host scalar
+  // gobj, k = gobj * B * H * W. Encode pass: the seed on logp is a device vector, k = H * W * S with S = sum_b g_b on the device
+  // (Tape::Bwd::seed_sum, written at the start of the pass); without a seed on logp the log-density has no gradient: no job.
+  void add_logdet_job(const float* x, float* y, int n, int H, int W) {
+    if (tape->kind == 4) {
+      if (tape->bwd.g_enc_logp) add_axpy_job(x, y, n, (float)H * (float)W, tape->bwd.seed_sum);
+      return;
+    }
+    add_axpy_job(x, y, n, tape->bwd.gobj * (float)B_ * (float)H * (float)W);
   }
   int flush_axpy_jobs() {
     if (axpy_jobs.host.empty() || rc != HCF_OK) { axpy_jobs.host.clear(); return rc; }
@@ -924,16 +937,15 @@
       b.part = spart;
       HCF_LAUNCH(launch_step_head_bwd(b, st));
       add_sum_job(spart, B_ * step_blocks_per_sample(H, W), s.C, s.cmax, b.g_bias, b.g_logs, 1.f);
-      const float k = tape->bwd.gobj * (float)B_ * (float)H * (float)W;          // d(sum_b logdet_b): logs * pixels, slogdet W * pixels
-      add_axpy_job(nullptr, b.g_logs, s.C, k);
+      add_logdet_job(nullptr, b.g_logs, s.C, H, W);                      // d(sum_b logdet_b): logs * pixels, slogdet W * pixels
       if (s.has_mat && !io) {
         WgradArgs w;
         memset(&w, 0, sizeof(w));
         w.src[0] = za.all(); w.nsrc = 1; w.g = zb.g.all(); w.B = B_; w.H = H; w.W = W; w.taps = 1;
         w.dw = step_dw_begin(s);
         HCF_LAUNCH(run_wgrad(w));                                       // dW = sum gzb za^T
-        if (s.lu) add_axpy_job(nullptr, gp(s.lu_pre + ".log_s"), s.C, k);                  // dlogdet = sum(log_s) * pixels
-        else add_axpy_job(s.winvT, w.dw, s.C * s.C, k);
+        if (s.lu) add_logdet_job(nullptr, gp(s.lu_pre + ".log_s"), s.C, H, W);             // dlogdet = sum(log_s) * pixels
+        else add_logdet_job(s.winvT, w.dw, s.C * s.C, H, W);
         step_dw_end(s);
       }
     });
@@ -1380,6 +1392,7 @@
     float* ghr;                           // kinds 1, 3, 4: receives dL / d hr (nullable)
     float* glr;                           // kind 1: receives dL / d lr of the Dirac term (nullable)
     const float* enc_z; const float* const* enc_eps; int n_enc_eps; const float* enc_logp;   // kind 4: the seeds (each nullable)
+    bool enc_params;                      // kind 4: a gradient buffer is accepted (hcf_train_backward_encode_ex); else refused
   };
   // phase: -1 the whole pass; 0 records [mark, end) + a flush of every pending parameter-gradient job; 1 the rest
   int run_backward(const BwdIn& in, float* dparams, size_t n, hipStream_t stream, int phase = -1) {
@@ -1395,9 +1408,10 @@
     // no gradient buffer at all = the gradients of the inputs (hr, lr, eps) alone, no parameter-gradient work: every whole pass; the
     // two-phase NLL backward exists for the parameter gradients' all-reduce and keeps refusing
     const bool inputs_only = phase < 0 && !dparams && n == 0;
-    // the encode's seed on logp is per sample: the log-det axpy jobs (logs += k, dW += k W^-T) would need a device-side sum of it
-    if (in.kind == 4 && !inputs_only)
-      return fail(HCF_ERR_UNSUPPORTED, "hcf_train_backward_encode: parameter gradients under per-sample logp seeds are not implemented (dparams must be NULL, numel 0)");
+    // hcf_train_backward_encode is input-gradient-only by definition and keeps refusing a gradient buffer; the full backward of the
+    // encode, whose log-det jobs read the sum of the per-sample logp seed from the device, is hcf_train_backward_encode_ex
+    if (in.kind == 4 && !inputs_only && !in.enc_params)
+      return fail(HCF_ERR_UNSUPPORTED, "hcf_train_backward_encode: input-gradient-only (dparams must be NULL, numel 0); parameter gradients under per-sample logp seeds: hcf_train_backward_encode_ex");
     if (!inputs_only && (n != ptotal || !dparams)) return fail(HCF_ERR_ARG, "backward: gradient buffer size mismatch");
     if (in.n_geps < 0 || (in.n_geps > 0 && !in.geps)) return fail(HCF_ERR_ARG, "backward: n_geps without the eps gradient array");
     if (in.n_enc_eps < 0 || (in.n_enc_eps > 0 && !in.enc_eps)) return fail(HCF_ERR_ARG, "backward: n_eps without the eps seed array");
@@ -1441,6 +1455,14 @@
     if (hipMemsetAsync(tape->g.base, 0, tape->g.top, st) != hipSuccess ||
         (dparams && hipMemsetAsync(dparams, 0, ptotal * sizeof(float), st) != hipSuccess))
       return fail(HCF_ERR_HIP, "hipMemsetAsync failed (backward)");
+    // the encode's seed on logp is per sample: its log-det jobs (logs += k, dW += k W^-T, log_s += k) read the seeds' sum from the device
+    if (tape->bwd.g_enc_logp && !inputs_only) {
+      if (!tape->bwd.seed_sum && hipMalloc((void**)&tape->bwd.seed_sum, 256) != hipSuccess) {
+        tape->bwd.seed_sum = nullptr;
+        return fail(HCF_ERR_NOMEM, "hipMalloc failed (seed sum)");
+      }
+      HCF_LAUNCH(launch_seed_sum(tape->bwd.g_enc_logp, B_, tape->bwd.seed_sum, st));
+    }
     sum_jobs.host.clear();
     wg_jobs.host.clear();
     rdb_wg.clear();

@@ -825,6 +825,28 @@ int hcf_op_lu_chain(const float* dW, const float* P, const float* L, const float
   return rc;
 }
 
+int hcf_op_seed_sum(const float* g, int32_t B, float* out, hcf_stream_t stream) {
+  if (!g || !out || B < 1) return HCF_ERR_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  const int rc = launch_seed_sum(g, B, out, st);
+  if (hipStreamSynchronize(st) != hipSuccess) return HCF_ERR_HIP;
+  return rc;
+}
+
+int hcf_op_axpy_job(const float* x, float* y, int32_t n, float alpha, const float* k_dev, hcf_stream_t stream) {
+  if (!y || n < 1) return HCF_ERR_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  Tmp t;
+  AxpyJob j;
+  j.x = x; j.y = y; j.n = n; j.alpha = alpha; j.k_dev = k_dev;
+  AxpyJob* jd = reinterpret_cast<AxpyJob*>(t.dev((sizeof(AxpyJob) + sizeof(float) - 1) / sizeof(float)));
+  if (!t.ok) return HCF_ERR_NOMEM;
+  if (hipMemcpy(jd, &j, sizeof(j), hipMemcpyHostToDevice) != hipSuccess) return HCF_ERR_HIP;
+  const int rc = launch_axpy_jobs(jd, 1, st);
+  if (hipStreamSynchronize(st) != hipSuccess) return HCF_ERR_HIP;
+  return rc;
+}
+
 }  // extern "C"
 
 // ---- the fused f16x3 conv launches of the inference path, one launch per call (tests/test_gpu_fused_convs.py) ----------

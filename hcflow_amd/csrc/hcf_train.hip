@@ -666,11 +666,34 @@ int launch_axpy(const float* x, float* y, size_t n, float alpha, hipStream_t st)
 
 __global__ __launch_bounds__(256) void axpy_jobs_kernel(const AxpyJob* jobs) {
   const AxpyJob j = jobs[blockIdx.x];
-  for (int i = threadIdx.x; i < j.n; i += 256) j.y[i] += j.alpha * (j.x ? j.x[i] : 1.f);
+  // block-uniform: a job without a device scalar multiplies by the host's alpha alone, as it always has
+  const float alpha = j.k_dev ? j.alpha * *j.k_dev : j.alpha;
+  for (int i = threadIdx.x; i < j.n; i += 256) j.y[i] += alpha * (j.x ? j.x[i] : 1.f);
 }
 int launch_axpy_jobs(const AxpyJob* jobs_dev, int njobs, hipStream_t st) {
   if (njobs <= 0) return HCF_OK;
   hipLaunchKernelGGL(axpy_jobs_kernel, dim3((unsigned)njobs), dim3(256), 0, st, jobs_dev);
+  HCF_RET_T();
+}
+
+// S = sum_b g[b] for the log-det jobs of an encode backward (AxpyJob::k_dev). One block: thread t adds g[t], g[t + 256], ... in
+// that order in float64, a tree over the 256 partials in LDS follows; one fp32 store. The order depends on B alone.
+__global__ __launch_bounds__(256) void seed_sum_kernel(const float* __restrict__ g, int B, float* __restrict__ out) {
+  __shared__ double sh[256];
+  const int tid = threadIdx.x;
+  double acc = 0.0;
+  for (int i = tid; i < B; i += 256) acc += (double)g[i];
+  sh[tid] = acc;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if (tid < s) sh[tid] += sh[tid + s];
+    __syncthreads();
+  }
+  if (tid == 0) out[0] = (float)sh[0];
+}
+int launch_seed_sum(const float* g, int B, float* out, hipStream_t st) {
+  if (!g || !out || B < 1) return HCF_ERR_ARG;
+  hipLaunchKernelGGL(seed_sum_kernel, dim3(1), dim3(256), 0, st, g, B, out);
   HCF_RET_T();
 }
 

@@ -68,6 +68,22 @@ def get_encode_z_and_nll(net, lq, hr, add_gt_noise=True, noise=None):
     return eps, (-objective) / (math.log(2.0) * pixels)
 
 
+def nll_per_sample(net, hr, lq, noise=None, add_gt_noise=True):
+    """[B] float64: the negative log-likelihood of ``hr`` given ``lq`` in bits per dimension PER SAMPLE, differentiable -- what
+    ``get_encode_z_and_nll`` computes without a graph. It is ``net.encode(..., param_grad=True)``'s ``logp`` (the taped pass when
+    a parameter or ``hr`` requires grad) plus the Dirac-LR term at ``lq`` (HCFlowNet_SR_arch.py:58-63) with Quant straight-through (Basic.py:186-195:
+    forward the rounded value, backward the identity), so any weighting of the samples -- hard-example weights, importance
+    weights, a curriculum -- trains the net: ``(w * nll_per_sample(net, hr, lq)).sum().backward()``. Its mean is the number
+    ``net(hr=hr, lr=lq)`` returns for the same noise. ``noise``: explicit U[0,1) tensor; otherwise drawn when ``add_gt_noise``."""
+    z, _, logp = net.encode(hr, noise=noise, add_gt_noise=add_gt_noise, param_grad=True)
+    zd = z.double()                                   # (Quant itself in float32, as the forward pass evaluates it)
+    zq = zd + (((torch.clamp(z, 0, 1) * 255.).round() / 255.).double() - zd).detach()
+    d = zq - lq.detach().to(z.device).double()
+    dirac = (-0.5 * (-12.0 + d * d * math.exp(12.0) + math.log(2 * math.pi))).sum(dim=[1, 2, 3])
+    pixels = int(hr.shape[2]) * int(hr.shape[3])
+    return -(logp.double() + dirac) / (math.log(2.0) * pixels)
+
+
 def get_sr_with_z(net, lq, heat=None, seed=None, eps=None):
     """(sr, eps): ``lq`` super-resolved with the given latents, or -- when ``eps`` is None -- with N(0, heat) draws made here
     (``seed``: a generator of its own; None: torch's global one; ``heat`` None = 1.0), returned so that the call can be repeated or

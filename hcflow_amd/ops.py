@@ -394,3 +394,22 @@ def lu_chain(dW, P, L, U, dl, du, dlog_s):
     dl, du, ds = _dev(dl).clone(), _dev(du).clone(), _dev(dlog_s).clone()
     _lib.launch("hcf_op_lu_chain", dW.device, dW, P, L, U, dl, du, ds, Cc)
     return dl, du, ds
+
+
+def seed_sum(g) -> torch.Tensor:
+    """sum_b g[b] of a [B] vector as one device float: one block, fixed order, float64 accumulation (hcf_op_seed_sum)."""
+    g = _dev(g).reshape(-1)
+    out = torch.empty(1, device=g.device, dtype=torch.float32)
+    _lib.launch("hcf_op_seed_sum", g.device, g, g.numel(), out)
+    return out
+
+
+def axpy_job(x, y, alpha: float, k_dev=None) -> torch.Tensor:
+    """One log-det job of the training backward on a copy of ``y``: y + k * (x if x is not None else 1) with k = ``alpha``, or
+    ``alpha * k_dev[0]`` when the one-float device tensor ``k_dev`` is given (hcf_op_axpy_job)."""
+    out = _dev(y).clone()
+    xd = _dev(x) if x is not None else None
+    assert xd is None or xd.numel() == out.numel()
+    kd = _dev(k_dev) if k_dev is not None else None
+    _lib.launch("hcf_op_axpy_job", out.device, xd, out, out.numel(), float(alpha), kd)
+    return out

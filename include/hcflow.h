@@ -258,12 +258,24 @@ int hcf_train_backward_rescale_ex(hcf_engine* e, const float* g_lr, const float*
  * seeds g_z = dL/d out_z, g_eps[i] = dL/d out_eps[i] (the array and each entry nullable; n_eps entries) and g_logp = dL/d out_logp
  * as a device vector [B] (nullable) -> grad_hr = dL/d hr (device [B,3,H,W]). Each conditional prior contributes through both of
  * its outputs, eps = (a - mean) e^-logs and its log-density (ConditionalFlow.py:46-57). The pass is input-gradient-only by
- * definition: dparams must be NULL and numel 0; anything else is refused with HCF_ERR_UNSUPPORTED (a per-sample seed on the
- * log-det terms would need a device-side sum in the parameter updates). d / d noise is not returned. */
+ * definition: dparams must be NULL and numel 0; anything else is refused with HCF_ERR_UNSUPPORTED (the full backward under a
+ * per-sample seed on the log-det terms is hcf_train_backward_encode_ex below). d / d noise is not returned. */
 int hcf_train_encode_sr(hcf_engine* e, const float* hr, const float* noise, float* out_z, float* const* out_eps, int32_t n_eps,
                         float* out_logp, int32_t B, int32_t H, int32_t W, uint32_t flags, hcf_stream_t stream);
 int hcf_train_backward_encode(hcf_engine* e, const float* g_z, const float* const* g_eps, int32_t n_eps, const float* g_logp,
                               float* dparams, int64_t numel, float* grad_hr, hcf_stream_t stream);
+/* The backward of hcf_train_encode_sr that also takes a gradient buffer (training the net on any objective over the encode's
+ * outputs: a per-sample weighted NLL, a latent regulariser, distillation on eps): the same seeds -> dparams = dL/d parameters
+ * (flat, state_dict order, fully defined on return as after hcf_train_backward_ex) and grad_hr (nullable: a plain hr under
+ * trainable weights). With dparams the pass is the full backward: the weight-gradient launches, the per-channel sums and the
+ * data-independent log-det updates (logs += k, dW += k W^-T, log_s += k) of the NLL backward. Where that pass has the host scalar
+ * k = grad_obj * B * H * W, the seed here is per sample: k = H * W * S with S = sum_b g_logp[b] summed once on the device (one
+ * block, fixed order, float64; hcf_op_seed_sum) into a float the tape slot owns, which the one batched log-det launch reads.
+ * g_logp = NULL: the log-density has no gradient, no log-det update is queued (hcf_train_backward_counts: out[3] = 0 while
+ * out[0..2] > 0). dparams = NULL with numel = 0 is hcf_train_backward_encode's input-gradient-only pass (counters 0/0/0/0), bit for
+ * bit; grad_hr is the same bits with and without dparams. The two-phase backward does not take an encode tape. */
+int hcf_train_backward_encode_ex(hcf_engine* e, const float* g_z, const float* const* g_eps, int32_t n_eps, const float* g_logp,
+                                 float* dparams, int64_t numel, float* grad_hr, hcf_stream_t stream);
 /* Parameter-gradient work of the LAST backward pass on the selected tape slot (hcf_train_select_tape): out[0] = weight-gradient
  * launches of one conv, out[1] = convs handed to the batched weight-gradient launches of the dense blocks, out[2] = per-channel
  * sum jobs, out[3] = axpy (log-det) jobs. All zero after an input-gradient-only pass. */
@@ -561,6 +573,12 @@ int hcf_op_conv_epilogue_backward(const float* gy, const float* y, const float* 
  * (hcf_common.h LuChainArgs). All device, row-major, C <= 48. */
 int hcf_op_lu_chain(const float* dW, const float* P, const float* L, const float* U, float* dl, float* du, float* dlog_s,
                     int32_t C, hcf_stream_t stream);
+/* out[0] = sum_b g[b] over a device vector [B]: one block, a fixed order that depends on B alone, float64 accumulation, one fp32
+ * store, no atomics -- the sum of a per-sample seed on logp that the log-det jobs of hcf_train_backward_encode_ex read. */
+int hcf_op_seed_sum(const float* g, int32_t B, float* out, hcf_stream_t stream);
+/* One data-independent log-det update as the training backward queues them: y[i] += k * (x ? x[i] : 1), i < n, with
+ * k = alpha (k_dev NULL: the host form of the NLL and rescaling passes) or alpha * *k_dev (k_dev: one device float). x nullable. */
+int hcf_op_axpy_job(const float* x, float* y, int32_t n, float alpha, const float* k_dev, hcf_stream_t stream);
 
 /* ---- auxiliary nets of the HCFlow+ / ++ recipes (reference: Discriminator_VGG_160 / VGGFeatureExtractor,
  *      codes/models/modules/discriminator_vgg_arch.py:68-157; used by HCFlow_SR_model.py:75-95,219-285) ------------------
