@@ -52,7 +52,7 @@ SYMBOLS = [
     "hcf_op_fcn12", "hcf_op_conv2d_step_inverse",
     "hcf_inverse_taus", "hcf_metric_stats_bytes", "hcf_metric_stats_add", "hcf_metric_stats_finish",
     "hcf_metric_pair_ref_bytes", "hcf_metric_pair_workspace", "hcf_metric_pair_embed", "hcf_metric_pair_compare",
-    "hcf_op_conv2d_views", "hcf_op_conv2d_wgrad_views", "hcf_op_conv_epilogue_backward_views",
+    "hcf_op_conv2d_views", "hcf_op_conv2d_wgrad_views", "hcf_op_conv_epilogue_backward_views", "hcf_op_conv2d_dgrad_fused_views",
     "hcf_op_seed_sum", "hcf_op_axpy_job", "hcf_train_backward_encode_ex",
 ]
 
@@ -206,6 +206,8 @@ def load() -> C.CDLL:
                                                C.POINTER(i32), vp]
     pv = C.POINTER(hcf_view)
     lib.hcf_op_conv2d_views.argtypes = [pv, i32, i32, i32, i32, fp, fp, fp, i32, i32, pv, f32, pv, f32, pv, i32, C.POINTER(i32), vp]
+    lib.hcf_op_conv2d_dgrad_fused_views.argtypes = [pv, i32, i32, i32, i32, fp, i32, pv, i32, fp, i32, f32, pv, fp, fp, fp, fp,
+                                                    C.POINTER(i32), vp]
     lib.hcf_op_conv2d_wgrad_views.argtypes = [pv, i32, i32, i32, i32, pv, i32, fp, C.POINTER(i32), vp]
     lib.hcf_op_conv_epilogue_backward_views.argtypes = [pv, pv, fp, i32, i32, f32, pv, i32, f32, pv, pv, fp, fp, f32, fp, fp, fp,
                                                         i32, i32, i32, C.POINTER(i32), vp]

@@ -606,7 +606,6 @@ __global__ __launch_bounds__((TH == 4) ? 256 : 32 * TH, (TH == 16) ? ((NTB == 1)
       const int n4 = a.out.n >> 2;
       const bool h1 = a.res1.p != nullptr, h2 = a.res2.p != nullptr;
       const bool fb = SCALED && a.fb_y.p != nullptr;        // fused epilogue backward of the conv whose dL/dy this is (ConvArgs::fb_y)
-      const float fb_neg = a.fb_act == ACT_RELU ? 0.f : a.fb_act == ACT_LRELU ? 0.2f : 1.f;
       f32x4 fb_sum = {0.f, 0.f, 0.f, 0.f}, fb_szy = {0.f, 0.f, 0.f, 0.f};
       f32x4 fb_sc = {1.f, 1.f, 1.f, 1.f};            // (this thread's channel quad is the same in every iteration: NTHR % C4 == 0)
       if (fb && a.fb_scale && (tid % C4) < n4) fb_sc = *reinterpret_cast<const f32x4*>(a.fb_scale + 4 * (tid % C4));
@@ -634,7 +633,8 @@ __global__ __launch_bounds__((TH == 4) ? 256 : 32 * TH, (TH == 16) ? ((NTB == 1)
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
               const bool pos = a.fb_act == ACT_RELU ? (yv[e] > 0.f) : (yv[e] >= 0.f);      // as conv_epilogue_bwd_kernel
-              const float dz = (a.fb_act == ACT_NONE || pos) ? v[e] : v[e] * fb_neg;
+              // (relu off: +0, not v * 0 -- the separate kernel's bits, also where v is negative or not finite)
+              const float dz = (a.fb_act == ACT_NONE || pos) ? v[e] : a.fb_act == ACT_RELU ? 0.f : v[e] * 0.2f;
               v[e] = dz * fb_sc[e];
               fb_sum[e] += v[e];
               fb_szy[e] += dz * yv[e];

@@ -531,7 +531,6 @@ __global__ __launch_bounds__(512, 1) void conv_wino2_kernel(const Args a, const 
     float chk = 0.f;                               // Inf / NaN anywhere in the accumulators reaches a partial output
     f32x4 fbs = {0.f, 0.f, 0.f, 0.f};              // fused epilogue backward: this unit's sums of the lane's channel quad, max |dL/dpre|
     float fbm = 0.f;
-    const float fb_neg = a.fb_act == 1 ? 0.f : a.fb_act == 2 ? 0.2f : 1.f;
     {
       char* const xbuf = lds + ((g - 1) & 1) * STAGE2 + tg * 16384;
       const int p8 = lane >> 3, qd = (lane >> 1) & 3, hd = lane & 1;            // reader role
@@ -611,7 +610,7 @@ __global__ __launch_bounds__(512, 1) void conv_wino2_kernel(const Args a, const 
                 for (int e = 0; e < 4; ++e) {
                   const float yv = rv1[sgrp][ob][e];
                   const bool pos = a.fb_act == 1 ? (yv > 0.f) : (yv >= 0.f);
-                  const float dz = (a.fb_act == 0 || pos) ? v[e] : v[e] * fb_neg;
+                  const float dz = (a.fb_act == 0 || pos) ? v[e] : a.fb_act == 1 ? 0.f : v[e] * 0.2f;      // (relu off: +0, as the separate kernel)
                   v[e] = dz;
                   fbs[e] += dz;
                   fbm = fmaxf(fbm, fabsf(dz));

@@ -1139,6 +1139,95 @@ int hcf_op_conv2d_views(const hcf_view* src, int32_t n_src, int32_t B, int32_t H
   return HCF_OK;
 }
 
+int hcf_op_conv2d_dgrad_fused_views(const hcf_view* src, int32_t n_src, int32_t B, int32_t H, int32_t W, const float* w, int32_t k,
+                                    const hcf_view* y, int32_t fb_act, const float* fb_scale, int32_t want_zy, float zy_mult,
+                                    const hcf_view* out, float* sum_pre, float* sum_zy, float* fb_max, float* fb_max2, int32_t* info,
+                                    hcf_stream_t stream) {
+  if (!w || !info || !sum_pre || !fb_max || (k != 1 && k != 3) || B < 1 || H < 1 || W < 1 || fb_act < ACT_NONE || fb_act > ACT_LRELU)
+    return HCF_ERR_ARG;
+  if (!view_ok(out, 0) || out->n > 64 || !view_ok(y, 0) || y->n != out->n || (want_zy && !sum_zy)) return HCF_ERR_ARG;
+  ConvArgs a;
+  memset(&a, 0, sizeof(a));
+  int cin = 0, srcs[kMaxSrc];
+  if (!views_of_sources(src, n_src, H, W, a.src, srcs, cin)) return HCF_ERR_ARG;
+  for (int i = 0; i < n_src; ++i)
+    if (src[i].up) return HCF_ERR_ARG;                   // a data gradient's sources are gradients at the output's size
+  for (int i = 0; i < 18; ++i) info[i] = 0;
+  if (g_op_precision != PREC_F16X3) return HCF_ERR_UNSUPPORTED;      // the fused form exists in f16x3 only
+  hipStream_t st = (hipStream_t)stream;
+  Tmp t;
+  int rc = HCF_OK;
+  const int n = out->n, taps = k * k;
+  const int npad = ((n + 31) / 32) * 32;
+  // launch_dgrad's arguments (hcf_engine_train.inc): unit bias and scale, no activation, plain store, the fused epilogue backward
+  a.nsrc = n_src;
+  a.B = B; a.H = H; a.W = W;
+  a.bias = fused_table(t, nullptr, n, npad, 0.f);
+  a.scale = fused_table(t, nullptr, n, npad, 1.f);
+  a.act = ACT_NONE;
+  a.out = as_view(out);
+  a.res1 = mkview(nullptr, 0, 0, 0);
+  a.res2 = mkview(nullptr, 0, 0, 0);
+  if (!t.ok) return HCF_ERR_NOMEM;
+  if ((rc = fused_flag(t, a, st)) != HCF_OK) return rc;
+  float* m = t.dev(1);
+  if (!m) return HCF_ERR_NOMEM;
+  if (hipMemsetAsync(m, 0, sizeof(float), st) != hipSuccess) return HCF_ERR_HIP;
+  if ((rc = sources_absmax(a.src, n_src, B, H, W, m, st)) != HCF_OK) { hipStreamSynchronize(st); return rc; }
+  a.in_max = m;
+  const int rows_cap = std::max(conv_f16x3_scaled_blocks_max(B, H, W), conv_wino_grid(B, H, W, 1));
+  a.fb_y = as_view(y); a.fb_act = fb_act; a.fb_max = fb_max; a.fb_max2 = fb_max2;
+  a.fb_part = part_rows(t, (size_t)rows_cap * 2 * n, st, rc);
+  if (rc != HCF_OK) { hipStreamSynchronize(st); return rc; }
+  if (fb_scale) a.fb_scale = fused_table(t, fb_scale, n, npad, 1.f);
+  a.fb_zy = want_zy ? 1 : 0;
+  std::vector<float> pk;
+  int nchunk = 0, np = 0;
+  if (!pack_conv_weights_f16x3(w, cin, n, taps, srcs, n_src, pk, nchunk, np)) { hipStreamSynchronize(st); return HCF_ERR_UNSUPPORTED; }
+  a.wpack = t.up(pk);
+  a.nchunk = nchunk;
+  if (!t.ok) { hipStreamSynchronize(st); return HCF_ERR_NOMEM; }
+  // the engine's order: fused Winograd first, then the fused scaled f16x3 kernel; never an unfused launch
+  rc = HCF_ERR_UNSUPPORTED;
+  int rows = 0;
+  if (k == 3 && !(g_f16x3_ablation & 256)) {
+    std::vector<float> pkw;
+    // (from 16 input channels on, the narrowest pack the engine builds for this kernel: a unit count beyond one round of blocks
+    //  stays affordable for a test only on a narrow source)
+    const float* wino = pack_conv_weights_wino(w, cin, n, srcs, n_src, pkw, 16) ? t.up(pkw) : nullptr;
+    if (!t.ok) { hipStreamSynchronize(st); return HCF_ERR_NOMEM; }
+    if (wino) {
+      ConvArgs wv = a;
+      wv.wpack = nullptr;
+      rc = launch_conv_wino(wv, wino, st);
+    }
+    if (rc != HCF_ERR_UNSUPPORTED) {
+      rows = conv_wino_grid(B, H, W, 1);
+      info[0] = 2; info[1] = rc; info[11] = rows; info[17] = (int32_t)wino_units(B, H, W, 1);
+    }
+  }
+  if (rc == HCF_ERR_UNSUPPORTED) {
+    const F16x3Plan p = plan_conv_f16x3(a, taps);
+    const int32_t v[14] = {p.status, p.v.ntb, p.v.vec, p.v.up, p.v.fuse2, p.v.tailc, p.v.th, p.v.scaled, p.v.k1, p.v.n16,
+                           (int32_t)p.grid, (int32_t)p.block, p.vec_epi, p.strip_w};
+    info[0] = 1;
+    for (int i = 0; i < 14; ++i) info[1 + i] = v[i];
+    int sw = 0, th = 8;
+    rows = conv_f16x3_scaled_blocks(B, H, W, &sw, &th);      // (conv_tile_blocks of the engine: the rows it hands to its sum job)
+    rc = p.status != HCF_OK ? p.status : ((long long)p.grid > rows_cap || rows > rows_cap) ? HCF_ERR_ARG : launch_conv_f16x3(a, taps, st);
+  }
+  if (rc == HCF_OK) {
+    info[16] = rows;
+    rc = reduce_rows(t, a.fb_part, rows, n, n, sum_pre, sum_zy, zy_mult, st);      // (want_zy off: the second row holds the kernel's zeros)
+  }
+  if (hipStreamSynchronize(st) != hipSuccess) return HCF_ERR_HIP;
+  if (rc != HCF_OK) return rc;
+  int h = 0;
+  if (hipMemcpy(&h, a.ovf, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return HCF_ERR_HIP;
+  info[15] = h;
+  return h ? HCF_ERR_UNSUPPORTED : HCF_OK;
+}
+
 int hcf_op_conv2d_wgrad_views(const hcf_view* src, int32_t n_src, int32_t B, int32_t H, int32_t W, const hcf_view* g, int32_t taps,
                               float* dw, int32_t* info, hcf_stream_t stream) {
   if (!dw || !info || (taps != 1 && taps != 9) || B < 1 || H < 1 || W < 1 || !view_ok(g, 0) || g->n > 96) return HCF_ERR_ARG;

@@ -198,6 +198,29 @@ def conv2d_views(srcs: Sequence[View], B: int, H: int, W: int, weight, bias, sca
                          fields=CONV_VIEWS_FIELDS)
 
 
+DGRAD_FUSED_FIELDS = CONV_VIEWS_FIELDS + ("rows", "units")
+
+
+def conv2d_dgrad_fused_views(srcs: Sequence[View], B: int, H: int, W: int, weight, y: View, out: View, sum_pre, fb_max, fb_max2=None,
+                             fb_act=None, fb_scale=None, sum_zy=None, want_zy: Optional[bool] = None, zy_mult: float = 1.0):
+    """ONE launch of the fused data-gradient form (include/hcflow.h: hcf_op_conv2d_dgrad_fused_views): dL/dpre of the conv that
+    produced ``y`` is written into ``out``'s window, its per-channel sums are ADDED to the CUDA tensors ``sum_pre`` / ``sum_zy``
+    (``want_zy``, default: whether ``sum_zy`` is given, asks the kernel for the sums of dz * y; without it the row holds zeros)
+    and the maxima folded into the one-element CUDA tensors ``fb_max`` / ``fb_max2``. Returns the launch record: CONV_VIEWS_FIELDS,
+    then the rows of partial sums reduced and the Winograd unit count."""
+    dev = out.buf.device
+    k = int(weight.shape[2])
+    assert int(weight.shape[0]) == out.n == y.n and int(weight.shape[1]) == sum(s.n for s in srcs)
+    for t in (sum_pre, sum_zy, fb_max, fb_max2):
+        assert t is None or (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous())
+    assert sum_pre.numel() == out.n and (sum_zy is None or sum_zy.numel() == out.n)
+    info = (C.c_int32 * 18)()
+    zy = sum_zy is not None if want_zy is None else bool(want_zy)
+    return _fused_launch("hcf_op_conv2d_dgrad_fused_views", dev, info, _views(srcs, dev), len(srcs), B, H, W, _host(weight), k,
+                         _views([y], dev), ACT[fb_act], _host(fb_scale), int(zy), float(zy_mult), _views([out], dev),
+                         sum_pre, sum_zy, fb_max, fb_max2, info, fields=DGRAD_FUSED_FIELDS)
+
+
 def conv2d_wgrad_views(srcs: Sequence[View], B: int, H: int, W: int, g: View, k: int):
     """(dw on the CPU [g.n, cin, k, k], the plan record) of hcf_op_conv2d_wgrad_views."""
     dev = g.buf.device

@@ -490,6 +490,23 @@ typedef struct hcf_view {
 int hcf_op_conv2d_views(const hcf_view* src, int32_t n_src, int32_t B, int32_t H, int32_t W, const float* w, const float* bias,
                         const float* scale, int32_t k, int32_t act, const hcf_view* res1, float rs1, const hcf_view* res2,
                         float rs2, const hcf_view* out, int32_t scaled, int32_t* info, hcf_stream_t stream);
+/* ONE launch of the training path's fused data-gradient form (ConvArgs::fb_y; tests/test_gpu_fused_dgrad.py): the conv's output is
+ * the complete dL/dy of the conv that produced `y`, and the launch applies that producer's epilogue backward in its own epilogue.
+ *   d = conv(cat(src_i), w), dz = d * act'(y) (fb_act: 0 none, 1 relu: y > 0, 2 leaky relu 0.2: y >= 0), out = dL/dpre = dz * fb_scale
+ *   sum_pre[c] += sum out, sum_zy[c] += zy_mult * sum dz * y (want_zy), *fb_max = max(*fb_max, max |out|),
+ *   *fb_max2 = max(*fb_max2, max |out|, max |src windows|); a launch whose out is all zero touches neither maximum.
+ * ConvArgs as launch_dgrad (hcf_engine_train.inc) fills them: unit bias and scale, no activation, no residuals, plain store, in_max =
+ * max |x| over the source windows in a slot of the entry's own, NaN-filled partial rows reduced by one sum job over exactly the rows
+ * the launch left. src: 1 .. 3 views (up = 0); w HOST [n, cin, k, k], k = 3 or 1; y and out: views of n <= 64 channels; fb_scale HOST
+ * [n] or NULL; sum_pre [n], sum_zy [n] (may be NULL without want_zy; given without it, it receives the zeros of the second partial
+ * row), fb_max, fb_max2 (NULL: not kept): the caller's DEVICE memory, the maxima in / out. Launch order as the engine's: the fused 32-channel Winograd kernel (k = 3, not ablated with bit 256; a pack from 16
+ * input channels on), where it refuses the fused SCALED rows of the f16x3 kernel. No fused form accepts the call, or the op
+ * precision is exact: HCF_ERR_UNSUPPORTED -- never an unfused launch.
+ *   info[18] (HOST): 0 .. 15 as hcf_op_conv2d_views (launcher 1 or 2), 16 rows of partial sums reduced, 17 Winograd: units walked. */
+int hcf_op_conv2d_dgrad_fused_views(const hcf_view* src, int32_t n_src, int32_t B, int32_t H, int32_t W, const float* w, int32_t k,
+                                    const hcf_view* y, int32_t fb_act, const float* fb_scale, int32_t want_zy, float zy_mult,
+                                    const hcf_view* out, float* sum_pre, float* sum_zy, float* fb_max, float* fb_max2, int32_t* info,
+                                    hcf_stream_t stream);
 /* dw HOST [g.n, cin, k, k] = the weight gradient of that conv given g = dL/d(conv output) as a view (taps = 9 or 1). f16x3 op
  * precision: the matrix-core kernel with max |g| taken over the window, the fp32 kernel when max |x| over the source windows is
  * not below 65504 (as hcf_op_conv2d_backward).
