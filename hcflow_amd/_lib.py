@@ -54,6 +54,7 @@ SYMBOLS = [
     "hcf_metric_pair_ref_bytes", "hcf_metric_pair_workspace", "hcf_metric_pair_embed", "hcf_metric_pair_compare",
     "hcf_op_conv2d_views", "hcf_op_conv2d_wgrad_views", "hcf_op_conv_epilogue_backward_views", "hcf_op_conv2d_dgrad_fused_views",
     "hcf_op_seed_sum", "hcf_op_axpy_job", "hcf_train_backward_encode_ex",
+    "hcf_metric_quantize", "hcf_metric_from_image",
 ]
 
 
@@ -140,6 +141,8 @@ def load() -> C.CDLL:
     lib.hcf_metric_pair_workspace.restype = C.c_size_t
     lib.hcf_metric_pair_embed.argtypes = [fp, i32, i32, i32, i32, i32, vp, C.c_size_t, vp]
     lib.hcf_metric_pair_compare.argtypes = [vp, C.c_size_t, fp, i32, i32, i32, i32, i32, fp, vp, vp, C.c_size_t, vp]
+    lib.hcf_metric_quantize.argtypes = [fp, i32, i32, i32, fp, vp, vp]
+    lib.hcf_metric_from_image.argtypes = [vp, i32, i32, i32, fp, vp]
     lib.hcf_train_inverse.argtypes = [vp, fp, C.POINTER(fp), i32, f32, u64, fp, i32, i32, i32, C.c_uint32, vp]
     lib.hcf_train_backward_inverse.argtypes = [vp, fp, fp, i64, fp, vp]
     lib.hcf_train_backward_inverse_ex.argtypes = [vp, fp, fp, i64, fp, C.POINTER(fp), i32, vp]

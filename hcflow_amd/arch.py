@@ -1370,6 +1370,34 @@ class HCFlowNet_Rescaling(_EngineModule):
         """lr (+ sampled z) -> clamp(HR)   (HCFlowNet_Rescaling_arch.py:49-54)."""
         return self._inverse(lr, eps_std, eps=eps, clamp=clamp, seed=seed, sample_offset=sample_offset, cache_cond=cache_cond)
 
+    # -- the net as a codec: what HCFLowRescalingModel.test() runs around the two passes (HCFlow_Rescaling_model.py:306-324)
+    def downscale(self, hr, image=False):
+        """hr -> (lr_q, z1, z2), or (lr_q, lr_u8, z1, z2) with ``image=True``: ``normal_flow_diracLR(hr)`` followed by
+        ``metrics.quantize`` -- lr_q is the reference's ``Quantization()(LR^)`` (Basic.py:186-202), the tensor its test samples
+        from; lr_u8 is the same LR as the uint8 [B,h,w,3] BGR image to store (``upscale`` takes either). Inference only: it
+        raises when grad mode is on and ``hr`` or a parameter requires grad -- a taped training step keeps the caller's own
+        straight-through ``Quantization`` on ``normal_flow_diracLR``'s output (HCFlow_Rescaling_model.py:214-218)."""
+        from . import metrics as M
+        if self._wants_grad() or self._image_wants_grad(hr):
+            raise NotImplementedError(
+                "HCFlowNet_Rescaling.downscale is inference only (the quantisation has no backward pass here): call it under "
+                "torch.no_grad(), or apply your own Quantization to normal_flow_diracLR(hr) in a training step.")
+        with torch.no_grad():
+            lr_hat, z1, z2 = self.normal_flow_diracLR(hr)
+            if image:
+                lr_q, lr_u8 = M.quantize(lr_hat, image=True)
+                return lr_q, lr_u8, z1, z2
+            return M.quantize(lr_hat), z1, z2
+
+    def upscale(self, lr, eps_std=1.0, seed=None, eps=None, cache_cond=False, clamp=True):
+        """lr -> clamp(HR^): ``reverse_flow_diracLR`` from an fp32 [B,3,h,w] tensor or from a stored uint8 [B,h,w,3] BGR image
+        (``downscale(..., image=True)``'s; it goes through ``metrics.from_image`` first, as a dataset would read it).
+        ``eps_std`` may be the per-sample vector."""
+        if torch.is_tensor(lr) and lr.dtype == torch.uint8:
+            from . import metrics as M
+            lr = M.from_image(lr)
+        return self.reverse_flow_diracLR(lr, None, None, eps_std=eps_std, eps=eps, clamp=clamp, seed=seed, cache_cond=cache_cond)
+
     # -- the interface HCFlowNet_SR.encode / decode has, over the existing calls
     def encode(self, hr):
         """hr -> (lr_raw, [z2, z1]): normal_flow_diracLR(hr, clamp=False) with the latents in the order the inverse pass takes

@@ -21,6 +21,14 @@ image, B = 16: 8.6 ms per image). This module is the drop-in for those two piece
   of one call are (image, heat) pairs, each with its own temperature, and the diversity comes from a streaming
   ``metrics.SampleStats`` instead of the held samples.
 
+``net`` is an ``HCFlowNet_SR`` or an ``HCFlowNet_Rescaling``; the three ``evaluate_*`` functions dispatch on ``net.cfg.sr`` and share
+everything behind the first pass. An SR net runs ``HCFlowSRModel.test()``: the NLL pass of (GT, LQ), then samples drawn from the
+dataset's LQ. A rescaling net runs ``HCFLowRescalingModel.test()`` (``HCFlow_Rescaling_model.py:306-324``): GT -> LR^ in one forward
+pass over the batch, ``metrics.quantize`` (the reference's ``Quantization``, ``Basic.py:186-202``), then every heat and sample is
+the inverse from the QUANTISED LR^ -- one tensor held for the whole call, so ``cache_cond=True`` hits. Its batch must hold "GT"; "LQ"
+is optional and only feeds the "lr" entry (bicubic LQ against the quantised LR^, the "LR" columns of the log line); its "nll" is the
+reference's ``fake_z1.mean()`` per image, the mean of the first split latent (not a likelihood: the log line's column name is kept).
+
 The numbers per image are identical to feeding the images one at a time (every op of the path is per sample)."""
 from __future__ import annotations
 
@@ -63,51 +71,92 @@ def evaluate_batch(net, batch: Dict, heats: Iterable[float], n_sample: int, scal
     reference's per-image log line (test_HCFlow.py:166-175). LPIPS needs the ``lpips`` package's pretrained AlexNet: pass the
     caller's own module as ``lpips_fn`` (``lpips.LPIPS(net='alex').to('cuda')``, test_HCFlow.py:48) and every heat entry gets
     "lpips" = the mean over the samples of ``lpips_fn(2 gt - 1, 2 sr - 1)`` per image (:132-133, :168), evaluated on the whole
-    batch at once; without it the key is absent. ``net`` is an eval()-mode HCFlowNet_SR on a GPU.
+    batch at once; without it the key is absent. ``net`` is an eval()-mode HCFlowNet_SR or HCFlowNet_Rescaling on a GPU; the
+    family (``net.cfg.sr``) decides what runs in front of the sampling and what the samples are drawn from (``_nll_pass``): for a
+    rescaling net the batch must hold "GT" (ValueError otherwise), "nll" is the reference's ``fake_z1.mean()`` per image, "lr"
+    (only with an "LQ" in the batch) compares the bicubic LQ with the quantised LR^, and every sample is drawn from that quantised
+    LR^ (HCFlow_Rescaling_model.py:306-324); ``noise`` must stay None.
     ``seed`` fixes the device draws of the samples, ``noise`` ([B,3,H,W] in [0,1)) replaces the dequantisation noise of the
     NLL pass (HCFlowNet_SR_arch.py:52); both default to fresh draws, as in the reference.
     The PSNR / SSIM block stays on the device (``metrics.PairMetrics``): the GT is prepared once per call, every sample is one
     ``compare`` into a device row, the per-sample LPIPS values stay on the device too, the means over the samples are taken
     there in float64 and each heat's numbers are read back once."""
     pm = M.PairMetrics()
+    crop = scale if crop_border is None else crop_border          # test_HCFlow.py:48
+    with torch.no_grad():
+        res, lq, gt = _nll_pass(net, batch, pm, noise)
+        _heat_entries(res, net, pm, lq, gt, heats, n_sample, scale, crop, seed, lpips_fn)
+    return res
+
+
+def _nll_pass(net, batch: Dict, pm: "M.PairMetrics", noise: Optional[torch.Tensor] = None):
+    """The part of a test step in front of the sampling, by model family (``net.cfg.sr``) -> (res, cond, gt): ``res`` the per-image
+    dicts holding "nll" and "lr", ``cond`` the ONE tensor every sample of the call is drawn from, ``gt`` the GT batch or None.
+
+    SR net (HCFlowSRModel.test(), HCFlow_SR_model.py:281-301): the NLL pass of (GT, LQ) when there is a GT; cond = LQ.
+    Rescaling net (HCFLowRescalingModel.test(), HCFlow_Rescaling_model.py:306-324): one forward pass GT -> LR^ over the batch, then
+    ``metrics.quantize``; cond = the quantised LR^ (``net.downscale``). "nll" is the reference's return value ``fake_z1.mean()``
+    per image (the mean of the first split latent, NOT a likelihood: the column name is the log line's); "lr" compares the
+    dataset's bicubic LQ with the quantised LR^ ("LR" columns of the line) and is present only when the batch has an "LQ"."""
     dev = next(net.parameters()).device
+    if not net.cfg.sr:
+        if "GT" not in batch:
+            raise ValueError("evaluating a rescaling net needs the batch's \"GT\": its test step starts from the HR image")
+        if noise is not None:
+            raise ValueError("noise= belongs to the SR nets' NLL pass; a rescaling net's forward pass draws nothing")
+        gt = batch["GT"].to(dev)
+        B = gt.shape[0]
+        res: List[Dict] = [dict() for _ in range(B)]
+        lr_q, z1, _ = net.downscale(gt)
+        # fake_z1.mean() of a batch of one, image by image (the same reduction as the reference's call); one readback
+        for b, v in enumerate(torch.stack([z1[b:b + 1].mean() for b in range(B)]).cpu().tolist()):
+            res[b]["nll"] = v
+        if "LQ" in batch:
+            for b, m in enumerate(M.rows_to_dicts(pm.compare(pm.embed(batch["LQ"].to(dev), 0, 0), lr_q))):
+                res[b]["lr"] = {k: m[k] for k in ("psnr", "ssim", "psnr_y", "ssim_y")}
+        return res, lr_q, gt
     lq = batch["LQ"].to(dev)
     gt = batch["GT"].to(dev) if "GT" in batch else None
     B = lq.shape[0]
-    crop = scale if crop_border is None else crop_border          # test_HCFlow.py:48
-    res: List[Dict] = [dict() for _ in range(B)]
-    with torch.no_grad():
-        if gt is not None:
-            # per-image NLL: the engine returns the objective (logdet + log p) of every sample; nll_b = -obj_b / (ln 2 * H W)
-            # (HCFlowNet_SR_arch.py:62-66: the reference's nll.mean() over a batch of one is exactly this)
-            lr_hat, _, obj, _ = net.normal_flow_diracLR(gt, lq, noise=noise, return_internals=True)
-            pix = float(gt.shape[2] * gt.shape[3])
-            for b, o in enumerate(obj.double().cpu().tolist()):
-                res[b]["nll"] = -o / (0.6931471805599453 * pix)
-            for b, m in enumerate(M.rows_to_dicts(pm.compare(pm.embed(lq, 0, 0), lr_hat))):
-                res[b]["lr"] = {k: m[k] for k in ("psnr", "ssim", "psnr_y", "ssim_y")}
-        ref = pm.embed(gt, crop, scale) if gt is not None and n_sample > 0 else None      # the GT is prepared once per call
-        for hi, heat in enumerate(heats):
-            samples, lps = [], []
-            pset = M.PairSampleSet(pm, ref, n_sample) if ref is not None else None
-            for s in range(n_sample):
-                kw = {} if seed is None else {"seed": seed + 1000 * hi + s}
-                # every heat / sample of the sweep conditions on the SAME lq: the deepest level's conditional features (the RRDB
-                # trunk: most of a Face x8 call) are computed once and reused, bit-identical outputs (arch.py: cache_cond)
-                sr = net(lr=lq, z=None, u=None, eps_std=heat, reverse=True, training=False, cache_cond=True, **kw)
-                samples.append(sr)
-                if pset is not None:                                   # one compare into a device row; LPIPS stays there too
-                    pset.add(sr)
-                    if lpips_fn is not None:
-                        lps.append(lpips_fn(2 * gt - 1, 2 * sr - 1).reshape(B, -1).mean(dim=1))      # [B, 1, 1, 1] -> one value per image
-            rows = _heat_rows(pset, lps) if pset is not None else [[0.0] * 9] * B             # no samples: zeros, as a sum of none
-            for b in range(B):
-                ent = dict(zip(M.KEYS, rows[b][:8])) if gt is not None else {}
-                if gt is not None and lpips_fn is not None:
-                    ent["lpips"] = rows[b][-1]
-                ent["diversity"] = M.diversity([s[b:b + 1] for s in samples]) if n_sample > 1 else 0.0
-                res[b][float(heat)] = ent
-    return res
+    res = [dict() for _ in range(B)]
+    if gt is not None:
+        # per-image NLL: the engine returns the objective (logdet + log p) of every sample; nll_b = -obj_b / (ln 2 * H W)
+        # (HCFlowNet_SR_arch.py:62-66: the reference's nll.mean() over a batch of one is exactly this)
+        lr_hat, _, obj, _ = net.normal_flow_diracLR(gt, lq, noise=noise, return_internals=True)
+        pix = float(gt.shape[2] * gt.shape[3])
+        for b, o in enumerate(obj.double().cpu().tolist()):
+            res[b]["nll"] = -o / (0.6931471805599453 * pix)
+        for b, m in enumerate(M.rows_to_dicts(pm.compare(pm.embed(lq, 0, 0), lr_hat))):
+            res[b]["lr"] = {k: m[k] for k in ("psnr", "ssim", "psnr_y", "ssim_y")}
+    return res, lq, gt
+
+
+def _heat_entries(res: List[Dict], net, pm: "M.PairMetrics", lq: torch.Tensor, gt: Optional[torch.Tensor], heats: Iterable[float],
+                  n_sample: int, scale: int, crop: int, seed: Optional[int], lpips_fn) -> None:
+    """``evaluate_batch``'s entry per heat, for either family: ``n_sample`` draws from ``lq`` (an SR net's LQ, a rescaling net's
+    quantised LR^) per heat, compared with the GT prepared once."""
+    B = lq.shape[0]
+    ref = pm.embed(gt, crop, scale) if gt is not None and n_sample > 0 else None      # the GT is prepared once per call
+    for hi, heat in enumerate(heats):
+        samples, lps = [], []
+        pset = M.PairSampleSet(pm, ref, n_sample) if ref is not None else None
+        for s in range(n_sample):
+            kw = {} if seed is None else {"seed": seed + 1000 * hi + s}
+            # every heat / sample of the sweep conditions on the SAME lq: the deepest level's conditional features (the RRDB
+            # trunk: most of a Face x8 call) are computed once and reused, bit-identical outputs (arch.py: cache_cond)
+            sr = net(lr=lq, z=None, u=None, eps_std=heat, reverse=True, training=False, cache_cond=True, **kw)
+            samples.append(sr)
+            if pset is not None:                                   # one compare into a device row; LPIPS stays there too
+                pset.add(sr)
+                if lpips_fn is not None:
+                    lps.append(lpips_fn(2 * gt - 1, 2 * sr - 1).reshape(B, -1).mean(dim=1))      # [B, 1, 1, 1] -> one value per image
+        rows = _heat_rows(pset, lps) if pset is not None else [[0.0] * 9] * B             # no samples: zeros, as a sum of none
+        for b in range(B):
+            ent = dict(zip(M.KEYS, rows[b][:8])) if gt is not None else {}
+            if gt is not None and lpips_fn is not None:
+                ent["lpips"] = rows[b][-1]
+            ent["diversity"] = M.diversity([s[b:b + 1] for s in samples]) if n_sample > 1 else 0.0
+            res[b][float(heat)] = ent
 
 
 def _heat_rows(pset: "M.PairSampleSet", lps: List[torch.Tensor]) -> List[List[float]]:
@@ -147,11 +196,10 @@ def evaluate_sweep(net, batch: Dict, heats: Iterable[float], n_sample: int, scal
     read back once at the end (see ``evaluate_batch``)."""
     heats = [float(t) for t in heats]
     dev = next(net.parameters()).device
-    lq = batch["LQ"].to(dev)
-    gt = batch["GT"].to(dev) if "GT" in batch else None
-    B, nH = lq.shape[0], len(heats)
     crop = scale if crop_border is None else crop_border          # test_HCFlow.py:48
-    res = evaluate_batch(net, batch, (), 0, scale, crop_border)   # "nll" and "lr" (no heats: the NLL pass alone)
+    with torch.no_grad():
+        res, lq, gt = _nll_pass(net, batch, M.PairMetrics())      # "nll" and "lr"; lq: the LQ, or a rescaling net's quantised LR^
+    B, nH = lq.shape[0], len(heats)
     chunks = sweep_chunks(B, nH, max_batch)
     if not chunks or n_sample < 1:
         return res
@@ -199,10 +247,14 @@ def evaluate_sample_set(net, batch: Dict, heats: Iterable[float], n_sample: int,
     "lpips_best": the best whole sample's map mean, "local_best": the mean of the per-pixel best over the samples, "score":
     (lpips_best - local_best) / lpips_best} as floats -- ``global_best`` / ``local_best`` / ``score`` of
     ``hcflow_amd.lpips.LPIPSMap.sample_set`` (defined there). ``lpips_map`` is an ``LPIPSMap`` on the net's device. Per heat the
-    samples are those of ``evaluate_batch`` (seeds ``seed + 1000 * hi + s``, ``cache_cond=True``); the GT goes through AlexNet once
+    samples are those of ``evaluate_batch`` (seeds ``seed + 1000 * hi + s``, ``cache_cond=True``; drawn from the LQ for an SR net,
+    from the quantised LR^ of ``net.downscale(gt)`` for a rescaling net, which needs no "LQ"); the GT goes through AlexNet once
     per heat, the samples accumulate on the device, and each result vector is read back once per heat."""
     dev = next(net.parameters()).device
-    lq, gt = batch["LQ"].to(dev), batch["GT"].to(dev)
+    gt = batch["GT"].to(dev)
+    with torch.no_grad():
+        # an SR net samples from the dataset's LQ, a rescaling net from its own quantised LR^ (one tensor for the whole call)
+        lq = batch["LQ"].to(dev) if net.cfg.sr else net.downscale(gt)[0]
     B = lq.shape[0]
     res: List[Dict] = [dict() for _ in range(B)]
     with torch.no_grad():

@@ -214,6 +214,57 @@ class PairSampleSet:
         return {"per_sample": rows, "mean": rows.mean(dim=0), "best_psnr": best, "best_psnr_index": idx}
 
 
+def _gpu_tensor(what: str, t, dtype, shape_ok, expected: str) -> torch.Tensor:
+    """The argument checks of ``quantize`` / ``from_image``: a CUDA tensor of ``dtype`` whose shape ``shape_ok`` accepts, contiguous."""
+    if not torch.is_tensor(t) or not t.is_cuda:
+        raise _lib.HcfError("%s needs a GPU tensor (got %s); hcflow_amd has no CPU fallback"
+                            % (what, t.device if torch.is_tensor(t) else type(t).__name__))
+    if t.dtype != dtype or not shape_ok(t.shape) or t.numel() == 0:
+        raise _lib.HcfError("%s: expected %s, got %s %s" % (what, expected, t.dtype, tuple(t.shape)))
+    return t.detach().contiguous()
+
+
+def _out_tensor(what: str, name: str, given: Optional[torch.Tensor], shape, dtype, device) -> torch.Tensor:
+    if given is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    if not torch.is_tensor(given) or given.dtype != dtype or tuple(given.shape) != tuple(shape) or given.device != device \
+            or not given.is_contiguous():
+        raise _lib.HcfError("%s: %s must be a contiguous %s %s on %s, got %s %s on %s"
+                            % (what, name, dtype, list(shape), device, getattr(given, "dtype", None),
+                               tuple(getattr(given, "shape", ())), getattr(given, "device", None)))
+    return given
+
+
+def quantize(x: torch.Tensor, out: Optional[torch.Tensor] = None, image: bool = False, image_out: Optional[torch.Tensor] = None):
+    """``(torch.clamp(x, 0, 1) * 255.).round() / 255.`` of a CUDA fp32 ``[B,3,H,W]`` tensor, bit for bit: the forward value of the
+    reference's ``Quantization`` (Basic.py:186-202), which its rescaling test applies to LR^ before every inverse
+    (HCFlow_Rescaling_model.py:306-324). With ``image=True`` (or an ``image_out``) the pair ``(q, [B,H,W,3] uint8 BGR)``: the same
+    integers as the image ``util.tensor2img`` makes of ``x``, i.e. what ``PairMetrics.compare(image=True)`` stores -- the LR as it
+    is written to disk; ``from_image`` is the way back. One launch writes both (include/hcflow.h: hcf_metric_quantize); ``out=`` /
+    ``image_out=`` are filled in place and nothing is allocated. Not differentiable: a training step keeps its own straight-through
+    ``Quantization``. No CPU fallback."""
+    x = _gpu_tensor("metrics.quantize", x, torch.float32, lambda s: len(s) == 4 and s[1] == 3, "float32 [B,3,H,W]")
+    B, _, H, W = x.shape
+    q = _out_tensor("metrics.quantize", "out", out, (B, 3, H, W), torch.float32, x.device)
+    img = None
+    if image or image_out is not None:
+        img = _out_tensor("metrics.quantize", "image_out", image_out, (B, H, W, 3), torch.uint8, x.device)
+    _lib.launch("hcf_metric_quantize", x.device, x, B, H, W, q, img)
+    return (q, img) if img is not None else q
+
+
+def from_image(u8: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """A stored image back as the tensor a net takes: CUDA uint8 ``[B,H,W,3]`` BGR (``quantize``'s image, ``util.tensor2img``'s
+    layout) -> fp32 ``[B,3,H,W]`` RGB = ``u8.astype(np.float32) / 255.`` transposed, bit for bit what the reference's datasets
+    produce from an image file (data/util.py:72-79). ``quantize(from_image(u8), image=True)`` returns ``(from_image(u8), u8)``
+    exactly: stored images are fixed points (include/hcflow.h: hcf_metric_from_image). No CPU fallback."""
+    u8 = _gpu_tensor("metrics.from_image", u8, torch.uint8, lambda s: len(s) == 4 and s[3] == 3, "uint8 [B,H,W,3]")
+    B, H, W, _ = u8.shape
+    o = _out_tensor("metrics.from_image", "out", out, (B, 3, H, W), torch.float32, u8.device)
+    _lib.launch("hcf_metric_from_image", u8.device, u8, B, H, W, o)
+    return o
+
+
 def rows_to_dicts(m: torch.Tensor) -> List[Dict[str, float]]:
     """A ``[B,8]`` result of ``PairMetrics.compare`` as ``psnr_ssim``'s list of dicts (one readback)."""
     return [dict(zip(KEYS, row)) for row in m.detach().double().cpu().tolist()]

@@ -407,6 +407,25 @@ int hcf_metric_pair_embed(const float* gt, int32_t B, int32_t H, int32_t W, int3
 int hcf_metric_pair_compare(const void* ref, size_t ref_bytes, const float* sr, int32_t B, int32_t H, int32_t W, int32_t crop_border,
                             int32_t scale, double* out, uint8_t* image_out, void* work, size_t work_bytes, hcf_stream_t stream);
 
+/* The 8-bit image boundary of a rescaling net used as a codec (hcf_image_codec.hip): HR -> LR^ -> stored 8-bit image -> HR^.
+ *   hcf_metric_quantize    x (device [B,3,H,W] RGB fp32) -> q (NULL or device [B,3,H,W] fp32) = rint(clamp(x, 0, 1) * 255.f) / 255.f,
+ *                          the forward value of the reference's Quantization (Basic.Quant.forward, models/modules/Basic.py:186-202,
+ *                          applied by HCFLowRescalingModel.test(), HCFlow_Rescaling_model.py:306-324): round half to even, an IEEE
+ *                          fp32 division. NaN stays NaN and -0.0 gives -0.0 (== 0), both as through torch.clamp on the host; +-inf are clamped. image_out
+ *                          (NULL or device uint8 [B][H][W][3] BGR): the same integers = util.tensor2img(x) of every image
+ *                          (utils/util.py:790-816), i.e. what hcf_metric_pair_compare's image_out holds for x (a NaN is byte 0
+ *                          there and here). One launch writes both; either may be NULL, not both.
+ *   hcf_metric_from_image  image (device uint8 [B][H][W][3] BGR) -> out (device [B,3,H,W] RGB fp32) = float(u) / 255.f with the same
+ *                          division: what the reference's datasets make of a stored image (data/util.py:72-79 read_img: astype(np.float32) / 255.;
+ *                          data/GT_dataset.py:107-111: BGR -> RGB, then HWC -> CHW). A stored image
+ *                          is a fixed point: quantize(from_image(u)) gives from_image(u) and u back, bit for bit.
+ * One thread owns the same pixels of all three planes; 16-byte accesses where H * W is a multiple of 4 and the addresses are
+ * aligned, else one pixel per thread (a batch slice of an odd-sized tensor is legal). Both only enqueue one kernel on `stream`: no
+ * allocation, copy, synchronisation or atomic. Checked before anything touches a device: null x / image / out, q and image_out
+ * both NULL, B, H, W < 1, B > 65535 or H * W > 2^36 -> HCF_ERR_ARG. */
+int hcf_metric_quantize(const float* x, int32_t B, int32_t H, int32_t W, float* q, uint8_t* image_out, hcf_stream_t stream);
+int hcf_metric_from_image(const uint8_t* image, int32_t B, int32_t H, int32_t W, float* out, hcf_stream_t stream);
+
 /* ---- per-op entry points (unit parity tests; tensors are device NCHW fp32) ------------------- */
 /* F.conv2d(x, w, stride 1, padding k/2) with the fused epilogue
  *   y = res2 + rs2 * (res1 + rs1 * act((conv + bias) * scale))
