@@ -50,7 +50,7 @@ SYMBOLS = [
     "hcf_op_quant_logp_backward_lr", "hcf_op_prior_encode_logp_backward", "hcf_op_input_grad",
     "hcf_data_prepare_batch", "hcf_data_prepare_paired",
     "hcf_op_fcn12", "hcf_op_conv2d_step_inverse",
-    "hcf_inverse_taus", "hcf_metric_stats_bytes", "hcf_metric_stats_add", "hcf_metric_stats_finish",
+    "hcf_inverse_taus", "hcf_inverse_logp", "hcf_metric_stats_bytes", "hcf_metric_stats_add", "hcf_metric_stats_finish",
     "hcf_metric_pair_ref_bytes", "hcf_metric_pair_workspace", "hcf_metric_pair_embed", "hcf_metric_pair_compare",
     "hcf_op_conv2d_views", "hcf_op_conv2d_wgrad_views", "hcf_op_conv_epilogue_backward_views", "hcf_op_conv2d_dgrad_fused_views",
     "hcf_op_seed_sum", "hcf_op_axpy_job", "hcf_train_backward_encode_ex",
@@ -105,6 +105,7 @@ def load() -> C.CDLL:
     lib.hcf_inverse.argtypes = [vp, fp, C.POINTER(fp), i32, f32, u64, fp, i32, i32, i32, u32, vp]
     lib.hcf_inverse_ex.argtypes = [vp, fp, C.POINTER(fp), i32, f32, u64, i64, fp, i32, i32, i32, u32, vp]
     lib.hcf_inverse_taus.argtypes = [vp, fp, C.POINTER(fp), i32, fp, u64, i64, fp, i32, i32, i32, u32, vp]
+    lib.hcf_inverse_logp.argtypes = [vp, fp, C.POINTER(fp), i32, f32, fp, u64, i64, fp, fp, i32, i32, i32, u32, vp]
     lib.hcf_check_range.argtypes = [vp, C.POINTER(i32)]
     lib.hcf_check_range_samples.argtypes = [vp, C.POINTER(i32), C.POINTER(u32)]
     lib.hcf_aux_stream.argtypes = [i32, i32, C.POINTER(vp)]

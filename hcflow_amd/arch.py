@@ -1013,18 +1013,24 @@ class _EngineModule(nn.Module):
     def _stream(idx):
         return C.c_void_p(torch.cuda.current_stream(idx).cuda_stream)
 
-    def _inverse(self, lr, eps_std, eps=None, clamp=True, seed=None, sample_offset=0, cache_cond=False):
+    def _inverse(self, lr, eps_std, eps=None, clamp=True, seed=None, sample_offset=0, cache_cond=False, want_logp=False):
         """``sample_offset``: this call is samples [offset, offset + B) of a larger (sharded) batch: the device draws are
         those of the global samples (hcf_inverse_ex). ``cache_cond``: keep / reuse the deepest level's conditional features
         while ``lr`` (same tensor, unchanged) and the parameters stay the same (tau sweeps, repeated sampling).
         ``eps_std``: the reference's scalar, or one temperature per sample (1-D float tensor / sequence of length B,
         hcf_inverse_taus): row b then holds the bits of the scalar call with ``eps_std[b]``, the same seed and the same global
-        sample index. Inference only; a wrong length or a negative / non-finite entry is a ValueError."""
+        sample index. Inference only; a wrong length or a negative / non-finite entry is a ValueError.
+        ``want_logp`` (HCFlowNet_SR.sample_with_logp, hcf_inverse_logp): returns (image, logp [B]); inference only."""
         taus = tau_vector(eps_std, int(lr.shape[0]) if torch.is_tensor(lr) and lr.dim() == 4 else None)
         if taus is not None:
             eps_std = taus                                         # validated: 1-D fp32, one temperature per sample
         eps_grad = eps is not None and any(torch.is_tensor(e) and e.requires_grad for e in eps)
         if self._wants_grad() or (torch.is_grad_enabled() and ((torch.is_tensor(lr) and lr.requires_grad) or eps_grad)):
+            if want_logp:
+                raise NotImplementedError(
+                    "HCFlowNet_SR.sample_with_logp is inference only (the taped inverse pass returns no density): call it under "
+                    "torch.no_grad() with frozen inputs. The differentiable route to the same number is "
+                    "encode(sr, param_grad=True)[2], the log-density of an image with a graph to the parameters.")
             if taus is not None:
                 raise _lib.HcfError(
                     "a per-sample eps_std vector has no differentiable (taped) inverse pass in hcflow_amd: call under "
@@ -1049,16 +1055,16 @@ class _EngineModule(nn.Module):
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())     # follows torch.manual_seed
         if not self.training and not _capturing():      # (a stale pass is drained with a stream sync: never while capturing)
             try:
-                return self._inverse_pass(lr, eps_std, eps, clamp, seed, sample_offset, cache_cond, defer=True)
+                return self._inverse_pass(lr, eps_std, eps, clamp, seed, sample_offset, cache_cond, defer=True, want_logp=want_logp)
             except _StaleParameters:
                 pass                                               # parameters changed since the last call: the checked path
             except _lib.HcfError:
                 if not self.__dict__.pop("_ran_unverified", False):
                     raise
                 # an error of a pass that ran on UNVERIFIED packs is not the caller's: the checked path decides
-        return self._inverse_pass(lr, eps_std, eps, clamp, seed, sample_offset, cache_cond, defer=False)
+        return self._inverse_pass(lr, eps_std, eps, clamp, seed, sample_offset, cache_cond, defer=False, want_logp=want_logp)
 
-    def _inverse_pass(self, lr, eps_std, eps, clamp, seed, sample_offset, cache_cond, defer):
+    def _inverse_pass(self, lr, eps_std, eps, clamp, seed, sample_offset, cache_cond, defer, want_logp=False):
         dev = self._device()
         eng, idx = self._engine_for(dev, defer=defer, twin_hint=self._nstreams[0] >= 2 and torch.is_tensor(lr) and lr.dim() == 4
                                     and int(lr.shape[0]) >= 4)
@@ -1068,8 +1074,11 @@ class _EngineModule(nn.Module):
         assert c == 3
         cfg = self.cfg
         out = torch.empty(B, 3, h * cfg.scale, w * cfg.scale, device=dev, dtype=torch.float32)
+        # want_logp: the density of every row leaves the same pass (hcf_inverse_logp); each half of a split call and each exact
+        # re-run of a flagged sample writes its own rows
+        logp = torch.empty(B, device=dev, dtype=torch.float32) if want_logp else None
         if B == 0:              # an empty batch samples to an empty batch (every op of the reference's reverse path accepts one)
-            return out
+            return (out, logp) if want_logp else out
         shapes = eps_shapes(cfg, B, h, w)
         keep = []
         keep_at = [None] * len(shapes)
@@ -1119,6 +1128,10 @@ class _EngineModule(nn.Module):
         def run(eng_, lo, hi, stream_, fl=flags):
             # samples [lo, hi): their LR rows, their rows of the injected draws (or the same seed with their global sample index:
             # the device draws are indexed by sample, hcf_inverse_ex), their output rows, their slice of a temperature vector
+            if logp is not None:
+                return eng_.lib.hcf_inverse_logp(eng_.handle, lr[lo:hi].data_ptr(), arr_for(lo, hi), len(shapes), tau,
+                                                 None if taus is None else taus[lo:hi].data_ptr(), seed, int(sample_offset) + lo,
+                                                 out[lo:hi].data_ptr(), logp[lo:hi].data_ptr(), hi - lo, h, w, fl, stream_)
             if taus is not None:
                 return eng_.lib.hcf_inverse_taus(eng_.handle, lr[lo:hi].data_ptr(), arr_for(lo, hi), len(shapes),
                                                  taus[lo:hi].data_ptr(), seed, int(sample_offset) + lo, out[lo:hi].data_ptr(),
@@ -1128,9 +1141,9 @@ class _EngineModule(nn.Module):
 
         def one_sample(b):
             return run(eng, b, b + 1, self._stream(idx), flags & ~(_lib.FLAG_KEEP_COND | _lib.FLAG_REUSE_COND))
-        self._run_checked(eng, idx, run, "hcf_inverse", batch=B, call_sample=None if cache_cond else one_sample,
-                          parts=parts, threaded=_split_threaded())
-        return out
+        self._run_checked(eng, idx, run, "hcf_inverse_logp" if want_logp else "hcf_inverse", batch=B,
+                          call_sample=None if cache_cond else one_sample, parts=parts, threaded=_split_threaded())
+        return (out, logp) if want_logp else out
 
     # convenience for benchmarks / multi-GPU sharding
     def engine(self):
@@ -1220,6 +1233,21 @@ class HCFlowNet_SR(_EngineModule):
                              cache_cond=False):
         """lr (+ sampled z) -> clamp(HR)   (HCFlowNet_SR_arch.py:70-75)."""
         return self._inverse(lr, eps_std, eps=eps, clamp=clamp, seed=seed, sample_offset=sample_offset, cache_cond=cache_cond)
+
+    def sample_with_logp(self, lr, eps_std, eps=None, seed=None, sample_offset=0, cache_cond=False, clamp=True):
+        """lr -> (sr, logp [B]): the sampling pass of ``net(lr=lr, eps_std=..., reverse=True)`` -- same arguments, the same image
+        bit for bit -- that also returns the log-density of what it drew (hcf_inverse_logp). ``logp[b]`` is what
+        ``encode(sr_unclamped)[2][b]`` returns: log-det + the prior log-densities in nats, with the constant -ln(quant) * H * W and
+        WITHOUT the Dirac-LR term, i.e. log p(x | lr) under the model at temperature 1 whatever ``eps_std`` drew the sample.
+        With ``clamp=True`` the image is clamped and the density is still that of the unclamped sample. The inverse pass computes
+        every term on its way (each coupling's logscale, the prior's logs and eps), so the cost is a few reductions, not the
+        second full pass ``encode`` is. Per-sample ``eps_std`` vectors, ``sample_offset``, ``cache_cond`` and the two-stream
+        split work as in the plain call, and a row's bits do not depend on the batch it sits in; a sample re-run exactly after an
+        f16-range overflow gets the ``logp`` of its exact pass.
+        Inference only: with grad mode on and a parameter, ``lr`` or an ``eps`` requiring grad it raises NotImplementedError;
+        ``encode(sr, param_grad=True)`` is the differentiable route to the density of an image."""
+        return self._inverse(lr, eps_std, eps=eps, clamp=clamp, seed=seed, sample_offset=sample_offset, cache_cond=cache_cond,
+                             want_logp=True)
 
     # -- latent encoding: hr -> (z_lr, eps per level, log-density) and its exact inverse
     def encode(self, hr, noise=None, add_gt_noise=False, param_grad=False):

@@ -68,6 +68,7 @@ struct ConvArgs {
   // f16x3 kernel, optional fused inverse flow-step tail (tC > 0): z <- actnorm^-1(W^-1 coupling^-1(z, h = this conv))
   View tz; View tzo; const float* tmat; const float* tbias; const float* tmul; int tC, tns, tmode;
   float* tzpad; int tzpad_n;       // ... and StepArgs::zpad16 / zpad_n
+  float* tpart; int tpart_stride;  // ... and StepArgs::partial / partial_stride: conv_f16x3_tail_slots() slots per sample (nullptr: none)
   const float* zeros;      // f16x3 kernel: >= 64 bytes of zeros in device memory (out-of-image halo reads)
   const float* in_max;     // f16x3 kernel, optional (training): device float = max |x| of source 0 -> power-of-two input scaling
   unsigned long long* dbg; // HCF_CONV_TIMERS builds only (tools/conv_bench.py): phase timers of a few mid-grid blocks
@@ -97,6 +98,7 @@ struct ConvArgs {
 // grid of the scaled f16x3 variant for a [B, H, W] tensor (= rows of ConvArgs::fb_part when tile_h is asked for), strips and the
 // 4-row tiles of small grids included
 int conv_f16x3_scaled_blocks(int B, int H, int W, int* strip_w = nullptr, int* tile_h = nullptr);
+int conv_f16x3_tail_slots(int H, int W);      // partial slots per sample of a fused-tail launch with ConvArgs::tpart
 
 enum { ACT_NONE = 0, ACT_RELU = 1, ACT_LRELU = 2 };
 // Branch-free activation for unrolled epilogues: a runtime `if (act == ...)` chain per accumulator compiles to a chain of
@@ -222,7 +224,7 @@ struct StepArgs {
   const float* mat;      // C x C row-major (W^-1 for inverse, W for forward) or nullptr (no permutation)
   const float* an_bias;  // [C]
   const float* an_mul;   // [C]  exp(-logs) (inverse) or exp(logs) (forward)
-  float* partial;        // forward couple: per-block partial sums of logscale, [B][nblk]; else nullptr
+  float* partial;        // forward couple, inverse tail (hcf_inverse_logp): per-block partial sums of logscale, [B][nblk]; else nullptr
   int partial_stride;    // floats between consecutive samples in `partial`
   View aux;              // forward head, training tape: also store the ActNorm output (input of W); p == nullptr: no
   float* zpad16; int zpad_n;   // inverse tail: also store out[:, :zpad_n] as a zero-padded 16-channel tensor (or nullptr)
@@ -232,6 +234,7 @@ int launch_step_tail_inv(const StepArgs& a, hipStream_t st);     // coupling^-1,
 int launch_step_head_fwd(const StepArgs& a, hipStream_t st);     // actnorm, W           (h unused)
 int launch_step_couple_fwd(const StepArgs& a, hipStream_t st);   // coupling (in place capable) + sum logscale
 int step_blocks_per_sample(int H, int W);
+int step_tail_inv_slots(int C, int H, int W);   // slots per sample launch_step_tail_inv may write through StepArgs::partial
 int step_cmax(int C);   // register-array bucket (8/12/24/48) used by the step kernels; -1 if C > 48
 
 // ---- backward kernels of the training path (hcf_train.hip) ---------------------------------
@@ -362,9 +365,10 @@ struct GaussArgs {
   int64_t b0;            // device draws: sample b of this call is sample b0 + b of the (sharded) batch, so shards reproduce the full batch
   View out;              // sample: latent out.  logp/encode: latent in
   float* aux;            // encode (rescale fwd): NCHW output z = (a-mean) exp(-logs)
-  float* partial; int partial_stride;
+  float* partial; int partial_stride;      // logp kernels; sample (hcf_inverse_logp, nullable): gauss_sample_slots() per sample
 };
 int launch_gauss_sample(const GaussArgs& a, hipStream_t st);
+int gauss_sample_slots(int C, int H, int W);     // blocks per sample of launch_gauss_sample = its partial slots
 int launch_gauss_logp(const GaussArgs& a, hipStream_t st);      // SR forward: partial sums of log p
 int launch_gauss_encode(const GaussArgs& a, hipStream_t st);    // rescaling forward
 int launch_gauss_encode_logp(const GaussArgs& a, hipStream_t st);   // SR encode: eps -> aux (NCHW) and the partial sums of log p

@@ -100,6 +100,8 @@ int conv_f16x3_scaled_blocks(int B, int H, int W, int* strip_w, int* tile_h) {
 }
 // the bound over both choices above: strips only ever replace MORE per-image tiles, and the 4-row tiles are the shorter ones
 int conv_f16x3_scaled_blocks_max(int B, int H, int W) { return B * ((W + 31) / 32) * ((H + 3) / 4); }
+// partial slots per sample of a fused-tail launch with ConvArgs::tpart: one per 4-row band of every 32-column tile
+int conv_f16x3_tail_slots(int H, int W) { return ((W + 31) / 32) * ((H + 3) / 4); }
 
 namespace f16x3 {
 
@@ -571,13 +573,26 @@ __global__ __launch_bounds__((TH == 4) ? 256 : 32 * TH, (TH == 16) ? ((NTB == 1)
     __syncthreads();
     const int ty = tid >> 5, tx = tid & 31;
     const int y = y0 + ty, x = x0 + tx;
+    float lsum = 0.f;
     if (ty < TH && y < H && x < W) {                  // (4-row tiles: the upper half of the block's threads has no pixel)
       const size_t pix = (size_t)((size_t)b * H + y) * W + x;
       float z[TAILC], yv[TAILC];
       load_pixel<TAILC>(a.tz, pix, a.tC, z);
-      step_tail_inverse_pixel<TAILC>(z, hl + tid * HCS, a.tC, a.tns, a.tmode, a.tmat, a.tbias, a.tmul, yv);
+      step_tail_inverse_pixel<TAILC>(z, hl + tid * HCS, a.tC, a.tns, a.tmode, a.tmat, a.tbias, a.tmul, yv, &lsum);
       store_pixel<TAILC>(a.tzo, pix, a.tC, yv);
       if (a.tzpad) store_pad16<TAILC>(a.tzpad, pix, a.tzpad_n, yv);
+    }
+    if (a.tpart) {
+      // hcf_inverse_logp: the tile's sum of logscale. One slot per FOUR rows of the tile (two waves), not per block: the 4- and
+      // the 8-row tile (chosen by the size of the whole grid, batch included) then add the same values in the same order, and a
+      // sample's sum keeps its bits whatever batch it sits in. Slot [sample][4-row band][tile column].
+      lsum = wave_sum(lsum);
+      __syncthreads();                               // every thread has read its h row
+      if (lane == 0) hl[wave] = lsum;
+      __syncthreads();
+      const int band = tyb * (TH / 4) + (tid >> 7);
+      if ((tid & 127) == 0 && tid < 32 * TH && 4 * band < H)
+        a.tpart[(size_t)b * a.tpart_stride + band * tiles_x + txb] = hl[2 * (tid >> 7)] + hl[2 * (tid >> 7) + 1];
     }
     return;
   }

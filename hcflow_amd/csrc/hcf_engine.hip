@@ -549,6 +549,18 @@ int hcf_inverse_taus(hcf_engine* e, const float* lr, const float* const* eps, in
                      (hipStream_t)stream, flags, {1, B, h, w});
 }
 
+int hcf_inverse_logp(hcf_engine* e, const float* lr, const float* const* eps, int32_t n_eps, float tau, const float* taus_dev,
+                     uint64_t seed, int64_t first_sample, float* out_hr, float* out_logp, int32_t B, int32_t h, int32_t w,
+                     uint32_t flags, hcf_stream_t stream) {
+  if (!e || !lr || !out_hr || !out_logp || B < 1 || h < 1 || w < 1 || first_sample < 0) return HCF_ERR_ARG;
+  if (e->cfg.kind != HCF_KIND_SR)
+    return e->fail(HCF_ERR_UNSUPPORTED, "hcf_inverse_logp on a rescaling engine: its forward pass tracks no log-det, so the density of a "
+                                        "sample has no reference (HCFlowNet_Rescaling_arch.py:39-46)"), HCF_ERR_UNSUPPORTED;
+  // (a plan of its own: the slot table joins the arena)
+  return e->run_pass([&]() { e->pass_inverse(lr, eps, n_eps, taus_dev ? 0.f : tau, seed, first_sample, out_hr, B, h, w, flags, taus_dev, out_logp); },
+                     (hipStream_t)stream, flags, {1, B, h, w, 1});
+}
+
 int hcf_inverse(hcf_engine* e, const float* lr, const float* const* eps, int32_t n_eps, float tau, uint64_t seed,
                 float* out_hr, int32_t B, int32_t h, int32_t w, uint32_t flags, hcf_stream_t stream) {
   return hcf_inverse_ex(e, lr, eps, n_eps, tau, seed, 0, out_hr, B, h, w, flags, stream);

@@ -110,6 +110,7 @@
         a.tz = tail->z; a.tzo = tail->out; a.tmat = tail->mat; a.tbias = tail->an_bias; a.tmul = tail->an_mul;
         a.tC = tail->C; a.tns = tail->ns; a.tmode = tail->mode;
         a.tzpad = tail->zpad16; a.tzpad_n = tail->zpad_n;
+        a.tpart = tail->partial; a.tpart_stride = tail->partial_stride;
       }
       r = HCF_ERR_UNSUPPORTED;
       if (fuse2 && !tail) {                 // one K chunk: the persistent small-K form (res1 = pre-activation term, if any)
@@ -346,6 +347,11 @@
     a.z = z.all(); a.h = sc.hout.v(0, s.f_out); a.out = z.all();
     const bool pad_next = next && next->C == s.C && w4f_ok(*next, u, H, W, sc);
     if (pad_next) { a.zpad16 = sc.zpad.p; a.zpad_n = next->ns; }
+    if (inv_part && s.mode == CPL_AFFINE) {           // hcf_inverse_logp: this step's sum of logscale, per block of whichever kernel finishes it
+      a.partial = inv_part + inv_pslot;
+      a.partial_stride = inv_pstride;
+      inv_pslot += inv_step_slots(s, H, W);
+    }
     if (can_fuse_tail(s)) {
       run_coupling_net(s, step_z1(s, z), u, H, W, sc, &a);      // conv3's epilogue finishes the step
     } else {
@@ -577,14 +583,36 @@
     return ld_const;
   }
 
+  // Sampling with the density (hcf_inverse_logp): per-sample partial-sum slots of the inverse pass, in the order it fills them. The
+  // three kernels that can finish a step have different grids: the fused conv tail one slot per 4-row band of a 32-column tile,
+  // the 48-channel tail kernel one per 64 pixels, the per-pixel tail one per 256; the prior sampler one per 256 ELEMENTS.
+  int inv_step_slots(const Step& s, int H, int W) const {
+    return can_fuse_tail(s) ? conv_f16x3_tail_slots(H, W) : step_tail_inv_slots(s.C, H, W);
+  }
+  int inv_logp_slots(int h, int w) const {
+    int n = 0;
+    for (int level = 0; level < cfg.L; ++level) {
+      const int H = h << (cfg.L - 1 - level), W = w << (cfg.L - 1 - level);
+      for (const Step& s : levels[level].steps) if (s.mode == CPL_AFFINE) n += inv_step_slots(s, H, W);
+      for (const Step& s : levels[level].cf.steps) if (s.mode == CPL_AFFINE) n += inv_step_slots(s, H, W);
+      n += gauss_sample_slots(levels[level].cf.Ca, H, W);      // prior log-density of the eps applied
+    }
+    return n;
+  }
+  float* inv_part = nullptr;     // the running pass's slot table (null: a plain sampling pass), its row length and the next free slot
+  int inv_pstride = 0, inv_pslot = 0;
+
   // ---------------------------------------------------------------- inverse pass
   // FlowNet.reverse_flow (FlowNet_SR_x4.py:106-123, FlowNet_SR_x8.py:121-144, FlowNet_Rescaling_x4.py:111-128)
   // taus_dev (hcf_inverse_taus): device [B], one temperature per sample of this call, read by the prior kernels; nullptr -> tau
   void pass_inverse(const float* lr, const float* const* eps, int n_eps, float tau, uint64_t seed, int64_t sample0, float* out,
-                    int B, int h, int w, uint32_t flags, const float* taus_dev = nullptr) {
+                    int B, int h, int w, uint32_t flags, const float* taus_dev = nullptr, float* out_logp = nullptr) {
     B_ = B;
     arena.top = 0;
     const int L = cfg.L;
+    // out_logp (hcf_inverse_logp): [B], the log-density hcf_encode_sr returns for the unclamped image of this pass
+    const int nslots = out_logp ? inv_logp_slots(h, w) : 0;
+    inv_part = nullptr; inv_pstride = nslots; inv_pslot = 0;
     // HCF_FLAG_KEEP_COND / HCF_FLAG_REUSE_COND: the deepest level's conditional features and prior-head output depend on lr
     // only (FlowNet_SR_x4.py:113-115, FlowNet_SR_x8.py:129): they sit at fixed arena offsets (first allocations of the pass) and
     // survive until another kind of pass, another shape or a parameter change touches the arena.
@@ -601,6 +629,10 @@
       const int H = h << (L - 1 - level), W = w << (L - 1 - level);
       cfb[level] = alloc(B, H, W, cond_ch());
       if (level == L - 1 && keep_c) hkeep = alloc(B, H, W, cf.Ca * 2);
+      if (level == L - 1 && out_logp) {               // (behind the kept buffers: their offsets are those of a plain pass)
+        inv_part = arena.alloc((size_t)B * nslots);
+        HCF_LAUNCH(launch_fill(inv_part, (size_t)B * nslots, 0.f, st));
+      }
       Buf z = alloc(B, H, W, lv.C);
       const bool cached = reuse_c && level == L - 1;
       if (level == L - 1) {
@@ -626,6 +658,11 @@
         const int draw = L - 1 - level;
         g.eps = (eps && draw < n_eps) ? eps[draw] : nullptr;
         g.tau = tau; g.seed = seed; g.offset = (uint64_t)draw; g.b0 = sample0; g.tau_b = taus_dev;
+        if (inv_part) {
+          g.partial = inv_part + inv_pslot;
+          g.partial_stride = nslots;
+          inv_pslot += gauss_sample_slots(cf.Ca, H, W);
+        }
         HCF_LAUNCH(launch_gauss_sample(g, st));
       }
       zpad_valid = false;
@@ -639,6 +676,12 @@
       if (level == 0)
         HCF_LAUNCH(launch_unsqueeze_nchw(z.all(), out, B, lv.C, H, W, cfg.squeeze == HCF_SQUEEZE_HAAR ? 1 : 0,
                                          (flags & HCF_FLAG_NO_CLAMP) ? 0 : 1, st));
+    }
+    if (out_logp) {
+      if (inv_pslot != nslots) fail(HCF_ERR_STATE, "internal: inverse partial slot count");
+      const int H0 = h << L, W0 = w << L;
+      HCF_LAUNCH(launch_reduce_partials(inv_part, nslots, nslots, B, ld_const_sum(H0, W0), (double)H0 * W0, out_logp, nullptr, st));
+      inv_part = nullptr;
     }
     if (!dry() && rc == HCF_OK) {
       if (keep_c) { cc_valid = true; cc_B = B; cc_h = h; cc_w = w; cc_f16 = use_f16; cc_base = arena.base; }

@@ -8,12 +8,6 @@
 
 namespace hcf {
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  return v;
-}
-
 // sum over the 256-thread block; result valid in thread 0
 __device__ __forceinline__ float block_sum(float v, float* sh) {
   v = wave_sum(v);
@@ -26,28 +20,39 @@ __device__ __forceinline__ float block_sum(float v, float* sh) {
 }
 
 // ---- inverse flow step tail: coupling^-1 -> W^-1 -> actnorm^-1  (FlowStep.py:53-64) -----------
+// a.partial (hcf_inverse_logp): also one partial sum of logscale per block, slot [sample][block] as step_couple_fwd_kernel writes
 template <int CMAX>
 __global__ __launch_bounds__(256) void step_tail_inv_kernel(const StepArgs a) {
+  __shared__ float sh[4];
   const int hw = a.H * a.W;
   const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= hw) return;
-  const size_t pix = (size_t)blockIdx.y * hw + i;
-  float z[CMAX];
-  load_pixel<CMAX>(a.z, pix, a.C, z);
-  const float* hp = a.h.p + pix * a.h.cs + a.h.c0;
-  float y[CMAX];
-  step_tail_inverse_pixel<CMAX>(z, hp, a.C, a.ns, a.mode, a.mat, a.an_bias, a.an_mul, y);
-  if (a.aux.p) store_pixel<CMAX>(a.aux, pix, a.C, z);          // training tape: z after coupling^-1 (input of W^-1)
-  store_pixel<CMAX>(a.out, pix, a.C, y);
-  if (a.zpad16) store_pad16<CMAX>(a.zpad16, pix, a.zpad_n, y);
+  float lsum = 0.f;
+  if (i < hw) {
+    const size_t pix = (size_t)blockIdx.y * hw + i;
+    float z[CMAX];
+    load_pixel<CMAX>(a.z, pix, a.C, z);
+    const float* hp = a.h.p + pix * a.h.cs + a.h.c0;
+    float y[CMAX];
+    step_tail_inverse_pixel<CMAX>(z, hp, a.C, a.ns, a.mode, a.mat, a.an_bias, a.an_mul, y, &lsum);
+    if (a.aux.p) store_pixel<CMAX>(a.aux, pix, a.C, z);          // training tape: z after coupling^-1 (input of W^-1)
+    store_pixel<CMAX>(a.out, pix, a.C, y);
+    if (a.zpad16) store_pad16<CMAX>(a.zpad16, pix, a.zpad_n, y);
+  }
+  if (a.partial) {
+    const float s = block_sum(lsum, sh);
+    if (threadIdx.x == 0) a.partial[(size_t)blockIdx.y * a.partial_stride + blockIdx.x] = s;
+  }
 }
 
 // The same for the 25..48-channel steps (the x8 net's deepest level: 20 x 20 pixels per sample, a C x C mat-vec of up to 2 304
 // FMAs per pixel): one thread per pixel leaves 4/5 of the chip idle for 40 us per step at B = 32. Here a block takes 64 pixels and
 // its four waves a quarter of the channels each (wave-uniform: the matrix rows still come through scalar loads): coupling^-1 on
 // the wave's own channels -> LDS [channel][pixel] -> every wave reads the whole vector and computes its 12 output rows.
+// a.partial: the block's sum of logscale crosses its four waves (each sums its own 12 channels over the 64 pixels), one slot per
+// 64-pixel block: [sample][block].
 __global__ __launch_bounds__(256) void step_tail_inv48_kernel(const StepArgs a) {
   __shared__ float zs[48 * 64];
+  __shared__ float sh[4];
   const int hw = a.H * a.W;
   const int lane = threadIdx.x & 63;
   const int part = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -55,6 +60,7 @@ __global__ __launch_bounds__(256) void step_tail_inv48_kernel(const StepArgs a) 
   const bool ok = i < hw;
   const size_t pix = (size_t)blockIdx.y * hw + (ok ? i : hw - 1);
   const int C = a.C, ns = a.ns, c0 = part * 12;
+  float lsum = 0.f;
   {
     const float* zp = a.z.p + pix * a.z.cs + a.z.c0;
     const float* hp = a.h.p + pix * a.h.cs + a.h.c0;
@@ -67,7 +73,9 @@ __global__ __launch_bounds__(256) void step_tail_inv48_kernel(const StepArgs a) 
         if (a.mode == CPL_AFFINE) {
           if (c >= ns) {
             const int j = c - ns;
-            v = v * expf(-logscale_of(hp[2 * j + 1])) - hp[2 * j];       // z2 * exp(-logscale) - shift  (AffineCouplings.py:65-87)
+            const float ls = logscale_of(hp[2 * j + 1]);
+            v = v * expf(-ls) - hp[2 * j];                               // z2 * exp(-logscale) - shift  (AffineCouplings.py:65-87)
+            lsum += ok ? ls : 0.f;                                       // (a lane past the sample's end re-reads its last pixel)
           }
         } else if (c < 3) {
           v = v - hp[c];                                                 // AffineCoupling3shift, LRvsothers = False (:150-153)
@@ -76,7 +84,12 @@ __global__ __launch_bounds__(256) void step_tail_inv48_kernel(const StepArgs a) 
       zs[c * 64 + lane] = v;
     }
   }
+  if (a.partial) {
+    lsum = wave_sum(lsum);
+    if (lane == 0) sh[part] = lsum;
+  }
   __syncthreads();
+  if (a.partial && threadIdx.x == 0) a.partial[(size_t)blockIdx.y * a.partial_stride + blockIdx.x] = sh[0] + sh[1] + sh[2] + sh[3];
   float z[48];
 #pragma unroll
   for (int c = 0; c < 48; ++c) z[c] = zs[c * 64 + lane];
@@ -180,6 +193,10 @@ __global__ __launch_bounds__(256) void step_couple_fwd_kernel(const StepArgs a) 
 }
 
 int step_blocks_per_sample(int H, int W) { return (H * W + 255) / 256; }
+// partial slots per sample that an inverse tail launch with StepArgs::partial may write: the 64-pixel blocks of the 48-channel
+// kernel bound the 256-pixel blocks of the per-pixel form, which a 25..48-channel step takes when it also pads the next step's z1
+int step_tail_inv_slots(int C, int H, int W) { return C > 24 ? (H * W + 63) / 64 : step_blocks_per_sample(H, W); }
+int gauss_sample_slots(int C, int H, int W) { return (int)(((long long)H * W * C + 255) / 256); }
 
 #define HCF_DISPATCH_CMAX(KERNEL, A, ST)                                                       \
   do {                                                                                         \
@@ -247,26 +264,37 @@ __device__ __forceinline__ float philox_normal(uint64_t seed, uint64_t offset, u
 // outputs of the NHWC records (the one-thread-per-pixel form walked its pixel's channels in a loop: every load of a wave touched 64
 // records, and the Philox / Box-Muller chains of a pixel's 6-21 channels ran back to back in one lane: 217 us for 8.6 M elements).
 // Same arithmetic per element, same Philox counter (the NCHW element index): bit-identical draws.
+// a.partial (hcf_inverse_logp): also the block's sum of log N(a; mean, exp(logs)) = -0.5 (2 logs + eps^2 + ln 2pi) over its 256
+// (pixel, channel) elements, eps being the value multiplied by exp(logs) below (injected as given, or tau * n; 0 for tau = 0):
+// the prior term at temperature 1 of what was drawn, in the form gauss_encode_logp_kernel gives it. Slot [sample][block].
 __global__ __launch_bounds__(256) void gauss_sample_kernel(const GaussArgs a) {
+  __shared__ float sh[4];
   const int hw = a.H * a.W;
   const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (t >= (long long)hw * a.C) return;
   const int b = blockIdx.y;
-  const int i = (int)(t / a.C), c = (int)(t - (long long)i * a.C);
-  const size_t pix = (size_t)b * hw + i;
-  const float* hp = a.h.p + pix * a.h.cs + a.h.c0;
-  float* op = a.out.p + pix * a.out.cs + a.out.c0;
-  const float mean = hp[2 * c], s = hp[2 * c + 1];
-  const float logs = a.rescale ? logscale_of(s) : s;
-  const size_t e = ((size_t)b * a.C + c) * hw + i;           // NCHW element index
-  float eps;
-  if (a.eps) eps = a.eps[e];
-  else {
-    // per-sample temperature (hcf_inverse_taus): the same arithmetic on tau_b[b], so a row holds the bits of the scalar call
-    const float t_ = a.tau_b ? a.tau_b[b] : a.tau;
-    eps = (t_ == 0.f) ? 0.f : t_ * philox_normal(a.seed, a.offset, e + (size_t)a.b0 * a.C * hw);
+  float lp = 0.f;
+  if (t < (long long)hw * a.C) {
+    const int i = (int)(t / a.C), c = (int)(t - (long long)i * a.C);
+    const size_t pix = (size_t)b * hw + i;
+    const float* hp = a.h.p + pix * a.h.cs + a.h.c0;
+    float* op = a.out.p + pix * a.out.cs + a.out.c0;
+    const float mean = hp[2 * c], s = hp[2 * c + 1];
+    const float logs = a.rescale ? logscale_of(s) : s;
+    const size_t e = ((size_t)b * a.C + c) * hw + i;           // NCHW element index
+    float eps;
+    if (a.eps) eps = a.eps[e];
+    else {
+      // per-sample temperature (hcf_inverse_taus): the same arithmetic on tau_b[b], so a row holds the bits of the scalar call
+      const float t_ = a.tau_b ? a.tau_b[b] : a.tau;
+      eps = (t_ == 0.f) ? 0.f : t_ * philox_normal(a.seed, a.offset, e + (size_t)a.b0 * a.C * hw);
+    }
+    op[c] = mean + expf(logs) * eps;
+    lp = -0.5f * (logs * 2.f + eps * eps + 1.8378770664093453f);
   }
-  op[c] = mean + expf(logs) * eps;
+  if (a.partial) {
+    const float sum = block_sum(lp, sh);
+    if (threadIdx.x == 0) a.partial[(size_t)b * a.partial_stride + blockIdx.x] = sum;
+  }
 }
 
 // logp: sum -0.5 (2 logs + (x - mean)^2 / exp(2 logs) + ln 2pi)   (Basic.py:78-94)

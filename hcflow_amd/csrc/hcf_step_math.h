@@ -116,23 +116,37 @@ __device__ __forceinline__ void matvec(step_cptr M, const float (&z)[CMAX], floa
 }
 
 
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+  return v;
+}
+
 // FlowStep.reverse_flow after the coupling network (FlowStep.py:53-64): coupling^-1 -> W^-1 -> actnorm^-1 on one
 // pixel. `hp` points at the pixel's coupling-net output (global memory or LDS), stride 1.
+// `lsum` (optional): receives the pixel's sum of logscale over the transformed channels, in channel order -- the FORWARD
+// coupling's log-det at this pixel (AffineCouplings.py:53-58), which the sampling pass needs for the density of what it drew. The
+// arithmetic of z is the same with and without it; an additive (3-shift) step adds nothing.
 template <int CMAX, typename HPtr>
 __device__ __forceinline__ void step_tail_inverse_pixel(float (&z)[CMAX], HPtr hp, int C, int ns, int mode,
                                                         const float* __restrict__ mat,
                                                         const float* __restrict__ an_bias,
-                                                        const float* __restrict__ an_mul, float (&y)[CMAX]) {
+                                                        const float* __restrict__ an_mul, float (&y)[CMAX],
+                                                        float* lsum = nullptr) {
   if (mode == CPL_AFFINE) {
     // z2 = z2 * exp(-logscale) - shift, (shift, scale) = h[0::2], h[1::2]  (AffineCouplings.py:65-87)
+    float acc = 0.f;
 #pragma unroll
     for (int c = 0; c < CMAX; ++c) {
       if (c >= ns && c < C) {
         const int j = c - ns;
         const float shift = hp[2 * j], scale = hp[2 * j + 1];
-        z[c] = z[c] * expf(-logscale_of(scale)) - shift;
+        const float ls = logscale_of(scale);
+        z[c] = z[c] * expf(-ls) - shift;
+        acc += ls;
       }
     }
+    if (lsum) *lsum = acc;
   } else {
     // AffineCoupling3shift, LRvsothers=False: z[:3] -= f(z[3:])  (AffineCouplings.py:150-153)
 #pragma unroll

@@ -99,6 +99,18 @@ def get_sr_with_z(net, lq, heat=None, seed=None, eps=None):
     return sr, eps
 
 
+def sample_nll(net, lq, heat, seed=None, eps=None):
+    """(sr, eps_or_None, nll): ``lq`` super-resolved at temperature ``heat`` (or with the given ``eps``, used as they are) by
+    ``net.sample_with_logp`` -- one inverse pass -- and the sample's negative log-likelihood given ``lq`` in bits per dimension,
+    [B] float64: -(logp + Dirac-LR term at ``lq``) / (ln 2 * H * W), the per-sample number of ``get_encode_z_and_nll`` for
+    hr = the unclamped sample without dequantisation noise. The flow's LR latent of its own sample is ``lq`` itself, so the Dirac
+    term is ``dirac_logp(lq, lq)``. ``sr`` is clamped; ``eps`` comes back as given (None: the device drew them from ``seed``)."""
+    sr, logp = net.sample_with_logp(lq, 1.0 if heat is None else heat, eps=eps, seed=seed)
+    pixels = int(sr.shape[2]) * int(sr.shape[3])
+    objective = logp.double() + dirac_logp(lq, lq.to(logp.device))
+    return sr, eps, (-objective) / (math.log(2.0) * pixels)
+
+
 def optimise(net, z_lr, eps, loss_fn, steps, lr=0.02, optimise_lr=False, optimizer=None):
     """Gradient descent in the latent space with the weights frozen: ``steps`` iterations of ``loss_fn(net.decode(z_lr, eps))``
     (a scalar) over clones of ``eps`` -- and of ``z_lr`` when ``optimise_lr`` -- with ``torch.optim.Adam(tensors, lr=lr)``, or

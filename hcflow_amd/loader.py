@@ -19,7 +19,9 @@ image, B = 16: 8.6 ms per image). This module is the drop-in for those two piece
   samples and their relative gap (defined in ``hcflow_amd/lpips.py``), the GT going through AlexNet once per heat;
 * ``evaluate_sweep(net, batch, heats, n_sample, scale)`` returns ``evaluate_batch``'s dict with the heats sharing calls: the rows
   of one call are (image, heat) pairs, each with its own temperature, and the diversity comes from a streaming
-  ``metrics.SampleStats`` instead of the held samples.
+  ``metrics.SampleStats`` instead of the held samples;
+* ``most_likely_samples(net, batch, heat, n_sample)`` keeps, per image, the most likely of ``n_sample`` draws under the model
+  itself (``HCFlowNet_SR.sample_with_logp``): best-of-M selection that needs no GT.
 
 ``net`` is an ``HCFlowNet_SR`` or an ``HCFlowNet_Rescaling``; the three ``evaluate_*`` functions dispatch on ``net.cfg.sr`` and share
 everything behind the first pass. An SR net runs ``HCFlowSRModel.test()``: the NLL pass of (GT, LQ), then samples drawn from the
@@ -272,3 +274,32 @@ def evaluate_sample_set(net, batch: Dict, heats: Iterable[float], n_sample: int,
                     mean += lp[s][b] / n_sample
                 res[b][float(heat)] = {"lpips": mean, "lpips_best": best[b], "local_best": local[b], "score": score[b]}
     return res
+
+
+def most_likely_samples(net, batch: Dict, heat, n_sample: int, seed: Optional[int] = None) -> Dict:
+    """{"sr": [B,3,H,W], "logp": [B], "index": [B]}: per image of the batch the sample with the highest log-density
+    log p(x | lr) among ``n_sample`` draws at temperature ``heat`` (a scalar or one value per image), its ``logp``
+    (``HCFlowNet_SR.sample_with_logp``'s: nats, temperature 1, no Dirac term) and the number of the draw it came from (int64; the
+    first of equal ones). Best-of-M without a ground truth, where ``evaluate_sample_set`` ranks by LPIPS against the GT. Draw s uses
+    ``seed + s`` (``seed=None``: fresh seeds) and ``cache_cond=True``, so the LR-only features are computed once. Only the running
+    best image and its ``logp`` live on the device: a row mask and ``torch.where`` per draw, no host read inside the loop. SR
+    nets only (a rescaling net has no ``sample_with_logp``)."""
+    if not net.cfg.sr:
+        raise ValueError("most_likely_samples needs an SR net: a rescaling net's forward pass tracks no log-det, so its samples have no density")
+    if n_sample < 1:
+        raise ValueError("most_likely_samples: n_sample >= 1 expected, got %r" % (n_sample,))
+    dev = next(net.parameters()).device
+    lq = batch["LQ"].to(dev)
+    best_sr = best_lp = best_ix = None
+    with torch.no_grad():
+        for s in range(n_sample):
+            kw = {} if seed is None else {"seed": seed + s}
+            sr, lp = net.sample_with_logp(lq, heat, cache_cond=True, **kw)
+            if best_sr is None:
+                best_sr, best_lp, best_ix = sr, lp, torch.zeros(lp.shape, dtype=torch.int64, device=lp.device)
+                continue
+            better = lp > best_lp
+            best_sr = torch.where(better.view(-1, 1, 1, 1), sr, best_sr)
+            best_lp = torch.where(better, lp, best_lp)
+            best_ix = torch.where(better, torch.full_like(best_ix, s), best_ix)
+    return {"sr": best_sr, "logp": best_lp, "index": best_ix}

@@ -135,6 +135,23 @@ int hcf_inverse_ex(hcf_engine* e, const float* lr, const float* const* eps, int3
 int hcf_inverse_taus(hcf_engine* e, const float* lr, const float* const* eps, int32_t n_eps, const float* taus_dev, uint64_t seed,
                      int64_t first_sample, float* out_hr, int32_t B, int32_t h, int32_t w, uint32_t flags, hcf_stream_t stream);
 
+/* Sampling that RETURNS THE DENSITY of what it drew (sample_and_log_prob): hcf_inverse_ex (taus_dev == NULL) or hcf_inverse_taus
+ * (taus_dev != NULL, tau ignored) with one more output. SR engines only: a rescaling engine's forward pass tracks no log-det, so
+ * the quantity has no reference there (HCF_ERR_UNSUPPORTED).
+ *   out_logp [B] fp32 device. DEFINITION: out_logp[b] is the out_logp that hcf_encode_sr returns for hr = the UNCLAMPED image of
+ *            this call with noise = NULL: log-det + the prior log-densities in nats, including -ln(quant) * H * W, WITHOUT the
+ *            Dirac-LR term. It is the density under the model at temperature 1, whatever tau drew the sample (tau = 0 gives the
+ *            density of the mean sample). Without HCF_FLAG_NO_CLAMP out_hr is clamped; the density is still that of the
+ *            unclamped sample.
+ * The pass evaluates every term already: each affine coupling's logscale on the z1 the forward pass would see, the prior's logs
+ * and the eps it applies, and the host-side ActNorm / slogdet constants; per-block fp32 partial sums (no atomics) are reduced in
+ * fp64 in a fixed order, so a row's bits depend neither on the call nor on the batch it sits in. out_hr, the flags and the other
+ * arguments are those of the two entries above, and out_hr holds their bits. Enqueue-only: no synchronisation, and no allocation
+ * in the steady state. */
+int hcf_inverse_logp(hcf_engine* e, const float* lr, const float* const* eps, int32_t n_eps, float tau, const float* taus_dev,
+                     uint64_t seed, int64_t first_sample, float* out_hr, float* out_logp, int32_t B, int32_t h, int32_t w,
+                     uint32_t flags, hcf_stream_t stream);
+
 /* netG(hr=hr, lr=lr, reverse=False) for HCFlowNet_SR: normal_flow_diracLR (HCFlowNet_SR_arch.py:47-67).
  *   hr [B,3,H,W], lr [B,3,H/scale,W/scale] (NULL -> no Dirac term), noise [B,3,H,W] U[0,1) or NULL
  *   (NULL -> no dequantisation noise is added)
