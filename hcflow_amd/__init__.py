@@ -10,7 +10,10 @@ from . import latent  # noqa: F401
 from . import data  # noqa: F401
 from .data import ImageBank, BankLoader, draw_crops, prepare_batch, whole_image  # noqa: F401
 from .data import PairedBank, PairedBankLoader, draw_paired_crops, center_crops, prepare_paired_batch, whole_pair  # noqa: F401
+from . import resize  # noqa: F401
+from .resize import imresize, lr_psnr  # noqa: F401
 
 __all__ = ["NetConfig", "preset", "param_spec", "eps_shapes", "make_params", "HCFlowNet_SR", "HCFlowNet_Rescaling", "latent",
            "data", "ImageBank", "BankLoader", "draw_crops", "prepare_batch", "whole_image",
-           "PairedBank", "PairedBankLoader", "draw_paired_crops", "center_crops", "prepare_paired_batch", "whole_pair"]
+           "PairedBank", "PairedBankLoader", "draw_paired_crops", "center_crops", "prepare_paired_batch", "whole_pair",
+           "resize", "imresize", "lr_psnr"]

@@ -55,6 +55,7 @@ SYMBOLS = [
     "hcf_op_conv2d_views", "hcf_op_conv2d_wgrad_views", "hcf_op_conv_epilogue_backward_views", "hcf_op_conv2d_dgrad_fused_views",
     "hcf_op_seed_sum", "hcf_op_axpy_job", "hcf_train_backward_encode_ex",
     "hcf_metric_quantize", "hcf_metric_from_image",
+    "hcf_resize_workspace", "hcf_resize_bicubic", "hcf_resize_bicubic_backward", "hcf_resize_tables",
 ]
 
 
@@ -236,13 +237,18 @@ def load() -> C.CDLL:
     lib.hcf_op_axpy_job.argtypes = [fp, fp, i32, f32, fp, vp]
     lib.hcf_data_prepare_batch.argtypes = [vp, C.c_size_t, vp, i32, vp, i32, i32, i32, i32, i32, fp, fp, vp]
     lib.hcf_data_prepare_paired.argtypes = [vp, C.c_size_t, vp, vp, C.c_size_t, vp, i32, vp, i32, i32, i32, i32, i32, fp, fp, vp]
+    lib.hcf_resize_workspace.argtypes = [i32, i32, i32, i32, i32, i32]
+    lib.hcf_resize_workspace.restype = C.c_size_t
+    lib.hcf_resize_bicubic.argtypes = [fp, i32, i32, i32, i32, i32, i32, fp, vp, C.c_size_t, vp]
+    lib.hcf_resize_bicubic_backward.argtypes = [fp, i32, i32, i32, i32, i32, i32, fp, vp, C.c_size_t, vp]
+    lib.hcf_resize_tables.argtypes = [i32, i32, i32, i32, fp, vp, vp, i64]
     for name in SYMBOLS:
         fn = getattr(lib, name)
         if name not in ("hcf_destroy", "hcf_last_error", "hcf_workspace_bytes", "hcf_weight_bytes",
                         "hcf_fallback_count", "hcf_debug_last_clock_mhz", "hcf_aux_conv2d_workspace", "hcf_lpips_workspace",
                         "hcf_lpips_backward_workspace", "hcf_lpips_embed_bytes", "hcf_lpips_map_workspace",
                         "hcf_aux_bn_act_workspace", "hcf_aux_feature_loss_workspace", "hcf_metric_stats_bytes",
-                        "hcf_metric_pair_ref_bytes", "hcf_metric_pair_workspace"):
+                        "hcf_metric_pair_ref_bytes", "hcf_metric_pair_workspace", "hcf_resize_workspace"):
             fn.restype = C.c_int
     _lib = lib
     return lib

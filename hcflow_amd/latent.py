@@ -2,6 +2,7 @@
 
 Plain torch on the tensors the engine returns -- a few elementwise operations on < 100 MB, no kernels of their own. ``eps`` is
 always the list the inverse pass takes: one [B, C_l, h_l, w_l] tensor per level, deepest level first (config.eps_shapes).
+``lr_consistency`` is the one helper that reaches a kernel: the bicubic degradation of ``hcflow_amd.resize``.
 
 The two ``get_*`` functions are the wrapper-level calls the reference's model class names (HCFlow_SR_model.py:328-351:
 get_encode_z_and_nll, get_sr_with_z) with working semantics: there they pass keywords HCFlowNet_SR.forward does not take.
@@ -109,6 +110,35 @@ def sample_nll(net, lq, heat, seed=None, eps=None):
     pixels = int(sr.shape[2]) * int(sr.shape[3])
     objective = logp.double() + dirac_logp(lq, lq.to(logp.device))
     return sr, eps, (-objective) / (math.log(2.0) * pixels)
+
+
+def lr_consistency(lq, scale, kind="l2", weight=1.0):
+    """The degradation's data term of every shipped configuration as a callable on ``hr``: the LR image is the MATLAB-style
+    bicubic down-scale of the HR image (``resize.imresize``: utils/imresize.py on the device, differentiable), so
+
+        ``kind="l2"``:  ``weight * mean((imresize(hr, 1 / scale) - lq) ** 2)``
+        ``kind="l1"``:  ``weight * mean(abs(imresize(hr, 1 / scale) - lq))``
+
+    ``scale`` is the integer SR factor 2 .. 8. Pass it as ``refine_image(data_loss=...)``, or composed with ``net.decode`` as
+    ``optimise(loss_fn=...)``. ``ValueError`` for an illegal scale or kind (here, before any engine call); ``HcfError`` for a
+    CPU ``lq`` (no fallback)."""
+    from fractions import Fraction
+    from . import _lib
+    from .resize import imresize, parse_scale
+    if isinstance(scale, bool) or not isinstance(scale, int):
+        raise ValueError("lr_consistency: scale is the integer SR factor 2..8, got %r" % (scale,))
+    down = Fraction(1, parse_scale(scale)[0])
+    if kind not in ("l2", "l1"):
+        raise ValueError("lr_consistency: kind must be 'l2' or 'l1', got %r" % (kind,))
+    if not isinstance(lq, torch.Tensor) or not lq.is_cuda:
+        raise _lib.HcfError("lr_consistency: lq must be a GPU tensor (no fallback)")
+    lq = lq.detach().float()
+    weight = float(weight)
+
+    def data_loss(hr):
+        d = imresize(hr, down) - lq
+        return weight * (d * d).mean() if kind == "l2" else weight * d.abs().mean()
+    return data_loss
 
 
 def optimise(net, z_lr, eps, loss_fn, steps, lr=0.02, optimise_lr=False, optimizer=None):

@@ -864,6 +864,46 @@ int hcf_data_prepare_paired(const uint8_t* gt_bank, size_t gt_bytes, const int64
                             const int32_t* crops, int32_t B, int32_t lr_h, int32_t lr_w, int32_t scale, int32_t bgr,
                             float* gt, float* lq, hcf_stream_t stream);
 
+/* ---- differentiable MATLAB-bicubic resize (hcf_resize.hip): tensor to tensor, down and up, with its transpose ----
+ * The reference's imresize of a float image with method 'bicubic' (utils/imresize.py:136-174), per plane of a dense NCHW fp32
+ * DEVICE tensor x [B,C,H,W], C >= 1: `up` = 0 scales by 1 / s (antialiased), `up` = 1 by s, s an integer in 2 .. 8. The output
+ * is [B,C,Ho,Wo] with Ho = ceil(H * scale), Wo = ceil(W * scale) (:31-35; non-multiples are legal: 13 x 18 at 1/4 -> 4 x 5).
+ * Nothing is clipped: up-scaling overshoots [0, 1] as the reference's float path does. Per axis the op is the matrix A of
+ * contributions (:63-83): u = o / scale + 0.5 (1 - 1 / scale) (1-based), P = ceil(4 max(1, 1 / scale)) + 2 taps, weights
+ * scale * cubic(scale * t) (down) or cubic(t) (up) (:53-60), each output row normalised to sum 1, indices mirrored through
+ * aux = [0 .. n-1, n-1 .. 0] modulo 2n (which wraps more than once when the image is shorter than the support). y = A_h x A_w^T,
+ * rows first (:157,169-171: equal scales keep dimension 0 first).
+ * Arithmetic: the weights are computed in float64 on the host and rounded once to fp32; each pass is one fp32 fma chain in tap
+ * order k = 0 .. P-1; the row pass runs first, then the column pass; no atomics. A result is bit-reproducible and independent
+ * of the batch around the image, and a contiguous view that is only 4-byte aligned gives the bits of an aligned copy.
+ * The backward is the exact transpose gx = A_h^T gy A_w, columns first, in gather form over transposed tables: per input index
+ * the (output index, weight) entries in ascending (output, tap) order, one fp32 fma chain in that order; mirrored taps that land
+ * on one input index stay separate entries. The same determinism properties hold.
+ *   hcf_resize_workspace         bytes of the caller-allocated device scratch of either call (the [B,C,Ho,W] intermediate of
+ *                                the two passes); 0 for arguments the calls refuse.
+ *   hcf_resize_bicubic           y [B,C,Ho,Wo] from x [B,C,H,W].
+ *   hcf_resize_bicubic_backward  gx [B,C,H,W] from gy [B,C,Ho,Wo]; H, W are the FORWARD input's size.
+ *   hcf_resize_tables            host only, touches no device: the table the kernels use for one axis of length in_len.
+ *                                transposed = 0: rows = out_len lists of L = P entries, entry k of row o = tap k of output o.
+ *                                transposed = 1: rows = in_len lists, row i = the (output, weight) entries of input index i in
+ *                                the order above, L = the longest list. Returns L (> 0) or a negative status. With w, idx and
+ *                                cnt all NULL only L is returned; otherwise w [rows * L] (float64: the kernels use each value
+ *                                rounded once to fp32), idx [rows * L] (-1 behind a list's end) and cnt [rows] are filled,
+ *                                entry k of row r at r * L + k; capacity = entries available in w and idx.
+ * The device tables are cached in the library per (device, length, s, direction) and uploaded once: the FIRST use of a key may
+ * allocate, copy from the host and synchronise once; every later call of that shape allocates nothing, copies nothing from the
+ * host and never synchronises. A graph capture therefore needs one warm-up call of the same shape outside the capture.
+ * Every entry checks its arguments before any HIP call: null pointers, B, C, H, W (in_len) < 1, s outside 2 .. 8, `up` /
+ * `transposed` other than 0 / 1 -> HCF_ERR_ARG; a work_bytes (capacity) that is too small, an output side beyond int32, a
+ * tensor (input, output or intermediate) whose byte count leaves int64, more than 65535^2 planes -> HCF_ERR_SHAPE. */
+size_t hcf_resize_workspace(int32_t B, int32_t C, int32_t H, int32_t W, int32_t s, int32_t up);
+int hcf_resize_bicubic(const float* x, int32_t B, int32_t C, int32_t H, int32_t W, int32_t s, int32_t up, float* y, void* work,
+                       size_t work_bytes, hcf_stream_t stream);
+int hcf_resize_bicubic_backward(const float* gy, int32_t B, int32_t C, int32_t H, int32_t W, int32_t s, int32_t up, float* gx,
+                                void* work, size_t work_bytes, hcf_stream_t stream);
+int hcf_resize_tables(int32_t in_len, int32_t s, int32_t up, int32_t transposed, double* w, int32_t* idx, int32_t* cnt,
+                      int64_t capacity);
+
 #ifdef __cplusplus
 }
 #endif
