@@ -56,6 +56,8 @@ SYMBOLS = [
     "hcf_op_seed_sum", "hcf_op_axpy_job", "hcf_train_backward_encode_ex",
     "hcf_metric_quantize", "hcf_metric_from_image",
     "hcf_resize_workspace", "hcf_resize_bicubic", "hcf_resize_bicubic_backward", "hcf_resize_tables",
+    "hcf_loss_pair_workspace", "hcf_loss_pair", "hcf_loss_pair_backward",
+    "hcf_loss_sumsq_workspace", "hcf_loss_sumsq", "hcf_loss_sumsq_backward", "hcf_loss_gan", "hcf_loss_gan_backward",
 ]
 
 
@@ -242,13 +244,25 @@ def load() -> C.CDLL:
     lib.hcf_resize_bicubic.argtypes = [fp, i32, i32, i32, i32, i32, i32, fp, vp, C.c_size_t, vp]
     lib.hcf_resize_bicubic_backward.argtypes = [fp, i32, i32, i32, i32, i32, i32, fp, vp, C.c_size_t, vp]
     lib.hcf_resize_tables.argtypes = [i32, i32, i32, i32, fp, vp, vp, i64]
+    f64 = C.c_double
+    lib.hcf_loss_pair_workspace.argtypes = [i64, i64]
+    lib.hcf_loss_pair_workspace.restype = C.c_size_t
+    lib.hcf_loss_pair.argtypes = [fp, fp, i64, i64, i32, f64, f64, f64, fp, fp, vp, C.c_size_t, vp]
+    lib.hcf_loss_pair_backward.argtypes = [fp, fp, i64, i64, i32, f64, f64, fp, i32, fp, fp, vp]
+    lib.hcf_loss_sumsq_workspace.argtypes = [C.POINTER(i64), i32]
+    lib.hcf_loss_sumsq_workspace.restype = C.c_size_t
+    lib.hcf_loss_sumsq.argtypes = [C.POINTER(vp), C.POINTER(i64), i32, fp, vp, C.c_size_t, vp]
+    lib.hcf_loss_sumsq_backward.argtypes = [C.POINTER(vp), C.POINTER(i64), i32, fp, C.POINTER(vp), vp]
+    lib.hcf_loss_gan.argtypes = [fp, i64, f64, fp, i64, f64, i32, i32, i32, fp, vp]
+    lib.hcf_loss_gan_backward.argtypes = [fp, i64, f64, fp, i64, f64, i32, i32, i32, fp, fp, fp, vp]
     for name in SYMBOLS:
         fn = getattr(lib, name)
         if name not in ("hcf_destroy", "hcf_last_error", "hcf_workspace_bytes", "hcf_weight_bytes",
                         "hcf_fallback_count", "hcf_debug_last_clock_mhz", "hcf_aux_conv2d_workspace", "hcf_lpips_workspace",
                         "hcf_lpips_backward_workspace", "hcf_lpips_embed_bytes", "hcf_lpips_map_workspace",
                         "hcf_aux_bn_act_workspace", "hcf_aux_feature_loss_workspace", "hcf_metric_stats_bytes",
-                        "hcf_metric_pair_ref_bytes", "hcf_metric_pair_workspace", "hcf_resize_workspace"):
+                        "hcf_metric_pair_ref_bytes", "hcf_metric_pair_workspace", "hcf_resize_workspace",
+                        "hcf_loss_pair_workspace", "hcf_loss_sumsq_workspace"):
             fn.restype = C.c_int
     _lib = lib
     return lib

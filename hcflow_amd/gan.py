@@ -3,8 +3,8 @@
 ``HCFlow_SR_model.py:75-95`` builds, beside netG, a VGG19 feature extractor (``networks.define_F`` -> ``VGGFeatureExtractor``,
 ``discriminator_vgg_arch.py:110-137``) for the perceptual loss and a ``Discriminator_VGG_160`` (``:68-107``; ``networks.define_D``
 also builds ``Discriminator_VGG_128`` and ``PatchGANDiscriminator``, ``networks.py:44-56``) trained with the
-reference's own ``GANLoss`` (``loss.py:19-51``: stock PyTorch criteria, no kernel behind it -- it stays the reference's file and is
-not restated here); ``optimize_parameters`` (``HCFlow_SR_model.py:219-285``) runs them forward and backward every
+reference's own ``GANLoss`` (``loss.py:19-51``: stock PyTorch criteria -- it stays the reference's file; the same criteria as one
+node each on the device are ``hcflow_amd.losses``); ``optimize_parameters`` (``HCFlow_SR_model.py:219-285``) runs them forward and backward every
 step on ``fake_H`` / ``real_H`` batches. The classes here keep the reference's constructor signatures, ``state_dict`` keys /
 shapes (the parameter holders ARE ``nn.Conv2d`` / ``nn.BatchNorm2d`` / ``nn.Linear`` modules, so checkpoints of the reference
 load strictly, ``load_network(..., netD)``) and call surface, and run EVERY CONVOLUTION -- > 99 % of their FLOPs -- through the

@@ -904,6 +904,67 @@ int hcf_resize_bicubic_backward(const float* gy, int32_t B, int32_t C, int32_t H
 int hcf_resize_tables(int32_t in_len, int32_t s, int32_t up, int32_t transposed, double* w, int32_t* idx, int32_t* cnt,
                       int64_t capacity);
 
+/* ---- training criteria (hcf_loss.hip): pixel, reconstruction, Charbonnier, latent and GAN terms, each with its backward ----
+ * Every term is evaluated in fp64 from the fp32 inputs and summed in fp64 through per-block partials of a grid that the SHAPE
+ * alone decides and one fixed-order final block: no atomics, no cross-block waiting, bit-reproducible. A result is rounded to
+ * fp32 once. No entry allocates, copies to or from the host or synchronises; all run on `stream`. Inputs need 4-byte alignment
+ * only: any base pointer and any row length give the bits an aligned copy gives. A backward recomputes from the inputs (the
+ * forward stores no gradient) and reads its upstream gradient `g` from DEVICE memory; where g == 0 it stores exact zeros,
+ * also for a non-finite difference, so a term the caller dropped does not poison its inputs.
+ *
+ * Pair criterion. x, y: [B][n] fp32 contiguous (y NULL: zeros), d = (double)x - (double)y,
+ *   kind 0  |d|                  nn.L1Loss (HCFlow_SR_model.py:47-52 cri_pix_hr)
+ *   kind 1  d^2                  nn.MSELoss; ReconstructionLoss('l2') (loss.py:83-84)
+ *   kind 2  sqrt(d^2 + eps)      CharbonnierLoss (loss.py:5-15); ReconstructionLoss('l1') (loss.py:85-87)
+ * A block never straddles a sample; S_b = the sample's partials joined in a fixed order that depends on n alone, so row b of
+ * a batch has the bits of the one-row call; S = S_0 + S_1 + ... in index order.
+ *   out (nullable)      one float, fp32(scale * S)
+ *   out_rows (nullable) [B], fp32(row_scale * S_b)                 (at least one of the two)
+ * The sums cover every element: one NaN or inf makes the result non-finite (the callers' isnan / isfinite gates need no pass
+ * of their own, HCFlow_SR_model.py:210, HCFlow_Rescaling_model.py:223-228).
+ * Backward: gx = fp32((double)g[b * g_stride] * scale * f'(d)), f' = sign(d) (0 at 0) / 2 d / d / sqrt(d^2 + eps); gy (nullable)
+ * = -gx in the same launch; at least one of gx, gy. g_stride 0: one upstream scalar; 1: one per sample (then `scale` is the
+ * forward's row_scale).
+ * HCF_ERR_ARG: x NULL, no output, B < 1, n < 1, kind outside 0 .. 2, eps negative or not finite, g NULL, g_stride outside
+ * 0 / 1, a pointer that is not 4-byte aligned, work NULL or not 8-byte aligned; HCF_ERR_SHAPE: B * n > 2^40 or more than 2^23
+ * blocks (B * min(ceil(n / 4096), 1024)); HCF_ERR_NOMEM: work_bytes below the workspace size. */
+size_t hcf_loss_pair_workspace(int64_t B, int64_t n);
+int hcf_loss_pair(const float* x, const float* y, int64_t B, int64_t n, int32_t kind, double eps, double scale, double row_scale,
+                  float* out, float* out_rows, void* work, size_t work_bytes, hcf_stream_t stream);
+int hcf_loss_pair_backward(const float* x, const float* y, int64_t B, int64_t n, int32_t kind, double eps, double scale,
+                           const float* g, int32_t g_stride, float* gx, float* gy, hcf_stream_t stream);
+
+/* Mean square over several tensors: out = fp32(sum_k sum_i z_k[i]^2 / N), N = sum_k len[k] -- the latent term
+ * (torch.cat([z1.flatten(), z2.flatten()]) ** 2).mean() of HCFlow_Rescaling_model.py:216 without the concatenation. z, len: HOST
+ * tables of `count` device pointers / lengths, 1 <= count <= 8, read during the call. Backward: gz[k][i] = fp32((double)g[0] *
+ * (2 / N) * z_k[i]) for every k with gz[k] != NULL (gz: a host table as z), exact zeros where g[0] == 0.
+ * HCF_ERR_ARG: a NULL table or tensor, count outside 1 .. 8, a length < 1, misaligned pointers, out / g NULL, no gz[k] at all;
+ * HCF_ERR_SHAPE: N > 2^40; HCF_ERR_NOMEM: work_bytes below the workspace size. */
+size_t hcf_loss_sumsq_workspace(const int64_t* len, int32_t count);
+int hcf_loss_sumsq(const float* const* z, const int64_t* len, int32_t count, float* out, void* work, size_t work_bytes,
+                   hcf_stream_t stream);
+int hcf_loss_sumsq_backward(const float* const* z, const int64_t* len, int32_t count, const float* g, float* const* gz,
+                            hcf_stream_t stream);
+
+/* GAN criteria (loss.py:19-51 GANLoss and its callers HCFlow_SR_model.py:242-247 generator step, :271-278 discriminator step).
+ * a: na logits with target ta; b (nullable: then nb must be 0): nb logits with target tb. The discriminator outputs [B,1]
+ * (Discriminator_VGG_128 / _160) and [B,1,h,w] (PatchGAN): na, nb <= 2^20, beyond that HCF_ERR_SHAPE.
+ *   type 0  max(v,0) - v t + log1p(exp(-|v|))    nn.BCEWithLogitsLoss, 'gan' / 'ragan'
+ *   type 1  (v - t)^2                            nn.MSELoss, 'lsgan'
+ *   type 2  t > 0.5 ? -v : v                     wgan_loss, 'wgan-gp'
+ * relativistic 0: v = a (and v = b); 1 (needs b): v_a = a - mean(b), v_b = b - mean(a). All arithmetic fp64, ONE block, fixed
+ * order. out[5] = {term_a = mean_i f(v_a[i], ta), term_b (0 without b), total, mean(a), mean(b) (0 without b)} as fp32; total =
+ * term_a + term_b, halved when `halve` != 0 (:247, :278).
+ * Backward: the analytic gradient of `total`, times the device scalar g[0], to ga (nullable) and gb (nullable), at least one;
+ * the relativistic form includes the paths through both means; one launch; exact zeros where g[0] == 0.
+ * HCF_ERR_ARG: a NULL, na < 1, nb < 0, b NULL with nb > 0 or the reverse, type outside 0 .. 2, relativistic / halve outside
+ * 0 / 1, relativistic without b, out / g NULL, neither ga nor gb, gb without b, misaligned pointers, a target that is not
+ * finite. */
+int hcf_loss_gan(const float* a, int64_t na, double ta, const float* b, int64_t nb, double tb, int32_t type,
+                 int32_t relativistic, int32_t halve, float* out, hcf_stream_t stream);
+int hcf_loss_gan_backward(const float* a, int64_t na, double ta, const float* b, int64_t nb, double tb, int32_t type,
+                          int32_t relativistic, int32_t halve, const float* g, float* ga, float* gb, hcf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
