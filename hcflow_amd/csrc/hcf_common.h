@@ -18,6 +18,7 @@
 #include <hip/hip_runtime.h>
 #include <vector>
 #include <stdint.h>
+#include "hcf_switches.h"
 
 #define HCF_OK 0
 #define HCF_ERR_ARG (-1)
@@ -161,7 +162,6 @@ struct WgradArgs {
   unsigned strip_magic;    // by side with one zero column between them (virtual width B (W + 1)) -- instead of every image's own
                            // ceil(W / 32) tiles: a 40-wide image fills 40 of 64 tile columns, the strip 640 of 656. Pixels are the
                            // reduction dimension here, so only the walk changes. strip_magic = 2^32 / strip_w + 1 (exact division).
-  int dbg;                 // timing ablations (HCF_WG_DBG): 1 no MFMAs, 2 no epilogue, 4 no global loads
 };
 size_t conv_wgrad_scratch_floats(const WgradArgs& a);      // = plan_conv_wgrad(a).scratch_floats
 // The fixed-order reduction of a launch's partial tiles as a JOB: launch_conv_wgrad(a, st, &job) leaves the partial tiles in a.part

@@ -71,7 +71,7 @@ __device__ __forceinline__ f32x4 split4(const f32x4 v) {
 typedef const float __attribute__((address_space(1)))* gfptr;
 typedef const f32x4 __attribute__((address_space(1)))* gf4ptr;
 
-int g_f16x3_ablation = 0;   // tools/conv_bench.py --ablate N (bit0/bit1 toggle the tall-tile variants, see plan_conv_f16x3)
+int g_f16x3_ablation = 0;   // tools/conv_bench.py --ablate N: the kAbl* bits of hcf_switches.h
 
 // Variants measured and NOT kept (profiles/r01_f16x3_notes.md has the numbers; the code is in the history):
 // a dx-major sliding-window tap loop (fewer LDS reads, same time), a pre-split activation format with register staging,
@@ -83,16 +83,15 @@ int conv_f16x3_scaled_blocks(int B, int H, int W, int* strip_w, int* tile_h) {
   int row_tiles = per_row;
   if (strip_w) *strip_w = 0;
   if (tile_h) *tile_h = 8;
-  const bool off = getenv("HCF_NO_DG_STRIP") != nullptr;             // A/B knob
-  if (!off && B >= 2 && (long long)B * (W + 1) < 65536) {
+  if (!sw<Sw::HCF_NO_DG_STRIP>() && B >= 2 && (long long)B * (W + 1) < 65536) {
     const int strips = (B * (W + 1) + 31) / 32;
     if (strips * 10 <= per_row * 9) {
       row_tiles = strips;
       if (strip_w) *strip_w = W + 1;
     }
   }
-  // 4-row tiles while even they leave the grid within one block per CU (HCF_NO_DG_TH4: A/B knob)
-  if (tile_h && getenv("HCF_NO_DG_TH4") == nullptr && (long long)row_tiles * ((H + 3) / 4) <= 256) {
+  // 4-row tiles while even they leave the grid within one block per CU (HCF_NO_DG_TH4: off)
+  if (tile_h && !sw<Sw::HCF_NO_DG_TH4>() && (long long)row_tiles * ((H + 3) / 4) <= 256) {
     *tile_h = 4;
     tiles_y = (H + 3) / 4;
   }
@@ -776,18 +775,18 @@ F16x3Plan plan_conv_f16x3(const ConvArgs& a, int taps) {
   const int ntb = (a.out.n + 31) / 32;
   const bool k1 = taps == 1;      // stand-alone 1x1 conv (training): 16-byte addressable windows, no upsample, vector epilogue
   if ((taps != 9 && !k1) || ntb < 1 || ntb > 2) return refuse(HCF_ERR_UNSUPPORTED);      // > 64 output channels stay on the exact kernel
-  if (k1 && (a.tC > 0 || a.w2 || getenv("HCF_NO_K1") != nullptr)) return refuse(HCF_ERR_UNSUPPORTED);      // HCF_NO_K1: 1x1 convs on the exact kernel (A/B)
+  if (k1 && (a.tC > 0 || a.w2 || sw<Sw::HCF_NO_K1>())) return refuse(HCF_ERR_UNSUPPORTED);      // HCF_NO_K1: 1x1 convs on the exact kernel
   const bool plain = !(a.tC > 0) && !a.w2 && !a.in_max;
-  const bool tall = !k1 && plain && (((f16x3::g_f16x3_tall ^ g_f16x3_ablation) >> (ntb - 1)) & 1) && a.H >= 16;   // --ablate 1/2/3 turns it off
+  const bool tall = !k1 && plain && ((f16x3::g_f16x3_tall ^ g_f16x3_ablation) & (ntb == 1 ? kAblTall32 : kAblTall64)) && a.H >= 16;   // --ablate 1/2/3 toggles it
   const int tiles_x = (a.W + f16x3::TW - 1) / f16x3::TW;
   long long nblk = (long long)a.B * tiles_x * ((a.H + (tall ? 15 : 7)) / (tall ? 16 : 8));
   const long long nblk4 = (long long)a.B * tiles_x * ((a.H + 3) / 4);
-  // small grids: 4-row tiles while even they stay within one block per CU (bit-identical to the 8-row form; HCF_NO_TH4: A/B knob)
-  auto th4_small = [&] { return nblk4 <= 256 && getenv("HCF_NO_TH4") == nullptr; };
+  // small grids: 4-row tiles while even they stay within one block per CU (bit-identical to the 8-row form; HCF_NO_TH4: off)
+  auto th4_small = [&] { return nblk4 <= 256 && !sw<Sw::HCF_NO_TH4>(); };
   const bool grid_bad = nblk <= 0 || nblk > 0x7fffffffLL;
   if (!k1 && grid_bad) return refuse(HCF_ERR_ARG);      // (the 3x3 form tests its grid first, the 1x1 form last: their statuses as they always were)
   p.vec_epi = a.out.p && (a.out.n & 3) == 0 && view_vec16_or_null(a.out) && view_vec16_or_null(a.res1) && view_vec16_or_null(a.res2) &&
-              (k1 || (!tall && !(a.tC > 0) && !(g_f16x3_ablation & 64)));                                   // --ablate 64: scalar epilogue
+              (k1 || (!tall && !(a.tC > 0) && !(g_f16x3_ablation & kAblScalarEpi)));
   if (k1 && !p.vec_epi) return refuse(HCF_ERR_UNSUPPORTED);
   // fused epilogue backward: the scaled, vector-epilogue variant only, 16-byte addressable y, whole channel quads
   if (a.fb_y.p && (!a.in_max || a.fb_max2 == a.in_max || !p.vec_epi || !a.fb_part || !view_vec16(a.fb_y) || (a.out.n & 3) ||
@@ -808,8 +807,7 @@ F16x3Plan plan_conv_f16x3(const ConvArgs& a, int taps) {
     const int cm = step_cmax(a.tC);
     // 45/48-channel steps (x8 level 2) keep the stand-alone tail kernel
     if (ntb != 1 || (cm != 8 && cm != 12 && cm != 24)) return refuse(HCF_ERR_UNSUPPORTED);
-    static const bool n16_off = getenv("HCF_NO_N16") != nullptr;              // A/B knob: the 16-wide channel tile (<= 16 output channels)
-    p.v.n16 = a.out.n <= 16 && !n16_off && !(g_f16x3_ablation & 2048) && cm != 24;
+    p.v.n16 = a.out.n <= 16 && !(g_f16x3_ablation & kAblNoN16) && cm != 24;      // the 16-wide channel tile (<= 16 output channels)
     p.v.tailc = cm;
     if (th4_small()) th = 4;
   } else if (a.w2) {      // fused FCN conv1 + conv2

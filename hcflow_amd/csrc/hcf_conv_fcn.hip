@@ -342,8 +342,6 @@ __global__ __launch_bounds__(256, 2) void fcn12_kernel(const ConvArgs a, const i
 // HCF_ERR_UNSUPPORTED: this call does not fit the small-K persistent form (the generic FUSE2 kernel takes it)
 // grid_out / ntiles_out (optional): the launch made, for the per-op entry that reports it (hcf_op_fcn12)
 int launch_fcn12(const ConvArgs& a, hipStream_t st, unsigned* grid_out, int* ntiles_out) {
-  static const bool off = getenv("HCF_NO_FCN12") != nullptr;         // A/B knob, read once
-  if (off) return HCF_ERR_UNSUPPORTED;
   auto v16 = [](const View& v) { return v.p && view_vec16(v); };      // (differs from view_vec16_or_null: both views are required)
   if (a.nsrc != 1 || a.nchunk != 1 || a.src[0].n > 16 || a.src[0].up || !a.w2 || !a.bias2 || !a.scale2 || a.out.n != 64 ||
       !v16(a.src[0]) || !v16(a.out) || a.res2.p || a.tC > 0 || a.in_max || !a.ovf || !a.zeros)

@@ -115,9 +115,8 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(const WgradArgs a) {
     }                                                                                                         \
   }
   const int t0 = blockIdx.x * a.tpb, t1 = min(ntiles, t0 + a.tpb);
-  const int dbg = a.dbg;
-  if (t0 < t1 && !(dbg & 4)) HCF_WG_LOAD(t0)
-  if (t0 < t1 && !(dbg & 4)) HCF_WG_LOAD_G(t0)
+  if (t0 < t1) HCF_WG_LOAD(t0)
+  if (t0 < t1) HCF_WG_LOAD_G(t0)
   for (int tile = t0; tile < t1; ++tile) {
     __syncthreads();                              // the previous tile's fragments have been read
 #pragma unroll
@@ -139,8 +138,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(const WgradArgs a) {
       *reinterpret_cast<f32x4*>(gs + (q >> 3) * 32 + c4t) = v;
     }
     __syncthreads();
-    if (tile + 1 < t1 && !(dbg & 4)) { HCF_WG_LOAD(tile + 1) HCF_WG_LOAD_G(tile + 1) }
-    if (dbg & 1) continue;
+    if (tile + 1 < t1) { HCF_WG_LOAD(tile + 1) HCF_WG_LOAD_G(tile + 1) }
     // ---- K loop: 8 rows x 8 groups of 4 pixels; A[m = l16][k = kk] = X[pixel + tap][16 qi + l16], B = G[pixel][16 qj + l16]
 #pragma unroll 1
     for (int row = 0; row < TH; ++row) {
@@ -160,9 +158,6 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(const WgradArgs a) {
 #undef HCF_WG_LOAD
 #undef HCF_WG_LOAD_G
 
-  // ---- cross-wave reduction through LDS; the block's partial dW tile goes to scratch (coalesced), a second kernel
-  // sums the blocks that share a tile in a fixed order (deterministic; same-address atomics were 10-25x slower)
-  if (dbg & 2) return;
   // ---- the block's partial dW tile goes to scratch ([tap][m][n], 64-byte runs); a second kernel sums the blocks that
   // share a tile in a fixed order (deterministic; same-address atomics were 10-25x slower)
   float* part = a.part + ((size_t)((size_t)blockIdx.x * gridDim.y + blockIdx.y) * gridDim.z + blockIdx.z) * (TAPS * 1024);
@@ -866,10 +861,10 @@ WgradPlan plan_conv_wgrad(const WgradArgs& a) {
   p.f16 = a.g_max != nullptr;      // f16 matrix cores
   p.taps = a.taps;
   p.nocb = (a.g.n + 31) >> 5;
-  // Tiles the kernel walks. f16x3 kernel: STRIPS (WgradArgs::strip_w) when they save >= 10 % of the tiles; HCF_NO_WG_STRIP: A/B knob
+  // Tiles the kernel walks. f16x3 kernel: STRIPS (WgradArgs::strip_w) when they save >= 10 % of the tiles (HCF_NO_WG_STRIP: off)
   const int tiles_y = (a.H + 7) / 8;
   int tiles = a.B * ((a.W + 31) / 32) * tiles_y;
-  if (p.f16 && getenv("HCF_NO_WG_STRIP") == nullptr && a.B >= 2 && (long long)a.B * (a.W + 1) < 65536) {
+  if (p.f16 && !sw<Sw::HCF_NO_WG_STRIP>() && a.B >= 2 && (long long)a.B * (a.W + 1) < 65536) {
     const int strips = ((a.B * (a.W + 1) + 31) / 32) * tiles_y;
     if (strips * 10 <= tiles * 9) { tiles = strips; p.strip_w = a.W + 1; }
   }
@@ -877,11 +872,10 @@ WgradPlan plan_conv_wgrad(const WgradArgs& a) {
   const int pairs = p.nicb * p.nocb;
   // fp32 kernel: one resident round of 256 CUs x 2 blocks (measured best of 512 / 768 / 1024 / 2048; phase-aligned rounds do
   // not overlap). The f16x3 kernel holds one 8-wave block per CU (92 KB of LDS).
-  static const int wg_blocks = getenv("HCF_WG_BLOCKS") ? atoi(getenv("HCF_WG_BLOCKS")) : 0;   // experiment knob, read once
   if (p.f16)                                        // at most one full round of 256 blocks (264 blocks would cost two)
-    p.nblk_x = (wg_blocks > 0 ? wg_blocks : (a.blocks_hint > 0 ? a.blocks_hint : 256)) / pairs;
+    p.nblk_x = (a.blocks_hint > 0 ? a.blocks_hint : 256) / pairs;
   else
-    p.nblk_x = ((wg_blocks > 0 ? wg_blocks : 512) + pairs - 1) / pairs;
+    p.nblk_x = (512 + pairs - 1) / pairs;
   p.nblk_x = std::max(1, std::min(p.nblk_x, tiles));
   p.tpb = (tiles + p.nblk_x - 1) / p.nblk_x;
   p.nblk_x = (tiles + p.tpb - 1) / p.tpb;
@@ -891,11 +885,7 @@ WgradPlan plan_conv_wgrad(const WgradArgs& a) {
   // profiles/r05_ab_wgrad_lds_forms.txt: batched launch 263.4 -> 229.2 us, one-conv 3x3 launch 56.3 -> 49.1 us, 1x1 launch
   // 25.3 -> 21.0 us), 1 = double-buffered with one block store per tile (HCF_WG_DB_BLOCK=1), 0 = single buffer (HCF_WG_SINGLE_BUF=1).
   // Read per launch: the tests compare the forms inside one process. All three are bit-identical.
-  if (p.f16) {
-    const char* const e = getenv("HCF_WG_SINGLE_BUF");
-    const char* const b = getenv("HCF_WG_DB_BLOCK");
-    p.db = (e && atoi(e) != 0) ? 0 : (b && atoi(b) != 0) ? 1 : 2;
-  }
+  if (p.f16) p.db = sw<Sw::HCF_WG_SINGLE_BUF>() ? 0 : sw<Sw::HCF_WG_DB_BLOCK>() ? 1 : 2;
   p.block = p.f16 ? 512 : 256;
   if (p.f16 && p.status == HCF_OK)      // (> 64 KB: opted in to per kernel, lds_opt_in)
     p.lds_bytes = p.taps == 9 ? (p.db ? wgrad::Wg16<9>::LDS2_BYTES : wgrad::Wg16<9>::LDS_BYTES) : (p.db ? wgrad::Wg16<1>::LDS2_BYTES : wgrad::Wg16<1>::LDS_BYTES);
@@ -905,10 +895,10 @@ WgradPlan plan_conv_wgrad(const WgradArgs& a) {
 size_t conv_wgrad_scratch_floats(const WgradArgs& a) { return plan_conv_wgrad(a).scratch_floats; }
 
 // the launcher's part of a job's arguments, and its reduce step
-static WgradReduceJob planned_job(const WgradArgs& a0, const WgradPlan& p, int dbg) {
+static WgradReduceJob planned_job(const WgradArgs& a0, const WgradPlan& p) {
   WgradReduceJob j;
   j.a = a0;
-  j.a.dbg = dbg; j.a.cin_total = p.cin_total; j.a.tpb = p.tpb; j.a.strip_w = p.strip_w; j.a.strip_magic = p.strip_magic;
+  j.a.cin_total = p.cin_total; j.a.tpb = p.tpb; j.a.strip_w = p.strip_w; j.a.strip_magic = p.strip_magic;
   j.nx = p.nblk_x; j.nicb = p.nicb; j.nocb = p.nocb; j.nbx = p.nbx; j.blk0 = 0;
   return j;
 }
@@ -924,8 +914,7 @@ int launch_conv_wgrad(const WgradArgs& a0, hipStream_t st, WgradReduceJob* defer
   const WgradPlan p = plan_conv_wgrad(a0);
   if (p.status != HCF_OK) return p.status;
   if (p.scratch_floats > a0.part_cap) return HCF_ERR_NOMEM;
-  static const int wg_dbg = getenv("HCF_WG_DBG") ? atoi(getenv("HCF_WG_DBG")) : 0;   // read once
-  const WgradReduceJob job = planned_job(a0, p, wg_dbg);
+  const WgradReduceJob job = planned_job(a0, p);
   const dim3 grid((unsigned)p.nblk_x, (unsigned)p.nicb, (unsigned)p.nocb);
   for (auto& row : wgrad::kVariants) {
     if (row.f16 != p.f16 || row.taps != p.taps || row.vec != p.vec || row.db != p.db) continue;
@@ -955,7 +944,7 @@ int launch_conv_wgrad_batch(const WgradArgs* jobs, int n, hipStream_t st, WgradR
     if (p.status != HCF_OK) return p.status;
     if (!p.vec) return HCF_ERR_UNSUPPORTED;
     if (p.scratch_floats > a.part_cap) return HCF_ERR_NOMEM;
-    defer[i] = planned_job(a, p, 0);
+    defer[i] = planned_job(a, p);
     b.a[i] = defer[i].a;
     b.nicb[i] = p.nicb; b.nocb[i] = p.nocb;
     b.blk0[i] = total;

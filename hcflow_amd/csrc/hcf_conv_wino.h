@@ -85,7 +85,6 @@ struct Args {
   int* ovf;
   const char* zeros;       // >= 64 bytes of zeros
   int rev;                 // walk the units in reverse order (the engine alternates per launch: the consumer starts on what the producer touched last, which the 256 MB MALL still holds)
-  int top_wait;            // A/B knob (HCF_WINO_TOP_WAIT=1): the 64-channel kernel waits at the top of every unit's first chunk as before round 5
   unsigned long long* dbg; // WINO_PROF builds: [0] vmcnt wait [1] barrier wait [2] life [3] epilogue [4] samples [5] setup+issue [6] loads+transform;
                            // 64-channel kernel, one unit boundary (wino64_epilogue): [8] entry barrier, round 0: [9] R + write [10] barrier [11] read
                            // [14] barrier "buffer read" [13] math [12] vmcnt(0), [15] round 0's stores among round 1's R + write, round 1: [16] barrier
@@ -1111,7 +1110,7 @@ __global__ __launch_bounds__(512, 1) void conv_wino4_kernel(const Args a, const 
       // (the first chunk of a LATER unit: its image, weights and fragments were requested during the previous unit's last chunk and
       //  waited for inside that unit's epilogue, before its first global store -- vmcnt counts stores too, and a wait here would
       //  sit out the epilogue's store acknowledgements, ~1 500 cycles per unit)
-      if (c > 0 || g == 0 || a.top_wait) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      if (c > 0 || g == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #if defined(WINO_PROF)
       const unsigned long long q1 = __builtin_readcyclecounter();
 #endif

@@ -13,8 +13,8 @@ namespace hcf {
 // w: PyTorch [cout][cin][3][3]; bytes of the pack (or 0 when the layer is not eligible / a weight leaves the f16 range)
 size_t pack_conv_weights_wino(const float* w, int cin, int cout, const int* srcs, int nsrc, std::vector<float>& out, int min_cin_arg) {
   out.clear();
-  static const int min_cin_env = getenv("HCF_WINO_MIN_CIN") ? atoi(getenv("HCF_WINO_MIN_CIN")) : 64;    // experiment knob, read once (bench A/B: 128 -> 112.2, 96 -> 113.5, 64 -> 114.5 img/s)
-  const int min_cin = min_cin_arg >= 0 ? min_cin_arg : min_cin_env;      // (the completion launches of the fat schedule: 32 input channels)
+  constexpr int kWinoMinCin = 64;      // (bench A/B: 128 -> 112.2, 96 -> 113.5, 64 -> 114.5 img/s)
+  const int min_cin = min_cin_arg >= 0 ? min_cin_arg : kWinoMinCin;      // (the completion launches of the fat schedule: 32 input channels)
   if (!w || cin < min_cin || (cout != 32 && cout != 64) || nsrc < 1 || nsrc > 3) return 0;
   int sum = 0;
   for (int i = 0; i < nsrc; ++i) {
@@ -210,12 +210,9 @@ int launch_conv_wino(const ConvArgs& a, const void* wpack_wino, hipStream_t st) 
     int dev_ = 0;
     if (hipGetDevice(&dev_) == hipSuccess && dev_ >= 0 && dev_ < 64) w.clk = g_wino_clk[dev_];
   }
-  static const int top_wait = getenv("HCF_WINO_TOP_WAIT") ? atoi(getenv("HCF_WINO_TOP_WAIT")) : 0;     // A/B knob, read once
-  w.top_wait = top_wait;
   // Consecutive launches walk their units in opposite directions (HCF_WINO_REV=0: all forward): the next conv of a dense block reads
   // what this one read and wrote, and the part touched last is still in the MALL when the walk starts there (profiles/r05_notes.md section 9).
-  const char* const rev_env = getenv("HCF_WINO_REV");                 // (read per launch: tests switch it inside one process)
-  const int rev_mode = rev_env ? atoi(rev_env) : 1;
+  const int rev_mode = (int)sw<Sw::HCF_WINO_REV>();                   // (read per launch: tests switch it inside one process)
   // (per enqueuing THREAD: the two half batches of a split call are enqueued by two threads, one engine each -- a process-wide
   //  counter would hand one of them the even and the other the odd numbers, i.e. no alternation inside either stream)
   static thread_local unsigned rev_flip = 0;

@@ -59,7 +59,7 @@ struct Spec {
 };
 
 // One fused conv layer, packed for conv_mfma_kernel
-extern int g_f16x3_ablation;   // hcf_conv_f16x3.hip (hcf_debug_set_ablation; bit 256: no Winograd kernels, bit 512: no Winograd form of FCN conv1 + conv2, bit 1024: no Winograd form of the DenseBlock coupling convs)
+extern int g_f16x3_ablation;   // hcf_conv_f16x3.hip (hcf_debug_set_ablation: the kAbl* bits of hcf_switches.h)
 
 struct Conv {
   int taps = 9, cout = 0, nsrc = 0, src_n[kMaxSrc] = {0, 0, 0}, nchunk = 0, npad = 0, act = ACT_NONE;
@@ -241,9 +241,6 @@ struct hcf_engine {
   int* ovf_flag = nullptr;     // device: [0] = range flag, bytes 64..191 = zero page for the f16x3 kernel
   int64_t n_fallbacks = 0;
   bool taping = false;         // a training forward is being recorded: no fused epilogues
-  // Winograd packs of the eligible convs (built by hcf_finalize, rebuilt on the device by hcf_refresh_from_device);
-  // HCF_NO_WINO=1 keeps them from being built at all.
-  bool wino_enabled = getenv("HCF_NO_WINO") == nullptr;
   // ActNorm data-dependent initialisation (ActNorms.py:29-43), armed for ONE forward pass by hcf_actnorm_init_request
   std::set<std::string> an_pending, an_fitted;
   bool an_active = false;

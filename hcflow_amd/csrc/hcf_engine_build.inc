@@ -43,10 +43,10 @@
     cv.scale = epi.scale;
     cv.wpack_wino = nullptr;
     cv.wino_ntile = 0;
-    if (cv.wpack16 && cv.taps == 9 && wino_enabled) {
+    if (cv.wpack16 && cv.taps == 9) {
       WinoRecipe w = wino_recipe({wp}, cin, cout, srcs.data(), cv.nsrc, -1);
       if ((cv.wpack_wino = run_wino(w))) return;
-      if (wino_pad_ok && cout >= 8 && cout < 64 && cout != 32 && (cout & 3) == 0 && !getenv("HCF_NO_WINO_PAD")) {       // (A/B knob)
+      if (wino_pad_ok && cout >= 8 && cout < 64 && cout != 32 && (cout & 3) == 0) {
         // other widths of the dense-block growth convs (the rescaling trunk's 16 channels): a zero-padded 32 / 64-channel tile
         // (the prior heads, 12 / 24 output channels at K = 128, measured even-to-slower in that form and keep the direct kernel)
         w.cout_tile = cout < 32 ? 32 : 64;
@@ -169,8 +169,7 @@
       build_conv_zeros(s.c[2], f + ".conv3", hid, s.f_out, srcs2(hid, 0));
       s.c1w = Conv();
       s.w4f_frag = nullptr;
-      static const bool no_w4f = getenv("HCF_NO_W4F") != nullptr;      // A/B knob, read once
-      if (!spec_mode && rc == HCF_OK && wino_enabled && !no_w4f && cond >= 16 && (cond & 15) == 0 && z1_n <= 16 && hid == 64 &&
+      if (!spec_mode && rc == HCF_OK && cond >= 16 && (cond & 15) == 0 && z1_n <= 16 && hid == 64 &&
           s.c[0].wpack16 && s.c[1].wpack16) {
         // conv1 over [z1 zero-padded to 16 | features] + the lane-order pack of conv2 (1x1) for its fused epilogue
         WinoPart p1 = wino_part(s.c[0].wkey, 16 + cond, hid), p2 = wino_part(s.c[1].wkey, 64, 64);
@@ -201,8 +200,7 @@
       }
       s.dw_pad = 0;
       for (int i = 0; i < 5; ++i) s.cw[i] = Conv();
-      static const bool no_dw = getenv("HCF_NO_DENSE_WINO") != nullptr;      // A/B knob, read once
-      if (!spec_mode && rc == HCF_OK && wino_enabled && !no_dw && cond == 0 && hid >= 16 && (hid & 15) == 0 && z1_n <= 48 && s.f_out <= 64) {
+      if (!spec_mode && rc == HCF_OK && cond == 0 && hid >= 16 && (hid & 15) == 0 && z1_n <= 48 && s.f_out <= 64) {
         const int npad = (z1_n + 15) & ~15;
         bool any = false;
         for (int i = 1; i < 5; ++i) {
@@ -279,11 +277,10 @@
     wino_pad_ok = false;
     build_conv(r.c[4], p + ".conv5", nf + 4 * gc, nf, srcs2(nf, 4 * gc), ACT_NONE);
     r.fat[0] = r.fat[1] = false;
-    static const bool no_fat = getenv("HCF_NO_FAT") != nullptr;          // A/B knob, read once
     // gc = 32: pairs as one 64-channel launch (tile 1 = the partial) + a 32 -> 32 completion. gc = 16 (the rescaling nets' trunks,
     // round 4): pairs as one 32-channel launch whose upper half-tile is the partial + a 16 -> 16 completion in a zero-padded tile
     // -- instead of four convs that each fill half of a 32-wide MFMA tile with padding.
-    if (spec_mode || rc != HCF_OK || !wino_enabled || no_fat || (gc != 32 && gc != 16) || (nf & 15) || nf < 32) return;
+    if (spec_mode || rc != HCF_OK || (gc != 32 && gc != 16) || (nf & 15) || nf < 32) return;
     for (int j = 0; j < 2 && rc == HCF_OK; ++j) {
       const std::string pa = p + ".conv" + std::to_string(2 * j + 1), pb = p + ".conv" + std::to_string(2 * j + 2);
       const int ka = nf + 2 * j * gc, kb = ka + gc;            // input channels of the two convs

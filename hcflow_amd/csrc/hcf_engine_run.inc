@@ -25,8 +25,6 @@
   // z1 (optional): the window conv1 reads first. Both fused forms need it 16-byte addressable (launch_fcn12 declines it otherwise and
   // plan_conv_f16x3 refuses the FUSE2 row with !vec): an Affine3shift step's shift half reads z[3:], which then takes two launches
   bool can_fuse_fcn(const Conv& c1, const Conv& c2, const View* z1 = nullptr) const {
-    static const bool off = getenv("HCF_NO_FUSE_FCN") != nullptr;      // debugging aid, read once
-    if (off) return false;
     if (taping) return false;                         // the backward pass needs the intermediate tensor
     if (z1 && ((z1->cs | z1->c0) & 3) != 0) return false;
     return use_f16 && c1.wpack16 && c2.wpack16 && c1.taps == 9 && c2.taps == 1 && c1.cout == 64 && c2.cout == 64 &&
@@ -90,7 +88,7 @@
     ++launch_seq;
     int r = HCF_ERR_UNSUPPORTED;
     const bool w4f = fat && fat->w4f_frag && fuse2;    // Winograd conv1 + the 1x1 layer in its epilogue
-    if (use_f16 && cv.wpack_wino && (!fuse2 || w4f) && !tail && !(g_f16x3_ablation & 256)) {
+    if (use_f16 && cv.wpack_wino && (!fuse2 || w4f) && !tail && !(g_f16x3_ablation & kAblNoWino)) {
       a.ovf = ovf_flag;
       a.zeros = reinterpret_cast<const float*>(ovf_flag) + 16;
       if (w4f) { a.wf1x1 = fat->w4f_frag; a.bias2 = fuse2->bias; a.scale2 = fuse2->scale; a.act2 = fuse2->act; }
@@ -256,8 +254,6 @@
   // coupling network f(z1 [, u]) -> sc.hout   (FCN: Basic.py:441-447, DenseBlock: :349-356)
   // f16x3 mode: the last conv of an FCN coupling net can finish the inverse flow step in its epilogue
   bool can_fuse_tail(const Step& s) const {
-    static const bool off = getenv("HCF_NO_FUSE_TAIL") != nullptr;     // debugging aid, read once
-    if (off) return false;
     if (taping) return false;
     const Conv& c = s.c[2];
     return use_f16 && s.fcn && c.wpack16 && c.taps == 9 && s.f_out <= 32 && s.cmax <= 24;   // the 48-channel variant spills
@@ -270,7 +266,7 @@
   bool wino_offsets_ok(int H, int W, int cs) const { return (long long)B_ * H * W * cs * 4 < 0x7fffe000LL; }
   bool w4f_ok(const Step& s, const View* u, int H, int W, const Scratch& sc) const {
     return s.fcn && s.w4f_frag && u && wino_offsets_ok(H, W, std::max(u->cs, 16)) && s.w4f_frag && s.cond > 0 && u && s.mode == CPL_AFFINE && can_fuse_fcn(s.c[0], s.c[1]) &&
-           !(g_f16x3_ablation & (256 | 512)) && u->up == 0 && sc.zpad.p && conv_wino_rounds_ok(B_, H, W, 2);
+           !(g_f16x3_ablation & (kAblNoWino | kAblNoWinoFcn12)) && u->up == 0 && sc.zpad.p && conv_wino_rounds_ok(B_, H, W, 2);
   }
 
   void run_coupling_net(const Step& s, View z1, const View* u, int H, int W, Scratch& sc, const StepArgs* tail = nullptr) {
@@ -301,7 +297,7 @@
       // DenseBlock: conv i >= 1 in Winograd form over [z1 padded | growth] where that form exists and this level qualifies
       bool need64 = false;
       for (int i = 1; i < 5; ++i) need64 = need64 || (s.cw[i].wpack_wino && (s.cw[i].wino_ntile == 2 || s.cw[i].cout == 64));
-      const bool dw = s.dw_pad > 0 && s.cond == 0 && use_f16 && !taping && !(g_f16x3_ablation & (256 | 1024)) &&
+      const bool dw = s.dw_pad > 0 && s.cond == 0 && use_f16 && !taping && !(g_f16x3_ablation & (kAblNoWino | kAblNoWinoDense)) &&
                       sc.zpadd.p && sc.zpadd.C >= s.dw_pad && conv_wino_rounds_ok(B_, H, W, 1) && (!need64 || conv_wino_rounds_ok(B_, H, W, 2)) &&
                       wino_offsets_ok(H, W, std::max(sc.grow.cs, sc.zpadd.cs));
       if (dw) HCF_LAUNCH(launch_copy_pad(z1, sc.zpadd.v(0, s.dw_pad), B_, H, W, st));
@@ -380,20 +376,20 @@
   }
 
   // ResidualDenseBlock (Basic.py:379-385) with optional second residual (RRDB tail, :394-398)
-  bool tape_fat = false;         // the taped forward of a training pass takes the fat schedule as well (t_rdb; HCF_NO_TAPE_FAT: A/B knob)
+  bool tape_fat = false;         // the taped forward of a training pass takes the fat schedule as well (t_rdb; HCF_NO_TAPE_FAT: off)
   void run_rdb(const Rdb& r, View xin, const Buf& grow, int H, int W, View out, View res2, float rs2, const Buf* fatp = nullptr) {
     const int gc = cfg.rrdb_gc;
     // Fat pairs (profiles/r03_notes.md): measured per-launch costs say pair (3, 4) pays at every size, pair (1, 2) only where the
     // launches are short (the 64-channel kernel's fixed cost: 350 + 146 us against 199 + 267 at 16 x 320^2, 82 + 43 against
     // 61 + 79 at 16 x 160^2) -> up to 200 x 200 pixels per sample. The rule looks at the SAMPLE size, not at the batch: a sample's
     // bits must not depend on how many others share its launch (tests/test_gpu_nets.py: batch independence).
-    const bool fat_ok = fatp && fatp->p && use_f16 && (!taping || tape_fat) && !(g_f16x3_ablation & 256) &&
+    const bool fat_ok = fatp && fatp->p && use_f16 && (!taping || tape_fat) && !(g_f16x3_ablation & kAblNoWino) &&
                         (gc == 16 || conv_wino_rounds_ok(B_, H, W, 2)) && conv_wino_rounds_ok(B_, H, W, 1) &&
                         wino_offsets_ok(H, W, std::max(std::max(xin.cs, grow.cs), fatp->cs));
-    static const long long fat12_pixels = getenv("HCF_FAT12_PIXELS") ? atoll(getenv("HCF_FAT12_PIXELS")) : 40000;   // experiment knob
+    constexpr long long kFat12Pixels = 40000;      // pair (1, 2) of a 32-channel block: up to 200 x 200 pixels per sample (above)
     // (16-channel blocks: both halves of a pair run on the 32-channel kernel, whose fixed cost the per-conv schedule pays too:
     //  pair (1, 2) at every size)
-    const bool use_fat[2] = {fat_ok && r.fat[0] && (gc == 16 || (long long)H * W <= fat12_pixels), fat_ok && r.fat[1]};
+    const bool use_fat[2] = {fat_ok && r.fat[0] && (gc == 16 || (long long)H * W <= kFat12Pixels), fat_ok && r.fat[1]};
     ConvOpt last;          // conv 5: out = res2 + rs2 * (xin + 0.2 * conv)
     last.res1 = xin; last.rs1 = 0.2f; last.res2 = res2; last.rs2 = rs2;
     if (use_fat[0] || use_fat[1]) {
@@ -440,7 +436,7 @@
   // 192-channel slab (78.6 MB per sample at 320 x 320) stays inside the 256 MB MALL between its five convs. Off by default:
   // the persistent Winograd kernels then see 3..6 units per CU and lose more to the ragged last round than the cache gives.
   void run_cond_features(const CondFlow& cf, std::vector<View> u, int H, int W, const Buf& cfbuf, Scratch& sc) {
-    static const int trunk_mb = getenv("HCF_TRUNK_MB") ? atoi(getenv("HCF_TRUNK_MB")) : 0;
+    const int trunk_mb = (int)sw<Sw::HCF_TRUNK_MB>();      // (read once per process)
     if (trunk_mb > 0 && trunk_mb < B_ && !taping && !an_active) {
       const int Bfull = B_;
       auto shiftv = [&](View v, int b0) { v.p += (size_t)b0 * (H >> v.up) * (W >> v.up) * v.cs; return v; };

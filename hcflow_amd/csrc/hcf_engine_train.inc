@@ -55,8 +55,8 @@
       float gobj = 0.f;                              // dL / d objective_b (same for every sample)
       bool f16 = false;                              // data-gradient 3x3 convs on the f16x3 kernels (scaled by gmax)
       long long dgrad_wino_min_pix = 4096;           // HCF_DGRAD_WINO_MIN_PIX, read at the start of each backward pass
-      bool epi_fuse_off = false;                     // HCF_NO_EPI_FUSE (A/B knob), read at the start of each backward pass
-      bool fcn_fuse_off = false;                     // HCF_NO_FCN_FUSE (A/B knob), likewise
+      bool epi_fuse_off = false;                     // HCF_NO_EPI_FUSE, read at the start of each backward pass
+      bool fcn_fuse_off = false;                     // HCF_NO_FCN_FUSE, likewise
       const float* g_out_nchw = nullptr;             // inverse pass: dL / d output
       float* g_in_nchw = nullptr;                    // inverse pass, optional: receives dL / d lr
       const float* g_fwd_lr = nullptr;               // rescaling forward: upstream gradients of (clamp(LR^), z1, z2)
@@ -191,12 +191,10 @@
   // backward ...): they run on a SECOND, low-priority stream of the engine, each behind an event recorded after the epilogue backward
   // that produced its dL/dpre, and the pass joins that stream before it touches a dW again (LU chain, log-det terms, return). Both
   // halves are latency-bound on their own at training sizes (100-400 blocks per launch); side by side they fill each other's gaps.
-  // HCF_NO_WGRAD_STREAM=1: everything on the caller's stream (A/B).
   SideStream wg_stream;
   hipStream_t wgs() const { return tape->bwd.wg_async ? wg_stream.s : st; }
   void wg_begin_pass() {
-    static const bool off = getenv("HCF_NO_WGRAD_STREAM") != nullptr;
-    tape->bwd.wg_async = !off && !tape->bwd.inputs_only && wg_stream.open(0);      // (nothing to fork for without weight gradients)
+    tape->bwd.wg_async = !tape->bwd.inputs_only && wg_stream.open(0);      // (nothing to fork for without weight gradients)
   }
   // the caller's stream waits for everything the weight-gradient stream has been given so far
   void wg_join() {
@@ -206,13 +204,11 @@
   // gradient w.r.t. the 128 feature channels (two 64-channel convs, ~65 us per step at 16 x 40 x 40) to ONE buffer that nothing reads
   // before the backward pass reaches the conditional net -- off the dependency chain they go, in program order on their own stream
   // (every writer of such a buffer: the accumulations stay ordered), joined by a tape entry in front of the conditional net's records.
-  // HCF_NO_DG_STREAM=1: on the caller's stream (A/B).
   SideStream dg_stream;
   bool is_late(const float* p) const { for (const float* q : tape->late_bufs) if (q == p) return true; return false; }
   void dg_begin_pass() {
-    static const bool off = getenv("HCF_NO_DG_STREAM") != nullptr;
     tape->bwd.dg_dirty = false;
-    tape->bwd.dg_async = !off && !tape->late_bufs.empty() && dg_stream.open(1);
+    tape->bwd.dg_async = !tape->late_bufs.empty() && dg_stream.open(1);
   }
   void dg_join() {
     if (!tape->bwd.dg_async || !tape->bwd.dg_dirty) return;
@@ -276,14 +272,14 @@
   }
 
   // The weight gradients of a dense block's five convs as ONE launch (launch_conv_wgrad_batch): bwd_conv parks them here and the
-  // block's last record (conv index 0) sends them off. Block budget of the launch: HCF_WG_BATCH_BLOCKS (default 160; backward 59.2 /
+  // block's last record (conv index 0) sends them off. Block budget of the launch: kWgBatchBlocks (backward 59.2 /
   // 45.3 / 40.1 / 39.7 / 39.7 / 41.1 / 42.7 ms at 64 / 96 / 128 / 144 / 160 / 208 / 256 against 42.2 with one launch per conv),
   // shared out in proportion to each conv's (input-channel block, output-channel block) pairs.
   std::vector<WgradArgs> rdb_wg;
   int flush_rdb_wgrad() {
     if (rdb_wg.empty() || rc != HCF_OK) { rdb_wg.clear(); return rc; }
     const int n = (int)rdb_wg.size();
-    bool batch = n >= 2 && n <= kWgBatchMax && getenv("HCF_NO_WG_BATCH") == nullptr;
+    bool batch = n >= 2 && n <= kWgBatchMax;
     int pairs[kWgBatchMax], total_pairs = 0;      // (input-channel block, output-channel block) pairs per conv
     for (int i = 0; i < n && batch; ++i) {
       const WgradArgs& w = rdb_wg[i];
@@ -301,10 +297,10 @@
       rdb_wg.clear();
       return rc;
     }
-    static const int budget = getenv("HCF_WG_BATCH_BLOCKS") ? atoi(getenv("HCF_WG_BATCH_BLOCKS")) : 160;
+    constexpr int kWgBatchBlocks = 160;
     size_t need[kWgBatchMax], sum = 0;
     for (int i = 0; i < n; ++i) {
-      rdb_wg[i].blocks_hint = std::max(pairs[i], (int)((long long)budget * pairs[i] / total_pairs));
+      rdb_wg[i].blocks_hint = std::max(pairs[i], (int)((long long)kWgBatchBlocks * pairs[i] / total_pairs));
       need[i] = (conv_wgrad_scratch_floats(rdb_wg[i]) + 63) & ~(size_t)63;
       sum += need[i];
     }
@@ -381,8 +377,7 @@
   // [x_0 (nf) | x_1 .. x_{j-1} (gc each)] and cout_j = gc (j < 5) / nf (j = 5) outputs. Pack of x_m: logical weight
   //   L[n][koff_j + oc][t] = w_j[oc][chan_off(m) + n][8 - t],  j = m + 1 .. 5,  chan_off(0) = 0, chan_off(m) = nf + (m - 1) gc
   // K order = the gradient slab's channel order [conv m+1 .. conv 4] followed by conv 5's gradient tensor.
-  static bool rdb_gather_off() { return getenv("HCF_NO_DGRAD_GATHER") != nullptr; }     // A/B knob, read when an engine prepares for training
-  static bool rdb_dgrad_wino_off() { return getenv("HCF_NO_DGRAD_WINO") != nullptr; }    // likewise: gather convs stay on the direct scaled kernel
+  static bool rdb_gather_off() { return sw<Sw::HCF_NO_DGRAD_GATHER>(); }     // read when an engine prepares for training
   // Policy of the record that launches the gather conv of x_m of this block: the Winograd pack it should try first at this size, or
   // null. HCF_DGRAD_WINO_MIN_PIX (default 4 096 = 64 x 64: at 40 x 40 both forms are one 24 us round) = smallest H * W that takes it.
   const float* rdb_dgrad_wino(const Rdb& rdb, int m, int H, int W) const {
@@ -423,7 +418,7 @@
       r.gt[m] = tp;
       // the same logical weight in Winograd form (round 6): the gather conv of x_m has the shape of the forward conv 5 - m, and at
       // the 80 x 80 level of the training patches the Winograd kernels run it in 30-65 us where the direct scaled kernel takes 60-150
-      r.gtw[m] = rdb_dgrad_wino_off() ? nullptr : run_wino(w);
+      r.gtw[m] = run_wino(w);
     }
     r.gather = (rc == HCF_OK);
     if (r.gather) for (int j = 0; j < 5; ++j) r.c[j].tpacks.clear();      // (none are built for a gathered block)
@@ -1338,7 +1333,7 @@
     if (wrong_net) return fail(HCF_ERR_STATE, wrong_net);
     tape_swap();
     taping = true;
-    tape_fat = getenv("HCF_NO_TAPE_FAT") == nullptr;
+    tape_fat = !sw<Sw::HCF_NO_TAPE_FAT>();
     tape->tfat.p = nullptr;
     cc_valid = false;
     use_f16 = (precision == PREC_F16X3);          // forward convs; fused epilogues are off while taping
@@ -1428,9 +1423,9 @@
       return finish_backward();
     }
     tape->bwd.f16 = (precision == PREC_F16X3) && ovf_flag != nullptr;
-    tape->bwd.epi_fuse_off = getenv("HCF_NO_EPI_FUSE") != nullptr;
-    tape->bwd.dgrad_wino_min_pix = getenv("HCF_DGRAD_WINO_MIN_PIX") ? atoll(getenv("HCF_DGRAD_WINO_MIN_PIX")) : 4096;
-    tape->bwd.fcn_fuse_off = getenv("HCF_NO_FCN_FUSE") != nullptr;
+    tape->bwd.epi_fuse_off = sw<Sw::HCF_NO_EPI_FUSE>();
+    tape->bwd.dgrad_wino_min_pix = sw<Sw::HCF_DGRAD_WINO_MIN_PIX>();
+    tape->bwd.fcn_fuse_off = sw<Sw::HCF_NO_FCN_FUSE>();
     if (tape->bwd.f16) { ovf_latch(); ovf_clear = false; }
     if (tape->bwd.f16 && hipMemsetAsync(ovf_flag, 0, 256, st) != hipSuccess) return fail(HCF_ERR_HIP, "hipMemsetAsync failed (backward)");
     tape->bwd.gparams = dparams;

@@ -57,7 +57,7 @@ static int pack_and_launch(Tmp& t, ConvArgs& a, const float* w, int cin, int cou
   a.nchunk = nchunk;
   if (!t.ok) return HCF_ERR_NOMEM;
   const float* wino = nullptr;             // eligible layers take the Winograd form, as in the engine (--ablate 256: off)
-  if (f16 && !(g_f16x3_ablation & 256)) {
+  if (f16 && !(g_f16x3_ablation & kAblNoWino)) {
     std::vector<float> pkw;
     if (pack_conv_weights_wino(w, cin, cout, srcs, n_src, pkw)) wino = t.up(pkw);
     if (!t.ok) return HCF_ERR_NOMEM;
@@ -297,7 +297,7 @@ double hcf_debug_last_clock_mhz(void) {
   return probe > 0.0 ? probe : g_last_clock_mhz;
 }
 int hcf_debug_clock_probe(int32_t enable) { return hcf::wino_clock_probe(enable); }
-// timing ablations of the f16x3 kernel (tools/conv_bench.py --ablate); 0 = off
+// the kAbl* bits of hcf_switches.h (tools/conv_bench.py --ablate, the tests' kernel-variant comparisons); 0 = off
 int hcf_debug_set_ablation(int32_t bits) { hcf::g_f16x3_ablation = bits; return HCF_OK; }
 
 // launch selection without a GPU (layouts: include/hcflow.h). The views get made-up addresses: the plans test them, nothing reads them
@@ -1106,7 +1106,7 @@ int hcf_op_conv2d_views(const hcf_view* src, int32_t n_src, int32_t B, int32_t H
   a.nchunk = nchunk;
   if (!t.ok) return HCF_ERR_NOMEM;
   rc = HCF_ERR_UNSUPPORTED;
-  if (f16 && k == 3 && !(g_f16x3_ablation & 256)) {      // eligible layers take the Winograd form, as in the engine
+  if (f16 && k == 3 && !(g_f16x3_ablation & kAblNoWino)) {      // eligible layers take the Winograd form, as in the engine
     std::vector<float> pkw;
     const float* wino = pack_conv_weights_wino(w, cin, cout, srcs, n_src, pkw) ? t.up(pkw) : nullptr;
     if (!t.ok) return HCF_ERR_NOMEM;
@@ -1190,7 +1190,7 @@ int hcf_op_conv2d_dgrad_fused_views(const hcf_view* src, int32_t n_src, int32_t 
   // the engine's order: fused Winograd first, then the fused scaled f16x3 kernel; never an unfused launch
   rc = HCF_ERR_UNSUPPORTED;
   int rows = 0;
-  if (k == 3 && !(g_f16x3_ablation & 256)) {
+  if (k == 3 && !(g_f16x3_ablation & kAblNoWino)) {
     std::vector<float> pkw;
     // (from 16 input channels on, the narrowest pack the engine builds for this kernel: a unit count beyond one round of blocks
     //  stays affordable for a test only on a narrow source)

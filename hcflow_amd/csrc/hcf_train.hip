@@ -168,13 +168,10 @@ __global__ __launch_bounds__(256) void conv_epilogue_bwd_vec_kernel(const EpiBwd
   }
 }
 
-static int epi_bwd_ppb() {                   // pixels per block; 192: ~530 blocks for a 16 x 80 x 80 tensor (96 / 192 / 384 measured 84.3 / 82.6 / 86.8 ms per training step) (HCF_EPI_PPB: experiments)
-  static const int v = getenv("HCF_EPI_PPB") ? std::max(32, atoi(getenv("HCF_EPI_PPB"))) : 192;
-  return v;
-}
+constexpr int kEpiBwdPpb = 192;              // pixels per block: ~530 blocks for a 16 x 80 x 80 tensor (96 / 192 / 384 measured 84.3 / 82.6 / 86.8 ms per training step)
 int conv_epilogue_bwd_blocks(int B, int H, int W) {
   const long long npix = (long long)B * H * W;
-  return (int)((npix + epi_bwd_ppb() - 1) / epi_bwd_ppb());
+  return (int)((npix + kEpiBwdPpb - 1) / kEpiBwdPpb);
 }
 
 __global__ __launch_bounds__(256) void sum_jobs_kernel(const SumJob* jobs) {
@@ -205,7 +202,7 @@ bool conv_epilogue_bwd_vec(const EpiBwdArgs& a) {
 int launch_conv_epilogue_bwd(const EpiBwdArgs& a, hipStream_t st) {
   if (a.gy.n < 1 || a.gy.n > 256 || a.gpre.n != a.gy.n) return HCF_ERR_ARG;
   const long long npix = (long long)a.B * a.H * a.W;
-  const int ppb = epi_bwd_ppb();
+  const int ppb = kEpiBwdPpb;
   const bool vec = conv_epilogue_bwd_vec(a);
   if (vec) hipLaunchKernelGGL(conv_epilogue_bwd_vec_kernel, dim3((unsigned)((npix + ppb - 1) / ppb)), dim3(256), 0, st, a, npix, ppb);
   else hipLaunchKernelGGL(conv_epilogue_bwd_kernel, dim3((unsigned)((npix + ppb - 1) / ppb)), dim3(256), 0, st, a, npix, ppb);

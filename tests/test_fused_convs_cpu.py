@@ -10,7 +10,7 @@ import torch
 from hcflow_amd import _lib
 from tests import fused_conv_cases as FC
 
-SWITCHES = ("HCF_NO_TH4", "HCF_NO_N16", "HCF_NO_FCN12")
+SWITCHES = ("HCF_NO_TH4",)
 
 
 def plan(c, monkeypatch):
