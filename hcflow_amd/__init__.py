@@ -14,10 +14,11 @@ from . import resize  # noqa: F401
 from .resize import imresize, lr_psnr  # noqa: F401
 from . import losses  # noqa: F401
 from .losses import (PixelLoss, ReconstructionLoss, CharbonnierLoss, GANLoss, Quantization, latent_l2,  # noqa: F401
-                     finite_sum)
+                     finite_sum, ssim, SSIMLoss)
 
 __all__ = ["NetConfig", "preset", "param_spec", "eps_shapes", "make_params", "HCFlowNet_SR", "HCFlowNet_Rescaling", "latent",
            "data", "ImageBank", "BankLoader", "draw_crops", "prepare_batch", "whole_image",
            "PairedBank", "PairedBankLoader", "draw_paired_crops", "center_crops", "prepare_paired_batch", "whole_pair",
            "resize", "imresize", "lr_psnr",
-           "losses", "PixelLoss", "ReconstructionLoss", "CharbonnierLoss", "GANLoss", "Quantization", "latent_l2", "finite_sum"]
+           "losses", "PixelLoss", "ReconstructionLoss", "CharbonnierLoss", "GANLoss", "Quantization", "latent_l2", "finite_sum",
+           "ssim", "SSIMLoss"]

@@ -58,6 +58,7 @@ SYMBOLS = [
     "hcf_resize_workspace", "hcf_resize_bicubic", "hcf_resize_bicubic_backward", "hcf_resize_tables",
     "hcf_loss_pair_workspace", "hcf_loss_pair", "hcf_loss_pair_backward",
     "hcf_loss_sumsq_workspace", "hcf_loss_sumsq", "hcf_loss_sumsq_backward", "hcf_loss_gan", "hcf_loss_gan_backward",
+    "hcf_loss_ssim_workspace", "hcf_loss_ssim", "hcf_loss_ssim_backward",
 ]
 
 
@@ -255,6 +256,10 @@ def load() -> C.CDLL:
     lib.hcf_loss_sumsq_backward.argtypes = [C.POINTER(vp), C.POINTER(i64), i32, fp, C.POINTER(vp), vp]
     lib.hcf_loss_gan.argtypes = [fp, i64, f64, fp, i64, f64, i32, i32, i32, fp, vp]
     lib.hcf_loss_gan_backward.argtypes = [fp, i64, f64, fp, i64, f64, i32, i32, i32, fp, fp, fp, vp]
+    lib.hcf_loss_ssim_workspace.argtypes = [i64, i32, i32, i32, i32]
+    lib.hcf_loss_ssim_workspace.restype = C.c_size_t
+    lib.hcf_loss_ssim.argtypes = [fp, fp, i64, i32, i32, i32, i32, f64, fp, fp, vp, C.c_size_t, vp]
+    lib.hcf_loss_ssim_backward.argtypes = [fp, fp, i64, i32, i32, i32, i32, f64, fp, i32, f64, fp, fp, vp]
     for name in SYMBOLS:
         fn = getattr(lib, name)
         if name not in ("hcf_destroy", "hcf_last_error", "hcf_workspace_bytes", "hcf_weight_bytes",
@@ -262,7 +267,7 @@ def load() -> C.CDLL:
                         "hcf_lpips_backward_workspace", "hcf_lpips_embed_bytes", "hcf_lpips_map_workspace",
                         "hcf_aux_bn_act_workspace", "hcf_aux_feature_loss_workspace", "hcf_metric_stats_bytes",
                         "hcf_metric_pair_ref_bytes", "hcf_metric_pair_workspace", "hcf_resize_workspace",
-                        "hcf_loss_pair_workspace", "hcf_loss_sumsq_workspace"):
+                        "hcf_loss_pair_workspace", "hcf_loss_sumsq_workspace", "hcf_loss_ssim_workspace"):
             fn.restype = C.c_int
     _lib = lib
     return lib

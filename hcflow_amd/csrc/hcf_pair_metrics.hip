@@ -26,6 +26,7 @@
 #include "../../include/hcflow.h"
 #include "hcf_common.h"
 #include "hcf_bicubic_tables.h"
+#include "hcf_ssim_window.h"
 
 namespace hcf {
 namespace pairm {
@@ -37,8 +38,6 @@ namespace pairm {
 #define PM_QUADS (PM_SH * (PM_SW / 4)) // 286 quads of 4 pixels
 #define PM_ITEMS 2                     // quads per thread (256 threads)
 #define PM_NQ 6                        // per block: sq(B,G,R), sq(Y), ssim B, G, R, Y
-
-struct Gauss11 { double g[11]; };
 
 // tensor2img of one value: clamp to [0, 1], * 255 in fp32, round half to even (numpy .round())
 __device__ __forceinline__ double quant255(float x) {
@@ -382,14 +381,6 @@ static const Table* table_for(int len, int scale) {
     contributions(len, (len + scale - 1) / scale, 1.0 / scale, t->w, t->idx, t->P);
   }
   return t;
-}
-
-static Gauss11 gauss11() {
-  Gauss11 gk;
-  double sum = 0;
-  for (int i = 0; i < 11; ++i) { gk.g[i] = exp(-((i - 5.0) * (i - 5.0)) / (2.0 * 1.5 * 1.5)); sum += gk.g[i]; }
-  for (int i = 0; i < 11; ++i) gk.g[i] /= sum;
-  return gk;
 }
 
 // the device buffers of a one-shot call, freed when it returns. The work queued on them is stream-ordered: the caller

@@ -12,7 +12,8 @@ are strings of small torch ops with host synchronisations in between (``torch.is
   soon as one element is, so ``finite_sum`` replaces the callers' ``isnan`` / ``isfinite`` gates without a pass of its own.
 
 GPU and fp32 only; anything else raises ``HcfError`` -- there is no fallback. A non-contiguous input is made contiguous (its
-autograd link is kept); when nothing requires grad no graph is built. ``GradientPenaltyLoss`` (``loss.py:54-74``) needs a double
+autograd link is kept); when nothing requires grad no graph is built. ``ssim`` / ``SSIMLoss`` (``hcf_ssim.hip``) add the
+structural measure the validation log reports (``utils/util.py:914-955``) under the same rules. ``GradientPenaltyLoss`` (``loss.py:54-74``) needs a double
 backward through the discriminator, no shipped yml uses it: it stays the reference's.
 """
 from __future__ import annotations
@@ -26,7 +27,8 @@ from torch.autograd.function import once_differentiable
 from . import _lib
 from . import metrics
 
-__all__ = ["PixelLoss", "ReconstructionLoss", "CharbonnierLoss", "GANLoss", "Quantization", "latent_l2", "finite_sum"]
+__all__ = ["PixelLoss", "ReconstructionLoss", "CharbonnierLoss", "GANLoss", "Quantization", "latent_l2", "finite_sum", "ssim",
+           "SSIMLoss"]
 
 _L1, _L2, _CHARB = 0, 1, 2
 _MAX_TENSORS = 8
@@ -313,6 +315,103 @@ class GANLoss(nn.Module):
         rel = 1 if self.gan_type == "ragan" else 0
         total, logs = _gan(pred_real, pred_fake, self._target(True), self._target(False), self._type, rel, rel)
         return total, logs.detach()
+
+
+# ---- SSIM ------------------------------------------------------------------------------------------------------------------------
+
+def _ssim_args(name, x, y, y_channel, data_range):
+    """The checked, contiguous pair and (B, C, H, W, y_channel, data_range). What the kernels would refuse as a status code
+    (a side under 11, y_channel without three channels) is worded here, before any launch."""
+    _typed(name, x, "input")
+    _typed(name, y, "target")
+    if x.shape != y.shape:
+        raise _lib.HcfError("%s: input is %s, target is %s" % (name, tuple(x.shape), tuple(y.shape)))
+    if x.dim() != 4:
+        raise ValueError("%s: the inputs must be [B, C, H, W], got %s" % (name, tuple(x.shape)))
+    B, Cn, H, W = (int(s) for s in x.shape)
+    if H < 11 or W < 11:
+        raise ValueError("%s: the 11 x 11 window does not fit into %d x %d images" % (name, H, W))
+    if y_channel and Cn != 3:
+        raise ValueError("%s: y_channel needs RGB inputs [B, 3, H, W], got %d channels" % (name, Cn))
+    data_range = float(data_range)
+    if not 0.0 < data_range < float("inf"):
+        raise ValueError("%s: data_range must be positive and finite, got %r" % (name, data_range))
+    x, y = _on_gpu(name, x, "input"), _on_gpu(name, y, "target")
+    if x.device != y.device:
+        raise _lib.HcfError("%s: input is on %s, target on %s" % (name, x.device, y.device))
+    return x, y, (B, Cn, H, W, 1 if y_channel else 0, data_range)
+
+
+def _ssim_forward(x, y, meta, loss):
+    """(rows [B], 1 - mean or None): two launches."""
+    dev = x.device
+    B, Cn, H, W, ych, R = meta
+    need = int(_lib.load().hcf_loss_ssim_workspace(B, Cn, H, W, ych))
+    if need == 0:
+        raise _lib.HcfError("ssim: shape %s is refused by hcf_loss_ssim_workspace" % (tuple(x.shape),))
+    wk = _workspace("ssim", dev, need)
+    rows = torch.empty(B, dtype=torch.float32, device=dev)
+    out = torch.empty((), dtype=torch.float32, device=dev) if loss else None
+    _lib.launch("hcf_loss_ssim", dev, x, y, B, Cn, H, W, ych, R, rows, out, wk, wk.numel())
+    return rows, out
+
+
+class _SsimFn(torch.autograd.Function):
+    """One node: the inputs are saved, nothing else; backward is one hcf_loss_ssim_backward launch for both gradients. `loss`:
+    the output is the scalar 1 - mean_b (upstream: one scalar), else the rows [B] (upstream: one value per sample)."""
+
+    @staticmethod
+    def forward(ctx, x, y, meta, loss):
+        ctx.save_for_backward(x, y)
+        ctx.meta, ctx.loss = meta, loss
+        rows, out = _ssim_forward(x, y, meta, loss)
+        return out if loss else rows
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        x, y = ctx.saved_tensors
+        B, Cn, H, W, ych, R = ctx.meta
+        g = g.to(torch.float32).contiguous()
+        gx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        gy = torch.empty_like(y) if ctx.needs_input_grad[1] else None
+        _lib.launch("hcf_loss_ssim_backward", x.device, x, y, B, Cn, H, W, ych, R, g, 0 if ctx.loss else 1,
+                    -1.0 / B if ctx.loss else 1.0, gx, gy)
+        return gx, gy, None, None
+
+
+def _ssim(name, x, y, y_channel, data_range, loss):
+    x, y, meta = _ssim_args(name, x, y, y_channel, data_range)
+    if _wants_grad(x, y):
+        return _SsimFn.apply(x, y, meta, loss)
+    rows, out = _ssim_forward(x.detach(), y.detach(), meta, loss)
+    return out if loss else rows
+
+
+def ssim(x, y, y_channel=False, data_range=1.0):
+    """The reference's SSIM (``utils/util.py:914-955``: 11 x 11 Gaussian window, sigma 1.5, "valid" map, mean over the channels
+    of the map means) of fp32 ``[B, C, H, W]`` tensors in ``[0, data_range]``, per sample: ``[B]``, differentiable with respect to
+    either input or both. On ``[0, 1]`` data with ``data_range=1`` it is the reference's number on the same data times 255.
+    ``y_channel=True`` (RGB, C = 3): on ``Y = (65.481 R + 128.553 G + 24.966 B + 16 data_range) / 255`` (``bgr2ycbcr(only_y=True)``),
+    the SSIM_Y the rescaling nets are ranked by. Unlike ``PairMetrics`` nothing is quantised and nothing is cropped: slice the
+    inputs for a ``crop_border``. Images under 11 pixels a side and ``y_channel`` without three channels raise ``ValueError``."""
+    return _ssim("ssim", x, y, y_channel, data_range, False)
+
+
+class SSIMLoss(nn.Module):
+    """``1 - ssim(x, y, y_channel, data_range).mean()`` as one node (two launches forward, one backward): a structural term for
+    the places that take a loss -- ``latent.refine_image(data_loss=...)``, ``latent.optimise(loss_fn=...)``, the HR term of the
+    HCFlow+ reverse step and of the rescaling objective. Identical inputs give exactly 0."""
+
+    def __init__(self, y_channel=False, data_range=1.0):
+        super().__init__()
+        data_range = float(data_range)
+        if not 0.0 < data_range < float("inf"):
+            raise ValueError("SSIMLoss: data_range must be positive and finite, got %r" % (data_range,))
+        self.y_channel, self.data_range = bool(y_channel), data_range
+
+    def forward(self, x, y):
+        return _ssim("SSIMLoss", x, y, self.y_channel, self.data_range, True)
 
 
 # ---- straight-through quantisation and the finite gate ---------------------------------------------------------------------------

@@ -965,6 +965,36 @@ int hcf_loss_gan(const float* a, int64_t na, double ta, const float* b, int64_t 
 int hcf_loss_gan_backward(const float* a, int64_t na, double ta, const float* b, int64_t nb, double tb, int32_t type,
                           int32_t relativistic, int32_t halve, const float* g, float* ga, float* gb, hcf_stream_t stream);
 
+/* ---- SSIM as a criterion (hcf_ssim.hip): the reference's ssim / calculate_ssim (utils/util.py:914-955) with its gradient ----
+ * x, y: dense NCHW fp32 DEVICE tensors [B,C,H,W] with values in [0, data_range]. Per plane the "valid" map of (H-10) x (W-10)
+ * values S = ((2 mu_x mu_y + C1)(2 s_xy + C2)) / ((mu_x^2 + mu_y^2 + C1)(s_x + s_y + C2)) under the window w = k k^T, k =
+ * cv2.getGaussianKernel(11, 1.5), C1 = (0.01 data_range)^2, C2 = (0.03 data_range)^2; a sample's value is the mean over its
+ * planes of the planes' map means. With data_range = 1 on [0, 1] data this is the reference's number on the same data times 255.
+ * y_channel = 1 (C must be 3, RGB order): one plane per sample, Y = (65.481 R + 128.553 G + 24.966 B + 16 data_range) / 255
+ * (data/util.py:209-230 bgr2ycbcr(only_y=True)); the gradient reaches the three channels by those weights.
+ * The rules of the training criteria above hold: fp64 terms from the fp32 inputs (the window is applied separably, rows then
+ * columns, one fma chain in tap order each), per-block fp64 partials of a grid that H and W alone decide, one fixed-order final
+ * block, one rounding to fp32; no atomics; nothing allocates, copies or synchronises. Results are bit-reproducible, row b does
+ * not depend on the batch around it, and any 4-byte aligned tensor gives the bits of an aligned copy. Identical inputs give
+ * exactly 1 per sample and a loss of exactly 0. One non-finite pixel makes its sample's value non-finite.
+ *   hcf_loss_ssim_workspace  bytes of the caller-allocated device scratch of hcf_loss_ssim; 0 for a shape it refuses.
+ *   hcf_loss_ssim            out_rows [B] = fp32(SSIM_b); out_loss (nullable) one float, fp32(1 - mean_b SSIM_b).
+ *   hcf_loss_ssim_backward   recomputes from x and y (the forward saves nothing). Upstream gradient from DEVICE memory:
+ *                            g_stride 1: g [B], one per sample (the gradient of out_rows; scale = 1); g_stride 0: g[0] for
+ *                            every sample (the gradient of out_loss; scale = -1 / B). gx = fp32(g_b * scale * dSSIM_b / dx),
+ *                            gy likewise, either nullable (at least one); both come from one launch. A sample whose g_b is 0
+ *                            gets exact zeros, also where its pixels are not finite.
+ * HCF_ERR_ARG: a NULL x, y, out_rows, work or g, neither gx nor gy, B, C, H or W < 1, y_channel / g_stride outside 0 / 1, a
+ * data_range that is not positive and finite, a scale that is not finite, a pointer that is not 4-byte aligned (work: 8);
+ * HCF_ERR_SHAPE: H or W < 11 (the map is empty) or > 2^20, y_channel with C != 3, more than 65535 planes (B * C, or B with
+ * y_channel); HCF_ERR_NOMEM: work_bytes below the workspace size. Every check comes before the first HIP call. */
+size_t hcf_loss_ssim_workspace(int64_t B, int32_t C, int32_t H, int32_t W, int32_t y_channel);
+int hcf_loss_ssim(const float* x, const float* y, int64_t B, int32_t C, int32_t H, int32_t W, int32_t y_channel, double data_range,
+                  float* out_rows, float* out_loss, void* work, size_t work_bytes, hcf_stream_t stream);
+int hcf_loss_ssim_backward(const float* x, const float* y, int64_t B, int32_t C, int32_t H, int32_t W, int32_t y_channel,
+                           double data_range, const float* g, int32_t g_stride, double scale, float* gx, float* gy,
+                           hcf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
