@@ -36,7 +36,7 @@ SYMBOLS = [
     "hcf_train_forward_sr", "hcf_train_backward", "hcf_train_backward_phase", "hcf_bind_param_device", "hcf_refresh_from_device",
     "hcf_train_inverse", "hcf_train_backward_inverse", "hcf_metric_psnr_ssim", "hcf_metric_imresize_down",
     "hcf_train_select_tape", "hcf_train_forward_rescale", "hcf_train_backward_rescale",
-    "hcf_debug_range_probe", "hcf_debug_range_probe_read", "hcf_debug_conv_plan",
+    "hcf_debug_range_probe", "hcf_debug_range_probe_read", "hcf_debug_conv_plan", "hcf_debug_conv_route",
     "hcf_aux_conv2d_workspace", "hcf_aux_conv2d", "hcf_aux_conv2d_backward", "hcf_adam_step",
     "hcf_lpips_workspace", "hcf_lpips_alex", "hcf_lpips_backward_workspace", "hcf_lpips_alex_backward",
     "hcf_lpips_embed_bytes", "hcf_lpips_alex_embed", "hcf_lpips_map_workspace", "hcf_lpips_alex_map",
@@ -190,6 +190,7 @@ def load() -> C.CDLL:
     lib.hcf_debug_range_probe.argtypes = [vp, i32]
     lib.hcf_debug_range_probe_read.argtypes = [vp, i32, C.c_char_p, i32, C.POINTER(f32), C.POINTER(i32)]
     lib.hcf_debug_conv_plan.argtypes = [C.POINTER(i32), i32, C.POINTER(i64), i32]
+    lib.hcf_debug_conv_route.argtypes = [i32, i32, i32, i32, C.POINTER(i32), i32]
     lib.hcf_bind_param_device.argtypes = [vp, C.c_char_p, fp]
     lib.hcf_refresh_from_device.argtypes = [vp, vp]
     lib.hcf_train_forward_sr.argtypes = [vp, fp, fp, fp, fp, fp, fp, i32, i32, i32, vp]

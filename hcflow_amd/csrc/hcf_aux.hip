@@ -127,21 +127,16 @@ int hcf_aux_conv2d(const float* x, int32_t cs_in, int32_t cin, int32_t B, int32_
       if (hipMemsetAsync(r.pk16, 0, pkb, st) != hipSuccess) return HCF_ERR_HIP;
       rc = launch_repack_conv(r, st);
       if (rc != HCF_OK) break;
-      ConvArgs a = conv_block_args(src, p.nchunk_f, out, act, B, H, W, bvec, svec);
-      a.ovf = (int*)wk;
-      a.zeros = reinterpret_cast<const float*>(wk) + 16;
-      rc = HCF_ERR_UNSUPPORTED;
+      const ConvArgs a = conv_block_args(src, p.nchunk_f, out, act, B, H, W, bvec, svec);
+      ConvPacks pk = {nullptr, (const float*)(wk + p.o_pk16), nullptr, nullptr, nullptr, (int*)wk};
       if ((cin & 15) == 0 && cin >= 64 && (nb == 32 || nb == 64)) {      // the dense 3x3 layers take the Winograd form
         // the kernels over-read ONE chunk behind the pack, which must be zero: the region is shared by the 64- and the 32-wide
         // layouts of successive output-channel blocks (cout = 96, 160 ...), whose chunk sizes and hence "behind the pack" differ
         const size_t chunk_b = (nb == 64) ? 65536 : 32768;
         if (hipMemsetAsync(wk + p.o_wino + (size_t)(cin / 16) * chunk_b, 0, chunk_b, st) != hipSuccess) return HCF_ERR_HIP;
-        if (launch_repack_wino(wb, cin, nb, nb, wk + p.o_wino, st) == HCF_OK) rc = launch_conv_wino(a, wk + p.o_wino, st);
+        if (launch_repack_wino(wb, cin, nb, nb, wk + p.o_wino, st) == HCF_OK) pk.wino = wk + p.o_wino;
       }
-      if (rc == HCF_ERR_UNSUPPORTED) {
-        a.wpack = (const float*)(wk + p.o_pk16);
-        rc = launch_conv_f16x3(a, p.taps, st);
-      }
+      rc = route_conv(a, pk, p.taps, kAllowAll, st).status;      // Winograd, then f16x3 (hcf_conv_route.hip)
     }
   }
   return rc;

@@ -1,6 +1,6 @@
-// hcf_engine_run.inc -- included INSIDE struct hcf_engine (hcf_engine.hip). ROUTING + EXECUTION: which kernel a conv call takes
-// (run_conv), the coupling nets, flow steps, dense blocks and conditional feature extractors as launch sequences, and the two
-// passes of the path (pass_inverse, pass_forward).
+// hcf_engine_run.inc -- included INSIDE struct hcf_engine (hcf_engine.hip). EXECUTION: a conv call's arguments and packs (run_conv;
+// which kernel family takes it is route_conv's decision, hcf_conv_route.hip), the coupling nets, flow steps, dense blocks and
+// conditional feature extractors as launch sequences, and the two passes of the path (pass_inverse, pass_forward).
 
   // ---------------------------------------------------------------- execution helpers
   hipStream_t st = nullptr;
@@ -55,7 +55,7 @@
     for (int i = cv.nsrc; i < kMaxSrc; ++i) a.src[i] = srcs[0];
     a.nsrc = cv.nsrc;
     a.B = B_; a.H = H; a.W = W;
-    a.wpack = cv.wpack; a.nchunk = cv.nchunk; a.bias = cv.bias; a.scale = cv.scale; a.act = cv.act;
+    a.nchunk = cv.nchunk; a.bias = cv.bias; a.scale = cv.scale; a.act = cv.act;
     a.out = out; a.out.n = cv.cout;
     a.res1 = res1; a.rs1 = rs1; a.res2 = res2; a.rs2 = rs2;
     if (fat) { a.out2 = fat->out2; a.act_t2 = fat->act2; a.res1_pre = fat->pre ? 1 : 0; }
@@ -86,41 +86,29 @@
       if (!prof_events[prof_used].chained) hipEventRecord(prof_events[prof_used].e0, st);
     }
     ++launch_seq;
-    int r = HCF_ERR_UNSUPPORTED;
+    // second layer and tail travel in the arguments, the packs say which forms exist; a fat dense-block launch is Winograd or
+    // nothing, a pre-activation term (res1 of a fused FCN) fcn12 or nothing
     const bool w4f = fat && fat->w4f_frag && fuse2;    // Winograd conv1 + the 1x1 layer in its epilogue
-    if (use_f16 && cv.wpack_wino && (!fuse2 || w4f) && !tail && !(g_f16x3_ablation & kAblNoWino)) {
-      a.ovf = ovf_flag;
-      a.zeros = reinterpret_cast<const float*>(ovf_flag) + 16;
-      if (w4f) { a.wf1x1 = fat->w4f_frag; a.bias2 = fuse2->bias; a.scale2 = fuse2->scale; a.act2 = fuse2->act; }
-      r = launch_conv_wino(a, cv.wpack_wino, st);      // HCF_ERR_UNSUPPORTED: this call's views do not qualify
-      if (r == HCF_OK && prof) prof_events[prof_used].kind = w4f ? 6 : (fat && fat->pre) ? 7 : 4;
+    if (fuse2) { a.bias2 = fuse2->bias; a.scale2 = fuse2->scale; a.act2 = fuse2->act; }
+    if (tail) {
+      a.tz = tail->z; a.tzo = tail->out; a.tmat = tail->mat; a.tbias = tail->an_bias; a.tmul = tail->an_mul;
+      a.tC = tail->C; a.tns = tail->ns; a.tmode = tail->mode;
+      a.tzpad = tail->zpad16; a.tzpad_n = tail->zpad_n;
+      a.tpart = tail->partial; a.tpart_stride = tail->partial_stride;
     }
+    ConvPacks pk = {fat ? nullptr : cv.wpack, nullptr, nullptr, nullptr, nullptr, ovf_flag};
+    if (use_f16) {
+      pk.wino = cv.wpack_wino;
+      if (!fat) pk.f16 = cv.wpack16;
+      if (fuse2) { pk.f16_2 = fuse2->wpack16; pk.wino_frag2 = w4f ? fat->w4f_frag : nullptr; }
+    }
+    const bool pre = fuse2 && !tail && res1.p;
+    const ConvRoute rt = route_conv(a, pk, cv.taps, fat ? 1u << CONV_WINO : pre ? 1u << CONV_FCN12 : kAllowAll, st);
+    const int r = rt.status;
     if (fat && r != HCF_OK) { fail(HCF_ERR_STATE, "internal: a fat dense-block launch did not take the Winograd kernel"); return; }
-    if (r != HCF_ERR_UNSUPPORTED) {
-    } else if (use_f16 && cv.wpack16 && (cv.taps == 9 || (cv.taps == 1 && !fuse2 && !tail))) {      // (a stand-alone 1x1: the training passes)
-      a.wpack = cv.wpack16;
-      a.ovf = ovf_flag;
-      a.zeros = reinterpret_cast<const float*>(ovf_flag) + 16;
-      if (fuse2) {
-        a.w2 = fuse2->wpack16; a.bias2 = fuse2->bias; a.scale2 = fuse2->scale; a.act2 = fuse2->act;
-      }
-      if (tail) {
-        a.tz = tail->z; a.tzo = tail->out; a.tmat = tail->mat; a.tbias = tail->an_bias; a.tmul = tail->an_mul;
-        a.tC = tail->C; a.tns = tail->ns; a.tmode = tail->mode;
-        a.tzpad = tail->zpad16; a.tzpad_n = tail->zpad_n;
-        a.tpart = tail->partial; a.tpart_stride = tail->partial_stride;
-      }
-      r = HCF_ERR_UNSUPPORTED;
-      if (fuse2 && !tail) {                 // one K chunk: the persistent small-K form (res1 = pre-activation term, if any)
-        r = launch_fcn12(a, st);
-        if (r == HCF_OK && prof) prof_events[prof_used].kind = 5;
-        if (r == HCF_ERR_UNSUPPORTED && res1.p) { fail(HCF_ERR_STATE, "internal: pre-activation term without the fcn12 kernel"); return; }
-      }
-      if (r == HCF_ERR_UNSUPPORTED) r = launch_conv_f16x3(a, cv.taps, st);
-      if (r == HCF_ERR_UNSUPPORTED && cv.taps == 1) { a.wpack = cv.wpack; r = launch_conv(a, cv.taps, st); }      // views the one-tap form does not take
-    } else {
-      r = launch_conv(a, cv.taps, st);
-    }
+    if (pre && r == HCF_ERR_UNSUPPORTED) { fail(HCF_ERR_STATE, "internal: pre-activation term without the fcn12 kernel"); return; }
+    if (r == HCF_OK && prof && rt.form == CONV_WINO) prof_events[prof_used].kind = w4f ? 6 : (fat && fat->pre) ? 7 : 4;
+    if (r == HCF_OK && prof && rt.form == CONV_FCN12) prof_events[prof_used].kind = 5;
     if (prof) {
       hipEventRecord(prof_events[prof_used].e1, st);
       prof_used++;

@@ -697,7 +697,7 @@
   // Winograd form where the caller wants that tried first, else null -- unit bias and scale, no activation, into `out` (`acc`: added
   // to it through the residual slot) on stream `s`. f16x3 backward: the scaled kernels, `in_max` = the slot of max |src|; the exact
   // kernel where they refuse. `k` non-null: the caller wants the epilogue backward of k->prev, whose dL/dy `out` then is (no other
-  // writer: plain store), done in this launch's epilogue. Forms in order: fused Winograd, fused scaled, Winograd, scaled, exact.
+  // writer: plain store), done in this launch's epilogue. Forms in order: fused Winograd, fused scaled, Winograd, scaled (route_conv, twice), exact.
   // Returns the rows of partial sums a fused launch left in k->prev_part (= its grid); 0: not fused, k->prev's record does its own.
   int launch_dgrad(const View* src, int nsrc, int H, int W, int taps, const Conv::TPack& tp, const float* wino, View out, bool acc,
                    float* in_max, const ConvLink* k, hipStream_t s) {
@@ -713,33 +713,22 @@
     int lr_ = HCF_ERR_UNSUPPORTED, rows = 0;
     if (tape->bwd.f16 && tp.wpack16 && (taps == 9 || taps == 1) && rc == HCF_OK) {
       ConvArgs f = a;
-      f.wpack = tp.wpack16;
-      f.ovf = ovf_flag;
-      f.zeros = reinterpret_cast<const float*>(ovf_flag) + 16;
+      f.wpack = nullptr;
       f.in_max = in_max;
-      // the scaled forms of `c`; *grid (optional): the blocks of the one that answered
-      auto scaled = [&](const ConvArgs& c, int* grid) {
-        if (wino) {
-          ConvArgs wv = c;
-          wv.wpack = nullptr;
-          const int r = launch_conv_wino(wv, wino, s);
-          if (grid) *grid = conv_wino_grid(B_, H, W, 1);      // (the fused epilogue backward: the 32-channel kernel only)
-          if (r != HCF_ERR_UNSUPPORTED) return r;
-        }
-        if (grid) *grid = conv_tile_blocks(B_, H, W);
-        return launch_conv_f16x3(c, taps, s);
-      };
+      // the scaled forms only (route_conv, hcf_conv_route.hip): the exact kernel below runs on `a`
+      const ConvPacks pk = {nullptr, tp.wpack16, wino, nullptr, nullptr, ovf_flag};
+      const unsigned scaled = 1u << CONV_WINO | 1u << CONV_F16X3;
       if (k) {
         ConvArgs fb = f;
         fb.res1 = mkview(nullptr, 0, 0, 0); fb.rs1 = 0.f;
         fb.fb_y = k->prev_y; fb.fb_act = k->prev->act; fb.fb_part = k->prev_part; fb.fb_max = k->prev_gmax;
         fb.fb_max2 = k->rdb ? k->gmax2 + k->m - 1 : nullptr;
         if (!k->prev->lkey.empty()) { fb.fb_scale = k->prev->scale; fb.fb_zy = 1; }      // (no logs key: the scale array is all ones)
-        int grid = 0;
-        lr_ = scaled(fb, &grid);
-        if (lr_ == HCF_OK) rows = grid;
+        const ConvRoute rt = route_conv(fb, pk, taps, scaled, s);
+        lr_ = rt.status;      // (the fused epilogue backward in Winograd form: the 32-channel kernel only)
+        if (lr_ == HCF_OK) rows = rt.form == CONV_WINO ? conv_wino_grid(B_, H, W, 1) : conv_tile_blocks(B_, H, W);
       }
-      if (lr_ == HCF_ERR_UNSUPPORTED) lr_ = scaled(f, nullptr);
+      if (lr_ == HCF_ERR_UNSUPPORTED) lr_ = route_conv(f, pk, taps, scaled, s).status;
     }
     if (lr_ == HCF_ERR_UNSUPPORTED) { HCF_LAUNCH(launch_conv(a, taps, s)); }
     else if (lr_ != HCF_OK) fail(lr_, "data-gradient conv launch failed");

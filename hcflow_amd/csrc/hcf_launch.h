@@ -60,4 +60,28 @@ WgradPlan plan_conv_wgrad(const WgradArgs& a);
 
 long long wino_units(int B, int H, int W, int ntile_n);      // units a Winograd launch walks (hcf_conv_wino.hip)
 
+// ---- which kernel family a conv call takes (hcf_conv_route.hip) ----
+// The one place that knows the order: the engine's forward and data-gradient convs, the per-op entries of hcf_ops.hip and the auxiliary
+// nets' hcf_aux_conv2d all launch through route_conv. What differs between callers arrives as a null pack or a cleared `allow` bit.
+enum ConvForm { CONV_NONE = -1, CONV_WINO = 0, CONV_FCN12 = 1, CONV_F16X3 = 2, CONV_EXACT = 3 };
+constexpr unsigned kAllowAll = 15u;                           // `allow`: bit (1 << form)
+struct ConvPacks {           // the weight packs a caller has for one conv; null: none, the forms that need it are not tried
+  const float* exact;        // fp32 pack (launch_conv)
+  const float* f16;          // f16x3 pack (launch_fcn12, launch_conv_f16x3)
+  const void* wino;          // Winograd pack (launch_conv_wino)
+  const float* f16_2;        // a fused 1x1 second layer: its f16x3 pack ... (these two pointers, not ConvArgs::bias2 / scale2 / act2 which the
+                             // caller fills as well, are what tells the router that a second layer is fused)
+  const void* wino_frag2;    // ... and its fragment for the 64-channel Winograd kernel's epilogue
+  int* flag;                 // the f16 forms' range flag, 64 bytes of zeros 64 bytes behind it (-> ConvArgs::ovf, zeros)
+};
+struct ConvRoute {
+  int form, status;          // the last form tried (CONV_NONE: none was) and its answer; HCF_ERR_UNSUPPORTED: every form tried declined
+  unsigned fcn_grid; int fcn_tiles;      // CONV_FCN12 only: what launch_fcn12 reports
+};
+// The forms route_conv would try for the call, in order, without a launch (PURE, as the plans above); returns how many
+int conv_route_forms(const ConvArgs& a, const ConvPacks& p, int taps, unsigned allow, int forms[4]);
+// Tries them until one answers something other than HCF_ERR_UNSUPPORTED. `a` is complete but for what depends on the form -- wpack,
+// w2, wf1x1, ovf, zeros -- which each form patches into a copy that it hands on to the next
+ConvRoute route_conv(const ConvArgs& a, const ConvPacks& p, int taps, unsigned allow, hipStream_t st);
+
 }  // namespace hcf

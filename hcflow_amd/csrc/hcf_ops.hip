@@ -1,6 +1,7 @@
 // Per-op C-ABI entry points used by the unit parity tests (tests/test_gpu_ops.py). They wrap the
 // same kernels the engine launches, on caller-provided NCHW device tensors; temporaries are
-// hipMalloc'ed per call (test path, not the hot path).
+// hipMalloc'ed per call (test path, not the hot path). The conv entries build host packs and launch
+// through route_conv (hcf_conv_route.hip), the engine's own router, so they take the kernel it takes.
 #include <math.h>
 #include <string.h>
 
@@ -39,39 +40,6 @@ struct Tmp {
   }
 };
 
-// pack + launch with the process-wide op precision; returns HCF_ERR_* (f16x3: also checks the range flag)
-static int pack_and_launch(Tmp& t, ConvArgs& a, const float* w, int cin, int cout, int k, const int* srcs, int n_src,
-                           hipStream_t st, int iters = 1) {
-  std::vector<float> pk;
-  int nchunk = 0, npad = 0;
-  const bool f16 = (g_op_precision == PREC_F16X3) && cout <= 64 && k == 3;
-  if (f16) {
-    if (!pack_conv_weights_f16x3(w, cin, cout, k * k, srcs, n_src, pk, nchunk, npad)) return HCF_ERR_UNSUPPORTED;
-    a.ovf = (int*)t.dev(64);
-    if (a.ovf && hipMemsetAsync(a.ovf, 0, 256, st) != hipSuccess) return HCF_ERR_HIP;
-    a.zeros = reinterpret_cast<const float*>(a.ovf) + 16;
-  } else {
-    pack_conv_weights(w, cin, cout, k * k, srcs, n_src, pk, nchunk, npad);
-  }
-  a.wpack = t.up(pk);
-  a.nchunk = nchunk;
-  if (!t.ok) return HCF_ERR_NOMEM;
-  const float* wino = nullptr;             // eligible layers take the Winograd form, as in the engine (--ablate 256: off)
-  if (f16 && !(g_f16x3_ablation & kAblNoWino)) {
-    std::vector<float> pkw;
-    if (pack_conv_weights_wino(w, cin, cout, srcs, n_src, pkw)) wino = t.up(pkw);
-    if (!t.ok) return HCF_ERR_NOMEM;
-  }
-  int rc = HCF_OK;
-  for (int i = 0; i < iters && rc == HCF_OK; ++i) {
-    rc = HCF_ERR_UNSUPPORTED;
-    if (wino) rc = launch_conv_wino(a, wino, st);
-    if (rc == HCF_ERR_UNSUPPORTED) rc = f16 ? launch_conv_f16x3(a, k * k, st) : launch_conv(a, k * k, st);
-  }
-  return rc;
-}
-
-
 static View nhwc_from_nchw(Tmp& t, const float* x, int B, int C, int H, int W, hipStream_t st, int& rc) {
   float* p = t.dev((size_t)B * H * W * ru4(C));
   View v = mkview(p, ru4(C), 0, C);
@@ -80,6 +48,134 @@ static View nhwc_from_nchw(Tmp& t, const float* x, int B, int C, int H, int W, h
   const int r = launch_nchw_to_nhwc(x, v, B, C, H, W, st);
   if (r != HCF_OK) rc = r;
   return v;
+}
+
+// ---- the shared pieces of the conv entries: arguments, host packs, the plan in info[], the range flag --------------------------
+static inline int ru32(int c) { return (c + 31) / 32 * 32; }
+static float* table(Tmp& t, const float* v, int n, int npad, float fill) {
+  std::vector<float> h(npad, fill);
+  for (int c = 0; c < n && v; ++c) h[c] = v[c];
+  return t.up(h);
+}
+
+// the process-wide op precision takes the f16 forms for convs of <= 64 output channels
+static bool op_f16(int cout) { return g_op_precision == PREC_F16X3 && cout <= 64; }
+
+// NCHW source tensors of a conv on [B, H, W] staged as NHWC views (source i at H >> up, W >> up)
+static void stage_sources(Tmp& t, const float* const* src, const int32_t* src_c, const int32_t* src_up, int n_src, int B, int H, int W,
+                          View* dst, int* srcs, int& cin, hipStream_t st, int& rc) {
+  cin = 0;
+  for (int i = 0; i < n_src; ++i) {
+    const int up = src_up ? src_up[i] : 0;
+    dst[i] = nhwc_from_nchw(t, src[i], B, src_c[i], H >> up, W >> up, st, rc);
+    dst[i].up = up;
+    srcs[i] = src_c[i];
+    cin += src_c[i];
+  }
+}
+
+// The arguments of one conv on [B, H, W]: the sources (unused slots repeat source 0), bias / scale tables of cout entries padded to
+// 32s (null: zeros / ones), the out view, no residuals, and -- f16: the call may take an f16 form -- the range flag with its zero
+// page (a.ovf, a.zeros and pk.flag). pk starts empty: conv_packs fills it.
+static int conv_call(Tmp& t, ConvArgs& a, ConvPacks& pk, const View* src, int n_src, int B, int H, int W, const float* bias,
+                     const float* scale, int cout, int act, View out, bool f16, hipStream_t st) {
+  memset(&a, 0, sizeof(a));
+  memset(&pk, 0, sizeof(pk));
+  for (int i = 0; i < kMaxSrc; ++i) a.src[i] = src[i < n_src ? i : 0];
+  a.nsrc = n_src;
+  a.B = B; a.H = H; a.W = W;
+  a.bias = table(t, bias, cout, ru32(cout), 0.f);
+  a.scale = table(t, scale, cout, ru32(cout), 1.f);
+  a.act = act;
+  a.out = out;
+  a.res1 = mkview(nullptr, 0, 0, 0);
+  a.res2 = mkview(nullptr, 0, 0, 0);
+  if (f16) {
+    a.ovf = pk.flag = (int*)t.dev(64);
+    if (a.ovf && hipMemsetAsync(a.ovf, 0, 256, st) != hipSuccess) return HCF_ERR_HIP;
+    a.zeros = reinterpret_cast<const float*>(a.ovf) + 16;
+  }
+  return t.ok ? HCF_OK : HCF_ERR_NOMEM;
+}
+
+// Host packs of w [cout][cin][k][k] in device memory, for the forms of `allow` (hcf_launch.h) -- f16: the f16x3 pack
+// (HCF_ERR_UNSUPPORTED: a weight beyond its range), the Winograd pack where the layer has one (wino_min: from that many input
+// channels on, -1 = the engine's rule) and the exact pack a 1x1 falls back to; else the exact pack alone. a.wpack = the first of them.
+static int conv_packs(Tmp& t, ConvArgs& a, ConvPacks& pk, const float* w, int cin, int cout, int taps, const int* srcs, int n_src,
+                      bool f16, unsigned allow, int wino_min = -1) {
+  std::vector<float> h16, hw, h;
+  int npad = 0;
+  if (f16) {
+    if (!pack_conv_weights_f16x3(w, cin, cout, taps, srcs, n_src, h16, a.nchunk, npad)) return HCF_ERR_UNSUPPORTED;
+    a.wpack = pk.f16 = t.up(h16);
+    if (taps == 9 && (allow & 1u << CONV_WINO) && pack_conv_weights_wino(w, cin, cout, srcs, n_src, hw, wino_min)) pk.wino = t.up(hw);
+  }
+  if ((allow & 1u << CONV_EXACT) && (!f16 || taps == 1)) {
+    pack_conv_weights(w, cin, cout, taps, srcs, n_src, h, a.nchunk, npad);
+    pk.exact = t.up(h);
+    if (!f16) a.wpack = pk.exact;
+  }
+  return t.ok ? HCF_OK : HCF_ERR_NOMEM;
+}
+
+// the plan launch_conv_f16x3 dispatched from -> info[0] = 1, info[1 .. nf] (include/hcflow.h: 12 fields for hcf_op_fcn12 and
+// hcf_op_conv2d_step_inverse, 14 for the view entries)
+static F16x3Plan info_f16x3(const ConvArgs& a, int taps, int nf, int32_t* info) {
+  const F16x3Plan p = plan_conv_f16x3(a, taps);
+  const int32_t v[14] = {p.status, p.v.ntb, p.v.vec, p.v.up, p.v.fuse2, p.v.tailc, p.v.th, p.v.scaled, p.v.k1, p.v.n16,
+                         (int32_t)p.grid, (int32_t)p.block, p.vec_epi, p.strip_w};
+  info[0] = 1;
+  for (int i = 0; i < nf; ++i) info[1 + i] = v[i];
+  return p;
+}
+
+// stream done, then the range flag (null: an exact call): HCF_ERR_UNSUPPORTED when an input left the f16 range, the caller must use
+// the exact kernel (info, where given: info[15] = the flag word)
+static int conv_finish(const int* flag, int32_t* info, hipStream_t st) {
+  if (hipStreamSynchronize(st) != hipSuccess) return HCF_ERR_HIP;
+  int h = 0;
+  if (flag && hipMemcpy(&h, flag, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return HCF_ERR_HIP;
+  if (flag && info) info[15] = h;
+  return h ? HCF_ERR_UNSUPPORTED : HCF_OK;
+}
+
+// host packs + launch of a conv2d / hcf_bench_conv call: the f16 forms for 3x3 convs only
+static int pack_and_launch(Tmp& t, ConvArgs& a, ConvPacks& pk, const float* w, int cin, int cout, int k, const int* srcs, int n_src,
+                           hipStream_t st) {
+  const int rc = conv_packs(t, a, pk, w, cin, cout, k * k, srcs, n_src, op_f16(cout) && k == 3, kAllowAll);
+  return rc != HCF_OK ? rc : route_conv(a, pk, k * k, kAllowAll, st).status;
+}
+
+// *slot (zero-initialised by the caller) = max |x| over the source windows, as the running maximum of the engine's backward is
+static int sources_absmax(const View* src, int n_src, int B, int H, int W, float* slot, hipStream_t st) {
+  int rc = HCF_OK;
+  for (int i = 0; i < n_src && rc == HCF_OK; ++i) rc = launch_absmax(src[i], B, H >> src[i].up, W >> src[i].up, slot, st);
+  return rc;
+}
+
+// a.in_max (the scaled f16x3 forms) = a fresh slot with max |x| over the sources
+static int conv_in_max(Tmp& t, ConvArgs& a, hipStream_t st) {
+  float* m = t.dev(1);
+  if (!m) return HCF_ERR_NOMEM;
+  if (hipMemsetAsync(m, 0, sizeof(float), st) != hipSuccess) return HCF_ERR_HIP;
+  a.in_max = m;
+  return sources_absmax(a.src, a.nsrc, a.B, a.H, a.W, m, st);
+}
+
+// The f16 weight gradient's ranges: g is scaled by a power of two from max |g| (wa.g_max), X is split without a scale -- an |x| beyond
+// the f16 range (nothing range-checked this caller's tensor) would turn the hi part into inf, so wa.g_max stays null and the fp32
+// kernel takes such inputs. Synchronises.
+static int wgrad_f16_range(Tmp& t, WgradArgs& wa, hipStream_t st) {
+  float* gm = t.dev(2);
+  if (!gm) return HCF_ERR_NOMEM;
+  if (hipMemsetAsync(gm, 0, 2 * sizeof(float), st) != hipSuccess) return HCF_ERR_HIP;
+  int rc = launch_absmax(wa.g, wa.B, wa.H, wa.W, gm, st);
+  if (rc == HCF_OK) rc = sources_absmax(wa.src, wa.nsrc, wa.B, wa.H, wa.W, gm + 1, st);
+  float xmax = 0.f;
+  if (hipMemcpyAsync(&xmax, gm + 1, sizeof(float), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+    return HCF_ERR_HIP;
+  if (rc == HCF_OK && xmax < 65504.f) wa.g_max = gm;           // NaN / inf compare false -> fp32 kernel
+  return rc;
 }
 
 static bool invert64(const float* Wm, int n, std::vector<float>& out_padded, int M) {
@@ -131,46 +227,22 @@ int hcf_op_conv2d(const float* const* src, const int32_t* src_c, const int32_t* 
   Tmp t;
   int rc = HCF_OK;
   ConvArgs a;
-  memset(&a, 0, sizeof(a));
-  int cin = 0;
-  int srcs[kMaxSrc];
-  for (int i = 0; i < n_src; ++i) {
-    const int up = src_up ? src_up[i] : 0;
-    a.src[i] = nhwc_from_nchw(t, src[i], B, src_c[i], H >> up, W >> up, st, rc);
-    a.src[i].up = up;
-    srcs[i] = src_c[i];
-    cin += src_c[i];
-  }
-  for (int i = n_src; i < kMaxSrc; ++i) a.src[i] = a.src[0];
-  a.nsrc = n_src;
-  a.B = B; a.H = H; a.W = W;
-  const int npad = ((cout + 31) / 32) * 32;
-  std::vector<float> hb(npad, 0.f), hs(npad, 1.f);
-  for (int n = 0; n < cout; ++n) {
-    if (bias) hb[n] = bias[n];
-    if (scale) hs[n] = scale[n];
-  }
-  a.bias = t.up(hb);
-  a.scale = t.up(hs);
-  a.act = act;
-  float* o = t.dev((size_t)B * H * W * ru4(cout));
-  a.out = mkview(o, ru4(cout), 0, cout);
-  a.res1 = mkview(nullptr, 0, 0, 0);
-  a.res2 = mkview(nullptr, 0, 0, 0);
+  ConvPacks pk;
+  View sv[kMaxSrc];
+  int cin = 0, srcs[kMaxSrc];
+  stage_sources(t, src, src_c, src_up, n_src, B, H, W, sv, srcs, cin, st, rc);
+  const View ov = mkview(t.dev((size_t)B * H * W * ru4(cout)), ru4(cout), 0, cout);
+  const int rb = conv_call(t, a, pk, sv, n_src, B, H, W, bias, scale, cout, act, ov, op_f16(cout) && k == 3, st);
   if (res1) { a.res1 = nhwc_from_nchw(t, res1, B, cout, H, W, st, rc); a.rs1 = rs1; }
   if (res2) { a.res2 = nhwc_from_nchw(t, res2, B, cout, H, W, st, rc); a.rs2 = rs2; }
   if (!t.ok) return HCF_ERR_NOMEM;
+  if (rc == HCF_OK) rc = rb;
   if (rc != HCF_OK) return rc;
-  rc = pack_and_launch(t, a, w, cin, cout, k, srcs, n_src, st);
+  rc = pack_and_launch(t, a, pk, w, cin, cout, k, srcs, n_src, st);
   if (rc != HCF_OK) return rc;
   rc = launch_nhwc_to_nchw(a.out, out, B, cout, H, W, 0, st);
-  if (hipStreamSynchronize(st) != hipSuccess) return HCF_ERR_HIP;
-  if (a.ovf) {
-    int h = 0;
-    if (hipMemcpy(&h, a.ovf, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return HCF_ERR_HIP;
-    if (h) return HCF_ERR_UNSUPPORTED;      // input beyond the f16 range: caller must use the exact kernel
-  }
-  return rc;
+  const int fin = conv_finish(pk.flag, nullptr, st);
+  return fin != HCF_OK ? fin : rc;
 }
 
 // Transposed weights for the data gradient of source window [off, off + n) of a conv with weight w [cout][cin][k][k]:
@@ -210,19 +282,10 @@ int hcf_op_conv2d_backward(const float* const* src, const int32_t* src_c, const 
         std::vector<float> wt;
         transpose_weights(w, cin, cout, taps, off + c0, nb, wt);
         ConvArgs a;
-        memset(&a, 0, sizeof(a));
-        a.src[0] = gv; a.src[1] = gv; a.src[2] = gv;
-        a.nsrc = 1;
-        a.B = B; a.H = H; a.W = W;
-        std::vector<float> hb(64, 0.f), hs(64, 1.f);
-        a.bias = t.up(hb);
-        a.scale = t.up(hs);
-        a.act = ACT_NONE;
-        a.out = mkview(full, ru4(n), c0, nb);
-        a.res1 = mkview(nullptr, 0, 0, 0);
-        a.res2 = mkview(nullptr, 0, 0, 0);
+        ConvPacks pk;
         int one = cout;
-        rc = pack_and_launch(t, a, wt.data(), cout, nb, k, &one, 1, st);
+        rc = conv_call(t, a, pk, &gv, 1, B, H, W, nullptr, nullptr, nb, ACT_NONE, mkview(full, ru4(n), c0, nb), op_f16(nb) && k == 3, st);
+        if (rc == HCF_OK) rc = pack_and_launch(t, a, pk, wt.data(), cout, nb, k, &one, 1, st);
       }
       if (rc != HCF_OK) break;
       View fv = mkview(full, ru4(n), 0, n);
@@ -242,11 +305,8 @@ int hcf_op_conv2d_backward(const float* const* src, const int32_t* src_c, const 
   if (rc == HCF_OK && dw) {
     WgradArgs wa;
     memset(&wa, 0, sizeof(wa));
-    for (int i = 0; i < n_src; ++i) {
-      const int up = src_up ? src_up[i] : 0;
-      wa.src[i] = nhwc_from_nchw(t, src[i], B, src_c[i], H >> up, W >> up, st, rc);
-      wa.src[i].up = up;
-    }
+    int srcs[kMaxSrc];
+    stage_sources(t, src, src_c, src_up, n_src, B, H, W, wa.src, srcs, cin, st, rc);
     wa.nsrc = n_src;
     wa.g = gv;
     wa.B = B; wa.H = H; wa.W = W; wa.taps = taps;
@@ -257,21 +317,7 @@ int hcf_op_conv2d_backward(const float* const* src, const int32_t* src_c, const 
     wa.part_cap = conv_wgrad_scratch_floats(wa);
     wa.part = t.dev(wa.part_cap);
     if (!t.ok) return HCF_ERR_NOMEM;
-    if (rc == HCF_OK && g_op_precision == PREC_F16X3) {        // f16 matrix cores: g is scaled by a power of two from max |g|
-      float* gm = t.dev(2);
-      if (!t.ok) return HCF_ERR_NOMEM;
-      if (hipMemsetAsync(gm, 0, 2 * sizeof(float), st) != hipSuccess) return HCF_ERR_HIP;
-      rc = launch_absmax(gv, B, H, W, gm, st);
-      // X is split without a scale: an |x| beyond the f16 range (nothing range-checked this caller's tensor) would turn the
-      // hi part into inf -> the fp32 weight-gradient kernel takes such inputs
-      for (int i = 0; i < n_src && rc == HCF_OK; ++i)
-        rc = launch_absmax(wa.src[i], B, H >> wa.src[i].up, W >> wa.src[i].up, gm + 1, st);
-      float xmax = 0.f;
-      if (rc == HCF_OK && (hipMemcpyAsync(&xmax, gm + 1, sizeof(float), hipMemcpyDeviceToHost, st) != hipSuccess ||
-                           hipStreamSynchronize(st) != hipSuccess))
-        rc = HCF_ERR_HIP;
-      if (xmax < 65504.f) wa.g_max = gm;           // NaN / inf compare false -> fp32 kernel
-    }
+    if (rc == HCF_OK && g_op_precision == PREC_F16X3) rc = wgrad_f16_range(t, wa, st);      // f16 matrix cores
     if (rc == HCF_OK) rc = launch_conv_wgrad(wa, st);
     if (rc == HCF_OK && hipMemcpyAsync(dw, wa.dw, nw * sizeof(float), hipMemcpyDeviceToHost, st) != hipSuccess) rc = HCF_ERR_HIP;
   }
@@ -344,6 +390,21 @@ int hcf_debug_conv_plan(const int32_t* in, int32_t n_in, int64_t* out, int32_t n
                                          q.strip_magic, (int64_t)q.scratch_floats, q.nbx};
   for (int i = 0; i < n_out; ++i) out[i] = in[0] == 0 ? conv[i] : wgrad[i];
   return HCF_OK;
+}
+
+// the forms route_conv would try, in order, without a launch (layout: include/hcflow.h)
+int hcf_debug_conv_route(int32_t taps, int32_t packs, int32_t tail, int32_t allow, int32_t* forms, int32_t n_forms) {
+  if (!forms || n_forms != 4 || (taps != 1 && taps != 9) || packs < 0 || packs > 31 || allow < 0 || allow > 15) return HCF_ERR_ARG;
+  ConvArgs c;
+  memset(&c, 0, sizeof(c));
+  c.tC = tail ? 12 : 0;
+  const ConvPacks p = {(packs & 1) ? plan_case_ptr(1, 1) : nullptr, (packs & 2) ? plan_case_ptr(2, 1) : nullptr,
+                       (packs & 4) ? plan_case_ptr(3, 1) : nullptr, (packs & 8) ? plan_case_ptr(4, 1) : nullptr,
+                       (packs & 16) ? plan_case_ptr(5, 1) : nullptr, nullptr};
+  int f[4] = {CONV_NONE, CONV_NONE, CONV_NONE, CONV_NONE};
+  const int n = conv_route_forms(c, p, taps, (unsigned)allow, f);
+  for (int i = 0; i < 4; ++i) forms[i] = f[i];
+  return n;
 }
 
 int hcf_op_set_precision(int32_t mode) {
@@ -847,57 +908,7 @@ int hcf_op_axpy_job(const float* x, float* y, int32_t n, float alpha, const floa
   return rc;
 }
 
-}  // extern "C"
-
 // ---- the fused f16x3 conv launches of the inference path, one launch per call (tests/test_gpu_fused_convs.py) ----------
-namespace hcf {
-
-// the range flag + the zero page every f16x3 launch needs (as pack_and_launch)
-static int fused_flag(Tmp& t, ConvArgs& a, hipStream_t st) {
-  a.ovf = (int*)t.dev(64);
-  if (!a.ovf) return HCF_ERR_NOMEM;
-  if (hipMemsetAsync(a.ovf, 0, 256, st) != hipSuccess) return HCF_ERR_HIP;
-  a.zeros = reinterpret_cast<const float*>(a.ovf) + 16;
-  return HCF_OK;
-}
-
-// an f16x3 host pack in device memory; HCF_ERR_UNSUPPORTED: a weight beyond the pack's range
-static int fused_pack(Tmp& t, const float* w, int cin, int cout, int taps, const int* srcs, int n_src, const float*& dev, int& nchunk) {
-  std::vector<float> pk;
-  int npad = 0;
-  if (!pack_conv_weights_f16x3(w, cin, cout, taps, srcs, n_src, pk, nchunk, npad)) return HCF_ERR_UNSUPPORTED;
-  dev = t.up(pk);
-  return t.ok ? HCF_OK : HCF_ERR_NOMEM;
-}
-
-static float* fused_table(Tmp& t, const float* v, int n, int npad, float fill) {
-  std::vector<float> h(npad, fill);
-  for (int c = 0; c < n && v; ++c) h[c] = v[c];
-  return t.up(h);
-}
-
-// launch_conv_f16x3 with the plan it dispatches from written to info[1 .. 12] (include/hcflow.h: hcf_op_fcn12)
-static int fused_launch_f16x3(const ConvArgs& a, int32_t* info, hipStream_t st) {
-  const F16x3Plan p = plan_conv_f16x3(a, 9);
-  const int32_t v[12] = {p.status, p.v.ntb, p.v.vec, p.v.up, p.v.fuse2, p.v.tailc, p.v.th, p.v.scaled, p.v.k1, p.v.n16, (int32_t)p.grid, (int32_t)p.block};
-  info[0] = 1;
-  for (int i = 0; i < 12; ++i) info[1 + i] = v[i];
-  if (p.status != HCF_OK) return p.status;
-  return launch_conv_f16x3(a, 9, st);
-}
-
-// stream done, then the range flag: HCF_ERR_UNSUPPORTED when an input left the f16 range (info[15] = the flag word)
-static int fused_finish(const ConvArgs& a, int32_t* info, hipStream_t st) {
-  if (hipStreamSynchronize(st) != hipSuccess) return HCF_ERR_HIP;
-  int h = 0;
-  if (hipMemcpy(&h, a.ovf, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return HCF_ERR_HIP;
-  info[15] = h;
-  return h ? HCF_ERR_UNSUPPORTED : HCF_OK;
-}
-
-}  // namespace hcf
-
-extern "C" {
 
 int hcf_op_fcn12(const float* const* src, const int32_t* src_c, const int32_t* src_up, int32_t n_src, int32_t B, int32_t H,
                  int32_t W, const float* w1, const float* bias1, const float* scale1, const float* w2, const float* bias2,
@@ -913,48 +924,37 @@ int hcf_op_fcn12(const float* const* src, const int32_t* src_c, const int32_t* s
   Tmp t;
   int rc = HCF_OK;
   ConvArgs a;
-  memset(&a, 0, sizeof(a));
+  ConvPacks pk;
+  View sv[kMaxSrc];
   int cin = 0, srcs[kMaxSrc];
-  for (int i = 0; i < n_src; ++i) {
-    const int up = src_up ? src_up[i] : 0;
-    a.src[i] = nhwc_from_nchw(t, src[i], B, src_c[i], H >> up, W >> up, st, rc);
-    a.src[i].up = up;
-    srcs[i] = src_c[i];
-    cin += src_c[i];
-  }
-  for (int i = n_src; i < kMaxSrc; ++i) a.src[i] = a.src[0];
-  a.nsrc = n_src;
-  a.B = B; a.H = H; a.W = W;
-  a.bias = fused_table(t, bias1, 64, 64, 0.f);
-  a.scale = fused_table(t, scale1, 64, 64, 1.f);
-  a.bias2 = fused_table(t, bias2, 64, 64, 0.f);
-  a.scale2 = fused_table(t, scale2, 64, 64, 1.f);
-  a.act = ACT_RELU; a.act2 = ACT_RELU;
+  stage_sources(t, src, src_c, src_up, n_src, B, H, W, sv, srcs, cin, st, rc);
   const size_t nout = (size_t)B * H * W * 64;
   float* o = t.dev(nout);
-  a.out = mkview(o, 64, 0, 64);
-  a.res1 = mkview(nullptr, 0, 0, 0);
-  a.res2 = mkview(nullptr, 0, 0, 0);
-  if (pre) a.res1 = nhwc_from_nchw(t, pre, B, 64, H, W, st, rc);        // the pre-activation term travels as res1, as in the engine
+  const int rb = conv_call(t, a, pk, sv, n_src, B, H, W, bias1, scale1, 64, ACT_RELU, mkview(o, 64, 0, 64), true, st);
+  a.bias2 = table(t, bias2, 64, 64, 0.f);
+  a.scale2 = table(t, scale2, 64, 64, 1.f);
+  a.act2 = ACT_RELU;
+  if (pre) a.res1 = nhwc_from_nchw(t, pre, B, 64, H, W, st, rc);        // the pre-activation term travels as res1
   if (!t.ok) return HCF_ERR_NOMEM;
+  if (rc == HCF_OK) rc = rb;
   if (rc != HCF_OK) return rc;
   if (hipMemsetAsync(o, 0xff, nout * sizeof(float), st) != hipSuccess) return HCF_ERR_HIP;      // a pixel the launch skips reads NaN
-  if ((rc = fused_flag(t, a, st)) != HCF_OK) return rc;
-  int one = 64, nchunk2 = 0;
-  if ((rc = fused_pack(t, w1, cin, 64, 9, srcs, n_src, a.wpack, a.nchunk)) != HCF_OK) return rc;
-  if ((rc = fused_pack(t, w2, 64, 64, 1, &one, 1, a.w2, nchunk2)) != HCF_OK) return rc;
-  rc = HCF_ERR_UNSUPPORTED;
-  if (form == 0) {
-    unsigned grid = 0;
-    int ntiles = 0;
-    rc = launch_fcn12(a, st, &grid, &ntiles);
-    if (rc != HCF_ERR_UNSUPPORTED) {
-      info[0] = 0; info[1] = rc; info[11] = (int32_t)grid; info[12] = 256; info[13] = ntiles; info[14] = pre ? 1 : 0;
-    }
+  const unsigned allow = (form == 0 ? 1u << CONV_FCN12 : 0u) | 1u << CONV_F16X3;
+  if ((rc = conv_packs(t, a, pk, w1, cin, 64, 9, srcs, n_src, true, allow)) != HCF_OK) return rc;
+  std::vector<float> h2;
+  int one = 64, nchunk2 = 0, npad2 = 0;
+  if (!pack_conv_weights_f16x3(w2, 64, 64, 1, &one, 1, h2, nchunk2, npad2)) return HCF_ERR_UNSUPPORTED;
+  a.w2 = pk.f16_2 = t.up(h2);
+  if (!t.ok) return HCF_ERR_NOMEM;
+  const ConvRoute rt = route_conv(a, pk, 9, allow, st);
+  rc = rt.status;
+  if (rt.form == CONV_FCN12) {
+    info[0] = 0; info[1] = rc; info[11] = (int32_t)rt.fcn_grid; info[12] = 256; info[13] = rt.fcn_tiles; info[14] = pre ? 1 : 0;
+  } else {
+    info_f16x3(a, 9, 12, info);
   }
-  if (rc == HCF_ERR_UNSUPPORTED) rc = fused_launch_f16x3(a, info, st);
   if (rc != HCF_OK) { hipStreamSynchronize(st); return rc; }      // (the temporaries are freed behind the staging launches)
-  if ((rc = fused_finish(a, info, st)) != HCF_OK) return rc;
+  if ((rc = conv_finish(pk.flag, info, st)) != HCF_OK) return rc;
   rc = launch_nhwc_to_nchw(a.out, out, B, 64, H, W, 0, st);
   if (hipStreamSynchronize(st) != hipSuccess) return HCF_ERR_HIP;
   return rc;
@@ -973,19 +973,12 @@ int hcf_op_conv2d_step_inverse(const float* h2, int32_t hid, const float* w3, co
   Tmp t;
   int rc = HCF_OK;
   ConvArgs a;
-  memset(&a, 0, sizeof(a));
-  a.src[0] = nhwc_from_nchw(t, h2, B, hid, H, W, st, rc);
-  a.src[1] = a.src[0]; a.src[2] = a.src[0];
-  a.nsrc = 1;
-  a.B = B; a.H = H; a.W = W;
-  const int npad = ((f_out + 31) / 32) * 32;
-  a.bias = fused_table(t, bias3, f_out, npad, 0.f);
-  a.scale = fused_table(t, scale3, f_out, npad, 1.f);
-  a.act = ACT_NONE;
-  a.out = mkview(t.dev((size_t)B * H * W * ru4(f_out)), ru4(f_out), 0, f_out);      // (sc.hout of the engine: the fused launch leaves it alone)
-  a.res1 = mkview(nullptr, 0, 0, 0);
-  a.res2 = mkview(nullptr, 0, 0, 0);
-  // the tail fields, as run_conv fills them from the step's StepArgs (in place on z)
+  ConvPacks pk;
+  const View hv = nhwc_from_nchw(t, h2, B, hid, H, W, st, rc);
+  // (out: sc.hout of the engine, the fused launch leaves it alone)
+  const int rb = conv_call(t, a, pk, &hv, 1, B, H, W, bias3, scale3, f_out, ACT_NONE,
+                           mkview(t.dev((size_t)B * H * W * ru4(f_out)), ru4(f_out), 0, f_out), true, st);
+  // the tail fields of the step's StepArgs (in place on z)
   a.tz = nhwc_from_nchw(t, z, B, C, H, W, st, rc);
   a.tzo = a.tz;
   std::vector<float> hb(M, 0.f), hm(M, 0.f);
@@ -1004,14 +997,15 @@ int hcf_op_conv2d_step_inverse(const float* h2, int32_t hid, const float* w3, co
     a.tzpad_n = zpad_n;
   }
   if (!t.ok) return HCF_ERR_NOMEM;
+  if (rc == HCF_OK) rc = rb;
   if (rc != HCF_OK) return rc;
   if (a.tzpad && hipMemsetAsync(a.tzpad, 0xff, npadz * sizeof(float), st) != hipSuccess) return HCF_ERR_HIP;
-  if ((rc = fused_flag(t, a, st)) != HCF_OK) return rc;
   int one = hid;
-  if ((rc = fused_pack(t, w3, hid, f_out, 9, &one, 1, a.wpack, a.nchunk)) != HCF_OK) return rc;
-  rc = fused_launch_f16x3(a, info, st);
+  if ((rc = conv_packs(t, a, pk, w3, hid, f_out, 9, &one, 1, true, 1u << CONV_F16X3)) != HCF_OK) return rc;
+  rc = route_conv(a, pk, 9, 1u << CONV_F16X3, st).status;
+  info_f16x3(a, 9, 12, info);
   if (rc != HCF_OK) { hipStreamSynchronize(st); return rc; }
-  if ((rc = fused_finish(a, info, st)) != HCF_OK) return rc;
+  if ((rc = conv_finish(pk.flag, info, st)) != HCF_OK) return rc;
   rc = launch_nhwc_to_nchw(a.tzo, out_z, B, C, H, W, 0, st);
   if (rc == HCF_OK && out_zpad) rc = launch_nhwc_to_nchw(mkview(a.tzpad, 16, 0, 16), out_zpad, B, 16, H, W, 0, st);
   if (hipStreamSynchronize(st) != hipSuccess) return HCF_ERR_HIP;
@@ -1043,13 +1037,6 @@ static bool views_of_sources(const hcf_view* src, int n_src, int H, int W, View*
   return true;
 }
 
-// *slot (zero-initialised by the caller) = max |x| over the source windows, as the running maximum of the engine's backward is
-static int sources_absmax(const View* src, int n_src, int B, int H, int W, float* slot, hipStream_t st) {
-  int rc = HCF_OK;
-  for (int i = 0; i < n_src && rc == HCF_OK; ++i) rc = launch_absmax(src[i], B, H >> src[i].up, W >> src[i].up, slot, st);
-  return rc;
-}
-
 }  // namespace hcf
 
 extern "C" {
@@ -1061,82 +1048,37 @@ int hcf_op_conv2d_views(const hcf_view* src, int32_t n_src, int32_t B, int32_t H
   if (!view_ok(out, 0) || out->n > 96) return HCF_ERR_ARG;
   if ((res1 && (!view_ok(res1, 0) || res1->n != out->n)) || (res2 && (!view_ok(res2, 0) || res2->n != out->n))) return HCF_ERR_ARG;
   ConvArgs a;
-  memset(&a, 0, sizeof(a));
+  ConvPacks pk;
+  View sv[kMaxSrc];
   int cin = 0, srcs[kMaxSrc];
-  if (!views_of_sources(src, n_src, H, W, a.src, srcs, cin)) return HCF_ERR_ARG;
+  if (!views_of_sources(src, n_src, H, W, sv, srcs, cin)) return HCF_ERR_ARG;
   for (int i = 0; i < 16; ++i) info[i] = 0;
   hipStream_t st = (hipStream_t)stream;
   Tmp t;
-  int rc = HCF_OK;
-  a.nsrc = n_src;
-  a.B = B; a.H = H; a.W = W;
   const int cout = out->n, taps = k * k;
-  const int npad = ((cout + 31) / 32) * 32;
-  a.bias = fused_table(t, bias, cout, npad, 0.f);
-  a.scale = fused_table(t, scale, cout, npad, 1.f);
-  a.act = act;
-  a.out = as_view(out);
+  const bool f16 = op_f16(cout);      // (a stand-alone 1x1 too, where the f16x3 plan accepts it)
+  int rc = conv_call(t, a, pk, sv, n_src, B, H, W, bias, scale, cout, act, as_view(out), f16, st);
+  if (rc != HCF_OK) return rc;
   a.res1 = as_view(res1); a.rs1 = res1 ? rs1 : 0.f;
   a.res2 = as_view(res2); a.rs2 = res2 ? rs2 : 0.f;
-  if (!t.ok) return HCF_ERR_NOMEM;
-  bool f16 = g_op_precision == PREC_F16X3 && cout <= 64;
-  if (f16) {
-    if ((rc = fused_flag(t, a, st)) != HCF_OK) return rc;
-    if (scaled) {
-      float* m = t.dev(1);
-      if (!m) return HCF_ERR_NOMEM;
-      if (hipMemsetAsync(m, 0, sizeof(float), st) != hipSuccess) return HCF_ERR_HIP;
-      if ((rc = sources_absmax(a.src, n_src, B, H, W, m, st)) != HCF_OK) { hipStreamSynchronize(st); return rc; }
-      a.in_max = m;
-    }
-    // a stand-alone 1x1 conv the f16x3 plan refuses runs on the exact kernel, as in the engine
-    if (k == 1 && plan_conv_f16x3(a, 1).status == HCF_ERR_UNSUPPORTED) {
-      f16 = false;
-      a.ovf = nullptr; a.zeros = nullptr; a.in_max = nullptr;
-    }
-  }
-  std::vector<float> pk;
-  int nchunk = 0, np = 0;
-  if (f16) {
-    if (!pack_conv_weights_f16x3(w, cin, cout, taps, srcs, n_src, pk, nchunk, np)) return HCF_ERR_UNSUPPORTED;
+  if (f16 && scaled && (rc = conv_in_max(t, a, st)) != HCF_OK) { hipStreamSynchronize(st); return rc; }
+  if ((rc = conv_packs(t, a, pk, w, cin, cout, taps, srcs, n_src, f16, kAllowAll)) != HCF_OK) { hipStreamSynchronize(st); return rc; }
+  // (a stand-alone 1x1 the f16x3 plan refuses reaches the exact kernel with ovf, zeros and in_max still set, as in the engine: that
+  //  kernel reads none of them, and the flag nobody raised is read into info[15] as 0)
+  const ConvRoute rt = route_conv(a, pk, taps, kAllowAll, st);
+  rc = rt.status;
+  if (rt.form == CONV_WINO) {
+    info[0] = cout == 64 ? 3 : 2; info[1] = rc; info[11] = conv_wino_grid(B, H, W, cout / 32);
+  } else if (rt.form == CONV_F16X3) {
+    info_f16x3(a, taps, 14, info);
   } else {
-    pack_conv_weights(w, cin, cout, taps, srcs, n_src, pk, nchunk, np);
-  }
-  a.wpack = t.up(pk);
-  a.nchunk = nchunk;
-  if (!t.ok) return HCF_ERR_NOMEM;
-  rc = HCF_ERR_UNSUPPORTED;
-  if (f16 && k == 3 && !(g_f16x3_ablation & kAblNoWino)) {      // eligible layers take the Winograd form, as in the engine
-    std::vector<float> pkw;
-    const float* wino = pack_conv_weights_wino(w, cin, cout, srcs, n_src, pkw) ? t.up(pkw) : nullptr;
-    if (!t.ok) return HCF_ERR_NOMEM;
-    if (wino) rc = launch_conv_wino(a, wino, st);
-    if (rc != HCF_ERR_UNSUPPORTED) {
-      info[0] = cout == 64 ? 3 : 2; info[1] = rc; info[11] = conv_wino_grid(B, H, W, cout / 32);
-    }
-  }
-  if (rc == HCF_ERR_UNSUPPORTED && f16) {
-    const F16x3Plan p = plan_conv_f16x3(a, taps);
-    const int32_t v[14] = {p.status, p.v.ntb, p.v.vec, p.v.up, p.v.fuse2, p.v.tailc, p.v.th, p.v.scaled, p.v.k1, p.v.n16,
-                           (int32_t)p.grid, (int32_t)p.block, p.vec_epi, p.strip_w};
-    info[0] = 1;
-    for (int i = 0; i < 14; ++i) info[1 + i] = v[i];
-    rc = p.status != HCF_OK ? p.status : launch_conv_f16x3(a, taps, st);
-  } else if (rc == HCF_ERR_UNSUPPORTED) {
     const ExactPlan p = plan_conv_exact(a, taps);
     info[0] = 0; info[1] = p.status; info[2] = p.vec; info[3] = p.vec_epi; info[4] = p.nt;
     info[11] = (int32_t)p.grid; info[12] = 256; info[13] = p.vec_epi;
-    rc = p.status != HCF_OK ? p.status : launch_conv(a, taps, st);
   }
-  if (hipStreamSynchronize(st) != hipSuccess) return HCF_ERR_HIP;      // (also behind a refusal: the temporaries are freed behind the staging work)
-  if (rc != HCF_OK) return rc;
-  if (a.ovf) {
-    int h = 0;
-    if (hipMemcpy(&h, a.ovf, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return HCF_ERR_HIP;
-    info[15] = h;
-    if (h) return HCF_ERR_UNSUPPORTED;      // an input beyond the f16 range
-  }
-  return HCF_OK;
+  // (a refusal synchronises too: the temporaries are freed behind the staging work)
+  if (rc != HCF_OK) return hipStreamSynchronize(st) != hipSuccess ? HCF_ERR_HIP : rc;
+  return conv_finish(pk.flag, info, st);
 }
 
 int hcf_op_conv2d_dgrad_fused_views(const hcf_view* src, int32_t n_src, int32_t B, int32_t H, int32_t W, const float* w, int32_t k,
@@ -1147,85 +1089,52 @@ int hcf_op_conv2d_dgrad_fused_views(const hcf_view* src, int32_t n_src, int32_t 
     return HCF_ERR_ARG;
   if (!view_ok(out, 0) || out->n > 64 || !view_ok(y, 0) || y->n != out->n || (want_zy && !sum_zy)) return HCF_ERR_ARG;
   ConvArgs a;
-  memset(&a, 0, sizeof(a));
+  ConvPacks pk;
+  View sv[kMaxSrc];
   int cin = 0, srcs[kMaxSrc];
-  if (!views_of_sources(src, n_src, H, W, a.src, srcs, cin)) return HCF_ERR_ARG;
+  if (!views_of_sources(src, n_src, H, W, sv, srcs, cin)) return HCF_ERR_ARG;
   for (int i = 0; i < n_src; ++i)
     if (src[i].up) return HCF_ERR_ARG;                   // a data gradient's sources are gradients at the output's size
   for (int i = 0; i < 18; ++i) info[i] = 0;
   if (g_op_precision != PREC_F16X3) return HCF_ERR_UNSUPPORTED;      // the fused form exists in f16x3 only
   hipStream_t st = (hipStream_t)stream;
   Tmp t;
-  int rc = HCF_OK;
   const int n = out->n, taps = k * k;
-  const int npad = ((n + 31) / 32) * 32;
   // launch_dgrad's arguments (hcf_engine_train.inc): unit bias and scale, no activation, plain store, the fused epilogue backward
-  a.nsrc = n_src;
-  a.B = B; a.H = H; a.W = W;
-  a.bias = fused_table(t, nullptr, n, npad, 0.f);
-  a.scale = fused_table(t, nullptr, n, npad, 1.f);
-  a.act = ACT_NONE;
-  a.out = as_view(out);
-  a.res1 = mkview(nullptr, 0, 0, 0);
-  a.res2 = mkview(nullptr, 0, 0, 0);
-  if (!t.ok) return HCF_ERR_NOMEM;
-  if ((rc = fused_flag(t, a, st)) != HCF_OK) return rc;
-  float* m = t.dev(1);
-  if (!m) return HCF_ERR_NOMEM;
-  if (hipMemsetAsync(m, 0, sizeof(float), st) != hipSuccess) return HCF_ERR_HIP;
-  if ((rc = sources_absmax(a.src, n_src, B, H, W, m, st)) != HCF_OK) { hipStreamSynchronize(st); return rc; }
-  a.in_max = m;
+  int rc = conv_call(t, a, pk, sv, n_src, B, H, W, nullptr, nullptr, n, ACT_NONE, as_view(out), true, st);
+  if (rc != HCF_OK) return rc;
+  if ((rc = conv_in_max(t, a, st)) != HCF_OK) { hipStreamSynchronize(st); return rc; }
   const int rows_cap = std::max(conv_f16x3_scaled_blocks_max(B, H, W), conv_wino_grid(B, H, W, 1));
   a.fb_y = as_view(y); a.fb_act = fb_act; a.fb_max = fb_max; a.fb_max2 = fb_max2;
   a.fb_part = part_rows(t, (size_t)rows_cap * 2 * n, st, rc);
   if (rc != HCF_OK) { hipStreamSynchronize(st); return rc; }
-  if (fb_scale) a.fb_scale = fused_table(t, fb_scale, n, npad, 1.f);
+  if (fb_scale) a.fb_scale = table(t, fb_scale, n, ru32(n), 1.f);
   a.fb_zy = want_zy ? 1 : 0;
-  std::vector<float> pk;
-  int nchunk = 0, np = 0;
-  if (!pack_conv_weights_f16x3(w, cin, n, taps, srcs, n_src, pk, nchunk, np)) { hipStreamSynchronize(st); return HCF_ERR_UNSUPPORTED; }
-  a.wpack = t.up(pk);
-  a.nchunk = nchunk;
-  if (!t.ok) { hipStreamSynchronize(st); return HCF_ERR_NOMEM; }
-  // the engine's order: fused Winograd first, then the fused scaled f16x3 kernel; never an unfused launch
-  rc = HCF_ERR_UNSUPPORTED;
-  int rows = 0;
-  if (k == 3 && !(g_f16x3_ablation & kAblNoWino)) {
-    std::vector<float> pkw;
-    // (from 16 input channels on, the narrowest pack the engine builds for this kernel: a unit count beyond one round of blocks
-    //  stays affordable for a test only on a narrow source)
-    const float* wino = pack_conv_weights_wino(w, cin, n, srcs, n_src, pkw, 16) ? t.up(pkw) : nullptr;
-    if (!t.ok) { hipStreamSynchronize(st); return HCF_ERR_NOMEM; }
-    if (wino) {
-      ConvArgs wv = a;
-      wv.wpack = nullptr;
-      rc = launch_conv_wino(wv, wino, st);
-    }
-    if (rc != HCF_ERR_UNSUPPORTED) {
-      rows = conv_wino_grid(B, H, W, 1);
-      info[0] = 2; info[1] = rc; info[11] = rows; info[17] = (int32_t)wino_units(B, H, W, 1);
-    }
+  // (the Winograd pack from 16 input channels on, the narrowest the engine builds for this kernel: a unit count beyond one round of
+  //  blocks stays affordable for a test only on a narrow source)
+  if ((rc = conv_packs(t, a, pk, w, cin, n, taps, srcs, n_src, true, 1u << CONV_WINO | 1u << CONV_F16X3, 16)) != HCF_OK) {
+    hipStreamSynchronize(st);
+    return rc;
   }
-  if (rc == HCF_ERR_UNSUPPORTED) {
-    const F16x3Plan p = plan_conv_f16x3(a, taps);
-    const int32_t v[14] = {p.status, p.v.ntb, p.v.vec, p.v.up, p.v.fuse2, p.v.tailc, p.v.th, p.v.scaled, p.v.k1, p.v.n16,
-                           (int32_t)p.grid, (int32_t)p.block, p.vec_epi, p.strip_w};
-    info[0] = 1;
-    for (int i = 0; i < 14; ++i) info[1 + i] = v[i];
+  // fused Winograd first, then the fused scaled f16x3 kernel once its rows are known to fit fb_part; never an unfused launch
+  int rows = conv_wino_grid(B, H, W, 1);
+  const ConvRoute rt = route_conv(a, pk, taps, 1u << CONV_WINO, st);
+  rc = rt.status;
+  if (rc != HCF_ERR_UNSUPPORTED) {
+    info[0] = 2; info[1] = rc; info[11] = rows; info[17] = (int32_t)wino_units(B, H, W, 1);
+  } else {
+    const F16x3Plan p = info_f16x3(a, taps, 14, info);
     int sw = 0, th = 8;
     rows = conv_f16x3_scaled_blocks(B, H, W, &sw, &th);      // (conv_tile_blocks of the engine: the rows it hands to its sum job)
-    rc = p.status != HCF_OK ? p.status : ((long long)p.grid > rows_cap || rows > rows_cap) ? HCF_ERR_ARG : launch_conv_f16x3(a, taps, st);
+    rc = (p.status == HCF_OK && ((long long)p.grid > rows_cap || rows > rows_cap)) ? HCF_ERR_ARG
+                                                                                   : route_conv(a, pk, taps, 1u << CONV_F16X3, st).status;
   }
   if (rc == HCF_OK) {
     info[16] = rows;
     rc = reduce_rows(t, a.fb_part, rows, n, n, sum_pre, sum_zy, zy_mult, st);      // (want_zy off: the second row holds the kernel's zeros)
   }
-  if (hipStreamSynchronize(st) != hipSuccess) return HCF_ERR_HIP;
-  if (rc != HCF_OK) return rc;
-  int h = 0;
-  if (hipMemcpy(&h, a.ovf, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return HCF_ERR_HIP;
-  info[15] = h;
-  return h ? HCF_ERR_UNSUPPORTED : HCF_OK;
+  if (rc != HCF_OK) return hipStreamSynchronize(st) != hipSuccess ? HCF_ERR_HIP : rc;
+  return conv_finish(pk.flag, info, st);
 }
 
 int hcf_op_conv2d_wgrad_views(const hcf_view* src, int32_t n_src, int32_t B, int32_t H, int32_t W, const hcf_view* g, int32_t taps,
@@ -1246,18 +1155,7 @@ int hcf_op_conv2d_wgrad_views(const hcf_view* src, int32_t n_src, int32_t B, int
   wa.dw = t.dev(nw);
   if (!t.ok) return HCF_ERR_NOMEM;
   if (hipMemsetAsync(wa.dw, 0, nw * sizeof(float), st) != hipSuccess) return HCF_ERR_HIP;
-  if (g_op_precision == PREC_F16X3) {          // as hcf_op_conv2d_backward: g scaled from max |g|, X must sit inside the f16 range
-    float* gm = t.dev(2);
-    if (!t.ok) return HCF_ERR_NOMEM;
-    if (hipMemsetAsync(gm, 0, 2 * sizeof(float), st) != hipSuccess) return HCF_ERR_HIP;
-    rc = launch_absmax(wa.g, B, H, W, gm, st);
-    if (rc == HCF_OK) rc = sources_absmax(wa.src, n_src, B, H, W, gm + 1, st);
-    float xmax = 0.f;
-    if (hipMemcpyAsync(&xmax, gm + 1, sizeof(float), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-      return HCF_ERR_HIP;
-    if (rc != HCF_OK) return rc;
-    if (xmax < 65504.f) wa.g_max = gm;           // NaN / inf compare false -> fp32 kernel
-  }
+  if (g_op_precision == PREC_F16X3 && (rc = wgrad_f16_range(t, wa, st)) != HCF_OK) return rc;
   wa.part_cap = conv_wgrad_scratch_floats(wa);
   wa.part = t.dev(wa.part_cap);
   if (!t.ok) return HCF_ERR_NOMEM;
@@ -1290,7 +1188,7 @@ int hcf_op_conv_epilogue_backward_views(const hcf_view* gy, const hcf_view* y, c
   e.gy = as_view(gy);
   e.gpre = as_view(gpre);
   e.y = y ? as_view(y) : mkview(nullptr, gy->cs, gy->c0, n);
-  if (scale) e.scale = fused_table(t, scale, n, ((n + 31) / 32) * 32, 1.f);
+  if (scale) e.scale = table(t, scale, n, ru32(n), 1.f);
   e.act = act;
   e.has1 = has1; e.rs1 = rs1; e.has2 = has2; e.rs2 = rs2;
   e.g1 = (has1 && g1) ? as_view(g1) : mkview(nullptr, gy->cs, gy->c0, n);
@@ -1320,7 +1218,8 @@ extern "C" int hcf_bench_conv(int32_t B, int32_t H, int32_t W, const int32_t* sr
   hipStream_t st = (hipStream_t)stream;
   Tmp t;
   ConvArgs a;
-  memset(&a, 0, sizeof(a));
+  ConvPacks pk;
+  View sv[kMaxSrc];
   int cin = 0, srcs[kMaxSrc];
   uint32_t rng = 12345u;
   auto rnd = [&]() { rng = rng * 1664525u + 1013904223u; return ((rng >> 8) * (1.0f / 8388608.0f)) - 1.0f; };
@@ -1329,29 +1228,24 @@ extern "C" int hcf_bench_conv(int32_t B, int32_t H, int32_t W, const int32_t* sr
     const size_t n = (size_t)B * H * W * cs;
     std::vector<float> h(n);
     for (size_t j = 0; j < n; ++j) h[j] = rnd();
-    a.src[i] = mkview(t.up(h), cs, 0, src_c[i]);
+    sv[i] = mkview(t.up(h), cs, 0, src_c[i]);
     srcs[i] = src_c[i];
     cin += src_c[i];
   }
-  for (int i = n_src; i < kMaxSrc; ++i) a.src[i] = a.src[0];
-  a.nsrc = n_src;
-  a.B = B; a.H = H; a.W = W;
   std::vector<float> w((size_t)cout * cin * k * k);
   for (auto& v : w) v = rnd() * 0.05f;
-  const int npad = ((cout + 31) / 32) * 32;
-  std::vector<float> hb(npad, 0.1f), hs(npad, 1.f);
-  a.bias = t.up(hb); a.scale = t.up(hs);
-  a.act = ACT_LRELU;
-  a.out = mkview(t.dev((size_t)B * H * W * ru4(cout)), ru4(cout), 0, cout);
-  a.res1 = mkview(nullptr, 0, 0, 0);
-  a.res2 = mkview(nullptr, 0, 0, 0);
-  if (!t.ok) return HCF_ERR_NOMEM;
+  const std::vector<float> hb(cout, 0.1f);
+  std::vector<float> hpad(ru32(cout), 0.1f);      // (the padding entries of the bias table too)
+  int rc = conv_call(t, a, pk, sv, n_src, B, H, W, hb.data(), nullptr, cout, ACT_LRELU,
+                     mkview(t.dev((size_t)B * H * W * ru4(cout)), ru4(cout), 0, cout), op_f16(cout) && k == 3, st);
+  if (rc != HCF_OK) return rc;
+  if (hipMemcpy(const_cast<float*>(a.bias), hpad.data(), hpad.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) return HCF_ERR_HIP;
   hipEvent_t e0, e1;
   hipEventCreate(&e0);
   hipEventCreate(&e1);
   a.dbg = (unsigned long long*)t.dev(32);
   if (a.dbg) hipMemsetAsync(a.dbg, 0, 128, st);
-  int rc = pack_and_launch(t, a, w.data(), cin, cout, k, srcs, n_src, st);     // pack + warm-up
+  rc = pack_and_launch(t, a, pk, w.data(), cin, cout, k, srcs, n_src, st);     // pack + warm-up
   if (a.dbg) hipMemsetAsync(a.dbg, 0, 128, st);
   const bool f16 = a.ovf != nullptr;
   hipEventRecord(e0, st);

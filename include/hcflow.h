@@ -809,6 +809,13 @@ int hcf_debug_set_ablation(int32_t bits);
 #define HCF_PLAN_N_IN 40
 #define HCF_PLAN_N_OUT 18
 int hcf_debug_conv_plan(const int32_t* in, int32_t n_in, int64_t* out, int32_t n_out);
+/* Which kernel families a conv call would try, in order, WITHOUT a GPU (tests/test_conv_route_cpu.py): the order every conv launch
+ * of the library goes through (engine, per-op entries, auxiliary nets). taps 1 / 9; packs: the weight packs the caller has, bit0 exact,
+ * bit1 f16x3, bit2 Winograd, bit3 a fused second layer's f16x3 pack, bit4 its Winograd fragment; tail != 0: a flow-step tail is fused;
+ * allow: the forms the caller admits, bit (1 << form). forms[4] receives the forms -- 0 Winograd, 1 fcn12, 2 f16x3, 3 exact, -1 beyond
+ * the last -- the launch stops at the first that does not answer HCF_ERR_UNSUPPORTED. Honours hcf_debug_set_ablation (256: no
+ * Winograd). Returns the number of forms, or HCF_ERR_ARG. */
+int hcf_debug_conv_route(int32_t taps, int32_t packs, int32_t tail, int32_t allow, int32_t* forms, int32_t n_forms);
 /* precision used by the per-op entry points hcf_op_conv2d / hcf_bench_conv (process-wide test knob) */
 int hcf_op_set_precision(int32_t mode);
 /* tools/conv_bench.py: times `iters` back-to-back launches of the conv kernel on random NHWC slabs */
